@@ -32,6 +32,14 @@ the JSON config reports the layout and the resident weight GB per rank.
 Timing: W untimed warmup steps, then a barrier + device sync, K timed steps, a device sync +
 barrier; the elapsed time is the MAX over ranks.  ``value`` = total queries answered by all
 replicas / that time.  Weights are random-init (no checkpoints offline), prompts are synthetic.
+
+A plain run does only what the headline figure needs: set-up, warmup, the K timed steps, the JSON
+line (``ms_per_step`` = that time / K).  ``--dump-outputs DIR`` then also writes the answers to the
+last timed step's queries as ``DIR/*.npy`` (see ``_dump_outputs``): weights and prompts are seeded
+and the dumped answers are produced in an order that does not depend on request arrival, so two
+runs with the same arguments write the same arrays.  ``--full`` is where measurements
+beyond the headline go; there are none today (every other workload is its own ``--mode`` /
+``--path`` / ``--model`` run), so it changes nothing.
 """
 from __future__ import annotations
 
@@ -89,6 +97,12 @@ def parse(argv=None):
                          "(the round-5 form, for A/B runs)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the answers to the last step's queries (greedy token "
+                         "ids and first-token logits per query) as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beyond the headline figure (none so far: the other "
+                         "workloads are --mode / --path / --model runs of their own)")
     a = ap.parse_args(argv)
     if a.mode == "latency":
         a.batch = 1
@@ -213,7 +227,7 @@ def run_rank(a) -> None:
                                  max_model_len=8192, max_prefill_tokens=a.max_prefill_tokens,
                                  chunked_prefill=bool(a.chunked_prefill), tp_size=a.tp,
                                  kv_cache_gb=a.kv_cache_gb if on_gpu else 0.0, use_graphs=not a.no_graphs,
-                                 seed=a.seed + ps.dp_rank, **admit), pstate=ps)
+                                 seed=a.seed + ps.dp_rank, **admit), device=ps.device, pstate=ps)
     if a.decode_fusion != "auto":
         eng.model.set_decode_fusion(rc=a.decode_fusion == "rc")
     eng.warmup()
@@ -227,6 +241,16 @@ def run_rank(a) -> None:
         return
 
     svc = EngineService(eng, max_queue=max(4 * a.batch, 256))
+    answers: list = []  # --dump-outputs: the future of every request, in submission order
+    if a.dump_outputs:
+        submit = svc.submit
+
+        def recording_submit(*args, **kw):
+            fut = submit(*args, **kw)
+            answers.append(fut)
+            return fut
+
+        svc.submit = recording_submit
     server = port = None
     if a.path in ("http", "podcomm"):
         from k8s_llm_monitor_amd.monitor.app import build_app_for_bench
@@ -325,12 +349,70 @@ def run_rank(a) -> None:
         server.shutdown()
     if loadgen is not None:
         loadgen.close()
+    if a.dump_outputs:  # the engine thread has stopped: the model is this thread's alone
+        _dump_outputs(a.dump_outputs, answers[-n:] if a.steps > 0 else [], a.max_new_tokens, ps.dp_rank,
+                      eng if a.tp == 1 else None)
     ptoks = sum(r.get("prompt_tokens", 0) for r in ok)
     gtoks = sum(r.get("completion_tokens", 0) for r in ok)
     # `value` counts complete answers: a production-mode answer cut at its deadline is reported
     # separately (requests.deadline_truncated_rank0), not as a served query
     n_full = sum(1 for r in ok if r.get("finish_reason") != "deadline")
     _finish(a, ps, comm, elapsed, n_full, ptoks, gtoks, res, stats, devices, eng, on_gpu, n_answered=len(ok))
+
+
+def _dump_outputs(out_dir: str, futs: list, max_new_tokens: int, dp_rank: int, eng=None) -> None:
+    """``--dump-outputs``: the answers to the last timed step's queries as float32 arrays (a token
+    id is below 2^24, so float32 holds it exactly), every one a function of the seeded inputs alone.
+
+    The tokens the step's clients received are not such a function: they are sampled (temperature
+    0.1) with random numbers keyed by a request's batch row and step, and which row and step a
+    request gets depends on the order its HTTP thread reached the engine (two runs of one build
+    agree on 70-80 % of the first tokens and hardly any later ones).  So, after the timed region
+    and with the engine thread stopped, the same queries are answered once more the way that does
+    not depend on arrival: in the order of their prompts' token ids, greedily, without prefix-cache
+    hits - through the same engine steps, prefill / decode kernels and decode graphs.
+
+    * ``prompt_tokens`` [queries]: the prompt lengths, rows in prompt order (as in every array).
+    * ``greedy_output_ids`` [queries, max_new_tokens] (``eng`` given, i.e. TP = 1): the token ids
+      of that second answer.
+    * ``first_token_logits`` [rows, vocab] (TP = 1): the logits the first answer token is chosen
+      from, one prefill per prompt; the first rows only, when all would exceed 48 MB.
+
+    Replicas other than the first write ``<name>_dp<k>.npy``."""
+    import numpy as np
+
+    seqs = []
+    for f in futs:
+        if f.done() and not f.cancelled() and f.exception() is None:
+            seqs.append(f.result()[1])
+    prompts = sorted(list(s.prompt_ids) for s in seqs)
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = f"_dp{dp_rank}" if dp_rank else ""
+    np.save(os.path.join(out_dir, f"prompt_tokens{sfx}.npy"), np.asarray([len(p) for p in prompts], dtype=np.float32))
+    if eng is None or not prompts:
+        return
+    import torch
+
+    from k8s_llm_monitor_amd.engine import SamplingParams
+    from k8s_llm_monitor_amd.models import AttnMeta
+
+    eng.blocks.prefix_caching = False  # which of the timed waves' blocks are still cached varies from run to run
+    again = eng.generate(prompts, SamplingParams(max_tokens=max_new_tokens, temperature=0.0, ignore_eos=True))
+    out = np.full((len(again), max_new_tokens), -1.0, dtype=np.float32)
+    for i, s in enumerate(again):
+        out[i, :len(s.output_ids)] = s.output_ids
+    np.save(os.path.join(out_dir, f"greedy_output_ids{sfx}.npy"), out)
+    dev = eng.device
+    rows = []
+    with torch.no_grad():
+        for p in prompts[:max(1, (48 << 20) // (4 * eng.model_cfg.vocab_size))]:
+            t = len(p)
+            meta = AttnMeta(is_prefill=True, positions=torch.arange(t, dtype=torch.int32, device=dev),
+                            slot_mapping=torch.full((t,), -1, dtype=torch.int32, device=dev),
+                            cu_seqlens=torch.tensor([0, t], dtype=torch.int32, device=dev),
+                            logits_idx=torch.tensor([t - 1], device=dev))
+            rows.append(eng.model.forward(torch.tensor(p, dtype=torch.int32, device=dev), meta, None).float().cpu())
+    np.save(os.path.join(out_dir, f"first_token_logits{sfx}.npy"), torch.cat(rows).numpy())
 
 
 def _finish(a, ps, comm, elapsed, n_ok, ptoks, gtoks, res, stats, devices, eng, on_gpu, n_answered=None) -> None:

@@ -115,7 +115,8 @@ def test_bench_ranks_under_torchrun_cpu(n):
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--standalone", "--local-addr", "127.0.0.1",
                         "--nnodes=1", "--nproc-per-node", str(n), "bench.py", "--gpus", str(n), "--steps", "1",
                         "--warmup", "1", "--model", "llama-tiny", "--batch", str(batch), "--max-new-tokens", "4"],
-                       capture_output=True, text=True, timeout=600, cwd=root, env={**os.environ, "OMP_NUM_THREADS": "1"})
+                       capture_output=True, text=True, timeout=600, cwd=root,
+                       env={**os.environ, "OMP_NUM_THREADS": "1", "K8SLLM_DEVICE": "cpu"})  # CPU ranks on any machine
     if r.returncode != 0:  # keep the failing ranks' stderr for the record (no relaunch)
         os.makedirs(os.path.join(root, "gpurun_out"), exist_ok=True)
         with open(os.path.join(root, "gpurun_out", f"torchrun_{n}_ranks_failure.err"), "w") as f:
@@ -136,6 +137,7 @@ def _bench(args):
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    env["K8SLLM_DEVICE"] = "cpu"  # the CPU engine (llama-tiny's head size has no HIP kernels), GPU visible or not
     r = subprocess.run([sys.executable, "bench.py", *args], capture_output=True, text=True, timeout=400, cwd=root,
                        env=env)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -156,6 +158,35 @@ def test_bench_self_launches_ranks_cpu(tp):
     assert d["value"] > 0 and "TP=%d" % tp in d["metric"]
     if tp == 2:
         assert d["dist"]["step_bus"] == "ShmStepBus"
+
+
+def test_bench_dump_outputs_cpu(tmp_path):
+    """``--dump-outputs DIR``: answers to the last timed wave's queries as float32 arrays, one row
+    per query (rows ordered by prompt), the same in two runs with the same arguments - the greedy
+    token ids of a query are its first-token logits' argmax, then the model's continuation;
+    ``--steps`` sets the timed steps and ``ms_per_step`` their mean; ``--full`` is accepted."""
+    import numpy as np
+
+    runs = []
+    for tag in ("a", "b"):
+        out = tmp_path / tag
+        d = _bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--model", "llama-tiny", "--batch", "3",
+                    "--max-new-tokens", "5", "--full", "--dump-outputs", str(out)])
+        assert d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] > 0
+        assert d["value"] == pytest.approx(2 * 3 / (2 * d["ms_per_step"] / 1e3), rel=1e-3)
+        assert sorted(p.name for p in out.iterdir()) == ["first_token_logits.npy", "greedy_output_ids.npy",
+                                                         "prompt_tokens.npy"]
+        runs.append({p.stem: np.load(p) for p in out.iterdir()})
+    r = runs[0]
+    ids, npt, lg = r["greedy_output_ids"], r["prompt_tokens"], r["first_token_logits"]
+    assert ids.dtype == np.float32 and ids.shape == (3, 5) and npt.dtype == np.float32 and npt.shape == (3,)
+    assert (ids >= 0).all() and (ids == np.round(ids)).all() and (npt > 100).all()
+    assert lg.dtype == np.float32 and lg.shape == (3, 512) and np.isfinite(lg).all() and lg.std() > 0
+    for k, x in r.items():  # same arguments, same inputs, same answers (logits: within one bf16 ulp of the largest)
+        if k == "first_token_logits":
+            np.testing.assert_allclose(runs[1][k], x, rtol=0, atol=2.0 ** -7 * float(np.abs(x).max()))
+        else:
+            np.testing.assert_array_equal(runs[1][k], x)
 
 
 def test_bench_open_loop_and_latency_modes_cpu():

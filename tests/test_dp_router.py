@@ -59,10 +59,15 @@ def test_router_backs_local_engine_backend_concurrently():
         router.close()
 
 
-def test_server_assembly_with_dp_replicas(tmp_path):
+def test_server_assembly_with_dp_replicas(tmp_path, monkeypatch):
+    import torch
+
     from k8s_llm_monitor_amd.monitor.app import make_llm_backend
     from k8s_llm_monitor_amd.monitor.config import load
 
+    # the CPU assembly (replica_devices' no-GPU answer), whatever this machine has: llama-tiny has
+    # no HIP kernels, and two GPU replicas would need two GPUs
+    monkeypatch.setattr(torch.cuda, "device_count", lambda: 0)
     p = tmp_path / "config.yaml"
     p.write_text("llm:\n  provider: local-rocm\n  model: llama-tiny\n  dp_replicas: 2\n  max_batch: 4\n"
                  "  max_model_len: 256\n  kv_cache_gb: 0.01\n  use_graphs: false\n  max_tokens: 3\n")

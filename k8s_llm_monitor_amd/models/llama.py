@@ -683,17 +683,18 @@ class CausalLM:
     def _logits(self, x: torch.Tensor, rows: Optional[int] = None) -> torch.Tensor:
         """LM head (+ the TP all-gather of the vocab shards).  ``x``: the final-normed rows,
         row-major, or fragment-packed with ``rows`` valid rows (decode).  With a decode copy of the
-        head (``lm_head_d``) up to 64 rows at a time go through gemm_decode.hip - the decode step's
-        and a prefill step's last-token logits alike; hipBLASLt otherwise."""
+        head (``lm_head_d``) up to dec_rows_max() rows at a time (128 for dense TP=1 models, else
+        64) go through gemm_decode.hip, one stream of the head per launch - the decode step's and a
+        prefill step's last-token logits alike; hipBLASLt otherwise."""
         hd = self.lm_head_d
         if x.dim() == 4:  # packed (decode): the decode copy exists by construction
             logits = torch.empty(rows, hd.shape[0] * 16, dtype=self.dtype, device=self.device)
             ops.dec_gemm(x, hd, 1, rows, out=logits)
-        elif hd is not None and x.is_cuda and x.shape[0] <= ops.SKINNY_MAX_M:
+        elif hd is not None and x.is_cuda and x.shape[0] <= self.dec_rows_max():
             logits = torch.empty(x.shape[0], hd.shape[0] * 16, dtype=self.dtype, device=self.device)
             ops.dec_gemm(ops.pack_activation(x), hd, 1, x.shape[0], out=logits)
-        elif self.lm_head.dim() == 4:  # ONE_LAYOUT: the packed head is the only copy - 64-row chunks
-            M, mc = x.shape[0], ops.SKINNY_MAX_M
+        elif self.lm_head.dim() == 4:  # ONE_LAYOUT: the packed head is the only copy - dec_rows_max()-row chunks
+            M, mc = x.shape[0], self.dec_rows_max()
             logits = torch.empty(M, hd.shape[0] * 16, dtype=self.dtype, device=self.device)
             for i in range(0, M, mc):
                 m = min(mc, M - i)
@@ -706,10 +707,37 @@ class CausalLM:
         return logits
 
     # ------------------------------------------------------------------ fused decode tail
+    # Row ceiling of the decode fast path for the models whose every projection runs on the dense
+    # shared-A decode GEMM (dec_rows_max).  Tests and tools set it to 64 for the routing before the
+    # 128-row kernels (A/B runs); values above ops.DEC_MAX_M are clamped.
+    DEC_ROWS_MAX = 128
+
+    def dec_rows_max(self) -> int:
+        """Most rows a decode step may have and stay on the skinny path (_decode_layers_skinny):
+        min(DEC_ROWS_MAX, ops.DEC_MAX_M) = 128 for a dense model at TP=1 whose layers hold wqkv_d /
+        wo_d / w13_d / w2_d and whose head has its decode copy (every GEMM of the step is then
+        ops.dec_gemm, with a 65..128-row configuration for each shape); 64 otherwise - MoE (the
+        grouped launches), TP > 1 (the IPC fused tail and its staging), gemm_skinny weights."""
+        if not getattr(self, "_dec_wide", False):
+            return ops.SKINNY_MAX_M
+        return max(ops.SKINNY_MAX_M, min(int(self.DEC_ROWS_MAX), ops.DEC_MAX_M))
+
+    def _dec_wide_ok(self) -> bool:
+        c = self.cfg
+        if self.tp != 1 or c.is_moe or not self.layers or self.lm_head_d is None:
+            return False
+        L = self.layers[0]
+        if not all(k in L for k in ("wqkv_d", "wo_d", "w13_d", "w2_d")):
+            return False
+        shapes = [ops.skinny_wdims(L[k]) + (2 if k == "w13_d" else 0,) for k in ("wqkv_d", "wo_d", "w13_d", "w2_d")]
+        shapes.append(ops.skinny_wdims(self.lm_head_d) + (1,))
+        return all(ops.dec_available(N, K, epi, rows=ops.DEC_MAX_M) for N, K, epi in shapes)
+
     def _use_skinny(self, meta: AttnMeta, h: torch.Tensor) -> bool:
-        """Dense Llama decode at TP=1 on the GPU with <= 64 rows runs every projection through
-        gemm_skinny over fragment-packed weights (see _init_skinny)."""
-        return (self._skinny_ws is not None and not meta.is_prefill and h.shape[0] <= ops.SKINNY_MAX_M
+        """Llama-family decode steps of up to dec_rows_max() rows (128 for dense TP=1 models on the
+        shared-A decode GEMM, 64 otherwise) run every projection through the decode GEMMs over
+        fragment-packed weights (see _init_skinny)."""
+        return (self._skinny_ws is not None and not meta.is_prefill and h.shape[0] <= self.dec_rows_max()
                 and meta.logits_idx is None and self.SKINNY_DECODE)
 
     def _init_skinny(self) -> None:
@@ -737,6 +765,7 @@ class CausalLM:
         self._skinny_ws = None
         self.lm_head_d = None
         self._rc_o = 0
+        self._dec_wide = False
         if self.lm_head.dim() == 4:
             self.lm_head = self.canonical_head().contiguous()
         if self._packed:  # re-initialised over ONE_LAYOUT weights: back to the canonical row-major form
@@ -786,16 +815,25 @@ class CausalLM:
         split = ops.SKINNY_SPLITS_FORCE  # 0: the launcher picks per call (kernel and batch dependent)
         self._split_qkv = self._split_o = self._split_d = split
         self._init_dec()
+        self._dec_wide = self._dec_wide_ok()
 
         def most(N: int, K: int) -> int:
+            # the most slabs any row count up to the limit can ask for: gemm_skinny's automatic
+            # split (row dependent up to 64 rows) and gemm_dec's configuration at <= 64 rows and,
+            # where the model decodes up to 128, at 65..128 rows (dec_config has these two classes)
             s_rm = split if split else max(ops.skinny_auto_splits(m, N, K) for m in (1, 33, 64))
-            cfg = ops.dec_config(N, K, 0) if self.layers and any(k.endswith("_d") for k in self.layers[0]) else None
-            return max(s_rm, cfg[0] if cfg else 1)
+            s_dec = 1
+            if self.layers and any(k.endswith("_d") for k in self.layers[0]):
+                for r in (1, ops.DEC_MAX_M) if self._dec_wide else (1,):
+                    cfg = ops.dec_config(N, K, 0, rows=r)
+                    s_dec = max(s_dec, cfg[0] if cfg else 1)
+            return max(s_rm, s_dec)
 
         n = max(most(nq, d) * nq, most(d, self.hq * self.D) * d,
                 (self.e_hi - self.e_lo) * ops.skinny_nslabs(ff, 1) * d if c.is_moe else most(d, ff) * d)
         # MoE: the EP all-to-all decode runs up to 128 received rows per grouped launch
-        rows = ops.SKINNY_GROUPED_MAX_M if c.is_moe else ops.SKINNY_MAX_M
+        # dense TP=1 on the shared-A decode GEMM: up to DEC_MAX_M rows per step (dec_rows_max)
+        rows = ops.SKINNY_GROUPED_MAX_M if c.is_moe else ops.DEC_MAX_M if self._dec_wide else ops.SKINNY_MAX_M
         self._skinny_ws = torch.empty(n * rows, dtype=torch.float32, device=self.device)
         self.set_decode_fusion()
 

@@ -48,6 +48,9 @@ class LLMConfig:
     # in-process engine (provider local-rocm)
     tp_size: int = 1
     dp_replicas: int = 1
+    # concurrent sequences per replica (the decode batch).  Up to 128 keeps every decode step of a
+    # dense Llama-family model at TP=1 on the decode GEMMs; MoE and TP > 1 take their fast path up
+    # to 64 rows (larger steps run the generic layer loop)
     max_batch: int = 64
     kv_cache_gb: float = 32.0
     max_model_len: int = 8192

@@ -72,8 +72,14 @@ def fused_add_rms_norm(x: torch.Tensor, residual: torch.Tensor, w: torch.Tensor,
 
 # ---------------------------------------------------------------- decode projections (skinny GEMM)
 
+# Row limits of the decode GEMMs, all in one place:
+#   64  gemm_skinny, the grouped (MoE) shared-A launches (dec_gemm_grouped), the row-complete o
+#       projection (dec_gemm_rc, used up to 32 rows) and every TP > 1 decode tail;
+#   128 the dense shared-A decode GEMM (dec_gemm: gemm_decode.hip with 5..8 m-tiles) - dense
+#       Llama-family models at TP=1 over the packed weights (CausalLM.dec_rows_max).
 SKINNY_MAX_M = 64
 SKINNY_GROUPED_MAX_M = 128  # grouped (expert) launches over row-major weights: gemm_skinny.hip
+DEC_MAX_M = 128  # dec_gemm (dense launches of gemm_dec_kernel)
 
 
 def pack_skinny(w: torch.Tensor) -> torch.Tensor:
@@ -179,7 +185,7 @@ def _cpu_a(a: torch.Tensor, rows: Optional[int]) -> torch.Tensor:
 
 
 def pack_activation(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """Row-major [M, K] (M <= 64) -> fragment-packed [ceil(M/16), K/32, 64, 8] (rows padded with
+    """Row-major [M, K] -> fragment-packed [ceil(M/16), K/32, 64, 8] (rows padded with
     zeros), the A-operand layout gemm_skinny reads with whole-line loads."""
     M, K = x.shape
     mt = -(-M // 16)
@@ -351,23 +357,46 @@ DEC_TABLE: dict = {
     (128256, 4096, 1): (1, 4, 8, 4),    # LM head 173.8 / 166.0  (hipBLASLt 202.2 / 176.2)
 }
 
+# The same at 65..128 rows (the 5..8 m-tile instantiations of gemm_dec_kernel), from the sweep
+# tools/bench_decode_gemm.py --ms 64,96,128 (profiles/r07/decode_gemm_m128_sweep.jsonl; us at
+# M = 128 / 96 / 64 on one box).  The 64-row picks stay the fastest: fewer split-K slabs for o / down
+# (half the slab bytes) lose more weight-streaming parallelism than they save - o (4, 1, 8, 8) 16.1
+# and (4, 1, 4, 8) 15.0 us against 14.0, down 38.2 and 33.6 against 29.7; qkv on 8- or 4-wave
+# workgroups 22.5 / 24.0 against 16.7.  The LM head takes two n-tiles per wave: 8 m-tiles x 4
+# n-tiles of accumulators exceed the 256 registers of a wave at two waves per SIMD.
+DEC_TABLE_M128: dict = {
+    (6144, 4096, 0): (4, 1, 6, 8),      # qkv      16.7 / 14.7 / 12.6
+    (4096, 4096, 0): (8, 1, 8, 8),      # o        14.0 / 11.8 / 10.2
+    (28672, 4096, 2): (1, 1, 7, 8),     # gate_up  49.6 / 42.7 / 39.7
+    (4096, 14336, 0): (8, 1, 8, 8),     # down     29.7 / 26.1 / 22.4
+    (128256, 4096, 1): (1, 2, 8, 8),    # LM head 186.4 / 182.2 / 180.2 (hipBLASLt 223.7 / 214.1 / 205.5)
+}
 
 
-def dec_config(N: int, K: int, epi: int, experts: int = 1) -> Optional[tuple]:
+def dec_config(N: int, K: int, epi: int, experts: int = 1, rows: int = 0) -> Optional[tuple]:
     """Launch configuration of gemm_dec for a weight [N, K]: (splits, ntw, waves, depth) or None
     when no configuration tiles the shape (the caller keeps gemm_skinny).  The candidates are the
     (ntw, waves, depth) forms gemm_decode.hip instantiates: every Llama-3-8B / 70B / Mixtral
     projection and LM head at TP 1..8 picks one of them (tools/bench_decode_gemm.py passes ``cfg``
     to dec_gemm to time others).  ``experts`` > 1: a grouped launch (grid.z = expert), whose
     workgroup count is per expert times experts (Mixtral down: 32 column groups x 8 experts, no
-    split - the expert slabs are the split)."""
-    hit = DEC_TABLE.get((N, K, epi)) if experts == 1 else None
+    split - the expert slabs are the split).  ``rows`` > 64 (dense launches only, up to
+    DEC_MAX_M): the pick among the forms instantiated with 5..8 m-tiles; ``rows`` <= 64 (or not
+    given) never changes the answer."""
+    wide = rows > SKINNY_MAX_M
+    if wide and (experts != 1 or rows > DEC_MAX_M):
+        return None
+    hit = (DEC_TABLE_M128 if wide else DEC_TABLE).get((N, K, epi)) if experts == 1 else None
     if hit is not None:
         return hit
     ntiles, ksteps = N // 16, K // 32
-    cands = ([(1, 1, 7, 8), (1, 1, 7, 16), (1, 1, 8, 16)] if epi == 2 else
-             [(1, 4, 8, 4), (1, 3, 8, 8), (1, 2, 8, 8), (1, 1, 8, 8)] if epi == 1 else
-             [(s, ntw, w, d) for s in (1, 2, 4, 8, 16) for (ntw, w, d) in ((1, 8, 8), (1, 4, 16), (1, 4, 8))])
+    if wide:
+        cands = ([(1, 1, 7, 8)] if epi == 2 else [(1, 2, 8, 8)] if epi == 1 else
+                 [(s, ntw, w, d) for s in (1, 2, 4, 8, 16) for (ntw, w, d) in ((1, 8, 8), (1, 4, 8))])
+    else:
+        cands = ([(1, 1, 7, 8), (1, 1, 7, 16), (1, 1, 8, 16)] if epi == 2 else
+                 [(1, 4, 8, 4), (1, 3, 8, 8), (1, 2, 8, 8), (1, 1, 8, 8)] if epi == 1 else
+                 [(s, ntw, w, d) for s in (1, 2, 4, 8, 16) for (ntw, w, d) in ((1, 8, 8), (1, 4, 16), (1, 4, 8))])
     best = None
     for s, ntw, w, d in cands:
         if experts > 1 and s > 1:  # grouped: the per-expert slabs are the split (workspace E x M x N)
@@ -385,8 +414,8 @@ def dec_config(N: int, K: int, epi: int, experts: int = 1) -> Optional[tuple]:
     return best[1] if best else None
 
 
-def dec_available(N: int, K: int, epi: int) -> bool:
-    return dec_config(N, K, epi) is not None
+def dec_available(N: int, K: int, epi: int, rows: int = 0) -> bool:
+    return dec_config(N, K, epi, rows=rows) is not None
 
 
 def dec_gemm(a: torch.Tensor, wp: torch.Tensor, epi: int, rows: int, workspace: Optional[torch.Tensor] = None,
@@ -395,14 +424,17 @@ def dec_gemm(a: torch.Tensor, wp: torch.Tensor, epi: int, rows: int, workspace: 
     """gemm_dec over a fragment-packed activation ``a`` and packed weight ``wp`` (decode-only copy).
     epi 0: fp32 split-K slabs into ``workspace`` [S, M, N], returns S; epi 1: ``out`` [M, N] bf16;
     epi 2: ``out`` packed SwiGLU [ceil(M/16), F/32, 64, 8] over an interleave_gate_up8 weight.
-    ``rownorm = (ss_part, eps)``: deferred RMSNorm of the A rows (add_norm_partial).  CPU: the fp32
-    reference with the same split-K slicing."""
+    ``rownorm = (ss_part, eps)``: deferred RMSNorm of the A rows (add_norm_partial).  Up to
+    DEC_MAX_M = 128 rows; the configuration is dec_config's for that row count (65..128 rows run
+    the 5..8 m-tile instantiations).  CPU: the fp32 reference with the same split-K slicing."""
     N, K = skinny_wdims(wp)
     M = rows
+    if M > DEC_MAX_M:
+        raise ValueError(f"gemm_dec: at most {DEC_MAX_M} rows, got {M}")
     if cfg is None:
-        cfg = dec_config(N, K, epi)
+        cfg = dec_config(N, K, epi, rows=M)
     if cfg is None:
-        raise ValueError(f"gemm_dec: no configuration for N={N} K={K} epi={epi}")
+        raise ValueError(f"gemm_dec: no configuration for N={N} K={K} epi={epi} rows={M}")
     S, ntw, waves, depth = cfg
     if not _gpu(a):
         x = _cpu_a(a, rows).float()

@@ -582,7 +582,8 @@ int64_t gemm_skinny(torch::Tensor a, torch::Tensor wp, c10::optional<torch::Tens
 // a packed [ceil(M/16), K/32, 64, 8] (`rows` valid), wp packed [N/16, K/32, 64, 8] (for epi 2 the
 // rows interleaved per 16-row n-tile as [8 gate | 8 up]).  epi 0: fp32 slabs partial[S][M][N],
 // returns S = splits; epi 1: y [M, N] bf16 (row stride y.stride(0)); epi 2: packed SwiGLU
-// y [ceil(M/16), N/64, 64, 8].  Returns the slab count (1 for epi 1/2); -1 if the configuration
+// y [ceil(M/16), N/64, 64, 8].  Up to 128 rows (above 64: the configurations gemm_decode.hip
+// instantiates with 5..8 m-tiles).  Returns the slab count (1 for epi 1/2); -1 if the configuration
 // is not available (the caller falls back to gemm_skinny).
 int64_t gemm_dec(torch::Tensor a, torch::Tensor wp, c10::optional<torch::Tensor> partial, c10::optional<torch::Tensor> y,
                  int64_t splits, int64_t epi, int64_t ntw, int64_t waves, int64_t depth, int64_t rows,
@@ -593,7 +594,7 @@ int64_t gemm_dec(torch::Tensor a, torch::Tensor wp, c10::optional<torch::Tensor>
   const int N = (int)wp.size(0) * 16, K = (int)wp.size(1) * 32, M = (int)rows;
   TORCH_CHECK(a.dim() == 4 && a.is_contiguous() && a.size(1) * 32 == K && a.size(2) == 64 && a.size(3) == 8,
               "gemm_dec: a must be fragment-packed [ceil(M/16), K/32, 64, 8]");
-  TORCH_CHECK(M > 0 && M <= 64 && (M + 15) / 16 <= a.size(0), "gemm_dec: 1..64 rows within the packed a");
+  TORCH_CHECK(M > 0 && M <= 128 && (M + 15) / 16 <= a.size(0), "gemm_dec: 1..128 rows within the packed a");
   float* pp = nullptr;
   void* yp = nullptr;
   long ldy = 0;

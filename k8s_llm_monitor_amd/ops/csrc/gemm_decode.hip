@@ -1,5 +1,6 @@
 // Decode-time GEMM, second design ("W stream, shared A"): Y[M, N] = A[M, K] . W[N, K]^T for
-// M <= 64 rows, bf16 in, fp32 accumulate, gfx950 v_mfma_f32_16x16x32_bf16.
+// M <= 128 rows (dense launches; grouped launches and the row-complete kernel M <= 64), bf16 in,
+// fp32 accumulate, gfx950 v_mfma_f32_16x16x32_bf16.
 //
 // Why a second kernel.  gemm_skinny_rm_kernel (gemm_skinny.hip) stages BOTH operands by LDS-DMA,
 // and at M = 64 every 64-column workgroup re-reads all 64 A rows - as many bytes as its weight
@@ -98,17 +99,38 @@ __global__ __launch_bounds__(64 * WAVES, 1) void gemm_dec_kernel(
   // add_norm_partial's per-512-column sums) one float per load; wide rows (16 | partials <= 256:
   // gemm_dec_rc_kernel's per-16-column sums) 16-byte loads, each thread a quarter of the row.
   // (RNW: the wide form, a compile-time choice - the host picks the instantiation by rn_nc)
-  float rnv[kRnMax];  // no initial value: read only under the same condition (no join wait)
+  // Above 64 rows the MT * 64 row-threads outnumber a 4-, 6- or 7-wave workgroup (and equal an
+  // 8-wave one): RNP passes over the rows, pass q taking row-thread threadIdx.x + q * 64 * WAVES,
+  // so every one of the MT * 16 entries of s_inv is written whatever WAVES is.  RNP == 1 for
+  // MT <= 4: the single pass of the 64-row kernel.
+  constexpr int RNP = (MT * 64 + 64 * WAVES - 1) / (64 * WAVES);
+  static_assert(!RNW || RNP == 1, "the wide deferred-norm form serves <= 64 rows (behind gemm_dec_rc)");
+  float rnv[RNP][kRnMax];  // no initial value: read only under the same condition (no join wait)
   f32x4 rnw[RNW ? kRnWide : 1];
   const bool rn_narrow = !RNW && rn_nc <= 4 * kRnMax, rn_wide = RNW && rn_nc % 16 == 0 && rn_nc <= 16 * kRnWide;
-  if (rn_ss != nullptr && threadIdx.x < MT * 64 && (rn_narrow || rn_wide)) {
+  if constexpr (RNP > 1) {
+    if (rn_ss != nullptr && rn_narrow) {
+      const __amdgpu_buffer_rsrc_t ss_rs = dec_rsrc(rn_ss, (long)M * rn_nc * 4);
+#pragma unroll
+      for (int q = 0; q < RNP; ++q) {
+        // row-threads past MT * 64 repeat row M - 1: every load unconditional and in bounds
+        const int rt = threadIdx.x + q * 64 * WAVES;
+        const int row = min(rt >> 2, M - 1), part = rt & 3;
+#pragma unroll
+        for (int j = 0; j < kRnMax; ++j) {
+          const uint32_t off = (uint32_t)((row * rn_nc + min(part + 4 * j, rn_nc - 1)) * 4);
+          rnv[q][j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(ss_rs, off, 0, 0));
+        }
+      }
+    }
+  } else if (rn_ss != nullptr && threadIdx.x < MT * 64 && (rn_narrow || rn_wide)) {
     const int row = min((int)(threadIdx.x >> 2), M - 1), part = threadIdx.x & 3;
     const __amdgpu_buffer_rsrc_t ss_rs = dec_rsrc(rn_ss, (long)M * rn_nc * 4);
     if constexpr (!RNW) {
 #pragma unroll
       for (int j = 0; j < kRnMax; ++j) {
         const uint32_t off = (uint32_t)((row * rn_nc + min(part + 4 * j, rn_nc - 1)) * 4);
-        rnv[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(ss_rs, off, 0, 0));
+        rnv[0][j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(ss_rs, off, 0, 0));
       }
     } else {
       const int q = rn_nc >> 2;  // this thread's quarter: floats part*q .. part*q + q - 1
@@ -151,14 +173,37 @@ __global__ __launch_bounds__(64 * WAVES, 1) void gemm_dec_kernel(
 
   // ---- deferred RMSNorm: 1/rms of each A row from its partial sums of squares (loads issued
   // above, ahead of the A staging and the weight ring, so this wait leaves both in flight)
-  if (rn_ss != nullptr && threadIdx.x < MT * 64) {
+  if constexpr (RNP > 1) {
+    if (rn_ss != nullptr) {
+#pragma unroll
+      for (int q = 0; q < RNP; ++q) {
+        const int rt = threadIdx.x + q * 64 * WAVES;
+        const int rl = rt >> 2, part = rt & 3;
+        float ss = 0.f;
+        if (rn_narrow) {
+#pragma unroll
+          for (int j = 0; j < kRnMax; ++j) {
+            asm volatile("" : "+v"(rnv[q][j]));  // the first use (and its wait) stays past the ring issue
+            ss += part + 4 * j < rn_nc ? rnv[q][j] : 0.f;
+          }
+        } else {  // other widths: a plain loop (no decode GEMM today)
+          const int row = min(rl, M - 1);
+          for (int c = part; c < rn_nc; c += 4) ss += rn_ss[row * rn_nc + c];
+        }
+        // 64 * WAVES is a multiple of 4: the 4 threads of a row sit in one wave in every pass
+        ss += __shfl_xor(ss, 1, kWave);
+        ss += __shfl_xor(ss, 2, kWave);
+        if (part == 0 && rl < MT * 16) s_inv[rl] = rsqrtf(ss * rn_inv_d + rn_eps);
+      }
+    }
+  } else if (rn_ss != nullptr && threadIdx.x < MT * 64) {
     const int rl = threadIdx.x >> 2, part = threadIdx.x & 3;
     float ss = 0.f;
     if (rn_narrow) {
 #pragma unroll
       for (int j = 0; j < kRnMax; ++j) {
-        asm volatile("" : "+v"(rnv[j]));  // keeps the first use (and its wait) here, past the ring issue
-        ss += part + 4 * j < rn_nc ? rnv[j] : 0.f;
+        asm volatile("" : "+v"(rnv[0][j]));  // keeps the first use (and its wait) here, past the ring issue
+        ss += part + 4 * j < rn_nc ? rnv[0][j] : 0.f;
       }
     } else if (rn_wide) {
       const int q = rn_nc >> 2;
@@ -375,6 +420,8 @@ using namespace k8sllm;
 // Weight layout for DEC_SWIGLU8: fragment-packed over rows interleaved per 16-row n-tile as
 // [8 gate | 8 up] (ops.interleave_gate_up8).  ntw x waves n-tiles per workgroup; grid
 // (ceil((N / 16) / (ntw * waves)), splits) - the last workgroup may hold fewer n-tiles.  depth: weight k-steps in flight per wave.
+// M <= 64 on every configuration listed below; 65..128 rows (5..8 m-tiles) on the dense ones
+// ops.dec_config picks above 64 rows, never grouped (experts > 1 or rw).
 // Returns 0, or a negative code when the shape / configuration is not supported (the caller then
 // uses gemm_skinny).
 extern "C" int k8sllm_gemm_dec(const void* A, const void* Wp, float* partial, void* Y, long ldy, int M, int N, int K,
@@ -383,7 +430,9 @@ extern "C" int k8sllm_gemm_dec(const void* A, const void* Wp, float* partial, vo
                                long y_es, const float* rw, int rw_ld, hipStream_t s) {
   if (M <= 0) return 0;
   if (experts < 1 || (rw != nullptr && epi != DEC_SLAB)) return -1;
-  if (M > 64 || N % 16 || K % 32 || splits < 1 || K % splits) return -1;
+  // 65..128 rows (5..8 m-tiles): dense launches only, on the configurations marked "<= 128 rows" below
+  if (M > 128 || (M > 64 && (experts > 1 || rw != nullptr))) return -1;
+  if (N % 16 || K % 32 || splits < 1 || K % splits) return -1;
   const int ntiles = N / 16, nwg_tiles = ntw * waves;
   const int kchunk = K / splits;
   const int iter = depth > kDecCH ? depth : kDecCH;
@@ -406,8 +455,20 @@ extern "C" int k8sllm_gemm_dec(const void* A, const void* Wp, float* partial, vo
     case 1: K8S_DEC(1, NTWV, WV, EPV, DV); break; \
     case 2: K8S_DEC(2, NTWV, WV, EPV, DV); break; \
     case 3: K8S_DEC(3, NTWV, WV, EPV, DV); break; \
-    default: K8S_DEC(4, NTWV, WV, EPV, DV); break; \
+    case 4: K8S_DEC(4, NTWV, WV, EPV, DV); break; \
+    default: break;                    \
   }
+  // the same with 5..8 m-tiles (65..128 rows): A chunks of MT * 8 KiB in the 2-slot LDS ring
+  // (128 KiB at MT = 8), MT x NTW accumulators per wave
+#define K8S_DEC_M8(NTWV, WV, EPV, DV) \
+  switch (MT) {                       \
+    case 5: K8S_DEC(5, NTWV, WV, EPV, DV); break; \
+    case 6: K8S_DEC(6, NTWV, WV, EPV, DV); break; \
+    case 7: K8S_DEC(7, NTWV, WV, EPV, DV); break; \
+    case 8: K8S_DEC(8, NTWV, WV, EPV, DV); break; \
+    default: K8S_DEC_M(NTWV, WV, EPV, DV) break;  \
+  }
+  if (rnw && MT > 4) return -5;  // the wide form follows gemm_dec_rc: <= 64 rows
   if (rnw) {  // consumers of gemm_dec_rc's per-16-column partials: gate_up behind the row-complete o
 #define K8S_DEC_MW(NTWV, WV, EPV, DV) \
   switch (MT) {                       \
@@ -424,21 +485,26 @@ extern "C" int k8sllm_gemm_dec(const void* A, const void* Wp, float* partial, vo
   }
   // configurations (ntw, waves, depth) per epilogue: exactly the ones ops.dec_config can pick - every
   // Llama-3-8B / 70B / Mixtral projection and LM head at TP 1..8 lands on one of them
+  // (K8S_DEC_M8: also at 65..128 rows - the dense TP=1 picks of ops.dec_config(rows > 64); every
+  // other configuration returns -5 there)
   if (epi == DEC_SLAB) {
-    if (ntw == 1 && waves == 8 && depth == 8) { K8S_DEC_M(1, 8, DEC_SLAB, 8) }         // o, down; TP 2-8 shapes
-    else if (ntw == 1 && waves == 6 && depth == 8) { K8S_DEC_M(1, 6, DEC_SLAB, 8) }    // qkv: 64 groups x 4 splits
-    else if (ntw == 1 && waves == 4 && depth == 8) { K8S_DEC_M(1, 4, DEC_SLAB, 8) }    // narrow TP shards
+    if (ntw == 1 && waves == 8 && depth == 8) { K8S_DEC_M8(1, 8, DEC_SLAB, 8) }        // o, down; TP 2-8 shapes
+    else if (ntw == 1 && waves == 6 && depth == 8) { K8S_DEC_M8(1, 6, DEC_SLAB, 8) }   // qkv: 64 groups x 4 splits
+    else if (ntw == 1 && waves == 4 && depth == 8) { K8S_DEC_M8(1, 4, DEC_SLAB, 8) }   // narrow TP shards
     else if (ntw == 1 && waves == 4 && depth == 16) { K8S_DEC_M(1, 4, DEC_SLAB, 16) }  // 70B TP=8 qkv
   } else if (epi == DEC_SWIGLU8) {
-    if (ntw == 1 && waves == 7 && depth == 8) { K8S_DEC_M(1, 7, DEC_SWIGLU8, 8) }      // gate_up
+    if (ntw == 1 && waves == 7 && depth == 8) { K8S_DEC_M8(1, 7, DEC_SWIGLU8, 8) }     // gate_up
     else if (ntw == 1 && waves == 7 && depth == 16) { K8S_DEC_M(1, 7, DEC_SWIGLU8, 16) }
     else if (ntw == 1 && waves == 8 && depth == 16) { K8S_DEC_M(1, 8, DEC_SWIGLU8, 16) }  // 70B TP=1 gate_up
   } else if (epi == DEC_BF16) {
-    if (ntw == 4 && waves == 8 && depth == 4) { K8S_DEC_M(4, 8, DEC_BF16, 4) }         // LM head, TP=1
-    else if (ntw == 2 && waves == 8 && depth == 8) { K8S_DEC_M(2, 8, DEC_BF16, 8) }    // vocab shards, TP 2-8
+    if (ntw == 4 && waves == 8 && depth == 4) { K8S_DEC_M(4, 8, DEC_BF16, 4) }         // LM head, TP=1, <= 64 rows
+    // the head above 64 rows: 8 m-tiles x 4 n-tiles of accumulators do not fit a 2-waves-per-SIMD
+    // register budget, so two n-tiles per wave
+    else if (ntw == 2 && waves == 8 && depth == 8) { K8S_DEC_M8(2, 8, DEC_BF16, 8) }   // vocab shards, TP 2-8
     else if (ntw == 3 && waves == 8 && depth == 8) { K8S_DEC_M(3, 8, DEC_BF16, 8) }
     else if (ntw == 1 && waves == 8 && depth == 8) { K8S_DEC_M(1, 8, DEC_BF16, 8) }    // Mixtral's 32000-row head
   }
+#undef K8S_DEC_M8
 #undef K8S_DEC_M
 #undef K8S_DEC
 #undef K8S_DEC_W

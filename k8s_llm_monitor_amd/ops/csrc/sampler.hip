@@ -6,7 +6,8 @@
 // Randomness is a counter hash of (seed, offset, row, index); `rng` lives in device memory so a
 // hipGraph-captured decode step draws fresh numbers on every replay (the engine bumps offset).
 //
-// Decomposition: a decode batch has only B <= 64 rows, and Gumbel-max over a 128K vocabulary is
+// Decomposition: a decode batch has few rows (B <= 128 on the decode fast path; any B is taken -
+// the part count comes from k8sllm_sample_parts(B, V)), and Gumbel-max over a 128K vocabulary is
 // VALU-bound (hash + two logs per element), so one workgroup per row used 64 of 256 CUs and took
 // 125 us at B = 64.  Rows are split into P parts: grid (B, P) of 1024-thread workgroups each
 // produce a partial (value, index) argmax, and a one-wave kernel picks the winner per row.  Rows

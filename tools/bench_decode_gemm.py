@@ -4,7 +4,10 @@ shared-A decode GEMM (gemm_decode.hip) over its packed weight copies, for a list
 configurations (splits, n-tiles per wave, waves, ring depth).  One process, interleaved rounds;
 each case is 32 hipGraph-captured calls rotating over > 512 MiB of weight copies, so weights
 stream from HBM as in a decode step.  Every dec configuration is checked against an fp32
-reference of the same product first (max |err| / max |ref|).
+reference of the same product first (max |err| / max |ref|).  Above 64 rows (``--ms 64,96,128``:
+the 5..8 m-tile instantiations) only gemm_decode.hip has a kernel: the row-major skinny case is
+left out, hipBLASLt stays for the LM head, and configurations without a 65..128-row instantiation
+are reported as errors and skipped.  ``pick`` lines give ops.dec_config's choice per row count.
 
     python tools/bench_decode_gemm.py [--ms 1,32,64] [--ops qkv,o,gate_up,down,lm_head] [--rounds 3]
 """
@@ -82,7 +85,10 @@ def main() -> None:
                 return ops.unpack_skinny(act)[:M].float()
 
             cases = {}
-            if epi == 0:
+            print(json.dumps({"op": name, "M": M, "pick": ops.dec_config(N, K, epi, rows=M)}), flush=True)
+            if M > ops.SKINNY_MAX_M and epi != 1:
+                pass  # gemm_skinny stops at 64 rows
+            elif epi == 0:
                 cases["rm"] = lambda i: ops.skinny_slabs(xp, wrm[i % ncopy], wsp, 0, rows=M)
             elif epi == 2:
                 cases["rm"] = lambda i: ops.skinny_swiglu(xp, wrm[i % ncopy], out=act, rows=M, packed_out=True)

@@ -12,6 +12,8 @@ also A/B'd write-through (sc1) epilogue stores in gemm_decode.hip with this tool
 ms per step, slower - profiles/r05/decode_step_writethrough_ab.jsonl.  Round 6: ``split4*`` - o /
 down on 4 split-K slabs instead of 8 (half the bytes add_norm_partial reads) - 6.02 vs 5.93 ms at 64
 rows, 3.78 vs 3.75 at 16: slower, DEC_TABLE unchanged; profiles/r06/decode_step_split4_ab.jsonl.)
+``rows128`` - CausalLM.DEC_ROWS_MAX 128 vs 64: a 128-row decode step on gemm_decode.hip's 8 m-tile
+kernels vs the generic layer loop (``--rows 64,128``; at 64 rows both sides run the same code).
 """
 from __future__ import annotations
 
@@ -32,7 +34,11 @@ SWITCHES = {"rc": lambda m, on: m.set_decode_fusion(rc=on),
             # instead of 8 x 32 of 8-wave ones): half the slab bytes add_norm_partial reads
             "split4": lambda m, on: _dec_table(on, {(4096, 4096, 0): (4, 1, 4, 16), (4096, 14336, 0): (4, 1, 4, 16)}),
             "split4o": lambda m, on: _dec_table(on, {(4096, 4096, 0): (4, 1, 4, 16)}),
-            "split4d": lambda m, on: _dec_table(on, {(4096, 14336, 0): (4, 1, 4, 16)})}
+            "split4d": lambda m, on: _dec_table(on, {(4096, 14336, 0): (4, 1, 4, 16)}),
+            # decode steps of 65..128 rows on the shared-A decode GEMM (on / reset) vs the routing
+            # before it (off: CausalLM.DEC_ROWS_MAX = 64, the generic layer loop on the tile GEMM);
+            # run with --rows 64,128
+            "rows128": lambda m, on: setattr(type(m), "DEC_ROWS_MAX", 64 if on is False else 128)}
 _DEC_DEFAULT: dict = {}
 
 

@@ -816,15 +816,18 @@ class CausalLM:
         self._split_qkv = self._split_o = self._split_d = split
         self._init_dec()
         self._dec_wide = self._dec_wide_ok()
+        # the ceiling of dec_rows_max(): dense TP=1 on the shared-A decode GEMM up to DEC_MAX_M rows
+        dec_rows = ops.DEC_MAX_M if self._dec_wide else ops.SKINNY_MAX_M
 
         def most(N: int, K: int) -> int:
             # the most slabs any row count up to the limit can ask for: gemm_skinny's automatic
-            # split (row dependent up to 64 rows) and gemm_dec's configuration at <= 64 rows and,
-            # where the model decodes up to 128, at 65..128 rows (dec_config has these two classes)
+            # split (row dependent up to 64 rows) and gemm_dec's configuration in every row class
+            # (ops.dec_row_classes) the model can decode in: up to the ceiling of dec_rows_max() -
+            # as the buffer's rows below, not bound to what DEC_ROWS_MAX says at the moment
             s_rm = split if split else max(ops.skinny_auto_splits(m, N, K) for m in (1, 33, 64))
             s_dec = 1
             if self.layers and any(k.endswith("_d") for k in self.layers[0]):
-                for r in (1, ops.DEC_MAX_M) if self._dec_wide else (1,):
+                for r in (r for r in ops.dec_row_classes() if r <= dec_rows):
                     cfg = ops.dec_config(N, K, 0, rows=r)
                     s_dec = max(s_dec, cfg[0] if cfg else 1)
             return max(s_rm, s_dec)
@@ -832,8 +835,7 @@ class CausalLM:
         n = max(most(nq, d) * nq, most(d, self.hq * self.D) * d,
                 (self.e_hi - self.e_lo) * ops.skinny_nslabs(ff, 1) * d if c.is_moe else most(d, ff) * d)
         # MoE: the EP all-to-all decode runs up to 128 received rows per grouped launch
-        # dense TP=1 on the shared-A decode GEMM: up to DEC_MAX_M rows per step (dec_rows_max)
-        rows = ops.SKINNY_GROUPED_MAX_M if c.is_moe else ops.DEC_MAX_M if self._dec_wide else ops.SKINNY_MAX_M
+        rows = ops.SKINNY_GROUPED_MAX_M if c.is_moe else dec_rows
         self._skinny_ws = torch.empty(n * rows, dtype=torch.float32, device=self.device)
         self.set_decode_fusion()
 

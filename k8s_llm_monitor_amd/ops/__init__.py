@@ -72,14 +72,54 @@ def fused_add_rms_norm(x: torch.Tensor, residual: torch.Tensor, w: torch.Tensor,
 
 # ---------------------------------------------------------------- decode projections (skinny GEMM)
 
+# The compiled forms of the shared-A decode GEMM: (epilogue, n-tiles per wave, waves, ring depth,
+# max m-tiles, wide-norm) - the rows of kDecForms in csrc/gemm_dec_forms.h, which
+# native().gemm_dec_forms() reports (tests/test_decode_rows_cpu.py compares the two).  A form
+# serves up to 16 * max m-tiles rows; wide-norm: also the deferred-norm form over per-16-column
+# sums (behind dec_gemm_rc).  Kept here as well because dec_config runs without the extension.
+# The order is dec_config's candidate order: the first of two equal candidates wins.
+DEC_SLAB, DEC_BF16, DEC_SWIGLU8 = 0, 1, 2
+DEC_FORMS: tuple = (
+    (DEC_SLAB, 1, 8, 8, 8, 0),
+    (DEC_SLAB, 1, 6, 8, 8, 0),
+    (DEC_SLAB, 1, 4, 16, 4, 0),
+    (DEC_SLAB, 1, 4, 8, 8, 0),
+    (DEC_SWIGLU8, 1, 7, 8, 8, 1),
+    (DEC_SWIGLU8, 1, 7, 16, 4, 1),
+    (DEC_SWIGLU8, 1, 8, 16, 4, 0),
+    (DEC_BF16, 4, 8, 4, 4, 0),
+    (DEC_BF16, 3, 8, 8, 4, 0),
+    (DEC_BF16, 2, 8, 8, 8, 0),
+    (DEC_BF16, 1, 8, 8, 4, 0),
+)
+# compiled, but never an automatic pick: only DEC_TABLE / DEC_TABLE_M128 (qkv) name it
+DEC_FORMS_TABLE_ONLY = frozenset({(DEC_SLAB, 1, 6, 8)})
+
 # Row limits of the decode GEMMs, all in one place:
-#   64  gemm_skinny, the grouped (MoE) shared-A launches (dec_gemm_grouped), the row-complete o
-#       projection (dec_gemm_rc, used up to 32 rows) and every TP > 1 decode tail;
-#   128 the dense shared-A decode GEMM (dec_gemm: gemm_decode.hip with 5..8 m-tiles) - dense
-#       Llama-family models at TP=1 over the packed weights (CausalLM.dec_rows_max).
+#   64  gemm_skinny, the grouped (MoE) shared-A launches (dec_gemm_grouped), the wide-norm form,
+#       the row-complete o projection (dec_gemm_rc, used up to 32 rows) and every TP > 1 decode
+#       tail;
+#   128 the dense shared-A decode GEMM (dec_gemm: the forms of 8 m-tiles) - dense Llama-family
+#       models at TP=1 over the packed weights (CausalLM.dec_rows_max).
 SKINNY_MAX_M = 64
 SKINNY_GROUPED_MAX_M = 128  # grouped (expert) launches over row-major weights: gemm_skinny.hip
-DEC_MAX_M = 128  # dec_gemm (dense launches of gemm_dec_kernel)
+DEC_NARROW_MAX_M = 64  # kDecNarrowMaxM: grouped and wide-norm launches of gemm_dec_kernel
+DEC_MAX_M = max(16 * f[4] for f in DEC_FORMS)  # dec_gemm (dense launches of gemm_dec_kernel)
+
+
+def dec_row_classes() -> tuple:
+    """The distinct row limits of the compiled forms, ascending: dec_config can answer differently
+    from one class to the next and never within one."""
+    return tuple(sorted({16 * f[4] for f in DEC_FORMS}))
+
+
+def dec_form_ok(epi: int, cfg: tuple, rows: int, grouped: bool = False, wide_norm: bool = False) -> bool:
+    """Whether gemm_decode.hip has an instantiation for ``cfg = (splits, ntw, waves, depth)`` at
+    ``rows`` rows: a DEC_FORMS row with that many m-tiles; ``grouped`` launches and the
+    ``wide_norm`` form (which the row must have) stop at DEC_NARROW_MAX_M rows."""
+    if (grouped or wide_norm) and rows > DEC_NARROW_MAX_M:
+        return False
+    return any(f[:4] == (epi,) + tuple(cfg[1:]) and rows <= 16 * f[4] and (f[5] or not wide_norm) for f in DEC_FORMS)
 
 
 def pack_skinny(w: torch.Tensor) -> torch.Tensor:
@@ -376,27 +416,25 @@ DEC_TABLE_M128: dict = {
 def dec_config(N: int, K: int, epi: int, experts: int = 1, rows: int = 0) -> Optional[tuple]:
     """Launch configuration of gemm_dec for a weight [N, K]: (splits, ntw, waves, depth) or None
     when no configuration tiles the shape (the caller keeps gemm_skinny).  The candidates are the
-    (ntw, waves, depth) forms gemm_decode.hip instantiates: every Llama-3-8B / 70B / Mixtral
-    projection and LM head at TP 1..8 picks one of them (tools/bench_decode_gemm.py passes ``cfg``
-    to dec_gemm to time others).  ``experts`` > 1: a grouped launch (grid.z = expert), whose
+    DEC_FORMS rows of the epilogue that serve ``rows``, in list order (the first of two equal
+    candidates wins: (1, 4, 16) over (1, 4, 8) where both tile), without the table-only ones; split-K
+    slabs try every form per split count.  Every Llama-3-8B / 70B / Mixtral projection and LM head
+    at TP 1..8 picks one of them (tools/bench_decode_gemm.py passes ``cfg`` to dec_gemm to time
+    others).  ``experts`` > 1: a grouped launch (grid.z = expert), whose
     workgroup count is per expert times experts (Mixtral down: 32 column groups x 8 experts, no
     split - the expert slabs are the split).  ``rows`` > 64 (dense launches only, up to
     DEC_MAX_M): the pick among the forms instantiated with 5..8 m-tiles; ``rows`` <= 64 (or not
     given) never changes the answer."""
-    wide = rows > SKINNY_MAX_M
+    wide = rows > DEC_NARROW_MAX_M
     if wide and (experts != 1 or rows > DEC_MAX_M):
         return None
     hit = (DEC_TABLE_M128 if wide else DEC_TABLE).get((N, K, epi)) if experts == 1 else None
     if hit is not None:
         return hit
     ntiles, ksteps = N // 16, K // 32
-    if wide:
-        cands = ([(1, 1, 7, 8)] if epi == 2 else [(1, 2, 8, 8)] if epi == 1 else
-                 [(s, ntw, w, d) for s in (1, 2, 4, 8, 16) for (ntw, w, d) in ((1, 8, 8), (1, 4, 8))])
-    else:
-        cands = ([(1, 1, 7, 8), (1, 1, 7, 16), (1, 1, 8, 16)] if epi == 2 else
-                 [(1, 4, 8, 4), (1, 3, 8, 8), (1, 2, 8, 8), (1, 1, 8, 8)] if epi == 1 else
-                 [(s, ntw, w, d) for s in (1, 2, 4, 8, 16) for (ntw, w, d) in ((1, 8, 8), (1, 4, 16), (1, 4, 8))])
+    forms = [f[1:4] for f in DEC_FORMS
+             if f[0] == epi and rows <= 16 * f[4] and f[:4] not in DEC_FORMS_TABLE_ONLY]
+    cands = [(s,) + f for s in ((1, 2, 4, 8, 16) if epi == DEC_SLAB else (1,)) for f in forms]
     best = None
     for s, ntw, w, d in cands:
         if experts > 1 and s > 1:  # grouped: the per-expert slabs are the split (workspace E x M x N)
@@ -458,6 +496,11 @@ def dec_gemm(a: torch.Tensor, wp: torch.Tensor, epi: int, rows: int, workspace: 
         out.copy_(pack_activation((torch.nn.functional.silu(g) * u).to(a.dtype)))
         return 1
     rn = (None, 0.0) if rownorm is None else (rownorm[0], float(rownorm[1]))
+    # more than 16 partial sums per row: gemm_dec_rc's per-16-column sums, the wide-norm form
+    wn = rownorm is not None and rownorm[0].shape[1] > 16
+    if not dec_form_ok(epi, cfg, M, wide_norm=wn):
+        raise RuntimeError(f"gemm_dec: form (epi, ntw, waves, depth) = {(epi,) + tuple(cfg[1:])} not compiled for "
+                           f"{M} rows" + (" with the wide deferred norm" if wn else ""))
     r = native().gemm_dec(a, wp, workspace, out, S, epi, ntw, waves, depth, M, *rn)
     if r < 0:
         raise RuntimeError(f"gemm_dec: configuration {cfg} not compiled for N={N} K={K} epi={epi}")
@@ -492,6 +535,9 @@ def dec_gemm_grouped(a: torch.Tensor, wp: torch.Tensor, epi: int, rows: int, wor
                 if row_w is not None:
                     ws.view(S, M, N).mul_(row_w[:M, e].float().view(1, M, 1))
         return E * S if epi == 0 else 1
+    if not dec_form_ok(epi, cfg, M, grouped=True):
+        raise RuntimeError(f"gemm_dec_grouped: form (epi, ntw, waves, depth) = {(epi,) + tuple(cfg[1:])} not "
+                           f"compiled for {M} rows of a grouped launch")
     r = native().gemm_dec_grouped(a, wp, workspace, out, S, epi, ntw, waves, depth, M, row_w)
     if r < 0:
         raise RuntimeError(f"gemm_dec_grouped: configuration {cfg} not compiled for N={N} K={K} epi={epi}")

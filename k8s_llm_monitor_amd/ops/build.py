@@ -100,7 +100,7 @@ def build_ops(force: bool = False, jobs: int = 8) -> Path:
 
     def cpp_obj(src: Path) -> Path:
         obj = out / (src.stem + ".o")
-        if force or _stale(obj, [src]):
+        if force or _stale(obj, [src] + hdrs):
             _run(["g++", "-O2", "-std=c++17", "-fPIC", *cflags, "-c", str(src), "-o", str(obj)])
         return obj
 

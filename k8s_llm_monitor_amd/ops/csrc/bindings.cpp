@@ -5,6 +5,8 @@
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime.h>
 
+#include "gemm_dec_forms.h"
+
 extern "C" {
 int k8sllm_rmsnorm(void* out, const void* x, void* residual, const void* w, long rows, int d, float eps,
                    long x_stride, long out_stride, hipStream_t s);
@@ -57,6 +59,7 @@ int k8sllm_gemm_skinny_auto_splits(int M, int N, int K);
 int k8sllm_gemm_dec(const void* A, const void* Wp, float* partial, void* Y, long ldy, int M, int N, int K, int splits,
                     int epi, int ntw, int waves, int depth, const float* rn_ss, int rn_nc, int rn_d, float rn_eps,
                     int experts, long a_es, long w_es, long y_es, const float* rw, int rw_ld, hipStream_t s);
+int k8sllm_gemm_dec_forms(int* out, int cap);
 int k8sllm_gemm_dec_rc(const void* A, const void* Wp, void* resid, const void* nw, void* xw, float* ss, int M, int N,
                        int K, hipStream_t s);
 int k8sllm_add_norm_partial(void* out, long out_stride, void* residual, const float* partial, int S, int M,
@@ -582,8 +585,8 @@ int64_t gemm_skinny(torch::Tensor a, torch::Tensor wp, c10::optional<torch::Tens
 // a packed [ceil(M/16), K/32, 64, 8] (`rows` valid), wp packed [N/16, K/32, 64, 8] (for epi 2 the
 // rows interleaved per 16-row n-tile as [8 gate | 8 up]).  epi 0: fp32 slabs partial[S][M][N],
 // returns S = splits; epi 1: y [M, N] bf16 (row stride y.stride(0)); epi 2: packed SwiGLU
-// y [ceil(M/16), N/64, 64, 8].  Up to 128 rows (above 64: the configurations gemm_decode.hip
-// instantiates with 5..8 m-tiles).  Returns the slab count (1 for epi 1/2); -1 if the configuration
+// y [ceil(M/16), N/64, 64, 8].  Up to kDecMaxM rows on the forms of gemm_dec_forms.h that have
+// that many m-tiles.  Returns the slab count (1 for epi 1/2); -1 if the configuration
 // is not available (the caller falls back to gemm_skinny).
 int64_t gemm_dec(torch::Tensor a, torch::Tensor wp, c10::optional<torch::Tensor> partial, c10::optional<torch::Tensor> y,
                  int64_t splits, int64_t epi, int64_t ntw, int64_t waves, int64_t depth, int64_t rows,
@@ -594,7 +597,8 @@ int64_t gemm_dec(torch::Tensor a, torch::Tensor wp, c10::optional<torch::Tensor>
   const int N = (int)wp.size(0) * 16, K = (int)wp.size(1) * 32, M = (int)rows;
   TORCH_CHECK(a.dim() == 4 && a.is_contiguous() && a.size(1) * 32 == K && a.size(2) == 64 && a.size(3) == 8,
               "gemm_dec: a must be fragment-packed [ceil(M/16), K/32, 64, 8]");
-  TORCH_CHECK(M > 0 && M <= 128 && (M + 15) / 16 <= a.size(0), "gemm_dec: 1..128 rows within the packed a");
+  TORCH_CHECK(M > 0 && M <= k8sllm::kDecMaxM && (M + 15) / 16 <= a.size(0), "gemm_dec: 1..", k8sllm::kDecMaxM,
+              " rows within the packed a");
   float* pp = nullptr;
   void* yp = nullptr;
   long ldy = 0;
@@ -640,7 +644,8 @@ int64_t gemm_dec_grouped(torch::Tensor a, torch::Tensor wp, c10::optional<torch:
               "gemm_dec_grouped: wp must be [E, N/16, K/32, 64, 8]");
   const int E = (int)wp.size(0), N = (int)wp.size(1) * 16, K = (int)wp.size(2) * 32, M = (int)rows;
   const int MT = (M + 15) / 16;
-  TORCH_CHECK(M > 0 && M <= 64 && E >= 1, "gemm_dec_grouped: 1..64 rows, >= 1 expert");
+  TORCH_CHECK(M > 0 && M <= k8sllm::kDecNarrowMaxM && E >= 1, "gemm_dec_grouped: 1..", k8sllm::kDecNarrowMaxM,
+              " rows, >= 1 expert");
   const bool per_e = a.dim() == 5;
   TORCH_CHECK(a.is_contiguous() && (per_e ? (a.size(0) == E && a.size(1) >= MT && a.size(2) * 32 == K &&
                                              a.size(3) == 64 && a.size(4) == 8)
@@ -680,6 +685,18 @@ int64_t gemm_dec_grouped(torch::Tensor a, torch::Tensor wp, c10::optional<torch:
   return epi == 0 ? (int64_t)E * splits : 1;
 }
 
+// The compiled forms of gemm_dec (kDecForms): (epi, ntw, waves, depth, max m-tiles, wide-norm) per row.
+std::vector<std::tuple<int64_t, int64_t, int64_t, int64_t, int64_t, int64_t>> gemm_dec_forms() {
+  std::vector<int> v(6 * k8sllm::kDecNForms);
+  const int n = k8sllm_gemm_dec_forms(v.data(), k8sllm::kDecNForms);
+  TORCH_CHECK(n == k8sllm::kDecNForms, "gemm_dec_forms: ", n, " rows compiled, ", k8sllm::kDecNForms,
+              " in the header");
+  std::vector<std::tuple<int64_t, int64_t, int64_t, int64_t, int64_t, int64_t>> rows;
+  for (int i = 0; i < n; ++i)
+    rows.emplace_back(v[6 * i], v[6 * i + 1], v[6 * i + 2], v[6 * i + 3], v[6 * i + 4], v[6 * i + 5]);
+  return rows;
+}
+
 // Row-complete decode GEMM + residual add + deferred-norm operands (gemm_decode.hip
 // gemm_dec_rc_kernel): a packed [ceil(M/16), K/32, 64, 8] (`rows` valid), wp packed [N/16, K/32,
 // 64, 8]; resid [M, N] bf16 += a . wp^T (in place); xw packed [ceil(M/16), N/32, 64, 8] = resid *
@@ -690,7 +707,7 @@ bool gemm_dec_rc(torch::Tensor a, torch::Tensor wp, torch::Tensor resid, torch::
   TORCH_CHECK(wp.dim() == 4 && wp.is_contiguous() && wp.size(2) == 64 && wp.size(3) == 8, "gemm_dec_rc: wp packed");
   const int N = (int)wp.size(0) * 16, K = (int)wp.size(1) * 32, M = (int)rows;
   TORCH_CHECK(a.dim() == 4 && a.is_contiguous() && a.size(1) * 32 == K && a.size(2) == 64 && a.size(3) == 8 &&
-                  M > 0 && M <= 64 && (M + 15) / 16 <= a.size(0), "gemm_dec_rc: a packed [ceil(M/16), K/32, 64, 8]");
+                  M > 0 && M <= k8sllm::kDecNarrowMaxM && (M + 15) / 16 <= a.size(0), "gemm_dec_rc: a packed [ceil(M/16), K/32, 64, 8]");
   TORCH_CHECK(resid.dim() == 2 && resid.is_contiguous() && resid.size(0) >= M && resid.size(1) == N,
               "gemm_dec_rc: resid [M, N]");
   TORCH_CHECK(nw.numel() == N && nw.is_contiguous(), "gemm_dec_rc: nw [N]");
@@ -968,6 +985,7 @@ PYBIND11_MODULE(_k8sllm_ops, m) {
   m.def("gemm_skinny_grouped", &gemm_skinny_grouped);
   m.def("gemm_dec", &gemm_dec);
   m.def("gemm_dec_grouped", &gemm_dec_grouped);
+  m.def("gemm_dec_forms", &gemm_dec_forms);
   m.def("gemm_dec_rc", &gemm_dec_rc);
   m.def("reduce_add_rms_norm", &reduce_add_rms_norm);
   m.def("reduce_slabs", &reduce_slabs);

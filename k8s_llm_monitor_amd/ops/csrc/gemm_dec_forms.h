@@ -1,0 +1,52 @@
+// The compiled forms of the shared-A decode GEMM (gemm_dec_kernel, gemm_decode.hip): THE table.
+// k8sllm_gemm_dec dispatches by walking it and instantiates nothing else; the row limits of the
+// launcher and of the bindings are derived from it; k8sllm_gemm_dec_forms reports it, and
+// ops.DEC_FORMS (the Python copy dec_config picks from) is tested against that report.  Adding a
+// form or a row class is one row here and the same row there.
+// Plain C++: bindings.cpp (g++) includes this file, so no HIP or torch headers.
+#pragma once
+
+namespace k8sllm {
+
+enum { DEC_SLAB = 0, DEC_BF16 = 1, DEC_SWIGLU8 = 2 };
+
+// One row = the instantiations <1..max_mt m-tiles, ntw, waves, epi, depth> (16 rows per m-tile:
+// max_mt 4 serves <= 64 rows, 8 <= 128; above 4 the A chunks are max_mt * 8 KiB in the 2-slot LDS
+// ring - 128 KiB at 8 - with max_mt x ntw accumulators per wave), and with wide_norm also the
+// RNW = true ones (deferred-norm sums per 16 columns, behind gemm_dec_rc) at 1..kDecNarrowMaxMT.
+struct DecForm {
+  int epi, ntw, waves, depth, max_mt, wide_norm;
+};
+
+// Every Llama-3-8B / 70B / Mixtral projection and LM head at TP 1..8 lands on one of these.  The
+// order is the candidate order of ops.dec_config (the first of two equal candidates wins).
+constexpr DecForm kDecForms[] = {
+    {DEC_SLAB, 1, 8, 8, 8, 0},      // o, down; TP 2-8 shapes
+    {DEC_SLAB, 1, 6, 8, 8, 0},      // qkv: 64 groups x 4 splits (ops.DEC_TABLE only, never an automatic pick)
+    {DEC_SLAB, 1, 4, 16, 4, 0},     // 70B TP=8 qkv
+    {DEC_SLAB, 1, 4, 8, 8, 0},      // narrow TP shards
+    {DEC_SWIGLU8, 1, 7, 8, 8, 1},   // gate_up; wide: behind the row-complete o projection
+    {DEC_SWIGLU8, 1, 7, 16, 4, 1},
+    {DEC_SWIGLU8, 1, 8, 16, 4, 0},  // 70B TP=1 gate_up
+    {DEC_BF16, 4, 8, 4, 4, 0},      // LM head, TP=1, <= 64 rows
+    {DEC_BF16, 3, 8, 8, 4, 0},
+    // the head above 64 rows: 8 m-tiles x 4 n-tiles of accumulators do not fit a 2-waves-per-SIMD
+    // register budget, so two n-tiles per wave
+    {DEC_BF16, 2, 8, 8, 8, 0},      // vocab shards, TP 2-8
+    {DEC_BF16, 1, 8, 8, 4, 0},      // Mixtral's 32000-row head
+};
+constexpr int kDecNForms = sizeof(kDecForms) / sizeof(kDecForms[0]);
+
+constexpr int dec_max_mt() {
+  int m = 0;
+  for (const DecForm& f : kDecForms) m = f.max_mt > m ? f.max_mt : m;
+  return m;
+}
+
+// Row limits: dense launches up to the largest form; grouped launches (experts > 1 or routing
+// weights), the wide deferred-norm form and the row-complete kernel stay at 4 m-tiles.
+constexpr int kDecNarrowMaxMT = 4;
+constexpr int kDecMaxM = 16 * dec_max_mt();        // 128
+constexpr int kDecNarrowMaxM = 16 * kDecNarrowMaxMT;  // 64
+
+}  // namespace k8sllm

@@ -1,6 +1,7 @@
 // Decode-time GEMM, second design ("W stream, shared A"): Y[M, N] = A[M, K] . W[N, K]^T for
 // M <= 128 rows (dense launches; grouped launches and the row-complete kernel M <= 64), bf16 in,
-// fp32 accumulate, gfx950 v_mfma_f32_16x16x32_bf16.
+// fp32 accumulate, gfx950 v_mfma_f32_16x16x32_bf16.  The compiled forms and the row limits:
+// kDecForms in gemm_dec_forms.h.
 //
 // Why a second kernel.  gemm_skinny_rm_kernel (gemm_skinny.hip) stages BOTH operands by LDS-DMA,
 // and at M = 64 every 64-column workgroup re-reads all 64 A rows - as many bytes as its weight
@@ -25,12 +26,11 @@
 #include <type_traits>
 
 #include "common.h"
+#include "gemm_dec_forms.h"
 
 namespace k8sllm {
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-enum { DEC_SLAB = 0, DEC_BF16 = 1, DEC_SWIGLU8 = 2 };
 
 // Grouped launches (MoE experts, grid.z = local expert e): A, W and the SWIGLU8 output advance by
 // a per-expert stride; SLAB partials land in slab e * S + split, scaled by the routing weight
@@ -417,11 +417,59 @@ __global__ __launch_bounds__(512, 1) void gemm_dec_rc_kernel(const bf16_t* __res
 
 using namespace k8sllm;
 
+namespace {
+
+struct DecLaunch {  // what every instantiation is launched with
+  dim3 grid, blk;
+  hipStream_t s;
+  const bf16_t *A, *W;
+  float* partial;
+  bf16_t* Y;
+  long ldy;
+  int M, N, K, kchunk;
+  const float* rn_ss;
+  int rn_nc;
+  float inv_d, rn_eps;
+  DecGroup dg;
+};
+
+// Launches <mt m-tiles, form F> for 1 <= mt <= MT: the instantiations 1..MT of the form and no
+// others (MT = 0: none).
+template <int F, bool RNW, int MT>
+bool dec_launch(int mt, const DecLaunch& l) {
+  if constexpr (MT == 0) {
+    return false;
+  } else {
+    if (mt != MT) return dec_launch<F, RNW, MT - 1>(mt, l);
+    constexpr DecForm f = kDecForms[F];
+    hipLaunchKernelGGL((gemm_dec_kernel<MT, f.ntw, f.waves, f.epi, f.depth, RNW>), l.grid, l.blk, 0, l.s, l.A, l.W,
+                       l.partial, l.Y, l.ldy, l.M, l.N, l.K, l.kchunk, l.rn_ss, l.rn_nc, l.inv_d, l.rn_eps, l.dg);
+    return true;
+  }
+}
+
+// The walk over kDecForms from row F on: false when no row is (epi, ntw, waves, depth) or the row
+// has no instantiation for mt m-tiles (rnw: of the wide deferred-norm form).
+template <int F = 0>
+bool dec_dispatch(int epi, int ntw, int waves, int depth, bool rnw, int mt, const DecLaunch& l) {
+  if constexpr (F == kDecNForms) {
+    return false;
+  } else {
+    constexpr DecForm f = kDecForms[F];
+    if (epi != f.epi || ntw != f.ntw || waves != f.waves || depth != f.depth)
+      return dec_dispatch<F + 1>(epi, ntw, waves, depth, rnw, mt, l);
+    return rnw ? dec_launch<F, true, f.wide_norm ? kDecNarrowMaxMT : 0>(mt, l) : dec_launch<F, false, f.max_mt>(mt, l);
+  }
+}
+
+}  // namespace
+
 // Weight layout for DEC_SWIGLU8: fragment-packed over rows interleaved per 16-row n-tile as
 // [8 gate | 8 up] (ops.interleave_gate_up8).  ntw x waves n-tiles per workgroup; grid
-// (ceil((N / 16) / (ntw * waves)), splits) - the last workgroup may hold fewer n-tiles.  depth: weight k-steps in flight per wave.
-// M <= 64 on every configuration listed below; 65..128 rows (5..8 m-tiles) on the dense ones
-// ops.dec_config picks above 64 rows, never grouped (experts > 1 or rw).
+// (ceil((N / 16) / (ntw * waves)), splits) - the last workgroup may hold fewer n-tiles.  depth:
+// weight k-steps in flight per wave.
+// (epi, ntw, waves, depth) must be a row of kDecForms (gemm_dec_forms.h) with ceil(M / 16) <= its
+// max_mt; grouped launches (experts > 1 or rw) and the wide deferred-norm form take M <= kDecNarrowMaxM.
 // Returns 0, or a negative code when the shape / configuration is not supported (the caller then
 // uses gemm_skinny).
 extern "C" int k8sllm_gemm_dec(const void* A, const void* Wp, float* partial, void* Y, long ldy, int M, int N, int K,
@@ -430,86 +478,34 @@ extern "C" int k8sllm_gemm_dec(const void* A, const void* Wp, float* partial, vo
                                long y_es, const float* rw, int rw_ld, hipStream_t s) {
   if (M <= 0) return 0;
   if (experts < 1 || (rw != nullptr && epi != DEC_SLAB)) return -1;
-  // 65..128 rows (5..8 m-tiles): dense launches only, on the configurations marked "<= 128 rows" below
-  if (M > 128 || (M > 64 && (experts > 1 || rw != nullptr))) return -1;
+  if (M > kDecMaxM || (M > kDecNarrowMaxM && (experts > 1 || rw != nullptr))) return -1;
   if (N % 16 || K % 32 || splits < 1 || K % splits) return -1;
   const int ntiles = N / 16, nwg_tiles = ntw * waves;
+  if (nwg_tiles < 1) return -5;
   const int kchunk = K / splits;
   const int iter = depth > kDecCH ? depth : kDecCH;
   if (kchunk % 32 || kchunk < 32 * iter || (kchunk / 32) % iter) return -3;
   if (epi != DEC_SLAB && splits != 1) return -4;
   const float inv_d = rn_d > 0 ? 1.f / (float)rn_d : 0.f;
   const int MT = (M + 15) / 16;
-  const dim3 grid((ntiles + nwg_tiles - 1) / nwg_tiles, splits, experts), blk(64 * waves);
-  const DecGroup dg{a_es, w_es, y_es, rw, rw_ld};
-  int rc = -5;
   const bool rnw = rn_ss != nullptr && rn_nc > 4 * kRnMax;  // the wide deferred-norm form (gemm_dec_rc sums)
   if (rnw && (rn_nc % 16 || rn_nc > 16 * kRnWide)) return -1;
-#define K8S_DEC_W(MTV, NTWV, WV, EPV, DV, RW)                                                                       \
-  hipLaunchKernelGGL((gemm_dec_kernel<MTV, NTWV, WV, EPV, DV, RW>), grid, blk, 0, s, (const bf16_t*)A,               \
-                     (const bf16_t*)Wp, partial, (bf16_t*)Y, ldy, M, N, K, kchunk, rn_ss, rn_nc, inv_d, rn_eps, dg);     \
-  rc = 0
-#define K8S_DEC(MTV, NTWV, WV, EPV, DV) K8S_DEC_W(MTV, NTWV, WV, EPV, DV, false)
-#define K8S_DEC_M(NTWV, WV, EPV, DV) \
-  switch (MT) {                      \
-    case 1: K8S_DEC(1, NTWV, WV, EPV, DV); break; \
-    case 2: K8S_DEC(2, NTWV, WV, EPV, DV); break; \
-    case 3: K8S_DEC(3, NTWV, WV, EPV, DV); break; \
-    case 4: K8S_DEC(4, NTWV, WV, EPV, DV); break; \
-    default: break;                    \
-  }
-  // the same with 5..8 m-tiles (65..128 rows): A chunks of MT * 8 KiB in the 2-slot LDS ring
-  // (128 KiB at MT = 8), MT x NTW accumulators per wave
-#define K8S_DEC_M8(NTWV, WV, EPV, DV) \
-  switch (MT) {                       \
-    case 5: K8S_DEC(5, NTWV, WV, EPV, DV); break; \
-    case 6: K8S_DEC(6, NTWV, WV, EPV, DV); break; \
-    case 7: K8S_DEC(7, NTWV, WV, EPV, DV); break; \
-    case 8: K8S_DEC(8, NTWV, WV, EPV, DV); break; \
-    default: K8S_DEC_M(NTWV, WV, EPV, DV) break;  \
-  }
-  if (rnw && MT > 4) return -5;  // the wide form follows gemm_dec_rc: <= 64 rows
-  if (rnw) {  // consumers of gemm_dec_rc's per-16-column partials: gate_up behind the row-complete o
-#define K8S_DEC_MW(NTWV, WV, EPV, DV) \
-  switch (MT) {                       \
-    case 1: K8S_DEC_W(1, NTWV, WV, EPV, DV, true); break; \
-    case 2: K8S_DEC_W(2, NTWV, WV, EPV, DV, true); break; \
-    case 3: K8S_DEC_W(3, NTWV, WV, EPV, DV, true); break; \
-    default: K8S_DEC_W(4, NTWV, WV, EPV, DV, true); break; \
-  }
-    if (epi == DEC_SWIGLU8 && ntw == 1 && waves == 7 && depth == 8) { K8S_DEC_MW(1, 7, DEC_SWIGLU8, 8) }
-    else if (epi == DEC_SWIGLU8 && ntw == 1 && waves == 7 && depth == 16) { K8S_DEC_MW(1, 7, DEC_SWIGLU8, 16) }
-#undef K8S_DEC_MW
-    if (rc) return rc;
-    return (int)hipGetLastError();
-  }
-  // configurations (ntw, waves, depth) per epilogue: exactly the ones ops.dec_config can pick - every
-  // Llama-3-8B / 70B / Mixtral projection and LM head at TP 1..8 lands on one of them
-  // (K8S_DEC_M8: also at 65..128 rows - the dense TP=1 picks of ops.dec_config(rows > 64); every
-  // other configuration returns -5 there)
-  if (epi == DEC_SLAB) {
-    if (ntw == 1 && waves == 8 && depth == 8) { K8S_DEC_M8(1, 8, DEC_SLAB, 8) }        // o, down; TP 2-8 shapes
-    else if (ntw == 1 && waves == 6 && depth == 8) { K8S_DEC_M8(1, 6, DEC_SLAB, 8) }   // qkv: 64 groups x 4 splits
-    else if (ntw == 1 && waves == 4 && depth == 8) { K8S_DEC_M8(1, 4, DEC_SLAB, 8) }   // narrow TP shards
-    else if (ntw == 1 && waves == 4 && depth == 16) { K8S_DEC_M(1, 4, DEC_SLAB, 16) }  // 70B TP=8 qkv
-  } else if (epi == DEC_SWIGLU8) {
-    if (ntw == 1 && waves == 7 && depth == 8) { K8S_DEC_M8(1, 7, DEC_SWIGLU8, 8) }     // gate_up
-    else if (ntw == 1 && waves == 7 && depth == 16) { K8S_DEC_M(1, 7, DEC_SWIGLU8, 16) }
-    else if (ntw == 1 && waves == 8 && depth == 16) { K8S_DEC_M(1, 8, DEC_SWIGLU8, 16) }  // 70B TP=1 gate_up
-  } else if (epi == DEC_BF16) {
-    if (ntw == 4 && waves == 8 && depth == 4) { K8S_DEC_M(4, 8, DEC_BF16, 4) }         // LM head, TP=1, <= 64 rows
-    // the head above 64 rows: 8 m-tiles x 4 n-tiles of accumulators do not fit a 2-waves-per-SIMD
-    // register budget, so two n-tiles per wave
-    else if (ntw == 2 && waves == 8 && depth == 8) { K8S_DEC_M8(2, 8, DEC_BF16, 8) }   // vocab shards, TP 2-8
-    else if (ntw == 3 && waves == 8 && depth == 8) { K8S_DEC_M(3, 8, DEC_BF16, 8) }
-    else if (ntw == 1 && waves == 8 && depth == 8) { K8S_DEC_M(1, 8, DEC_BF16, 8) }    // Mixtral's 32000-row head
-  }
-#undef K8S_DEC_M8
-#undef K8S_DEC_M
-#undef K8S_DEC
-#undef K8S_DEC_W
-  if (rc) return rc;
+  const DecLaunch l{dim3((ntiles + nwg_tiles - 1) / nwg_tiles, splits, experts), dim3(64 * waves), s,
+                    (const bf16_t*)A, (const bf16_t*)Wp, partial, (bf16_t*)Y, ldy, M, N, K, kchunk, rn_ss, rn_nc,
+                    inv_d, rn_eps, DecGroup{a_es, w_es, y_es, rw, rw_ld}};
+  if (!dec_dispatch(epi, ntw, waves, depth, rnw, MT, l)) return -5;
   return (int)hipGetLastError();
+}
+
+// The rows of kDecForms as six ints each (epi, ntw, waves, depth, max_mt, wide_norm), at most cap
+// rows into out; returns the row count.
+extern "C" int k8sllm_gemm_dec_forms(int* out, int cap) {
+  for (int i = 0; i < kDecNForms && i < cap; ++i) {
+    const DecForm& f = kDecForms[i];
+    const int row[6] = {f.epi, f.ntw, f.waves, f.depth, f.max_mt, f.wide_norm};
+    for (int j = 0; j < 6; ++j) out[6 * i + j] = row[j];
+  }
+  return kDecNForms;
 }
 
 
@@ -519,7 +515,7 @@ extern "C" int k8sllm_gemm_dec(const void* A, const void* Wp, float* partial, vo
 extern "C" int k8sllm_gemm_dec_rc(const void* A, const void* Wp, void* resid, const void* nw, void* xw, float* ss,
                                   int M, int N, int K, hipStream_t s) {
   if (M <= 0) return 0;
-  if (M > 64 || N % 32 || K % 32 || (K / 32) % 8) return -1;
+  if (M > kDecNarrowMaxM || N % 32 || K % 32 || (K / 32) % 8) return -1;
   const int nks = K / 32 / 8;
   const int MT = (M + 15) / 16;
   const dim3 grid(N / 16), blk(512);

@@ -94,3 +94,138 @@ def test_row_limit_per_model():
     tp2 = CausalLM(get_config("llama-tiny-d128"), device="cpu", dtype=torch.float32, seed=1,
                    pstate=ParallelState(world_size=2, tp_size=2))
     assert tp2.tp == 2 and tp2._skinny_ws is not None and tp2.dec_rows_max() == 64
+
+
+# ---------------------------------------------------------------- the table of compiled forms
+
+# ops.dec_config's picks for every projection and LM head of Llama-3-8B, Llama-3-70B and
+# Mixtral-8x7B at TP 1, 2, 4, 8, recorded before dec_config built its candidates from
+# ops.DEC_FORMS: they must not move.
+MODELS = {  # d_model, q heads, kv heads (D = 128), ffn, vocab, experts
+    "llama-3-8b": (4096, 32, 8, 14336, 128256, 0),
+    "llama-3-70b": (8192, 64, 8, 28672, 128256, 0),
+    "mixtral-8x7b": (4096, 32, 8, 14336, 32000, 8),
+}
+DENSE_PINS = {  # (N, K, epi): (pick at 64 rows, pick at 128 rows)
+    (768, 4096, 0): ((16, 1, 4, 8), (16, 1, 4, 8)),
+    (1280, 8192, 0): ((16, 1, 4, 16), (16, 1, 4, 8)),
+    (1536, 4096, 0): ((16, 1, 8, 8), (16, 1, 8, 8)),
+    (2560, 8192, 0): ((16, 1, 8, 8), (16, 1, 8, 8)),
+    (3072, 4096, 0): ((8, 1, 8, 8), (8, 1, 8, 8)),
+    (3584, 4096, 2): ((1, 1, 7, 8), (1, 1, 7, 8)),
+    (4032, 4096, 1): ((1, 1, 8, 8), (1, 2, 8, 8)),
+    (4096, 512, 0): ((2, 1, 8, 8), (2, 1, 8, 8)),
+    (4096, 1024, 0): ((4, 1, 4, 8), (4, 1, 4, 8)),
+    (4096, 1792, 0): ((1, 1, 8, 8), (1, 1, 8, 8)),
+    (4096, 2048, 0): ((8, 1, 8, 8), (8, 1, 8, 8)),
+    (4096, 3584, 0): ((2, 1, 8, 8), (2, 1, 8, 8)),
+    (4096, 4096, 0): ((8, 1, 8, 8), (8, 1, 8, 8)),
+    (4096, 7168, 0): ((4, 1, 4, 8), (4, 1, 4, 8)),
+    (4096, 14336, 0): ((8, 1, 8, 8), (8, 1, 8, 8)),
+    (5120, 8192, 0): ((8, 1, 8, 8), (8, 1, 8, 8)),
+    (6144, 4096, 0): ((4, 1, 6, 8), (4, 1, 6, 8)),
+    (7168, 4096, 2): ((1, 1, 7, 8), (1, 1, 7, 8)),
+    (7168, 8192, 2): ((1, 1, 7, 8), (1, 1, 7, 8)),
+    (8000, 4096, 1): ((1, 1, 8, 8), (1, 2, 8, 8)),
+    (8192, 1024, 0): ((4, 1, 8, 8), (4, 1, 8, 8)),
+    (8192, 2048, 0): ((4, 1, 8, 8), (4, 1, 8, 8)),
+    (8192, 3584, 0): ((2, 1, 4, 8), (2, 1, 4, 8)),
+    (8192, 4096, 0): ((4, 1, 8, 8), (4, 1, 8, 8)),
+    (8192, 7168, 0): ((4, 1, 8, 8), (4, 1, 8, 8)),
+    (8192, 8192, 0): ((4, 1, 8, 8), (4, 1, 8, 8)),
+    (8192, 14336, 0): ((4, 1, 8, 8), (4, 1, 8, 8)),
+    (8192, 28672, 0): ((4, 1, 8, 8), (4, 1, 8, 8)),
+    (10240, 8192, 0): ((4, 1, 8, 8), (4, 1, 8, 8)),
+    (14336, 4096, 2): ((1, 1, 7, 8), (1, 1, 7, 8)),
+    (14336, 8192, 2): ((1, 1, 7, 8), (1, 1, 7, 8)),
+    (16000, 4096, 1): ((1, 1, 8, 8), (1, 2, 8, 8)),
+    (16064, 4096, 1): ((1, 1, 8, 8), (1, 2, 8, 8)),
+    (16064, 8192, 1): ((1, 1, 8, 8), (1, 2, 8, 8)),
+    (28672, 4096, 2): ((1, 1, 7, 8), (1, 1, 7, 8)),
+    (28672, 8192, 2): ((1, 1, 7, 8), (1, 1, 7, 8)),
+    (32000, 4096, 1): ((1, 1, 8, 8), (1, 2, 8, 8)),
+    (32064, 4096, 1): ((1, 1, 8, 8), (1, 2, 8, 8)),
+    (32064, 8192, 1): ((1, 1, 8, 8), (1, 2, 8, 8)),
+    (57344, 8192, 2): ((1, 1, 8, 16), (1, 1, 7, 8)),
+    (64128, 4096, 1): ((1, 2, 8, 8), (1, 2, 8, 8)),
+    (64128, 8192, 1): ((1, 2, 8, 8), (1, 2, 8, 8)),
+    (128256, 4096, 1): ((1, 4, 8, 4), (1, 2, 8, 8)),
+    (128256, 8192, 1): ((1, 4, 8, 4), (1, 2, 8, 8)),
+}
+GROUPED_PINS = {  # Mixtral's expert gate_up / down, (N, K, epi, local experts): pick
+    (4096, 14336, 0, 1): (8, 1, 8, 8),
+    (4096, 14336, 0, 2): (1, 1, 8, 8),
+    (4096, 14336, 0, 4): (1, 1, 4, 16),
+    (4096, 14336, 0, 8): (1, 1, 8, 8),
+    (28672, 4096, 2, 1): (1, 1, 7, 8),
+    (28672, 4096, 2, 2): (1, 1, 8, 16),
+    (28672, 4096, 2, 4): (1, 1, 8, 16),
+    (28672, 4096, 2, 8): (1, 1, 8, 16),
+}
+
+
+def _model_shapes():
+    """(dense (N, K, epi), grouped (N, K, epi, local experts)) over MODELS at TP 1, 2, 4, 8."""
+    dense, grouped = set(), set()
+    for d, hq, hkv, ff, vocab, E in MODELS.values():
+        for tp in (1, 2, 4, 8):
+            q, kv = hq // tp, max(1, hkv // tp)
+            dense |= {((q + 2 * kv) * 128, d, 0), (d, q * 128, 0), (-(-vocab // (64 * tp)) * 64, d, 1)}
+            if E:  # experts are sharded by count
+                grouped |= {(2 * ff, d, 2, E // tp), (d, ff, 0, E // tp)}
+            else:
+                dense |= {(2 * ff // tp, d, 2), (d, ff // tp, 0)}
+    return dense, grouped
+
+
+def test_dec_config_picks_pinned():
+    dense, grouped = _model_shapes()
+    assert dense == set(DENSE_PINS) and grouped == set(GROUPED_PINS)
+    for (N, K, epi), picks in DENSE_PINS.items():
+        assert (ops.dec_config(N, K, epi, rows=64), ops.dec_config(N, K, epi, rows=128)) == picks, (N, K, epi)
+    for (N, K, epi, E), pick in GROUPED_PINS.items():
+        assert ops.dec_config(N, K, epi, experts=E) == pick, (N, K, epi, E)
+        assert ops.dec_config(N, K, epi, experts=E, rows=64) == pick
+
+
+def test_every_pick_is_a_compiled_form():
+    for (_, _, epi), cfg in ops.DEC_TABLE.items():
+        assert ops.dec_form_ok(epi, cfg, 64)
+    for (_, _, epi), cfg in ops.DEC_TABLE_M128.items():
+        assert ops.dec_form_ok(epi, cfg, 128)
+    for (_, _, epi), (c64, c128) in DENSE_PINS.items():
+        assert ops.dec_form_ok(epi, c64, 64) and ops.dec_form_ok(epi, c128, 128)
+    for (_, _, epi, E), cfg in GROUPED_PINS.items():
+        assert ops.dec_form_ok(epi, cfg, 64, grouped=E > 1)
+
+
+def test_dec_form_ok_refuses_what_is_not_compiled():
+    narrow = [f for f in ops.DEC_FORMS if f[4] == 4]
+    assert narrow and any(f[4] == 8 for f in ops.DEC_FORMS)
+    for epi, ntw, waves, depth, mt, wide in ops.DEC_FORMS:
+        cfg = (1, ntw, waves, depth)
+        assert ops.dec_form_ok(epi, cfg, 1) and ops.dec_form_ok(epi, cfg, 16 * mt)
+        assert ops.dec_form_ok(epi, cfg, 65) == (mt > 4)  # a 4 m-tile form stops at 64 rows
+        assert not ops.dec_form_ok(epi, cfg, 129)
+        assert ops.dec_form_ok(epi, cfg, 64, grouped=True) and not ops.dec_form_ok(epi, cfg, 65, grouped=True)
+        assert ops.dec_form_ok(epi, cfg, 64, wide_norm=True) == bool(wide)
+        assert not ops.dec_form_ok(epi, cfg, 65, wide_norm=True)
+    assert not ops.dec_form_ok(0, (1, 2, 8, 8), 1)  # (ntw 2, 8 waves, depth 8) is a BF16 form only
+    assert any(f[5] for f in ops.DEC_FORMS) and not all(f[5] for f in ops.DEC_FORMS)
+    assert ops.dec_row_classes() == (64, 128)
+    assert ops.DEC_MAX_M == 128 == ops.dec_row_classes()[-1]
+    assert all(any(g[:4] == f for g in ops.DEC_FORMS) for f in ops.DEC_FORMS_TABLE_ONLY)
+
+
+def test_split_k_workspace_of_the_tiny_model_unchanged():
+    """TP=1 dense llama-tiny-d128: the workspace is sized over the row classes, as it was over
+    (1, DEC_MAX_M) - 393216 floats."""
+    dense = CausalLM(get_config("llama-tiny-d128"), device="cpu", dtype=torch.float32, seed=1)
+    assert dense._skinny_ws.numel() == 393216
+
+
+def test_dec_forms_match_the_extension():
+    """ops.DEC_FORMS is the table gemm_decode.hip was compiled from, row for row (no launch)."""
+    if not ops.native_available():
+        pytest.skip("the extension is not built")
+    assert [tuple(r) for r in ops.native().gemm_dec_forms()] == list(ops.DEC_FORMS)

@@ -7,7 +7,7 @@ stream from HBM as in a decode step.  Every dec configuration is checked against
 reference of the same product first (max |err| / max |ref|).  Above 64 rows (``--ms 64,96,128``:
 the 5..8 m-tile instantiations) only gemm_decode.hip has a kernel: the row-major skinny case is
 left out, hipBLASLt stays for the LM head, and configurations without a 65..128-row instantiation
-are reported as errors and skipped.  ``pick`` lines give ops.dec_config's choice per row count.
+(ops.dec_form_ok) are reported as errors and skipped.  ``pick`` lines give ops.dec_config's choice per row count.
 
     python tools/bench_decode_gemm.py [--ms 1,32,64] [--ops qkv,o,gate_up,down,lm_head] [--rounds 3]
 """
@@ -28,7 +28,7 @@ from tools.bench_skinny import timeit  # noqa: E402
 
 D, FF, V = 4096, 14336, 128256
 SHAPES = {"qkv": (6144, D, 0), "o": (D, D, 0), "gate_up": (2 * FF, D, 2), "down": (D, FF, 0), "lm_head": (V, D, 1)}
-CFGS = {  # configurations gemm_decode.hip instantiates (other sweeps: add the instantiation first)
+CFGS = {  # the sweep list: forms of ops.DEC_FORMS (another form: add its row to the table first)
     "qkv": [(4, 1, 6, 8), (8, 1, 8, 8), (4, 1, 4, 16), (4, 1, 4, 8)],
     "o": [(4, 1, 4, 16), (4, 1, 4, 8), (8, 1, 8, 8), (16, 1, 8, 8)],
     "gate_up": [(1, 1, 7, 16), (1, 1, 7, 8), (1, 1, 8, 16)],
@@ -95,11 +95,12 @@ def main() -> None:
             else:
                 cases["hipblaslt"] = lambda i: torch.matmul(x, wrm[i % ncopy].t(), out=yb)
             for cfg in cfgs[name]:
-                try:
-                    err = (dec_out(cfg) - ref).abs().max().item() / max(scale, 1e-6)
-                except (RuntimeError, ValueError) as e:
-                    print(json.dumps({"op": name, "M": M, "cfg": cfg, "error": str(e)[:200]}), flush=True)
+                if not ops.dec_form_ok(epi, cfg, M):
+                    print(json.dumps({"op": name, "M": M, "cfg": cfg,
+                                      "error": f"gemm_dec: form {(epi,) + cfg[1:]} not compiled for {M} rows"}),
+                          flush=True)
                     continue
+                err = (dec_out(cfg) - ref).abs().max().item() / max(scale, 1e-6)
                 tag = "dec" + "_".join(map(str, cfg))
                 cases[tag] = (lambda i, cfg=cfg: ops.dec_gemm(xp, wdec[i % ncopy], epi, M, workspace=wsp,
                                                               out=act if epi == 2 else yb, cfg=cfg))

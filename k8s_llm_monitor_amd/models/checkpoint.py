@@ -170,6 +170,7 @@ def load_checkpoint(model, path: PathLike, strict: bool = True) -> list[str]:
     kv_lo, kv_hi = kv_head_range(c.n_kv_heads, D, tp, r)
     f_lo, f_hi = shard_range(c.ffn_dim, tp, r)
 
+    model.begin_load()  # out of service, derived tensors dropped, until _init_skinny below
     if c.arch == "gpt2":
         pre = "transformer." if "transformer.wte.weight" in src else ""
         model.embed = vocab_rows(pre + "wte.weight")
@@ -194,13 +195,6 @@ def load_checkpoint(model, path: PathLike, strict: bool = True) -> list[str]:
             L["w2"] = put(get(p + "mlp.c_proj.weight").t()[:, f_lo:f_hi])
             L["b2"] = put(get(p + "mlp.c_proj.bias"))
     else:
-        # the resident layout's derived tensors (decode copies; under ONE_LAYOUT the packed weights
-        # themselves) go before their replacements arrive: peak memory stays ~one copy of the model
-        # (Llama-3-70B at TP = 1 would not fit two)
-        model.lm_head_d = None
-        for L in model.layers:
-            for k in [k for k in L if k.endswith(("_p", "_d", "_pg", "_dg"))]:
-                del L[k]
         model.embed = vocab_rows("model.embed_tokens.weight")
         if c.tie_embeddings or "lm_head.weight" not in src:
             model.lm_head = model.embed
@@ -231,8 +225,7 @@ def load_checkpoint(model, path: PathLike, strict: bool = True) -> list[str]:
     unused = [k for k in unused if k not in rope_buffers]
     if strict and unused:
         raise ValueError(f"checkpoint tensors not consumed by {c.name}: {unused[:8]}{' ...' if len(unused) > 8 else ''}")
-    model._w13_il = False  # w13 was just loaded as [gate; up]
-    model._init_skinny()  # interleave w13, (re)build the decode-path views from the loaded weights
+    model._init_skinny()  # the loaded canonical weights into the resident layout, decode path rebuilt
     return unused
 
 

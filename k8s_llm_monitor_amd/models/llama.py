@@ -4,8 +4,10 @@ GPT-2 (the CPU plumbing config), with Megatron tensor parallelism.
 Nothing here exists in the reference ("no LLM, no GPU code"); the model replaces
 the remote ``callLLMAPI`` step of the doc sketch ``docs/metrics-usage-example.md:244-306``.
 
-Prefill layer (GPU, >= 1024 rows, TP=1; ``_prefill_fused_norm``), every GEMM on the hand-written
-256 x 256 MFMA tile kernel (ops/csrc/gemm_tile.hip) with its epilogue doing the elementwise work:
+Prefill layer (GPU, TP=1), every GEMM on the hand-written 256 x 256 MFMA tile kernel
+(ops/csrc/gemm_tile.hip) with its epilogue doing the elementwise work - fragment-packed weights go
+there at any row count, row-major ones from ops.TILE_MIN_M rows, and from that many rows the
+RMSNorms live in the epilogues as well (``_prefill_fused_norm``):
 
   qkv (+ RoPE of q / k, rows scaled by 1/rms) -> rope_and_cache (paged KV write) -> flash_prefill
   -> o (+ residual add, next norm's operand and sums of squares) -> gate_up (+ SwiGLU, row scale)
@@ -16,15 +18,29 @@ compute (``_prefill_overlap``).
 
 Decode layer (``_decode_layers_skinny``, 7 launches inside one hipGraph): qkv (split-K slabs) ->
 paged_decode_fused (slab reduce + RoPE + KV write + attention) -> o (slabs) -> add_norm_partial
-(residual add, deferred norm) -> gate_up + SwiGLU -> down (slabs) -> add_norm_partial.  Dense
-models whose weights fit a quarter of the device run the projections and the LM head on the
-shared-A decode GEMM over decode-only fragment-packed copies (ops/csrc/gemm_decode.hip); larger
-ones (70B at TP=1) on the row-major skinny kernel over the prefill tensors (gemm_skinny.hip).
+(residual add, deferred norm) -> gate_up + SwiGLU -> down (slabs) -> add_norm_partial.  The
+projections and the LM head run on the shared-A decode GEMM over fragment-packed weights
+(ops/csrc/gemm_decode.hip), or on the row-major skinny kernel (gemm_skinny.hip) where no packed
+form exists.
 
 Weights are stored fused and pre-sharded: ``wqkv`` [(Hq+2Hkv)/tp * D, d] (column-parallel),
-``wo`` [d, Hq/tp * D] (row-parallel), ``w13`` [2F/tp, d] (this rank's gate and up rows, stored
-interleaved per 128 rows as [64 gate | 64 up] - see _init_skinny), ``w2`` [d, F/tp].  Random init is seeded per tensor name, and every rank generates the
-full tensor then keeps its shard, so any TP degree reproduces the TP=1 model exactly.
+``wo`` [d, Hq/tp * D] (row-parallel), ``w13`` [2F/tp, d] (this rank's gate and up rows), ``w2``
+[d, F/tp].  Random init is seeded per tensor name, and every rank generates the full tensor then
+keeps its shard, so any TP degree reproduces the TP=1 model exactly.
+
+The four projections of every layer are resident in ONE of three layouts (``CausalLM._layout``):
+
+  CANONICAL    row-major [out, in], w13 as [gate; up] - the checkpoint's form (GPT-2; F no multiple of 64)
+  INTERLEAVED  row-major, w13 interleaved per 128 rows as [64 gate | 64 up] (the SwiGLU
+               epilogues' pairing); decode reads views (``*_p`` / ``*_pg``) or packed copies
+               (``*_d`` / ``*_dg``) next to it
+  PACKED       ``ONE_LAYOUT``: the fragment-packed tensor [out/16, in/32, 64, 8] is the only copy
+               (w13 paired per 16 rows as [8 gate | 8 up]); prefill's tile GEMM reads it too and
+               ``*_d`` / ``*_dg`` are the weights themselves
+
+``to_resident`` / ``to_canonical`` convert one projection between CANONICAL and another layout;
+``_init_skinny`` / ``_init_dec`` move a model forward, ``begin_load`` takes it out of service
+(LOADING) until the loader's closing ``_init_skinny``.
 """
 from __future__ import annotations
 
@@ -82,6 +98,43 @@ def _seed_for(name: str, seed: int) -> int:
     return int.from_bytes(h, "little") & 0x7FFF_FFFF_FFFF_FFFF
 
 
+# CausalLM._layout: the resident layout of the projections (module docstring); LOADING = no usable
+# weights, between begin_load() and the _init_skinny() that closes a load
+CANONICAL, INTERLEAVED, PACKED, LOADING = "canonical", "interleaved", "packed", "loading"
+PROJ = ("wqkv", "wo", "w13", "w2")
+# layer-dict keys with these suffixes are derived from the projections, not parameters: the
+# gemm_skinny views (dense, expert stack) and the decode GEMM's packed copies (dense, expert stack)
+DERIVED = ("_p", "_pg", "_d", "_dg")
+
+
+def _each(w: torch.Tensor, fn) -> torch.Tensor:
+    """``fn`` of a dense weight, or of every expert of an [E, ...] stack (row-major or packed)."""
+    return torch.stack([fn(e) for e in w]) if w.dim() in (3, 5) else fn(w)
+
+
+def to_resident(w: torch.Tensor, key: str, form: str) -> torch.Tensor:
+    """Projection ``key`` (or its expert stack) from CANONICAL to the layout ``form``."""
+    if form == PACKED:
+        return _each(w, lambda e: ops.pack_skinny(ops.interleave_gate_up8(e) if key == "w13" else e))
+    return _each(w, ops.interleave_gate_up) if key == "w13" and form == INTERLEAVED else w
+
+
+def to_canonical(w: torch.Tensor, key: str, form: str) -> torch.Tensor:
+    """Projection ``key`` (or its expert stack) resident as ``form``, back to CANONICAL."""
+    if form == PACKED:
+        return _each(w, lambda e: ops.deinterleave_gate_up8(ops.unpack_skinny(e)) if key == "w13"
+                     else ops.unpack_skinny(e))
+    return _each(w, ops.deinterleave_gate_up) if key == "w13" and form == INTERLEAVED else w
+
+
+def relayout(w: torch.Tensor, key: str, src: str, dst: str) -> torch.Tensor:
+    """``src`` -> CANONICAL -> ``dst``, expert by expert (one expert's intermediates at a time);
+    ``w`` itself where the two layouts store this projection alike."""
+    if key != "w13":  # only w13 tells INTERLEAVED from CANONICAL
+        src, dst = (f if f == PACKED else CANONICAL for f in (src, dst))
+    return w if src == dst else _each(w, lambda e: to_resident(to_canonical(e, key, src), key, dst))
+
+
 class CausalLM:
     # path selection for tests and tools (class attributes, not environment switches):
     # SKINNY_DECODE False = decode through the plain row-major path (the fp32-reference form of the
@@ -134,10 +187,11 @@ class CausalLM:
         # static-capacity all-to-alls (_moe_a2a_decode, graph-capturable)
         self.moe_decode = os.environ.get("K8SLLM_MOE_DECODE", "allreduce")
         self.layers: list[dict] = []
-        self._w13_il = False  # w13 gate/up-interleaved per 128 rows (set by _init_skinny)
-        self._packed = False  # ONE_LAYOUT: the dense projections are resident fragment-packed only
-        self._swg = True  # gemm_tile's SwiGLU pairing of w13: True = per 128 rows, 8 = per 16 (packed)
+        self._layout = CANONICAL  # what _build makes; assigned by _init_skinny / _init_dec / begin_load only
         self.skinny_layout = None
+        # the decode path's state, (re)built by _init_skinny
+        self._skinny_ws = self.lm_head_d = None
+        self._rc_o, self._dec_wide, self._attn_rope = 0, False, False
         self._build()
         self._init_skinny()
         self.cos_sin = None
@@ -146,6 +200,39 @@ class CausalLM:
                                             device=self.device)
 
     # ------------------------------------------------------------------ weights
+    # what the kernels' callers ask of the layout (read-only: _layout is the state)
+    @property
+    def _w13_il(self) -> bool:
+        """w13's gate / up rows are interleaved: per 128 rows, or per 16 inside the packed form,
+        which the per-expert fallback paths unpack to the per-128 pairing (_expert)."""
+        return self._layout in (INTERLEAVED, PACKED)
+
+    @property
+    def _packed(self) -> bool:
+        """ONE_LAYOUT: the projections are resident fragment-packed only."""
+        return self._layout == PACKED
+
+    @property
+    def _swg(self):
+        """gemm_tile's SwiGLU pairing of w13: True = per 128 rows, 8 = per 16 (packed)."""
+        return 8 if self._layout == PACKED else True
+
+    @staticmethod
+    def _drop_derived(L: dict) -> None:
+        for k in [k for k in L if k.endswith(DERIVED)]:
+            del L[k]
+
+    def begin_load(self) -> None:
+        """Before a loader replaces the weights: the derived tensors (decode copies; under
+        ONE_LAYOUT aliases of the packed weights) go first, so that peak memory stays about one
+        copy of the model (Llama-3-70B at TP=1 would not fit two), and the model is out of service
+        (LOADING: forward raises) until the loader's closing ``_init_skinny``, which takes the
+        projections it finds for CANONICAL."""
+        self.lm_head_d = None
+        for L in self.layers:
+            self._drop_derived(L)
+        self._layout = LOADING
+
     def _rand(self, name: str, shape, std: Optional[float] = None) -> torch.Tensor:
         if self._empty_init:
             return torch.empty(shape, dtype=self.dtype, device=self.device)
@@ -237,7 +324,7 @@ class CausalLM:
         """Bytes of every distinct weight tensor this rank holds (parameters, decode-layout copies
         and the LM head's packed copy; a tensor referenced under two keys counts once)."""
         seen, n = set(), 0
-        ts = [self.embed, self.lm_head, getattr(self, "lm_head_d", None), self.final_norm]
+        ts = [self.embed, self.lm_head, self.lm_head_d, self.final_norm]
         for L in self.layers:
             for v in L.values():
                 ts.extend(v if isinstance(v, tuple) else (v,))
@@ -251,7 +338,7 @@ class CausalLM:
         n = self.embed.numel() + (0 if self.cfg.tie_embeddings else self.lm_head.numel())
         for L in self.layers:
             for k, v in L.items():
-                if k.endswith(("_p", "_d", "_pg", "_dg")):  # decode-layout copies (_init_skinny) are not parameters
+                if k.endswith(DERIVED):
                     continue
                 if isinstance(v, tuple):
                     n += sum(t.numel() for t in v)
@@ -541,6 +628,8 @@ class CausalLM:
         """Returns logits [rows, vocab_size] for the rows selected by ``meta.logits_idx`` (all rows
         when None)."""
         c = self.cfg
+        if self._layout == LOADING:
+            raise RuntimeError(f"{c.name}: a checkpoint load began (begin_load) and did not finish; load again")
         if meta.dec_src is not None:
             if (self.tp == 1 and ids.is_cuda and c.arch != "gpt2" and self._use_skinny(meta, ids)
                     and c.d_model % 512 == 0):
@@ -718,7 +807,7 @@ class CausalLM:
         wo_d / w13_d / w2_d and whose head has its decode copy (every GEMM of the step is then
         ops.dec_gemm, with a 65..128-row configuration for each shape); 64 otherwise - MoE (the
         grouped launches), TP > 1 (the IPC fused tail and its staging), gemm_skinny weights."""
-        if not getattr(self, "_dec_wide", False):
+        if not self._dec_wide:
             return ops.SKINNY_MAX_M
         return max(ops.SKINNY_MAX_M, min(int(self.DEC_ROWS_MAX), ops.DEC_MAX_M))
 
@@ -741,18 +830,16 @@ class CausalLM:
                 and meta.logits_idx is None and self.SKINNY_DECODE)
 
     def _init_skinny(self) -> None:
-        """Decode-path weights.  Dense Llama (``ONE_LAYOUT``, round 6): ``_init_dec`` packs every
-        projection and the LM head into the shared-A decode GEMM's fragment-packed layout
-        (gemm_decode.hip) and that packed tensor REPLACES the row-major one - prefill's tile GEMM
-        reads it too (Llama-3-8B: 16.1 GB resident, Llama-3-70B at TP=1: 141 GB with every
-        projection on gemm_decode).  Otherwise (MoE experts, ``ONE_LAYOUT`` off) the row-major
-        tensors prefill reads serve decode through gemm_skinny_rm_kernel (ops/csrc/gemm_skinny.hip:
-        whole 128-B lines by LDS-DMA; a shape it does not take keeps fragment-packed copies), and
-        ``_init_dec`` adds decode-only packed copies where they fit (``_want_dec``).
-
-        w13 is stored gate/up-interleaved per 128 rows ([64 gate | 64 up], the SwiGLU epilogue's
-        pairing): called on canonical [gate; up] tensors (after _build or load_checkpoint), it
-        interleaves them in place and prefill's silu_mul reads the interleaved GEMM output.
+        """(Re)build everything derived from the weights: the resident layout of the projections
+        (module docstring) and the decode path's views, copies and workspace.  Whatever layout
+        the model is in, each layer first drops its derived tensors and then moves its projections,
+        through their canonical form, to the row-major layout this model serves from - INTERLEAVED
+        for Llama-family models whose F is a multiple of 64, else CANONICAL - so peak residency is
+        the model plus one layer's projections; after ``begin_load`` the loader's tensors are
+        CANONICAL.  The row-major tensors then serve decode through gemm_skinny_rm_kernel
+        (ops/csrc/gemm_skinny.hip: whole 128-B lines by LDS-DMA; a shape it does not take gets
+        fragment-packed ``*_p`` copies), and ``_init_dec`` adds the decode GEMM's packed copies or,
+        under ``ONE_LAYOUT``, makes them the only copy (PACKED).
 
         Per layer at decode (5-7 launches): qkv skinny (split-K slabs) -> paged_decode_fused (slab
         reduce, RoPE, KV write, attention) -> o skinny (slabs) -> add_norm_partial (residual add,
@@ -762,30 +849,25 @@ class CausalLM:
         RCCL, reduce_slabs + all-reduce + fused_add_rms_norm + pack_activation.
         On the CPU the same ops run as fp32 references with the kernels' split-K slicing, so the
         control flow (and TP over gloo) is covered by the CPU tests."""
-        self._skinny_ws = None
-        self.lm_head_d = None
-        self._rc_o = 0
-        self._dec_wide = False
+        c = self.cfg
+        self._skinny_ws = self.lm_head_d = None
+        self._rc_o, self._dec_wide, self._attn_rope = 0, False, False
         if self.lm_head.dim() == 4:
             self.lm_head = self.canonical_head().contiguous()
-        if self._packed:  # re-initialised over ONE_LAYOUT weights: back to the canonical row-major form
-            for L in self.layers:
-                for key in ("wqkv", "wo", "w13", "w2"):
-                    L[key] = self.canonical(L, key).contiguous()
-            self._packed, self._swg, self._w13_il = False, True, False
-        for L in self.layers:  # (re)built below from the current weights
-            for key in ("wqkv_d", "wo_d", "w13_d", "w2_d", "w13_dg", "w2_dg"):
-                L.pop(key, None)
-        c = self.cfg
         ff = c.ffn_dim if c.is_moe else self.f_local  # experts are sharded by count (EP), not by F
-        if not getattr(self, "_w13_il", False) and c.arch == "llama" and ff % 64 == 0:
-            for L in self.layers:
-                w = L["w13"]
-                L["w13"] = (torch.stack([ops.interleave_gate_up(e) for e in w]) if w.dim() == 3
-                            else ops.interleave_gate_up(w)).contiguous()
-                del w
-            self._w13_il = True
-        self._w13_il = getattr(self, "_w13_il", False)
+        old = CANONICAL if self._layout == LOADING else self._layout
+        new = INTERLEAVED if c.arch == "llama" and ff % 64 == 0 else CANONICAL
+        for L in self.layers:
+            self._drop_derived(L)
+            if old != new:
+                for key in PROJ:
+                    L[key] = relayout(L[key], key, old, new).contiguous()
+        self._layout = new
+        if c.arch != "llama" or not self.SKINNY_DECODE or new != INTERLEAVED:
+            return
+        d, nq = c.d_model, (self.hq + 2 * self.hkv) * self.D
+        if d % 64 or nq % 64 or (self.hq * self.D) % 32:
+            return
         # (In-launch split-K epilogues - RoPE + KV write in the qkv GEMM, residual add + norm
         # producer in the o / down GEMMs, reduced by each tile's last-arriving workgroup - measured
         # 5-6 us per layer-op SLOWER than the slab GEMM + separate reduce kernel on the row-major
@@ -793,51 +875,47 @@ class CausalLM:
         # decode RoPE + KV write inside the attention kernel (paged_decode_fused), reading the qkv
         # GEMM's split-K slabs directly: one launch per layer fewer
         self._attn_rope = self.D == 128
-        if c.arch != "llama" or not self.SKINNY_DECODE or not self._w13_il:
-            self._attn_rope = False
-            return
-        d, nq = c.d_model, (self.hq + 2 * self.hkv) * self.D
-        if d % 64 or nq % 64 or (self.hq * self.D) % 32:
-            self._attn_rope = False
-            return
         rowmajor = (self.hq * self.D) % 64 == 0
         self.skinny_layout = "rowmajor" if rowmajor else "packed"
-        keep = (lambda w: w) if rowmajor else ops.pack_skinny
         for L in self.layers:
-            L["wqkv_p"] = keep(L["wqkv"])
-            L["wo_p"] = keep(L["wo"])
-            if c.is_moe:  # stacked per local expert for the grouped (grid.z = expert) launches
-                L["w13_pg"] = L["w13"] if rowmajor else torch.stack([keep(w) for w in L["w13"]])
-                L["w2_pg"] = L["w2"] if rowmajor else torch.stack([keep(w) for w in L["w2"]])
-            else:
-                L["w13_p"] = keep(L["w13"])
-                L["w2_p"] = keep(L["w2"])
+            for key in PROJ:  # MoE: stacked per local expert for the grouped (grid.z = expert) launches
+                sfx = "_pg" if L[key].dim() == 3 else "_p"
+                L[key + sfx] = L[key] if rowmajor else _each(L[key], ops.pack_skinny)
         split = ops.SKINNY_SPLITS_FORCE  # 0: the launcher picks per call (kernel and batch dependent)
         self._split_qkv = self._split_o = self._split_d = split
         self._init_dec()
         self._dec_wide = self._dec_wide_ok()
-        # the ceiling of dec_rows_max(): dense TP=1 on the shared-A decode GEMM up to DEC_MAX_M rows
+        self._skinny_ws = torch.empty(self._skinny_ws_numel(), dtype=torch.float32, device=self.device)
+        self.set_decode_fusion()
+
+    def _skinny_ws_numel(self) -> int:
+        """fp32 elements of the split-K slab workspace every decode projection shares: the most
+        slabs x output columns of any projection, times the most rows a step can have.  The most
+        slabs of an [N, K] projection is taken over every row count up to the limit: gemm_skinny's
+        automatic split (row dependent up to 64 rows) and, where the layers hold decode copies,
+        gemm_dec's configuration in every row class (ops.dec_row_classes) up to the CEILING of
+        dec_rows_max() - DEC_MAX_M for a model on the wide path - not what DEC_ROWS_MAX says at
+        the moment, so flipping that switch at run time stays inside the buffer.  MoE: the expert
+        down projections write one slab group per local expert, and the EP all-to-all decode runs
+        up to SKINNY_GROUPED_MAX_M received rows per grouped launch."""
+        c, split = self.cfg, self._split_qkv
+        d, nq, no = c.d_model, (self.hq + 2 * self.hkv) * self.D, self.hq * self.D
         dec_rows = ops.DEC_MAX_M if self._dec_wide else ops.SKINNY_MAX_M
+        dec_copies = bool(self.layers) and any(k.endswith(DERIVED[2:]) for k in self.layers[0])
 
         def most(N: int, K: int) -> int:
-            # the most slabs any row count up to the limit can ask for: gemm_skinny's automatic
-            # split (row dependent up to 64 rows) and gemm_dec's configuration in every row class
-            # (ops.dec_row_classes) the model can decode in: up to the ceiling of dec_rows_max() -
-            # as the buffer's rows below, not bound to what DEC_ROWS_MAX says at the moment
-            s_rm = split if split else max(ops.skinny_auto_splits(m, N, K) for m in (1, 33, 64))
-            s_dec = 1
-            if self.layers and any(k.endswith("_d") for k in self.layers[0]):
-                for r in (r for r in ops.dec_row_classes() if r <= dec_rows):
-                    cfg = ops.dec_config(N, K, 0, rows=r)
-                    s_dec = max(s_dec, cfg[0] if cfg else 1)
-            return max(s_rm, s_dec)
+            s = split if split else max(ops.skinny_auto_splits(m, N, K) for m in (1, 33, 64))
+            for r in (r for r in ops.dec_row_classes() if dec_copies and r <= dec_rows):
+                cfg = ops.dec_config(N, K, 0, rows=r)
+                s = max(s, cfg[0] if cfg else 1)
+            return s
 
-        n = max(most(nq, d) * nq, most(d, self.hq * self.D) * d,
-                (self.e_hi - self.e_lo) * ops.skinny_nslabs(ff, 1) * d if c.is_moe else most(d, ff) * d)
-        # MoE: the EP all-to-all decode runs up to 128 received rows per grouped launch
-        rows = ops.SKINNY_GROUPED_MAX_M if c.is_moe else dec_rows
-        self._skinny_ws = torch.empty(n * rows, dtype=torch.float32, device=self.device)
-        self.set_decode_fusion()
+        if c.is_moe:
+            mlp = (self.e_hi - self.e_lo) * ops.skinny_nslabs(c.ffn_dim, 1) * d
+        else:
+            mlp = most(d, self.f_local) * d
+        n = max(most(nq, d) * nq, most(d, no) * d, mlp)
+        return n * (ops.SKINNY_GROUPED_MAX_M if c.is_moe else dec_rows)
 
     # decode buckets up to this many rows take the row-complete o projection by default: per decode
     # step 1.4 % faster at 1-2 rows, 0.9 % at 4-16, 0.4 % at 32 (profiles/r05/rc_rows_ab.jsonl;
@@ -882,39 +960,35 @@ class CausalLM:
                 # o projection row-complete: residual += o and the gate_up GEMM's normed input in
                 # the same launch (no split-K slabs, no add_norm launch)
                 rc = ops.dec_gemm_rc(op, L["wo_d"], M, residual, L["mlp_norm"], eps)
-            if rc is not None:
-                xw, rn = rc
+            if rc is None:
+                ns = self._proj_slabs(L, "wo", op, M, self._split_o)
+                if c.is_moe and self.tp > 1 and self.moe_decode == "a2a":
+                    # EP all-to-all MoE: residual += o (all-reduced), then the complete, replicated
+                    # MLP output comes back from _moe_a2a_decode
+                    xn = self._tp_tail(ws, ns, residual, L["mlp_norm"], packed=False)
+                    if xn is None:
+                        xn = ops.fused_add_rms_norm(self._row_parallel_sum(ws, ns, M, residual), residual,
+                                                    L["mlp_norm"], eps)
+                    z = self._moe_a2a_decode(L, xn)
+                    nw = self.layers[i + 1]["attn_norm"] if i + 1 < n else self.final_norm
+                    xr = ops.fused_add_rms_norm(z, residual, nw, eps)
+                    if i + 1 < n:
+                        xw, rn = ops.pack_activation(xr), None
+                        continue
+                    return self._logits(xr)
+                if c.is_moe:
+                    ns = self._moe_skinny(L, residual, ws, ns, M)
+                    if i + 1 < n:
+                        xw, rn = self._norm_tail(residual, ws, ns, self.layers[i + 1]["attn_norm"], rows=M)
+                    continue
+                rc = self._norm_tail(residual, ws, ns, L["mlp_norm"], rows=M)
+            xw, rn = rc  # the dense MLP's input, from either form of the o projection
+            if "w13_d" in L:
                 act = ops.packed_empty(M, self.f_local, self.dtype, self.device)
                 ops.dec_gemm(xw, L["w13_d"], 2, M, out=act, rownorm=rn)
-                ns = self._proj_slabs(L, "w2", act, M, self._split_d)
-                if i + 1 < n:
-                    xw, rn = self._norm_tail(residual, ws, ns, self.layers[i + 1]["attn_norm"], rows=M)
-                continue
-            ns = self._proj_slabs(L, "wo", op, M, self._split_o)
-            if c.is_moe and self.tp > 1 and self.moe_decode == "a2a":
-                # EP all-to-all MoE: residual += o (all-reduced), then the complete, replicated
-                # MLP output comes back from _moe_a2a_decode
-                xn = self._tp_tail(ws, ns, residual, L["mlp_norm"], packed=False)
-                if xn is None:
-                    xn = ops.fused_add_rms_norm(self._row_parallel_sum(ws, ns, M, residual), residual,
-                                                L["mlp_norm"], eps)
-                z = self._moe_a2a_decode(L, xn)
-                nw = self.layers[i + 1]["attn_norm"] if i + 1 < n else self.final_norm
-                xr = ops.fused_add_rms_norm(z, residual, nw, eps)
-                if i + 1 < n:
-                    xw, rn = ops.pack_activation(xr), None
-                    continue
-                return self._logits(xr)
-            if c.is_moe:
-                ns = self._moe_skinny(L, residual, ws, ns, M)
             else:
-                xw, rn = self._norm_tail(residual, ws, ns, L["mlp_norm"], rows=M)
-                if "w13_d" in L:
-                    act = ops.packed_empty(M, self.f_local, self.dtype, self.device)
-                    ops.dec_gemm(xw, L["w13_d"], 2, M, out=act, rownorm=rn)
-                else:
-                    act = ops.skinny_swiglu(xw, L["w13_p"], rows=M, packed_out=True, rownorm=rn)
-                ns = self._proj_slabs(L, "w2", act, M, self._split_d)
+                act = ops.skinny_swiglu(xw, L["w13_p"], rows=M, packed_out=True, rownorm=rn)
+            ns = self._proj_slabs(L, "w2", act, M, self._split_d)
             if i + 1 < n:
                 xw, rn = self._norm_tail(residual, ws, ns, self.layers[i + 1]["attn_norm"], rows=M)
         # final norm feeds the LM head: fragment-packed for the decode GEMM (gemm_decode.hip), or
@@ -976,15 +1050,15 @@ class CausalLM:
         return ops.skinny_slabs(x, L[key + "_p"], self._skinny_ws, split, rows=rows, rownorm=rownorm)
 
     def _want_dec(self) -> set:
-        """Which decode-only fragment-packed copies gemm_decode.hip gets (``DECODE_GEMM`` = auto |
-        dec | rm): a subset of {"head", "attn", "mlp", "experts"}.  auto, on the GPU, with W the
-        weights' bytes: the LM head always (<= 2.1 GB, Llama-3-70B); the attention projections
-        while W + their copies fit 70 % of the device; a dense MLP while 2W fits half of it
-        (Llama-3-8B: 16 GB of 288); MoE experts while 2W fits 70 % (Mixtral-8x7B at TP=1: 93 + 93
-        GB).  Llama-3-70B at TP=1 (141 GB) would get head + attention copies (+24 GB) and keep its
-        MLP on the row-major skinny kernel - but dense Llama now runs ONE_LAYOUT: every projection
-        is packed and the packed tensor is the only copy (no extra memory at any size); Mixtral's
-        experts too."""
+        """Which projections gemm_decode.hip gets in its fragment-packed form (``DECODE_GEMM`` =
+        auto | dec | rm): a subset of {"head", "attn", "mlp", "experts"}.  Every one where
+        ONE_LAYOUT applies - the packed tensors become the only copy (PACKED), at no extra memory
+        at any size - and on the CPU.  Otherwise (INTERLEAVED plus packed copies) auto weighs the
+        copies against the device, W being the weights' bytes: the LM head always (<= 2.1 GB,
+        Llama-3-70B); the attention projections while W + their copies fit 70 % of the device; a
+        dense MLP while 2W fits half of it (Llama-3-8B: 16 GB of 288; Llama-3-70B at TP=1, 141 GB,
+        would keep its MLP on the row-major skinny kernel); MoE experts while 2W fits 70 %
+        (Mixtral-8x7B at TP=1: 93 + 93 GB)."""
         mode = self.DECODE_GEMM
         if mode in ("rm", "0", "off") or self.cfg.arch != "llama":
             return set()
@@ -1027,14 +1101,7 @@ class CausalLM:
     def _expert(self, L: dict, key: str, j: int) -> torch.Tensor:
         """Local expert j's weight row-major as the per-expert fallback paths read it (w13 in the
         ``_w13_il`` pairing), whatever the resident layout (ONE_LAYOUT: packed [E, N/16, K/32, 64, 8])."""
-        w = L[key][j]
-        if w.dim() == 2:
-            return w
-        w = ops.unpack_skinny(w)
-        if key == "w13":
-            w = ops.deinterleave_gate_up8(w)
-            return ops.interleave_gate_up(w) if self._w13_il else w
-        return w
+        return relayout(L[key][j], key, self._layout, INTERLEAVED if self._packed else self._layout)
 
     def canonical_head(self) -> torch.Tensor:
         """The LM head as row-major [vocab shard, d] (ONE_LAYOUT keeps only its packed copy)."""
@@ -1045,24 +1112,14 @@ class CausalLM:
         """A dense projection as the row-major [out, in] weight of the reference / the checkpoint
         format (w13 as [gate; up]), whatever its resident layout (row-major, gate/up interleaved
         per 128 rows, or the one fragment-packed copy)."""
-        w = L[key]
-        if w.dim() == 5 or (w.dim() == 3 and self.cfg.is_moe):  # MoE experts [E, ...]
-            return torch.stack([self._canon2(e, key, e.dim() == 4) for e in w])
-        return self._canon2(w, key, w.dim() == 4)
-
-    def _canon2(self, w: torch.Tensor, key: str, packed: bool) -> torch.Tensor:
-        if packed:  # ONE_LAYOUT: fragment-packed (w13: interleaved per 16 rows)
-            w = ops.unpack_skinny(w)
-            return ops.deinterleave_gate_up8(w) if key == "w13" else w
-        return ops.deinterleave_gate_up(w) if key == "w13" and self._w13_il else w
+        return to_canonical(L[key], key, self._layout)
 
     @torch.no_grad()
     def copy_weights_from(self, src: "CausalLM") -> None:
         """Copy ``src``'s weights into this model (same config and TP shard; any device / dtype /
-        resident layout on either side - the dense projections go through their canonical form),
-        then rebuild this model's derived decode copies.  Used to give an fp32 CPU reference the
-        GPU model's exact weights."""
-        dense = ("wqkv", "wo", "w13", "w2")
+        resident layout on either side - the projections go through their canonical form), then
+        rebuild what this model derives from them.  Used to give an fp32 CPU reference the GPU
+        model's exact weights."""
         self.embed.copy_(src.embed)
         if self.lm_head is not self.embed:
             h = src.canonical_head().to(self.lm_head.device)
@@ -1073,74 +1130,61 @@ class CausalLM:
         derived = False
         for Ld, Ls in zip(self.layers, src.layers):
             for k, v in Ld.items():
-                if k.endswith(("_p", "_pg", "_d", "_dg")):
+                if k.endswith(DERIVED):
                     derived = True
-                    continue
-                if k in dense and (self._packed or src._packed):
-                    w = src.canonical(Ls, k).to(v.device)
-                    ws = list(w) if w.dim() == 3 else [w]  # MoE: per expert
-                    vs = list(v) if v.dim() in (3, 5) else [v]
-                    for vd, wd in zip(vs, ws):
-                        if vd.dim() == 4:
-                            vd.copy_(ops.pack_skinny(ops.interleave_gate_up8(wd) if k == "w13" else wd))
-                        else:
-                            vd.copy_(ops.interleave_gate_up(wd) if k == "w13" and self._w13_il else wd)
+                elif k in PROJ:
+                    v.copy_(relayout(Ls[k], k, src._layout, self._layout))
                 elif isinstance(v, tuple):
                     for a, b in zip(v, Ls[k]):
                         a.copy_(b)
                 else:
                     v.copy_(Ls[k])
-        if derived and not self._packed:  # separate decode copies (two-layout / MoE) are stale now
+        # what is derived from the copied weights is stale now: under PACKED the layers' derived keys
+        # ARE the weights and only a tied head keeps a separate packed copy (of the embedding)
+        if self._packed and self.lm_head_d is not None and self.lm_head_d is not self.lm_head:
+            self.lm_head_d.copy_(ops.pack_skinny(self.lm_head))
+        elif derived and not self._packed:
             self._init_skinny()
 
     def _init_dec(self) -> None:
         """Packed copies for the shared-A decode GEMM, per projection where gemm_decode has a
         launch configuration for its shape (ops.dec_config): wqkv_d / wo_d / w2_d
         ([N/16, K/32, 64, 8]), w13_d (gate/up interleaved per 16 rows as [8 gate | 8 up]), and the
-        LM head; MoE expert stacks w13_dg / w2_dg ([E, ...], grid.z = expert).  ONE_LAYOUT (Llama
-        and Mixtral): the packed copy REPLACES the row-major tensor layer by layer (peak memory =
-        the weights + one layer's copy) and prefill reads it too; otherwise prefill keeps reading
-        the row-major tensors."""
-        self.lm_head_d = None
-        parts = self._want_dec()
-        c = self.cfg
-        one = self._one_layout_wanted()
+        LM head; MoE expert stacks w13_dg / w2_dg ([E, ...], grid.z = expert).  Where ONE_LAYOUT
+        applies (``_one_layout_wanted``) each layer adopts its packed copies as the weights before
+        the next layer is packed (peak memory = the weights + one layer's copy) and the model ends
+        PACKED; otherwise it stays INTERLEAVED and prefill keeps reading the row-major tensors."""
+        parts, one = self._want_dec(), self._one_layout_wanted()
         for L in self.layers:
-            keys = (("wqkv", "wo") if "attn" in parts else ()) + (("w2",) if "mlp" in parts and not c.is_moe else ())
-            for key in keys:
-                N, K = L[key].shape
-                if ops.dec_available(N, K, 0):
-                    L[key + "_d"] = ops.pack_skinny(L[key])
-            if "mlp" in parts and not c.is_moe:
-                w = ops.deinterleave_gate_up(L["w13"]) if self._w13_il else L["w13"]
-                if ops.dec_available(w.shape[0], w.shape[1], 2):
-                    L["w13_d"] = ops.pack_skinny(ops.interleave_gate_up8(w))
-                del w
-            if one and not c.is_moe:
-                for key in ("wqkv", "wo", "w13", "w2"):
-                    L[key] = L[key + "_d"]
-                    L.pop(key + "_p", None)  # the skinny kernel's reference to the row-major tensor
-            elif "experts" in parts and c.is_moe:  # [E, ...] stacks for the grouped (grid.z = expert) launches
-                E, F2, d = L["w13"].shape
-                if (ops.dec_config(F2, d, 2, experts=E) is not None
-                        and ops.dec_config(d, F2 // 2, 0, experts=E) is not None):
-                    L["w13_dg"] = torch.stack([ops.pack_skinny(ops.interleave_gate_up8(
-                        ops.deinterleave_gate_up(w) if self._w13_il else w)) for w in L["w13"]])
-                    L["w2_dg"] = torch.stack([ops.pack_skinny(w) for w in L["w2"]])
-                if one:  # ONE_LAYOUT: the packed attention projections and experts are the only copies
-                    for key in ("wqkv", "wo"):
-                        L[key] = L[key + "_d"]
-                        L.pop(key + "_p", None)
-                    L["w13"], L["w2"] = L["w13_dg"], L["w2_dg"]
-                    L.pop("w13_pg", None)
-                    L.pop("w2_pg", None)
-        N, K = ops.w_out(self.lm_head), ops.w_in(self.lm_head)
+            for key in ("wqkv", "wo", "w2", "w13"):  # w13 (three passes of temporaries) last: a fixed allocation order
+                w = L[key]
+                if w.dim() == 3:  # an [E, ...] stack for the grouped launches: both projections or neither
+                    E, F2, d = L["w13"].shape
+                    sfx, ok = "_dg", "experts" in parts and all(
+                        ops.dec_config(n, k, epi, experts=E) is not None for n, k, epi in ((F2, d, 2), (d, F2 // 2, 0)))
+                else:
+                    sfx, ok = "_d", (("attn" if key in ("wqkv", "wo") else "mlp") in parts
+                                     and ops.dec_available(*w.shape, 2 if key == "w13" else 0))
+                if ok:
+                    L[key + sfx] = relayout(w, key, self._layout, PACKED)
+            if one:
+                self._adopt_packed(L)
+        N, K = self.lm_head.shape
         if "head" in parts and N % 16 == 0 and K % 32 == 0 and ops.dec_available(N, K, 1):
-            self.lm_head_d = self.lm_head if self.lm_head.dim() == 4 else ops.pack_skinny(self.lm_head)
+            self.lm_head_d = ops.pack_skinny(self.lm_head)
             if one and self.lm_head is not self.embed:
                 self.lm_head = self.lm_head_d  # ONE_LAYOUT: the packed head is the only copy too
-        self._packed = one
-        self._swg = 8 if one else True  # the prefill SwiGLU's gate/up interleave (gemm_tile swiglu)
+        if one:
+            self._layout = PACKED
+
+    @staticmethod
+    def _adopt_packed(L: dict) -> None:
+        """ONE_LAYOUT: the layer's packed decode copies become its weights; the row-major tensors
+        go with the gemm_skinny views that still referenced them."""
+        for key in PROJ:
+            L[key] = L[key + ("_dg" if key + "_dg" in L else "_d")]
+            L.pop(key + "_p", None)
+            L.pop(key + "_pg", None)
 
     def _tp_tail(self, ws, ns: int, residual: torch.Tensor, norm_w, packed: bool) -> Optional[torch.Tensor]:
         """TP>1 on the GPU with the IPC all-reduce: the row-parallel tail (slab sum, all-reduce,

@@ -459,7 +459,8 @@ def dec_available(N: int, K: int, epi: int, rows: int = 0) -> bool:
 def dec_gemm(a: torch.Tensor, wp: torch.Tensor, epi: int, rows: int, workspace: Optional[torch.Tensor] = None,
              out: Optional[torch.Tensor] = None, rownorm: Optional[tuple] = None,
              cfg: Optional[tuple] = None) -> int:
-    """gemm_dec over a fragment-packed activation ``a`` and packed weight ``wp`` (decode-only copy).
+    """gemm_dec over a fragment-packed activation ``a`` and packed weight ``wp`` (pack_skinny: under
+    ONE_LAYOUT the model's only copy, which prefill's tile GEMM reads too; else a copy for decode).
     epi 0: fp32 split-K slabs into ``workspace`` [S, M, N], returns S; epi 1: ``out`` [M, N] bf16;
     epi 2: ``out`` packed SwiGLU [ceil(M/16), F/32, 64, 8] over an interleave_gate_up8 weight.
     ``rownorm = (ss_part, eps)``: deferred RMSNorm of the A rows (add_norm_partial).  Up to

@@ -500,9 +500,10 @@ static void rownorm_args(const c10::optional<torch::Tensor>& rn_ss, int M, int K
   rn_nc = (int)rn_ss->size(1);
 }
 
-// Weight of a skinny GEMM: fragment-packed [N/16, K/32, 64, 8] (a decode-only copy), or the
-// row-major [N, K] tensor itself (gemm_skinny_rm_kernel, the single resident copy prefill's GEMMs
-// read as well).  `lead` = leading (expert) dimensions.  Returns w_rm.
+// Weight of a skinny GEMM: fragment-packed [N/16, K/32, 64, 8] (the model's one resident copy, or
+// a copy kept for decode next to the row-major tensor), or the row-major [N, K] tensor itself
+// (gemm_skinny_rm_kernel reads what prefill's GEMMs read).  `lead` = leading (expert) dimensions.
+// Returns w_rm.
 static int skinny_weight_dims(const torch::Tensor& wp, int lead, int& N, int& K, const char* what) {
   TORCH_CHECK(wp.is_contiguous(), what, ": weight must be contiguous");
   if (wp.dim() == lead + 4 && wp.size(lead + 2) == 64 && wp.size(lead + 3) == 8) {

@@ -360,7 +360,7 @@ __global__ __launch_bounds__(256, TW == 32 ? 2 : 1) void paged_decode_kernel(bf1
   }
   if constexpr (MERGE) {
     if (nvalid == 1) return;  // uniform
-    // hand-off (the grid seam's protocol, gemm_decode.hip DecNorm): every wave drains its
+    // hand-off to the last-arriving split (a ticket counter in global memory): every wave drains its
     // write-through stores, a barrier, ONE lane takes a ticket on the (sequence, kv head) counter;
     // the split holding the last ticket resets the counter for the next launch and merges every
     // split's partials with L2-coherent (sc1) loads

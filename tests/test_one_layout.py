@@ -3,6 +3,8 @@ decode GEMMs' fragment-packed layout, read by the prefill tile GEMM as well.  CP
 packed model computes what the row-major model computes (prefill and decode), its canonical
 weights round-trip bit-exactly, and checkpoint export sees row-major tensors.  (GPU numerics of
 the packed tile GEMM: test_gemm_tile_gpu.py; end to end: test_tile_real_shapes_gpu.py.)"""
+import dataclasses
+
 import pytest
 import torch
 
@@ -85,7 +87,16 @@ def test_one_layout_reinit_restores_rowmajor(monkeypatch, model):
     tensors again instead of packing the packed copy."""
     ref, one = _pair(monkeypatch, model)
     monkeypatch.setattr(CausalLM, "ONE_LAYOUT", False)
+    # going back works layer by layer: while the packed tensors are unpacked the model never holds
+    # more than what it held before plus one layer's projections (70B at TP=1 would not fit more)
+    before = one.resident_weight_bytes()
+    layer = sum(one.layers[0][key].numel() * one.layers[0][key].element_size() for key in ("wqkv", "wo", "w13", "w2"))
+    seen = []
+    unpack = ops.unpack_skinny
+    monkeypatch.setattr(ops, "unpack_skinny", lambda w: (seen.append(one.resident_weight_bytes()), unpack(w))[1])
     one._init_skinny()
+    monkeypatch.setattr(ops, "unpack_skinny", unpack)
+    assert seen and max(seen) <= before + layer, (max(seen), before, layer)
     assert not one._packed
     for L, L0 in zip(one.layers, ref.layers):
         for key in ("wqkv", "wo", "w13", "w2"):
@@ -136,6 +147,17 @@ def test_copy_weights_between_layouts(monkeypatch):
             assert torch.equal(a.canonical(La, key), ref.canonical(L0, key))
             assert torch.equal(b.canonical(Lb, key), ref.canonical(L0, key))
         assert torch.equal(La["wo_d"], L0["wo_d"])  # a's decode copies were rebuilt from the new weights
+    # a tied head under ONE_LAYOUT: lm_head is the (row-major) embedding and lm_head_d a packed copy
+    # of it, which the copy has to rebuild - the decode path reads that copy
+    tied = dataclasses.replace(cfg, tie_embeddings=True)
+    ta = CausalLM(tied, device="cpu", dtype=torch.float32, seed=1)
+    tb = CausalLM(tied, device="cpu", dtype=torch.float32, seed=2)
+    assert ta._packed and ta.lm_head is ta.embed
+    ta.copy_weights_from(tb)
+    x = torch.randn(3, cfg.d_model)
+    assert ta.lm_head is ta.embed
+    assert torch.equal(ta._logits(ops.pack_activation(x), rows=3), tb._logits(ops.pack_activation(x), rows=3))
+    assert torch.equal(ta._logits(x), tb._logits(x))
 
 
 @pytest.mark.parametrize("model", ["llama-tiny-d128", "mixtral-tiny-d128"])
@@ -158,6 +180,35 @@ def test_checkpoint_roundtrip_into_one_layout(monkeypatch, tmp_path, model):
             assert torch.equal(one.canonical(L, key), src.canonical(L0, key))
     x = torch.randn(5, cfg.d_model)
     assert (one._logits(x) - src._logits(x)).abs().max().item() < 1e-4
+
+
+def test_failed_load_takes_the_model_out_of_service(monkeypatch, tmp_path):
+    """A load that raises after the weights were replaced (here: a checkpoint tensor nobody
+    consumed, strict) leaves no half-converted model behind: forward refuses to run until a load
+    finishes, and the next load starts from the loader's canonical tensors, not from the layout the
+    model was in before."""
+    from safetensors.torch import save_file
+
+    from k8s_llm_monitor_amd.models.checkpoint import load_checkpoint, save_checkpoint
+
+    cfg = get_config("llama-tiny-d128")
+    monkeypatch.setattr(CausalLM, "ONE_LAYOUT", False)
+    src = CausalLM(cfg, device="cpu", dtype=torch.float32, seed=77)
+    save_checkpoint(src, tmp_path)
+    save_file({"model.layers.0.self_attn.stray.weight": torch.zeros(4)}, str(tmp_path / "stray.safetensors"))
+    monkeypatch.setattr(CausalLM, "ONE_LAYOUT", "force")
+    one = CausalLM(cfg, device="cpu", dtype=torch.float32, seed=11)
+    assert one._packed
+    ids = torch.tensor([3, 4, 5, 6], dtype=torch.int32)
+    meta = AttnMeta(is_prefill=True, positions=torch.arange(4, dtype=torch.int32),
+                    slot_mapping=torch.full((4,), -1, dtype=torch.int32), cu_seqlens=torch.tensor([0, 4], dtype=torch.int32))
+    with pytest.raises(ValueError, match="not consumed"):
+        load_checkpoint(one, tmp_path)
+    with pytest.raises(RuntimeError, match="load"):
+        one.forward(ids, meta, None)
+    assert load_checkpoint(one, tmp_path, strict=False) == ["model.layers.0.self_attn.stray.weight"]
+    assert one._packed and one.lm_head is one.lm_head_d
+    assert (one.forward(ids, meta, None) - src.forward(ids, meta, None)).abs().max().item() < 1e-4
 
 
 def test_moe_grouped_gemm_packed_cpu_path():

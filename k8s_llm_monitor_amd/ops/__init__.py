@@ -101,8 +101,10 @@ DEC_FORMS_TABLE_ONLY = frozenset({(DEC_SLAB, 1, 6, 8)})
 #       tail;
 #   128 the dense shared-A decode GEMM (dec_gemm: the forms of 8 m-tiles) - dense Llama-family
 #       models at TP=1 over the packed weights (CausalLM.dec_rows_max).
+# mirrors of kSkinnyMaxM / kSkinnyGroupedMaxM (csrc/gemm_skinny_plan.h); tests/test_skinny_pack.py
+# compares them with the extension's
 SKINNY_MAX_M = 64
-SKINNY_GROUPED_MAX_M = 128  # grouped (expert) launches over row-major weights: gemm_skinny.hip
+SKINNY_GROUPED_MAX_M = 128  # grouped (expert) launches over row-major weights
 DEC_NARROW_MAX_M = 64  # kDecNarrowMaxM: grouped and wide-norm launches of gemm_dec_kernel
 DEC_MAX_M = max(16 * f[4] for f in DEC_FORMS)  # dec_gemm (dense launches of gemm_dec_kernel)
 
@@ -176,18 +178,22 @@ def skinny_workspace(max_m: int, N: int, splits: int, device) -> torch.Tensor:
     return torch.empty(splits * min(max_m, SKINNY_MAX_M) * N, dtype=torch.float32, device=device)
 
 
-def skinny_kchunk(K: int, S: int) -> int:
-    """The K slice of each split (mirror of skinny_kchunk in gemm_skinny.hip): rounded up to whole
-    128-deep wave groups where that keeps S slices, else to whole 32-deep k-steps."""
+def skinny_kchunk(K: int, S: int, rm: bool = False) -> int:
+    """The K slice of each split (mirror of skinny_kchunk in csrc/gemm_skinny_plan.h, compared with
+    it by tests/test_skinny_pack.py): rounded up to whole 128-deep wave groups where that keeps S
+    slices, else to whole granules - 32-deep k-steps, or the 64-deep stages of the kernel over a
+    row-major weight (``rm``)."""
     kc = -(-K // S)
     kc128 = -(-kc // 128) * 128
     if -(-K // kc128) == S:
         return kc128
-    return -(-kc // 32) * 32
+    gran = 64 if rm else 32
+    return -(-kc // gran) * gran
 
 
-def skinny_nslabs(K: int, S: int) -> int:
-    return -(-K // skinny_kchunk(K, S))
+def skinny_nslabs(K: int, S: int, rm: bool = False) -> int:
+    """The slabs a split-K launch with ``S`` splits writes: never more than S."""
+    return -(-K // skinny_kchunk(K, S, rm))
 
 
 # CPU forms of the skinny ops: the same packed layouts, split-K slicing and roundings as the
@@ -254,9 +260,9 @@ def _rn_args(rownorm) -> tuple:
 
 
 def skinny_auto_splits(M: int, N: int, K: int) -> int:
-    """Mirror of k8sllm_gemm_skinny_auto_splits: the largest power-of-two split that keeps the grid
-    (64 columns per workgroup) within one workgroup per CU, K slices >= 512 deep and whole 256-deep
-    rounds of the waves."""
+    """Mirror of skinny_auto_splits (csrc/gemm_skinny_plan.h): the largest power-of-two split that
+    keeps the grid (64 columns per workgroup) within one workgroup per CU, K slices >= 512 deep
+    and whole 256-deep rounds of the waves."""
     tiles = max(1, N // 64)
     sp = 1
     while sp < 16 and tiles * sp * 2 <= 256 and K // (sp * 2) >= 512 and K % (sp * 2 * 256) == 0:
@@ -317,7 +323,7 @@ def skinny_slabs(a: torch.Tensor, wp: torch.Tensor, workspace: torch.Tensor, spl
         N, K = skinny_wdims(wp)
         if splits <= 0:
             splits = skinny_auto_splits(M, N, K)
-        kc, ns = skinny_kchunk(K, splits), skinny_nslabs(K, splits)
+        kc, ns = skinny_kchunk(K, splits, wp.dim() == 2), skinny_nslabs(K, splits, wp.dim() == 2)
         w = _cpu_w(wp)
         sc = _rn_scale(rownorm, M, K)
         slabs = workspace[: ns * M * N].view(ns, M, N)
@@ -354,7 +360,7 @@ def skinny_grouped_slabs(act: torch.Tensor, wp2: torch.Tensor, workspace: torch.
     E, (N, K) = wp2.shape[0], skinny_wdims(wp2[0])
     M = rows
     if not _gpu(act):
-        kc, ns = skinny_kchunk(K, splits), skinny_nslabs(K, splits)
+        kc, ns = skinny_kchunk(K, splits, wp2.dim() == 3), skinny_nslabs(K, splits, wp2.dim() == 3)
         slabs = workspace[: E * ns * M * N].view(E * ns, M, N)
         for e in range(E):
             x = unpack_skinny(act[e])[:M].float()

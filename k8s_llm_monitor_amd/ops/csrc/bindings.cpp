@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include "gemm_dec_forms.h"
+#include "gemm_skinny_plan.h"
 
 extern "C" {
 int k8sllm_rmsnorm(void* out, const void* x, void* residual, const void* w, long rows, int d, float eps,
@@ -55,7 +56,6 @@ int k8sllm_gemm_skinny(const void* A, long lda, const void* Wp, float* partial, 
                        int S, int epi, int nt_tiles, int a_packed, const float* rn_ss, int rn_nc, int rn_d,
                        float rn_eps, int waves, int experts, long w_es, long a_es, long y_es,
                        const float* row_w, int row_w_ld, int w_rm, hipStream_t s);
-int k8sllm_gemm_skinny_auto_splits(int M, int N, int K);
 int k8sllm_gemm_dec(const void* A, const void* Wp, float* partial, void* Y, long ldy, int M, int N, int K, int splits,
                     int epi, int ntw, int waves, int depth, const float* rn_ss, int rn_nc, int rn_d, float rn_eps,
                     int experts, long a_es, long w_es, long y_es, const float* rw, int rw_ld, hipStream_t s);
@@ -67,7 +67,6 @@ int k8sllm_add_norm_partial(void* out, long out_stride, void* residual, const fl
 int k8sllm_embed_norm_partial(void* out, long out_stride, void* residual, const int* ids, const int* src,
                               const int* prev, const void* emb, int vocab, const void* w, int M, int d,
                               float* ss_part, hipStream_t s);
-int k8sllm_gemm_skinny_slabs(int K, int S);
 int k8sllm_reduce_slabs(void* out, const float* partial, int S, long n, hipStream_t s);
 int k8sllm_reduce_add_rmsnorm(void* out, void* residual, const float* partial, int S, int M, const void* w, int d,
                               float eps, long out_stride, void* out2, hipStream_t s);
@@ -500,6 +499,27 @@ static void rownorm_args(const c10::optional<torch::Tensor>& rn_ss, int M, int K
   rn_nc = (int)rn_ss->size(1);
 }
 
+// The fp32 slab buffer (split-K partials) of a decode GEMM: at least n elements.
+static float* slab_buffer(const c10::optional<torch::Tensor>& partial, int64_t n, const char* what) {
+  TORCH_CHECK(partial.has_value() && partial->is_cuda() && partial->scalar_type() == torch::kFloat32 &&
+                  partial->is_contiguous() && partial->numel() >= n,
+              what, ": partial must be a contiguous fp32 GPU tensor of at least ", n, " elements");
+  return partial->data_ptr<float>();
+}
+
+// The packed SwiGLU output of a decode GEMM over N gate / up rows: [ceil(M/16), N/64, 64, 8] bf16,
+// or with experts > 0 one per expert, [E, ceil(M/16), N/64, 64, 8].
+static void* swiglu_packed_out(const c10::optional<torch::Tensor>& y, int experts, int M, int N, const char* what) {
+  TORCH_CHECK(y.has_value(), what, ": output tensor required");
+  dev_bf16(*y, "y");
+  const int g = experts > 0 ? 1 : 0;
+  TORCH_CHECK(y->dim() == 4 + g && y->is_contiguous() && (!g || y->size(0) == experts) &&
+                  y->size(g) == (M + 15) / 16 && y->size(g + 1) * 64 == N && y->size(g + 2) == 64 &&
+                  y->size(g + 3) == 8,
+              what, ": packed SwiGLU output must be ", g ? "[E, " : "[", "ceil(M/16), N/64, 64, 8]");
+  return y->data_ptr();
+}
+
 // Weight of a skinny GEMM: fragment-packed [N/16, K/32, 64, 8] (the model's one resident copy, or
 // a copy kept for decode next to the row-major tensor), or the row-major [N, K] tensor itself
 // (gemm_skinny_rm_kernel reads what prefill's GEMMs read).  `lead` = leading (expert) dimensions.
@@ -543,43 +563,32 @@ int64_t gemm_skinny(torch::Tensor a, torch::Tensor wp, c10::optional<torch::Tens
     TORCH_CHECK(a.size(1) == K, "gemm_skinny: a has ", a.size(1), " columns, weight K=", K);
     M = (int)a.size(0);
   }
-  TORCH_CHECK(M <= 64, "gemm_skinny: at most 64 rows");
-  TORCH_CHECK(N % (16 * nt_tiles) == 0, "gemm_skinny: N not divisible by the workgroup tile");
-  if (epi == 0 && splits <= 0) splits = k8sllm_gemm_skinny_auto_splits(M, N, K);
-  const int S = epi == 0 ? k8sllm_gemm_skinny_slabs(K, (int)splits) : 1;
+  const int S = epi == 0 ? (int)splits : 1;
+  const auto p = k8sllm::skinny_plan(M, N, K, S, (int)epi, (int)nt_tiles, a_packed ? 1 : 0, (int)waves, 1, w_rm);
+  TORCH_CHECK(p.err == 0, "gemm_skinny: at most ", k8sllm::kSkinnyMaxM, " rows of a shape it tiles, rc=", p.err);
   float* pp = nullptr;
   void* yp = nullptr;
   long ldy = 0;
   if (epi == 0) {
-    TORCH_CHECK(partial.has_value(), "gemm_skinny: split-K needs a partial buffer");
-    TORCH_CHECK(partial->is_cuda() && partial->scalar_type() == torch::kFloat32 && partial->is_contiguous(),
-                "partial must be contiguous fp32 on the GPU");
-    TORCH_CHECK(partial->numel() >= (int64_t)S * M * N, "partial buffer too small");
-    pp = partial->data_ptr<float>();
+    pp = slab_buffer(partial, (int64_t)p.slabs * M * N, "gemm_skinny");
+  } else if (epi == 3) {  // SwiGLU written fragment-packed [ceil(M/16), F/32, 64, 8]
+    yp = swiglu_packed_out(y, 0, M, N, "gemm_skinny");
   } else {
     TORCH_CHECK(y.has_value(), "gemm_skinny: output tensor required");
     dev_bf16(*y, "y");
-    if (epi == 3) {  // SwiGLU written fragment-packed [ceil(M/16), F/32, 64, 8]
-      TORCH_CHECK(y->dim() == 4 && y->is_contiguous() && y->size(0) * 16 >= M && y->size(1) * 64 == N &&
-                      y->size(2) == 64 && y->size(3) == 8,
-                  "gemm_skinny: packed SwiGLU output must be [ceil(M/16), F/32, 64, 8]");
-      TORCH_CHECK(y->size(0) == (M + 15) / 16, "gemm_skinny: packed output m-tiles");
-    } else {
-      const int ncol = epi == 2 ? N / 2 : N;
-      TORCH_CHECK(y->dim() == 2 && y->size(0) >= M && y->size(1) == ncol && y->stride(1) == 1,
-                  "gemm_skinny: y shape");
-      ldy = y->stride(0);
-    }
+    const int ncol = epi == 2 ? N / 2 : N;
+    TORCH_CHECK(y->dim() == 2 && y->size(0) >= M && y->size(1) == ncol && y->stride(1) == 1, "gemm_skinny: y shape");
+    ldy = y->stride(0);
     yp = y->data_ptr();
   }
   const float* rp = nullptr;
   int rn_nc = 0;
   rownorm_args(rn_ss, M, K, rp, rn_nc);
-  check(k8sllm_gemm_skinny(a.data_ptr(), a_packed ? 0 : a.stride(0), wp.data_ptr(), pp, yp, ldy, M, N, K,
-                           epi == 0 ? (int)splits : 1, (int)epi, (int)nt_tiles, a_packed ? 1 : 0, rp, rn_nc, K,
-                           (float)rn_eps, (int)waves, 1, 0, 0, 0, nullptr, 0, w_rm, cur()),
+  check(k8sllm_gemm_skinny(a.data_ptr(), a_packed ? 0 : a.stride(0), wp.data_ptr(), pp, yp, ldy, M, N, K, S, (int)epi,
+                           (int)nt_tiles, a_packed ? 1 : 0, rp, rn_nc, K, (float)rn_eps, (int)waves, 1, 0, 0, 0,
+                           nullptr, 0, w_rm, cur()),
         "gemm_skinny");
-  return S;
+  return p.slabs;
 }
 
 // Decode GEMM over a fragment-packed weight copy with A shared through LDS (gemm_decode.hip):
@@ -604,23 +613,18 @@ int64_t gemm_dec(torch::Tensor a, torch::Tensor wp, c10::optional<torch::Tensor>
   void* yp = nullptr;
   long ldy = 0;
   if (epi == 0) {
-    TORCH_CHECK(partial.has_value() && partial->is_cuda() && partial->scalar_type() == torch::kFloat32 &&
-                    partial->is_contiguous() && partial->numel() >= splits * M * N,
-                "gemm_dec: partial must be contiguous fp32 with splits x M x N elements");
-    pp = partial->data_ptr<float>();
+    pp = slab_buffer(partial, splits * M * N, "gemm_dec");
   } else {
     TORCH_CHECK(splits == 1, "gemm_dec: bf16 / SwiGLU epilogues need splits == 1");
-    TORCH_CHECK(y.has_value(), "gemm_dec: output tensor required");
-    dev_bf16(*y, "y");
     if (epi == 2) {
-      TORCH_CHECK(y->dim() == 4 && y->is_contiguous() && y->size(0) == (M + 15) / 16 && y->size(1) * 64 == N &&
-                      y->size(2) == 64 && y->size(3) == 8,
-                  "gemm_dec: packed SwiGLU output must be [ceil(M/16), N/64, 64, 8]");
+      yp = swiglu_packed_out(y, 0, M, N, "gemm_dec");
     } else {
+      TORCH_CHECK(y.has_value(), "gemm_dec: output tensor required");
+      dev_bf16(*y, "y");
       TORCH_CHECK(y->dim() == 2 && y->size(0) >= M && y->size(1) == N && y->stride(1) == 1, "gemm_dec: y [M, N]");
       ldy = y->stride(0);
+      yp = y->data_ptr();
     }
-    yp = y->data_ptr();
   }
   const float* rp = nullptr;
   int rn_nc = 0;
@@ -660,10 +664,7 @@ int64_t gemm_dec_grouped(torch::Tensor a, torch::Tensor wp, c10::optional<torch:
   const float* rw = nullptr;
   int rw_ld = 0;
   if (epi == 0) {
-    TORCH_CHECK(partial.has_value() && partial->is_cuda() && partial->scalar_type() == torch::kFloat32 &&
-                    partial->is_contiguous() && partial->numel() >= (long)E * splits * M * N,
-                "gemm_dec_grouped: partial must hold E x splits x M x N fp32");
-    pp = partial->data_ptr<float>();
+    pp = slab_buffer(partial, (int64_t)E * splits * M * N, "gemm_dec_grouped");
     if (row_w.has_value()) {
       TORCH_CHECK(row_w->is_cuda() && row_w->scalar_type() == torch::kFloat32 && row_w->dim() == 2 &&
                       row_w->size(0) >= M && row_w->size(1) == E && row_w->stride(1) == 1,
@@ -672,11 +673,8 @@ int64_t gemm_dec_grouped(torch::Tensor a, torch::Tensor wp, c10::optional<torch:
       rw_ld = (int)row_w->stride(0);
     }
   } else {
-    TORCH_CHECK(epi == 2 && splits == 1 && y.has_value(), "gemm_dec_grouped: SwiGLU output needs splits 1 and y");
-    dev_bf16(*y, "y");
-    TORCH_CHECK(y->dim() == 5 && y->is_contiguous() && y->size(0) == E && y->size(1) == MT && y->size(2) * 64 == N &&
-                    y->size(3) == 64 && y->size(4) == 8, "gemm_dec_grouped: y [E, ceil(M/16), N/64, 64, 8]");
-    yp = y->data_ptr();
+    TORCH_CHECK(epi == 2 && splits == 1, "gemm_dec_grouped: only the SwiGLU output, with splits 1");
+    yp = swiglu_packed_out(y, E, M, N, "gemm_dec_grouped");
     y_es = y->stride(0);
   }
   const int rc = k8sllm_gemm_dec(a.data_ptr(), wp.data_ptr(), pp, yp, 0, M, N, K, (int)splits, (int)epi, (int)ntw,
@@ -696,6 +694,24 @@ std::vector<std::tuple<int64_t, int64_t, int64_t, int64_t, int64_t, int64_t>> ge
   for (int i = 0; i < n; ++i)
     rows.emplace_back(v[6 * i], v[6 * i + 1], v[6 * i + 2], v[6 * i + 3], v[6 * i + 4], v[6 * i + 5]);
   return rows;
+}
+
+// The compiled forms of gemm_skinny (kSkinnyForms): (family, epi, nt, waves, a_packed, min m-tiles,
+// max m-tiles) per row.
+std::vector<std::vector<int64_t>> gemm_skinny_forms() {
+  std::vector<std::vector<int64_t>> rows;
+  for (const k8sllm::SkinnyForm& f : k8sllm::kSkinnyForms)
+    rows.push_back({f.family, f.epi, f.nt, f.waves, f.a_packed, f.min_mt, f.max_mt});
+  return rows;
+}
+
+// skinny_plan (gemm_skinny_plan.h), what a launch with these arguments does: (err, family, m-tiles,
+// nt, waves, kchunk, slabs, grid x).  No launch.
+std::vector<int64_t> gemm_skinny_plan(int64_t M, int64_t N, int64_t K, int64_t S, int64_t epi, int64_t nt_tiles,
+                                      int64_t a_packed, int64_t waves, int64_t experts, int64_t w_rm) {
+  const k8sllm::SkinnyPlan p = k8sllm::skinny_plan((int)M, (int)N, (int)K, (int)S, (int)epi, (int)nt_tiles,
+                                                   (int)a_packed, (int)waves, (int)experts, (int)w_rm);
+  return {p.err, p.family, p.mt, p.nt, p.waves, p.kchunk, p.slabs, p.gx};
 }
 
 // Row-complete decode GEMM + residual add + deferred-norm operands (gemm_decode.hip
@@ -737,9 +753,11 @@ int64_t gemm_skinny_grouped(torch::Tensor a, torch::Tensor wp, c10::optional<tor
   TORCH_CHECK(epi == 0 || epi == 3, "gemm_skinny_grouped: epi must be 0 (slabs) or 3 (packed SwiGLU)");
   const int E = (int)wp.size(0), M = (int)rows;
   const long w_es = wp[0].numel();
-  TORCH_CHECK(M > 0 && (M <= 64 || (M <= 128 && w_rm && E > 1)),
-              "gemm_skinny_grouped: 1..64 rows (1..128 over row-major expert weights)");
-  const int MT = (M + 15) / 16;
+  const int S = epi == 0 && splits > 0 ? (int)splits : 1;
+  const auto p = k8sllm::skinny_plan(M, N, K, S, (int)epi, 4, 1, (int)waves, E, w_rm);
+  TORCH_CHECK(M > 0 && p.err == 0, "gemm_skinny_grouped: 1..", k8sllm::kSkinnyMaxM, " rows (1..",
+              k8sllm::kSkinnyGroupedMaxM, " over row-major weights of 2+ experts) of a shape it tiles, rc=", p.err);
+  const int MT = p.mt;
   long a_es = 0;
   TORCH_CHECK(a.is_contiguous() && a.size(-1) == 8 && a.size(-2) == 64 && a.size(-3) * 32 == K,
               "gemm_skinny_grouped: a must be fragment-packed with K = ", K);
@@ -753,14 +771,8 @@ int64_t gemm_skinny_grouped(torch::Tensor a, torch::Tensor wp, c10::optional<tor
   void* yp = nullptr;
   long y_es = 0;
   const float* rw = nullptr;
-  int S = 1;
   if (epi == 0) {
-    if (splits <= 0) splits = 1;
-    S = k8sllm_gemm_skinny_slabs(K, (int)splits);
-    TORCH_CHECK(partial.has_value() && partial->is_cuda() && partial->scalar_type() == torch::kFloat32 &&
-                    partial->is_contiguous() && partial->numel() >= (int64_t)E * S * M * N,
-                "gemm_skinny_grouped: partial must be fp32 with room for E * S * M * N");
-    pp = partial->data_ptr<float>();
+    pp = slab_buffer(partial, (int64_t)E * p.slabs * M * N, "gemm_skinny_grouped");
     if (row_w.has_value()) {
       TORCH_CHECK(row_w->is_cuda() && row_w->scalar_type() == torch::kFloat32 && row_w->is_contiguous() &&
                       row_w->dim() == 2 && row_w->size(0) >= M && row_w->size(1) == E,
@@ -768,19 +780,13 @@ int64_t gemm_skinny_grouped(torch::Tensor a, torch::Tensor wp, c10::optional<tor
       rw = row_w->data_ptr<float>();
     }
   } else {
-    TORCH_CHECK(y.has_value(), "gemm_skinny_grouped: output required");
-    dev_bf16(*y, "y");
-    TORCH_CHECK(y->dim() == 5 && y->is_contiguous() && y->size(0) == E && y->size(1) == MT &&
-                    y->size(2) * 64 == N && y->size(3) == 64 && y->size(4) == 8,
-                "gemm_skinny_grouped: y must be [E, MT, N/64, 64, 8]");
-    yp = y->data_ptr();
-    y_es = (*y)[0].numel();
+    yp = swiglu_packed_out(y, E, M, N, "gemm_skinny_grouped");
+    y_es = y->stride(0);
   }
-  check(k8sllm_gemm_skinny(a.data_ptr(), 0, wp.data_ptr(), pp, yp, 0, M, N, K, epi == 0 ? (int)splits : 1,
-                           (int)epi, 4, 1, nullptr, 0, K, 0.f, (int)waves, E, w_es, a_es, y_es, rw, E, w_rm,
-                           cur()),
+  check(k8sllm_gemm_skinny(a.data_ptr(), 0, wp.data_ptr(), pp, yp, 0, M, N, K, S, (int)epi, 4, 1, nullptr, 0, K, 0.f,
+                           (int)waves, E, w_es, a_es, y_es, rw, E, w_rm, cur()),
         "gemm_skinny_grouped");
-  return epi == 0 ? (int64_t)E * S : 1;
+  return epi == 0 ? (int64_t)E * p.slabs : 1;
 }
 
 // residual += sum of S slabs; out = residual * w (row-major or fragment-packed); ss_part[m][c] =
@@ -984,6 +990,10 @@ PYBIND11_MODULE(_k8sllm_ops, m) {
   m.def("gather_rows", &gather_rows);
   m.def("gemm_skinny", &gemm_skinny);
   m.def("gemm_skinny_grouped", &gemm_skinny_grouped);
+  m.def("gemm_skinny_forms", &gemm_skinny_forms);
+  m.def("gemm_skinny_plan", &gemm_skinny_plan);
+  m.attr("SKINNY_MAX_M") = k8sllm::kSkinnyMaxM;
+  m.attr("SKINNY_GROUPED_MAX_M") = k8sllm::kSkinnyGroupedMaxM;
   m.def("gemm_dec", &gemm_dec);
   m.def("gemm_dec_grouped", &gemm_dec_grouped);
   m.def("gemm_dec_forms", &gemm_dec_forms);

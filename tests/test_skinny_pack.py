@@ -76,6 +76,60 @@ def test_skinny_auto_splits_whole_rounds(monkeypatch):
         assert s == 1 or ((N // 64) * s <= 256 and K % (s * 256) == 0)
 
 
+def test_cpu_slabs_slice_a_rowmajor_weight_as_the_kernel_does():
+    """K = 256 in 3 splits over a row-major weight: the kernel's 64-deep stages make that two
+    128-deep slices, so two slabs (three 96-deep ones over the fragment-packed weight)."""
+    torch.manual_seed(0)
+    M, N, K, S = 5, 128, 256, 3
+    a, w = torch.randn(M, K), torch.randn(N, K)
+    assert (ops.skinny_kchunk(K, S, rm=True), ops.skinny_nslabs(K, S, rm=True)) == (128, 2)
+    assert (ops.skinny_kchunk(K, S), ops.skinny_nslabs(K, S)) == (96, 3)
+    ws = torch.full((S * M * N,), 7.0)
+    assert ops.skinny_slabs(ops.pack_activation(a), w, ws, S, rows=M) == 2
+    torch.testing.assert_close(ws[: 2 * M * N].view(2, M, N).sum(0), a @ w.t(), atol=1e-4, rtol=1e-5)
+    assert torch.all(ws[2 * M * N:] == 7.0)
+    ws.fill_(7.0)
+    assert ops.skinny_slabs(ops.pack_activation(a), ops.pack_skinny(w), ws, S, rows=M) == 3
+    torch.testing.assert_close(ws.view(3, M, N).sum(0), a @ w.t(), atol=1e-4, rtol=1e-5)
+    wd = torch.rand(M, 2)
+    ws2 = torch.full((2 * S * M * N,), 7.0)
+    act = torch.stack([ops.pack_activation(a), ops.pack_activation(2 * a)])
+    assert ops.skinny_grouped_slabs(act, torch.stack([w, w]), ws2, M, wd, splits=S) == 4
+    want = (a @ w.t()) * wd[:, :1] + (2 * a @ w.t()) * wd[:, 1:]
+    torch.testing.assert_close(ws2[: 4 * M * N].view(4, M, N).sum(0), want, atol=1e-4, rtol=1e-5)
+    assert torch.all(ws2[4 * M * N:] == 7.0)
+
+
+def test_skinny_mirrors_match_the_extension():
+    """ops.skinny_kchunk / skinny_nslabs / skinny_auto_splits, the row limits and the form count
+    against csrc/gemm_skinny_plan.h as the extension was compiled from it (no launch)."""
+    if not ops.native_available():
+        pytest.skip("the extension is not built")
+    nat = ops.native()
+    assert (nat.SKINNY_MAX_M, nat.SKINNY_GROUPED_MAX_M) == (ops.SKINNY_MAX_M, ops.SKINNY_GROUPED_MAX_M)
+    M, N = 64, 64
+    for rm in (0, 1):
+        for K in range(64, 4096 + 1, 64):
+            for S in range(0, 17):
+                err, fam, mt, nt, waves, kc, slabs, gx = nat.gemm_skinny_plan(M, N, K, S, 0, 4, 1, 0, 1, rm)
+                s = S if S > 0 else ops.skinny_auto_splits(M, N, K)
+                assert (err, fam, mt) == (0, rm, 4)
+                assert (kc, slabs) == (ops.skinny_kchunk(K, s, bool(rm)), ops.skinny_nslabs(K, s, bool(rm))), (K, S, rm)
+                assert slabs <= s
+    # the automatic split alone, over the projection shapes of test_skinny_auto_splits_whole_rounds:
+    # its power-of-two slices are whole 256-deep rounds, so the plan's slab count is the split
+    for N, K in ((6144, 4096), (4096, 4096), (4096, 14336), (1280, 8192), (256, 128), (28672, 4096)):
+        for rm in (0, 1):
+            assert nat.gemm_skinny_plan(64, N, K, 0, 0, 4, 1, 0, 1, rm)[6] == ops.skinny_auto_splits(64, N, K)
+    # rows above the limits are the plan's to refuse
+    assert nat.gemm_skinny_plan(ops.SKINNY_MAX_M + 1, 64, 256, 1, 0, 4, 1, 0, 1, 1)[0] < 0
+    assert nat.gemm_skinny_plan(ops.SKINNY_GROUPED_MAX_M, 64, 256, 1, 0, 4, 1, 0, 2, 1)[0] == 0
+    assert nat.gemm_skinny_plan(ops.SKINNY_GROUPED_MAX_M + 1, 64, 256, 1, 0, 4, 1, 0, 2, 1)[0] < 0
+    forms = [tuple(f) for f in nat.gemm_skinny_forms()]
+    assert len(set(forms)) == len(forms)
+    assert sum(f[6] - f[5] + 1 for f in forms) == 140  # the kernels gemm_skinny.hip instantiates
+
+
 @pytest.mark.parametrize("model", ["llama-tiny-d128", "mixtral-tiny-d128"])
 def test_decode_skinny_path_matches_generic_cpu(monkeypatch, model):
     """The decode control flow over packed weights (split-K slabs reduced in rope / the norm tail;

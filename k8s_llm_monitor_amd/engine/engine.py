@@ -69,6 +69,11 @@ class EngineConfig:
     # a Hugging Face model directory (config.json, *.safetensors, optional tokenizer.json): real
     # weights instead of the seeded random init (models/checkpoint.py); None = random init
     weights: Optional[str] = None
+    # "bf16" | "fp8": the encoding the decode GEMMs stream the dense projections and the LM head from
+    # (CausalLM.DEC_WEIGHTS).  fp8 quantises each weight row to e4m3 with a power-of-two scale; the
+    # model's bf16 weights become the dequantised values and the fp8 copy is kept beside them
+    # (resident weights grow by half; prefill still reads bf16; only decode streams fewer bytes)
+    decode_weights: str = "bf16"
 
 
 class _View:
@@ -102,7 +107,7 @@ class LLMEngine:
         self.model_cfg = mc
         t0 = time.perf_counter()
         self.model = CausalLM(mc, device=self.device, dtype=getattr(torch, cfg.dtype), seed=cfg.seed, pstate=self.ps,
-                              init="empty" if cfg.weights else "random")
+                              init="empty" if cfg.weights else "random", dec_weights=cfg.decode_weights)
         if cfg.weights:
             load_checkpoint(self.model, cfg.weights)
         self.runner = ModelRunner(self.model, RunnerConfig(
@@ -455,7 +460,10 @@ class LLMEngine:
         d = dict(self.counters)
         d.update(self.sched.stats())
         d.update({"model": self.model_cfg.name, "tp_size": self.ps.tp_size, "device": str(self.device),
-                  "graph_buckets": sorted(self.runner.graphs), "max_num_seqs": self.cfg.max_num_seqs})
+                  "graph_buckets": sorted(self.runner.graphs), "max_num_seqs": self.cfg.max_num_seqs,
+                  "decode_weights": self.cfg.decode_weights,
+                  "resident_weight_bytes": self.model.resident_weight_bytes(),
+                  "decode_encodings": self.model.decode_encodings()})
         return d
 
     # ----------------------------------------------------------------- tensor parallel

@@ -45,6 +45,7 @@ The four projections of every layer are resident in ONE of three layouts (``Caus
 from __future__ import annotations
 
 import hashlib
+import logging
 import math
 import os
 from dataclasses import dataclass
@@ -60,6 +61,7 @@ from ..parallel.comm import (kv_head_range, shard_range, tp_all_gather_last, tp_
 from ..parallel.state import ParallelState, get_state
 from .config import ModelConfig
 
+log = logging.getLogger(__name__)
 
 @dataclass
 class AttnMeta:
@@ -103,8 +105,10 @@ def _seed_for(name: str, seed: int) -> int:
 CANONICAL, INTERLEAVED, PACKED, LOADING = "canonical", "interleaved", "packed", "loading"
 PROJ = ("wqkv", "wo", "w13", "w2")
 # layer-dict keys with these suffixes are derived from the projections, not parameters: the
-# gemm_skinny views (dense, expert stack) and the decode GEMM's packed copies (dense, expert stack)
-DERIVED = ("_p", "_pg", "_d", "_dg")
+# gemm_skinny views (dense, expert stack), the decode GEMM's packed copies (dense, expert stack)
+# and, with DEC_WEIGHTS = "fp8", the fp8 encoding of a dense projection (packed e4m3 codes, per-row scales)
+DERIVED = ("_p", "_pg", "_d", "_dg", "_q", "_qs")
+DEC_COPIES = ("_d", "_dg")  # the decode GEMM's packed bf16 copies among them
 
 
 def _each(w: torch.Tensor, fn) -> torch.Tensor:
@@ -146,14 +150,29 @@ class CausalLM:
     # row-major form and within +-1.4 % of its speed: profiles/r06/gemm_packed_w_*.jsonl); the
     # row-major tensors are dropped.  "force": also on the CPU (tests).
     ONE_LAYOUT = True
+    # The encoding the decode GEMMs stream the dense projections and the LM head from: "bf16", or
+    # "fp8" - per weight row e4m3 codes times a power-of-two scale (ops.quantize_rows_fp8).  The
+    # model's bf16 weights then ARE the dequantised values (one model, two encodings: prefill, the
+    # row-complete o projection, the TP tails, canonical() / save_checkpoint and the fp32 reference
+    # read them unchanged) and the fp8 copy sits beside them (resident weights grow by half; only
+    # decode gets faster).  Per launch the fp8 encoding is used where gemm_decode.hip has an fp8
+    # form for the shape and row count (ops.dec_config(f8=True)), the bf16 copy otherwise.
+    DEC_WEIGHTS = "bf16"
 
     def __init__(self, cfg: ModelConfig, device: torch.device | str = "cpu", dtype=torch.bfloat16, seed: int = 0,
-                 pstate: Optional[ParallelState] = None, init_std: float = 0.02, init: str = "random"):
+                 pstate: Optional[ParallelState] = None, init_std: float = 0.02, init: str = "random",
+                 dec_weights: Optional[str] = None):
         """``init``: "random" (seeded per tensor name) or "empty" (uninitialised storage, for
-        models about to be filled by models/checkpoint.load_checkpoint)."""
+        models about to be filled by models/checkpoint.load_checkpoint).  ``dec_weights``: this
+        model's DEC_WEIGHTS ("bf16" | "fp8"; None = the class constant)."""
         if init not in ("random", "empty"):
             raise ValueError(f"init must be 'random' or 'empty', not {init!r}")
+        if dec_weights is not None:
+            self.DEC_WEIGHTS = dec_weights
+        if self.DEC_WEIGHTS not in ("bf16", "fp8"):
+            raise ValueError(f"decode weights must be 'bf16' or 'fp8', not {self.DEC_WEIGHTS!r}")
         self._empty_init = init == "empty"
+        self._f8_defer = self._empty_init  # uninitialised storage is not quantised: the load's closing _init_skinny does
         self.cfg = cfg
         self.device = torch.device(device)
         self.dtype = dtype
@@ -190,7 +209,7 @@ class CausalLM:
         self._layout = CANONICAL  # what _build makes; assigned by _init_skinny / _init_dec / begin_load only
         self.skinny_layout = None
         # the decode path's state, (re)built by _init_skinny
-        self._skinny_ws = self.lm_head_d = None
+        self._skinny_ws = self.lm_head_d = self.lm_head_q = self.lm_head_qs = None
         self._rc_o, self._dec_wide, self._attn_rope = 0, False, False
         self._build()
         self._init_skinny()
@@ -228,7 +247,8 @@ class CausalLM:
         copy of the model (Llama-3-70B at TP=1 would not fit two), and the model is out of service
         (LOADING: forward raises) until the loader's closing ``_init_skinny``, which takes the
         projections it finds for CANONICAL."""
-        self.lm_head_d = None
+        self.lm_head_d = self.lm_head_q = self.lm_head_qs = None
+        self._f8_defer = False
         for L in self.layers:
             self._drop_derived(L)
         self._layout = LOADING
@@ -321,10 +341,11 @@ class CausalLM:
             self.layers.append(L)
 
     def resident_weight_bytes(self) -> int:
-        """Bytes of every distinct weight tensor this rank holds (parameters, decode-layout copies
-        and the LM head's packed copy; a tensor referenced under two keys counts once)."""
+        """Bytes of every distinct weight tensor this rank holds (parameters, decode-layout copies,
+        the LM head's packed copy and the fp8 encodings with their scales; a tensor referenced
+        under two keys counts once)."""
         seen, n = set(), 0
-        ts = [self.embed, self.lm_head, self.lm_head_d, self.final_norm]
+        ts = [self.embed, self.lm_head, self.lm_head_d, self.lm_head_q, self.lm_head_qs, self.final_norm]
         for L in self.layers:
             for v in L.values():
                 ts.extend(v if isinstance(v, tuple) else (v,))
@@ -778,10 +799,10 @@ class CausalLM:
         hd = self.lm_head_d
         if x.dim() == 4:  # packed (decode): the decode copy exists by construction
             logits = torch.empty(rows, hd.shape[0] * 16, dtype=self.dtype, device=self.device)
-            ops.dec_gemm(x, hd, 1, rows, out=logits)
+            self._dec(x, hd, self.lm_head_q, self.lm_head_qs, 1, rows, out=logits)
         elif hd is not None and x.is_cuda and x.shape[0] <= self.dec_rows_max():
             logits = torch.empty(x.shape[0], hd.shape[0] * 16, dtype=self.dtype, device=self.device)
-            ops.dec_gemm(ops.pack_activation(x), hd, 1, x.shape[0], out=logits)
+            self._dec(ops.pack_activation(x), hd, self.lm_head_q, self.lm_head_qs, 1, x.shape[0], out=logits)
         elif self.lm_head.dim() == 4:  # ONE_LAYOUT: the packed head is the only copy - dec_rows_max()-row chunks
             M, mc = x.shape[0], self.dec_rows_max()
             logits = torch.empty(M, hd.shape[0] * 16, dtype=self.dtype, device=self.device)
@@ -850,7 +871,7 @@ class CausalLM:
         On the CPU the same ops run as fp32 references with the kernels' split-K slicing, so the
         control flow (and TP over gloo) is covered by the CPU tests."""
         c = self.cfg
-        self._skinny_ws = self.lm_head_d = None
+        self._skinny_ws = self.lm_head_d = self.lm_head_q = self.lm_head_qs = None
         self._rc_o, self._dec_wide, self._attn_rope = 0, False, False
         if self.lm_head.dim() == 4:
             self.lm_head = self.canonical_head().contiguous()
@@ -901,13 +922,15 @@ class CausalLM:
         c, split = self.cfg, self._split_qkv
         d, nq, no = c.d_model, (self.hq + 2 * self.hkv) * self.D, self.hq * self.D
         dec_rows = ops.DEC_MAX_M if self._dec_wide else ops.SKINNY_MAX_M
-        dec_copies = bool(self.layers) and any(k.endswith(DERIVED[2:]) for k in self.layers[0])
+        dec_copies = bool(self.layers) and any(k.endswith(DEC_COPIES) for k in self.layers[0])
+        f8 = bool(self.layers) and any(k.endswith("_q") for k in self.layers[0])
 
         def most(N: int, K: int) -> int:
             s = split if split else max(ops.skinny_auto_splits(m, N, K) for m in (1, 33, 64))
             for r in (r for r in ops.dec_row_classes() if dec_copies and r <= dec_rows):
-                cfg = ops.dec_config(N, K, 0, rows=r)
-                s = max(s, cfg[0] if cfg else 1)
+                for enc in ((False, True) if f8 else (False,)):  # the fp8 encoding may pick another split
+                    cfg = ops.dec_config(N, K, 0, rows=r, f8=enc)
+                    s = max(s, cfg[0] if cfg else 1)
             return s
 
         if c.is_moe:
@@ -938,7 +961,11 @@ class CausalLM:
         c = self.cfg
         ok = (self.tp == 1 and not c.is_moe and bool(self.layers) and "w13_d" in self.layers[0]
               and c.d_model % 512 == 0)
-        rows = self.RC_O_MAX_ROWS if rc is None else (1 << 30 if rc is True else int(rc))
+        # fp8 decode weights: the row-complete kernel reads bf16 and leaves the gate_up GEMM the wide
+        # deferred norm, which has no fp8 form - o and gate_up (3/4 of a layer's bytes with it)
+        # would stay on the bf16 encoding, so the default there is off
+        dflt = 0 if ok and "w13_q" in self.layers[0] else self.RC_O_MAX_ROWS
+        rows = dflt if rc is None else (1 << 30 if rc is True else int(rc))
         self._rc_o = rows if ok and "wo_d" in self.layers[0] else 0
 
     def _decode_layers_skinny(self, x: torch.Tensor, residual: torch.Tensor, meta: AttnMeta,
@@ -985,7 +1012,7 @@ class CausalLM:
             xw, rn = rc  # the dense MLP's input, from either form of the o projection
             if "w13_d" in L:
                 act = ops.packed_empty(M, self.f_local, self.dtype, self.device)
-                ops.dec_gemm(xw, L["w13_d"], 2, M, out=act, rownorm=rn)
+                self._dec(xw, L["w13_d"], L.get("w13_q"), L.get("w13_qs"), 2, M, out=act, rownorm=rn)
             else:
                 act = ops.skinny_swiglu(xw, L["w13_p"], rows=M, packed_out=True, rownorm=rn)
             ns = self._proj_slabs(L, "w2", act, M, self._split_d)
@@ -1046,8 +1073,30 @@ class CausalLM:
         ``L[key + "_p"]``.  Returns the slab count."""
         wd = L.get(key + "_d")
         if wd is not None:
-            return ops.dec_gemm(x, wd, 0, rows, workspace=self._skinny_ws, rownorm=rownorm)
+            return self._dec(x, wd, L.get(key + "_q"), L.get(key + "_qs"), 0, rows, workspace=self._skinny_ws,
+                             rownorm=rownorm)
         return ops.skinny_slabs(x, L[key + "_p"], self._skinny_ws, split, rows=rows, rownorm=rownorm)
+
+    @staticmethod
+    def _dec(x: torch.Tensor, wd: torch.Tensor, wq: Optional[torch.Tensor], wqs: Optional[torch.Tensor], epi: int,
+             rows: int, rownorm: Optional[tuple] = None, **kw) -> int:
+        """ops.dec_gemm over the fp8 encoding (``wq``, ``wqs``) of a weight where one exists and
+        gemm_decode.hip has an fp8 form for the shape at ``rows`` rows with this deferred norm (the
+        wide form of the row-complete o projection's sums reads bf16), else over the bf16 copy
+        ``wd`` - the same values either way, so the choice is one of speed only."""
+        if wq is not None and not (rownorm is not None and rownorm[0].shape[1] > 16):
+            N, K = ops.skinny_wdims(wq)
+            if ops.dec_config(N, K, epi, rows=rows, f8=True) is not None:
+                return ops.dec_gemm(x, wq, epi, rows, rownorm=rownorm, wscale=wqs, **kw)
+        return ops.dec_gemm(x, wd, epi, rows, rownorm=rownorm, **kw)
+
+    def decode_encodings(self) -> dict:
+        """Which encoding each decode projection streams from ("fp8" | "bf16" per key of wqkv, wo,
+        w13, w2, head) where the decode GEMM has both; layer 0 speaks for all."""
+        L = self.layers[0] if self.layers else {}
+        enc = {k: "fp8" if k + "_q" in L else "bf16" for k in PROJ if k in L}
+        enc["head"] = "fp8" if self.lm_head_q is not None else "bf16"
+        return enc
 
     def _want_dec(self) -> set:
         """Which projections gemm_decode.hip gets in its fragment-packed form (``DECODE_GEMM`` =
@@ -1141,7 +1190,11 @@ class CausalLM:
                     v.copy_(Ls[k])
         # what is derived from the copied weights is stale now: under PACKED the layers' derived keys
         # ARE the weights and only a tied head keeps a separate packed copy (of the embedding)
-        if self._packed and self.lm_head_d is not None and self.lm_head_d is not self.lm_head:
+        # (an fp8-decoding model requantises: its bf16 weights become the new dequantised values)
+        if self.DEC_WEIGHTS == "fp8":
+            self._f8_defer = False  # the weights are real now, whatever the model was built with
+            self._init_skinny()
+        elif self._packed and self.lm_head_d is not None and self.lm_head_d is not self.lm_head:
             self.lm_head_d.copy_(ops.pack_skinny(self.lm_head))
         elif derived and not self._packed:
             self._init_skinny()
@@ -1153,8 +1206,19 @@ class CausalLM:
         LM head; MoE expert stacks w13_dg / w2_dg ([E, ...], grid.z = expert).  Where ONE_LAYOUT
         applies (``_one_layout_wanted``) each layer adopts its packed copies as the weights before
         the next layer is packed (peak memory = the weights + one layer's copy) and the model ends
-        PACKED; otherwise it stays INTERLEAVED and prefill keeps reading the row-major tensors."""
+        PACKED; otherwise it stays INTERLEAVED and prefill keeps reading the row-major tensors.
+
+        ``DEC_WEIGHTS`` = "fp8": every dense projection (and the head) that gets a packed copy and
+        has an fp8 decode configuration is first quantised per output row, its resident tensor
+        overwritten with the dequantised values (so the packed copy, prefill and the checkpoint
+        hold exactly what the fp8 kernel computes with; a tied embedding table with them), and its
+        codes and scales kept as ``*_q`` / ``*_qs`` in the packed copy's row order - layer by
+        layer, so peak memory stays the model plus one layer.  MoE expert stacks stay bf16."""
         parts, one = self._want_dec(), self._one_layout_wanted()
+        f8 = self.DEC_WEIGHTS == "fp8" and not self._f8_defer
+        if f8 and self.cfg.is_moe:
+            log.info("%s: decode_weights=fp8 leaves the MoE expert stacks on bf16 (grouped launches have no fp8 form)",
+                     self.cfg.name)
         for L in self.layers:
             for key in ("wqkv", "wo", "w2", "w13"):  # w13 (three passes of temporaries) last: a fixed allocation order
                 w = L[key]
@@ -1165,17 +1229,49 @@ class CausalLM:
                 else:
                     sfx, ok = "_d", (("attn" if key in ("wqkv", "wo") else "mlp") in parts
                                      and ops.dec_available(*w.shape, 2 if key == "w13" else 0))
+                if ok and f8 and sfx == "_d":
+                    self._quantize_fp8(L, key)
                 if ok:
                     L[key + sfx] = relayout(w, key, self._layout, PACKED)
             if one:
                 self._adopt_packed(L)
         N, K = self.lm_head.shape
         if "head" in parts and N % 16 == 0 and K % 32 == 0 and ops.dec_available(N, K, 1):
+            if f8 and self._f8_shape_ok(N, K, 1):
+                q, self.lm_head_qs = ops.quantize_rows_fp8(self.lm_head)
+                self.lm_head.copy_(ops.dequantize_rows_fp8(q, self.lm_head_qs, self.dtype))  # tied: the embedding too
+                self.lm_head_q = ops.pack_skinny_f8(q)
+                del q
             self.lm_head_d = ops.pack_skinny(self.lm_head)
             if one and self.lm_head is not self.embed:
                 self.lm_head = self.lm_head_d  # ONE_LAYOUT: the packed head is the only copy too
         if one:
             self._layout = PACKED
+
+    @staticmethod
+    def _f8_shape_ok(N: int, K: int, epi: int) -> bool:
+        """gemm_decode.hip has an fp8 form for the weight [N, K] in some row class."""
+        return any(ops.dec_config(N, K, epi, rows=r, f8=True) is not None for r in ops.dec_row_classes())
+
+    def _quantize_fp8(self, L: dict, key: str) -> None:
+        """The fp8 encoding of the dense projection ``L[key]`` (resident row-major, INTERLEAVED or
+        CANONICAL): the tensor is overwritten in place with the dequantised values (the gemm_skinny
+        view ``*_p`` aliases it; a packed ``*_p`` copy is refreshed) and ``*_q`` / ``*_qs`` hold
+        the codes, fragment-packed, and the scales in the row order of the packed copy ``*_d``
+        (w13: [8 gate | 8 up] per 16 rows - a row permutation, which per-row scales follow)."""
+        w = L[key]
+        N, K = w.shape
+        if not self._f8_shape_ok(N, K, 2 if key == "w13" else 0):
+            return
+        q, s = ops.quantize_rows_fp8(to_canonical(w, key, self._layout))
+        w.copy_(to_resident(ops.dequantize_rows_fp8(q, s, self.dtype), key, self._layout))
+        p = L.get(key + "_p")
+        if p is not None and p is not w:
+            L[key + "_p"] = ops.pack_skinny(w)
+        if key == "w13":
+            q = ops.interleave_gate_up8(q.view(torch.uint8)).view(torch.float8_e4m3fn)
+            s = ops.interleave_gate_up8(s[:, None])[:, 0]
+        L[key + "_q"], L[key + "_qs"] = ops.pack_skinny_f8(q), s.contiguous()
 
     @staticmethod
     def _adopt_packed(L: dict) -> None:

@@ -115,13 +115,67 @@ def dec_row_classes() -> tuple:
     return tuple(sorted({16 * f[4] for f in DEC_FORMS}))
 
 
-def dec_form_ok(epi: int, cfg: tuple, rows: int, grouped: bool = False, wide_norm: bool = False) -> bool:
+def dec_form_ok(epi: int, cfg: tuple, rows: int, grouped: bool = False, wide_norm: bool = False,
+                f8: bool = False) -> bool:
     """Whether gemm_decode.hip has an instantiation for ``cfg = (splits, ntw, waves, depth)`` at
     ``rows`` rows: a DEC_FORMS row with that many m-tiles; ``grouped`` launches and the
-    ``wide_norm`` form (which the row must have) stop at DEC_NARROW_MAX_M rows."""
-    if (grouped or wide_norm) and rows > DEC_NARROW_MAX_M:
+    ``wide_norm`` form (which the row must have) stop at DEC_NARROW_MAX_M rows.  ``f8``: over fp8
+    weights - a row listed in DEC_F8_FORMS, dense launches with the narrow deferred norm only."""
+    if (grouped or wide_norm) and (f8 or rows > DEC_NARROW_MAX_M):
         return False
-    return any(f[:4] == (epi,) + tuple(cfg[1:]) and rows <= 16 * f[4] and (f[5] or not wide_norm) for f in DEC_FORMS)
+    forms = [DEC_FORMS[i] for i in DEC_F8_FORMS] if f8 else DEC_FORMS
+    return any(f[:4] == (epi,) + tuple(cfg[1:]) and rows <= 16 * f[4] and (f[5] or not wide_norm) for f in forms)
+
+
+# ---------------------------------------------------------------- fp8 (e4m3) decode weights
+# One model, two encodings: a weight row is stored as OCP e4m3 codes times a power-of-two scale
+# 2^e, e = ceil(log2(amax_row / 448)).  Every dequantised value code * 2^e is a bf16 value, so the
+# bf16 tensors of an fp8-decoding model hold exactly what the fp8 kernel computes with, and the
+# scale commutes with every rounding of the decode GEMM (applied to the fp32 accumulator).
+
+# the DEC_FORMS rows (indices) that gemm_decode.hip also instantiates over fp8 weights: kDecF8Forms
+# in csrc/gemm_dec_forms.h, reported by native().gemm_dec_f8_forms()
+DEC_F8_FORMS: tuple = (0, 1, 4, 6, 7, 9)
+FP8_MAX = 448.0  # largest finite e4m3fn magnitude
+
+
+def quantize_rows_fp8(w: torch.Tensor) -> tuple:
+    """Row-major weight [N, K] -> (codes [N, K] float8_e4m3fn, scale [N] fp32): per output row the
+    power-of-two scale 2^e with e = ceil(log2(amax / 448)) (0 for an all-zero row) and
+    code = w / 2^e rounded to e4m3 as ``Tensor.to(torch.float8_e4m3fn)`` rounds.  |w / 2^e| <= 448,
+    so no code is NaN."""
+    wf = w.float()
+    m, x = torch.frexp(wf.abs().amax(dim=1) / FP8_MAX)  # amax / 448 = m 2^x, m in [0.5, 1) (0, 0 for zero)
+    e = torch.where(m == 0.5, x - 1, x).clamp(-100, 119).to(torch.int32)
+    scale = ((e + 127) << 23).view(torch.float32)  # 2^e exactly
+    return (wf / scale[:, None]).to(torch.float8_e4m3fn), scale
+
+
+def dequantize_rows_fp8(codes: torch.Tensor, scale: torch.Tensor, dtype=torch.bfloat16) -> torch.Tensor:
+    """code * 2^e per row, exact in bf16 (an e4m3 value has 4 significant bits)."""
+    return (codes.float() * scale.float()[:, None]).to(dtype)
+
+
+def pack_skinny_f8(q: torch.Tensor) -> torch.Tensor:
+    """e4m3 codes [N, K] -> the fragment-packed [N/16, K/64, 64, 16] layout of gemm_dec's fp8 form:
+    block (n-tile j, k-step pair p) holds, for lane l = 16 q + r, the 8 codes
+    W[16 j + r, 64 p + 8 q : +8] (k-step 2p, pack_skinny's fragment order) followed by the 8 codes
+    W[16 j + r, 64 p + 32 + 8 q : +8] (k-step 2p + 1): 1 KiB contiguous per block, two k-steps."""
+    N, K = q.shape
+    if N % 16 or K % 64:
+        raise ValueError(f"pack_skinny_f8: [{N}, {K}] needs N % 16 == 0 and K % 64 == 0")
+    b = q.contiguous().view(torch.uint8).reshape(N // 16, 16, K // 64, 2, 4, 8).permute(0, 2, 4, 1, 3, 5)
+    return b.reshape(N // 16, K // 64, 64, 16).contiguous().view(torch.float8_e4m3fn)
+
+
+def unpack_skinny_f8(qp: torch.Tensor) -> torch.Tensor:
+    nt, kp = qp.shape[0], qp.shape[1]
+    b = qp.contiguous().view(torch.uint8).reshape(nt, kp, 4, 16, 2, 8).permute(0, 3, 1, 4, 2, 5)
+    return b.reshape(nt * 16, kp * 64).contiguous().view(torch.float8_e4m3fn)
+
+
+def is_fp8(w: Optional[torch.Tensor]) -> bool:
+    return w is not None and w.dtype == torch.float8_e4m3fn
 
 
 def pack_skinny(w: torch.Tensor) -> torch.Tensor:
@@ -200,13 +254,16 @@ def skinny_nslabs(K: int, S: int, rm: bool = False) -> int:
 # kernels, so the decode control flow (and TP over gloo) is exercised by the CPU test suite.
 def skinny_wdims(wp: torch.Tensor) -> tuple:
     """(N, K) of a skinny-GEMM weight: fragment-packed [N/16, K/32, 64, 8] or row-major [N, K]
-    (the single resident copy, read by gemm_skinny_rm_kernel)."""
+    (the single resident copy, read by gemm_skinny_rm_kernel), or the fp8 decode encoding
+    [N/16, K/64, 64, 16] (pack_skinny_f8)."""
     if wp.dim() == 4:
-        return wp.shape[0] * 16, wp.shape[1] * 32
+        return wp.shape[0] * 16, wp.shape[1] * (64 if is_fp8(wp) else 32)
     return wp.shape[0], wp.shape[1]
 
 
-def _cpu_w(wp: torch.Tensor) -> torch.Tensor:
+def _cpu_w(wp: torch.Tensor, wscale: Optional[torch.Tensor] = None) -> torch.Tensor:
+    if is_fp8(wp):  # the dequantised values, exactly the bf16 encoding's
+        return unpack_skinny_f8(wp).float() * wscale.float()[:, None]
     return (unpack_skinny(wp) if wp.dim() == 4 else wp).float()
 
 
@@ -419,7 +476,14 @@ DEC_TABLE_M128: dict = {
 }
 
 
-def dec_config(N: int, K: int, epi: int, experts: int = 1, rows: int = 0) -> Optional[tuple]:
+# fp8 weights: picks that differ from the bf16 tables' (keys as there plus the row class: 64 or
+# 128).  A value of None routes the shape and row class to the bf16 encoding (dec_config answers
+# None: not faster in fp8).  Empty: on the Llama-3-8B shapes and the 70B TP=1 gate_up, fp8 with the
+# bf16 pick was the fastest in every row class, 1.13-2.05x over bf16 (profiles/r08/README.md).
+DEC_TABLE_F8: dict = {}
+
+
+def dec_config(N: int, K: int, epi: int, experts: int = 1, rows: int = 0, f8: bool = False) -> Optional[tuple]:
     """Launch configuration of gemm_dec for a weight [N, K]: (splits, ntw, waves, depth) or None
     when no configuration tiles the shape (the caller keeps gemm_skinny).  The candidates are the
     DEC_FORMS rows of the epilogue that serve ``rows``, in list order (the first of two equal
@@ -430,15 +494,22 @@ def dec_config(N: int, K: int, epi: int, experts: int = 1, rows: int = 0) -> Opt
     workgroup count is per expert times experts (Mixtral down: 32 column groups x 8 experts, no
     split - the expert slabs are the split).  ``rows`` > 64 (dense launches only, up to
     DEC_MAX_M): the pick among the forms instantiated with 5..8 m-tiles; ``rows`` <= 64 (or not
-    given) never changes the answer."""
+    given) never changes the answer.  ``f8``: the configuration over the fp8 encoding of the
+    weight (dense launches, K a multiple of 64) - the same tables and candidates restricted to
+    DEC_F8_FORMS, DEC_TABLE_F8 first; None where the shape decodes from bf16."""
     wide = rows > DEC_NARROW_MAX_M
     if wide and (experts != 1 or rows > DEC_MAX_M):
         return None
+    if f8 and (experts != 1 or K % 64):
+        return None
+    compiled = [DEC_FORMS[i] for i in DEC_F8_FORMS] if f8 else DEC_FORMS
+    if f8 and (N, K, epi, 128 if wide else 64) in DEC_TABLE_F8:
+        return DEC_TABLE_F8[(N, K, epi, 128 if wide else 64)]
     hit = (DEC_TABLE_M128 if wide else DEC_TABLE).get((N, K, epi)) if experts == 1 else None
-    if hit is not None:
+    if hit is not None and (not f8 or dec_form_ok(epi, hit, rows, f8=True)):
         return hit
     ntiles, ksteps = N // 16, K // 32
-    forms = [f[1:4] for f in DEC_FORMS
+    forms = [f[1:4] for f in compiled
              if f[0] == epi and rows <= 16 * f[4] and f[:4] not in DEC_FORMS_TABLE_ONLY]
     cands = [(s,) + f for s in ((1, 2, 4, 8, 16) if epi == DEC_SLAB else (1,)) for f in forms]
     best = None
@@ -464,26 +535,33 @@ def dec_available(N: int, K: int, epi: int, rows: int = 0) -> bool:
 
 def dec_gemm(a: torch.Tensor, wp: torch.Tensor, epi: int, rows: int, workspace: Optional[torch.Tensor] = None,
              out: Optional[torch.Tensor] = None, rownorm: Optional[tuple] = None,
-             cfg: Optional[tuple] = None) -> int:
+             cfg: Optional[tuple] = None, wscale: Optional[torch.Tensor] = None) -> int:
     """gemm_dec over a fragment-packed activation ``a`` and packed weight ``wp`` (pack_skinny: under
     ONE_LAYOUT the model's only copy, which prefill's tile GEMM reads too; else a copy for decode).
     epi 0: fp32 split-K slabs into ``workspace`` [S, M, N], returns S; epi 1: ``out`` [M, N] bf16;
     epi 2: ``out`` packed SwiGLU [ceil(M/16), F/32, 64, 8] over an interleave_gate_up8 weight.
     ``rownorm = (ss_part, eps)``: deferred RMSNorm of the A rows (add_norm_partial).  Up to
     DEC_MAX_M = 128 rows; the configuration is dec_config's for that row count (65..128 rows run
-    the 5..8 m-tile instantiations).  CPU: the fp32 reference with the same split-K slicing."""
+    the 5..8 m-tile instantiations).  ``wp`` may be the fp8 encoding (pack_skinny_f8 codes) with
+    ``wscale`` its per-row scales in packed row order: the same launch over half the weight
+    bytes, bit-identical to the bf16 launch of the same configuration over the dequantised
+    weights; a form without an fp8 instantiation raises.  CPU: the fp32 reference with the same
+    split-K slicing (over the dequantised values)."""
     N, K = skinny_wdims(wp)
     M = rows
+    f8 = is_fp8(wp)
+    if f8 and (wscale is None or wscale.numel() != N):
+        raise ValueError(f"gemm_dec: an fp8 weight needs its [{N}] scale vector")
     if M > DEC_MAX_M:
         raise ValueError(f"gemm_dec: at most {DEC_MAX_M} rows, got {M}")
     if cfg is None:
-        cfg = dec_config(N, K, epi, rows=M)
+        cfg = dec_config(N, K, epi, rows=M, f8=f8)
     if cfg is None:
         raise ValueError(f"gemm_dec: no configuration for N={N} K={K} epi={epi} rows={M}")
     S, ntw, waves, depth = cfg
     if not _gpu(a):
         x = _cpu_a(a, rows).float()
-        w = _cpu_w(wp)
+        w = _cpu_w(wp, wscale)
         sc = _rn_scale(rownorm, M, K)
         if epi == 0:
             kc = K // S
@@ -505,10 +583,13 @@ def dec_gemm(a: torch.Tensor, wp: torch.Tensor, epi: int, rows: int, workspace: 
     rn = (None, 0.0) if rownorm is None else (rownorm[0], float(rownorm[1]))
     # more than 16 partial sums per row: gemm_dec_rc's per-16-column sums, the wide-norm form
     wn = rownorm is not None and rownorm[0].shape[1] > 16
-    if not dec_form_ok(epi, cfg, M, wide_norm=wn):
+    if not dec_form_ok(epi, cfg, M, wide_norm=wn, f8=f8):
         raise RuntimeError(f"gemm_dec: form (epi, ntw, waves, depth) = {(epi,) + tuple(cfg[1:])} not compiled for "
-                           f"{M} rows" + (" with the wide deferred norm" if wn else ""))
-    r = native().gemm_dec(a, wp, workspace, out, S, epi, ntw, waves, depth, M, *rn)
+                           f"{M} rows" + (" with the wide deferred norm" if wn else "") + (" over fp8 weights" if f8 else ""))
+    if f8:
+        r = native().gemm_dec_f8(a, wp, wscale, workspace, out, S, epi, ntw, waves, depth, M, *rn)
+    else:
+        r = native().gemm_dec(a, wp, workspace, out, S, epi, ntw, waves, depth, M, *rn)
     if r < 0:
         raise RuntimeError(f"gemm_dec: configuration {cfg} not compiled for N={N} K={K} epi={epi}")
     return r

@@ -60,6 +60,10 @@ int k8sllm_gemm_dec(const void* A, const void* Wp, float* partial, void* Y, long
                     int epi, int ntw, int waves, int depth, const float* rn_ss, int rn_nc, int rn_d, float rn_eps,
                     int experts, long a_es, long w_es, long y_es, const float* rw, int rw_ld, hipStream_t s);
 int k8sllm_gemm_dec_forms(int* out, int cap);
+int k8sllm_gemm_dec_f8(const void* A, const void* Wq, const float* wscale, float* partial, void* Y, long ldy, int M,
+                       int N, int K, int splits, int epi, int ntw, int waves, int depth, const float* rn_ss, int rn_nc,
+                       int rn_d, float rn_eps, hipStream_t s);
+int k8sllm_gemm_dec_f8_forms(int* out, int cap);
 int k8sllm_gemm_dec_rc(const void* A, const void* Wp, void* resid, const void* nw, void* xw, float* ss, int M, int N,
                        int K, hipStream_t s);
 int k8sllm_add_norm_partial(void* out, long out_stride, void* residual, const float* partial, int S, int M,
@@ -636,6 +640,61 @@ int64_t gemm_dec(torch::Tensor a, torch::Tensor wp, c10::optional<torch::Tensor>
   return epi == 0 ? splits : 1;
 }
 
+// gemm_dec over fp8 weights: wq e4m3 codes fragment-packed [N/16, K/64, 64, 16] (ops.pack_skinny_f8;
+// for epi 2 over the [8 gate | 8 up] row order), wscale [N] fp32, one power-of-two scale per packed
+// weight row.  Everything else as gemm_dec; only the forms of kDecF8Forms, the narrow deferred norm.
+int64_t gemm_dec_f8(torch::Tensor a, torch::Tensor wq, torch::Tensor wscale, c10::optional<torch::Tensor> partial,
+                    c10::optional<torch::Tensor> y, int64_t splits, int64_t epi, int64_t ntw, int64_t waves,
+                    int64_t depth, int64_t rows, c10::optional<torch::Tensor> rn_ss, double rn_eps) {
+  dev_bf16(a, "a");
+  TORCH_CHECK(wq.is_cuda() && wq.scalar_type() == torch::kFloat8_e4m3fn && wq.dim() == 4 && wq.is_contiguous() &&
+                  wq.size(2) == 64 && wq.size(3) == 16,
+              "gemm_dec_f8: wq must be float8_e4m3fn, fragment-packed [N/16, K/64, 64, 16]");
+  const int N = (int)wq.size(0) * 16, K = (int)wq.size(1) * 64, M = (int)rows;
+  TORCH_CHECK(wscale.is_cuda() && wscale.scalar_type() == torch::kFloat32 && wscale.is_contiguous() &&
+                  wscale.numel() == N,
+              "gemm_dec_f8: wscale must be [N] fp32");
+  TORCH_CHECK(a.dim() == 4 && a.is_contiguous() && a.size(1) * 32 == K && a.size(2) == 64 && a.size(3) == 8,
+              "gemm_dec_f8: a must be fragment-packed [ceil(M/16), K/32, 64, 8]");
+  TORCH_CHECK(M > 0 && M <= k8sllm::kDecMaxM && (M + 15) / 16 <= a.size(0), "gemm_dec_f8: 1..", k8sllm::kDecMaxM,
+              " rows within the packed a");
+  float* pp = nullptr;
+  void* yp = nullptr;
+  long ldy = 0;
+  if (epi == 0) {
+    pp = slab_buffer(partial, splits * M * N, "gemm_dec_f8");
+  } else {
+    TORCH_CHECK(splits == 1, "gemm_dec_f8: bf16 / SwiGLU epilogues need splits == 1");
+    if (epi == 2) {
+      yp = swiglu_packed_out(y, 0, M, N, "gemm_dec_f8");
+    } else {
+      TORCH_CHECK(y.has_value(), "gemm_dec_f8: output tensor required");
+      dev_bf16(*y, "y");
+      TORCH_CHECK(y->dim() == 2 && y->size(0) >= M && y->size(1) == N && y->stride(1) == 1, "gemm_dec_f8: y [M, N]");
+      ldy = y->stride(0);
+      yp = y->data_ptr();
+    }
+  }
+  const float* rp = nullptr;
+  int rn_nc = 0;
+  rownorm_args(rn_ss, M, K, rp, rn_nc);
+  const int rc = k8sllm_gemm_dec_f8(a.data_ptr(), wq.data_ptr(), wscale.data_ptr<float>(), pp, yp, ldy, M, N, K,
+                                    (int)splits, (int)epi, (int)ntw, (int)waves, (int)depth, rp, rn_nc, K,
+                                    (float)rn_eps, cur());
+  if (rc < 0) return -1;
+  check(rc, "gemm_dec_f8");
+  return epi == 0 ? splits : 1;
+}
+
+// The rows of kDecForms with fp8-weight instantiations (kDecF8Forms), as indices into gemm_dec_forms().
+std::vector<int64_t> gemm_dec_f8_forms() {
+  std::vector<int> v(k8sllm::kDecNF8Forms);
+  const int n = k8sllm_gemm_dec_f8_forms(v.data(), k8sllm::kDecNF8Forms);
+  TORCH_CHECK(n == k8sllm::kDecNF8Forms, "gemm_dec_f8_forms: ", n, " rows compiled, ", k8sllm::kDecNF8Forms,
+              " in the header");
+  return std::vector<int64_t>(v.begin(), v.end());
+}
+
 // Grouped decode GEMM over the local experts of a MoE layer (grid.z = expert): wp [E, N/16, K/32,
 // 64, 8]; a packed [ceil(M/16), K/32, 64, 8] shared by every expert (gate_up) or [E, ceil(M/16),
 // K/32, 64, 8] per expert (down).  epi 2: y [E, ceil(M/16), N/64, 64, 8] packed SwiGLU per expert;
@@ -997,6 +1056,8 @@ PYBIND11_MODULE(_k8sllm_ops, m) {
   m.def("gemm_dec", &gemm_dec);
   m.def("gemm_dec_grouped", &gemm_dec_grouped);
   m.def("gemm_dec_forms", &gemm_dec_forms);
+  m.def("gemm_dec_f8", &gemm_dec_f8);
+  m.def("gemm_dec_f8_forms", &gemm_dec_f8_forms);
   m.def("gemm_dec_rc", &gemm_dec_rc);
   m.def("reduce_add_rms_norm", &reduce_add_rms_norm);
   m.def("reduce_slabs", &reduce_slabs);

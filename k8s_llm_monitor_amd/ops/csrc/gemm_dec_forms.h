@@ -37,6 +37,20 @@ constexpr DecForm kDecForms[] = {
 };
 constexpr int kDecNForms = sizeof(kDecForms) / sizeof(kDecForms[0]);
 
+// The rows of kDecForms that also have the fp8-weight instantiations (k8sllm_gemm_dec_f8: e4m3
+// codes [N/16][K/64][64][16] plus one fp32 power-of-two scale per packed weight row; dense
+// launches, narrow deferred norm, 1..max_mt m-tiles): the Llama-3-8B picks of ops.DEC_TABLE /
+// DEC_TABLE_M128 and the 70B TP=1 gate_up form.  k8sllm_gemm_dec_f8_forms reports the list and
+// ops.DEC_F8_FORMS mirrors it.
+constexpr int kDecF8Forms[] = {0, 1, 4, 6, 7, 9};
+constexpr int kDecNF8Forms = sizeof(kDecF8Forms) / sizeof(kDecF8Forms[0]);
+
+constexpr bool dec_form_f8(int form) {
+  for (int i : kDecF8Forms)
+    if (i == form) return true;
+  return false;
+}
+
 constexpr int dec_max_mt() {
   int m = 0;
   for (const DecForm& f : kDecForms) m = f.max_mt > m ? f.max_mt : m;

@@ -60,11 +60,31 @@ struct DecGeom {
   static constexpr int NLD = (PIECES + 64 * WAVES - 1) / (64 * WAVES);  // staging loads per thread
 };
 
-template <int MT, int NTW, int WAVES, int EPI, int DEPTH, bool RNW = false>
+// 8 OCP e4m3 codes (two dwords, the first code in the low byte) -> the bf16x8 MFMA operand, unscaled:
+// four v_cvt_scalef32_pk_bf16_fp8.  Exact: every finite e4m3 value is a bf16 value.
+__device__ __forceinline__ bf16x8 dec_f8x8(uint32_t lo, uint32_t hi) {
+  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+  const bf16x2 a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, 1.0f, false);
+  const bf16x2 b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, 1.0f, true);
+  const bf16x2 c = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, 1.0f, false);
+  const bf16x2 d = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, 1.0f, true);
+  return bf16x8{a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
+}
+
+// F8: W holds e4m3 codes [N/16][K/64][64][16] (pack_skinny_f8: lane l's 16 bytes are its 8 codes of
+// k-step 2j, then its 8 of k-step 2j + 1, in the bf16 layout's fragment order), so one 1-KiB wave
+// load feeds two k-steps and the ring holds DEPTH / 2 loads per n-tile.  A fragment is converted
+// once per (k-step, n-tile), unscaled, and runs the bf16 MFMA sequence in the bf16 order; the
+// weight row's power-of-two scale wscale[packed row] multiplies the fp32 accumulator in the
+// epilogue (after the deferred-norm row scale, before any bf16 rounding), which commutes with
+// every rounding: bit-identical to the bf16 launch over the dequantised weights.  Dense launches
+// with the narrow deferred norm only.
+template <int MT, int NTW, int WAVES, int EPI, int DEPTH, bool RNW = false, bool F8 = false>
 __global__ __launch_bounds__(64 * WAVES, 1) void gemm_dec_kernel(
     const bf16_t* __restrict__ A, const bf16_t* __restrict__ W, float* __restrict__ partial,
     bf16_t* __restrict__ Y, long ldy, int M, int N, int K, int kchunk, const float* __restrict__ rn_ss, int rn_nc,
-    float rn_inv_d, float rn_eps, DecGroup grp) {
+    float rn_inv_d, float rn_eps, DecGroup grp, const float* __restrict__ wscale) {
+  static_assert(!F8 || (!RNW && DEPTH % 2 == 0), "fp8 weights: narrow deferred norm, whole k-step pairs in the ring");
   using G = DecGeom<MT, WAVES>;
   const int ex = blockIdx.z;  // expert of a grouped launch (0 otherwise)
   A += ex * grp.a_es;
@@ -82,14 +102,24 @@ __global__ __launch_bounds__(64 * WAVES, 1) void gemm_dec_kernel(
 
   // ---- weight stream: DEPTH k-steps x NTW fragments in flight per wave, filled after chunk 0's
   // staging loads (below)
+  // (F8: one load = a pair of k-steps; kb and DEPTH are even, so pairs never straddle a slice)
+  constexpr int RING = F8 ? DEPTH / 2 : DEPTH;
+  const int wsteps = F8 ? ksteps >> 1 : ksteps, wkb = F8 ? kb >> 1 : kb;
   const u32x4* wp[NTW];
 #pragma unroll
   for (int t = 0; t < NTW; ++t)
-    wp[t] = reinterpret_cast<const u32x4*>(W) + ((long)min(tile0 + t, (N >> 4) - 1) * ksteps + kb) * 64 + lane;
-  u32x4 wr[DEPTH][NTW];
+    wp[t] = reinterpret_cast<const u32x4*>(W) + ((long)min(tile0 + t, (N >> 4) - 1) * wsteps + wkb) * 64 + lane;
+  // F8: the scales of this lane's output columns, the oldest loads in flight (waited for once,
+  // below the ring's first loads)
+  float wsc[F8 ? NTW : 1];
+  if constexpr (F8) {
+#pragma unroll
+    for (int t = 0; t < NTW; ++t) wsc[t] = wscale[min(tile0 + t, (N >> 4) - 1) * 16 + (lane & 15)];
+  }
+  u32x4 wr[RING][NTW];
   auto ring_fill = [&]() {
 #pragma unroll
-    for (int d = 0; d < DEPTH; ++d)
+    for (int d = 0; d < RING; ++d)
 #pragma unroll
       for (int t = 0; t < NTW; ++t) wr[d][t] = __builtin_nontemporal_load(wp[t] + d * 64);
   };
@@ -170,6 +200,10 @@ __global__ __launch_bounds__(64 * WAVES, 1) void gemm_dec_kernel(
   // last, the merged wait drained the ring at every chunk boundary).
   stage_load(0);
   ring_fill();
+  if constexpr (F8) {
+#pragma unroll
+    for (int t = 0; t < NTW; ++t) asm volatile("" : "+v"(wsc[t]));  // a counted wait here, none in the epilogue
+  }
 
   // ---- deferred RMSNorm: 1/rms of each A row from its partial sums of squares (loads issued
   // above, ahead of the A staging and the weight ring, so this wait leaves both in flight)
@@ -260,11 +294,23 @@ __global__ __launch_bounds__(64 * WAVES, 1) void gemm_dec_kernel(
       if ((j + 1) % kDecCH != 0) read_a(an, ks + 1);
 #pragma unroll
       for (int t = 0; t < NTW; ++t) {
-        const bf16x8 b = __builtin_bit_cast(bf16x8, wr[j % DEPTH][t]);
+        bf16x8 b;
+        if constexpr (F8) {
+          const u32x4 q = wr[(j % DEPTH) >> 1][t];
+          b = (j & 1) ? dec_f8x8(q[2], q[3]) : dec_f8x8(q[0], q[1]);
+        } else {
+          b = __builtin_bit_cast(bf16x8, wr[j % DEPTH][t]);
+        }
 #pragma unroll
         for (int m = 0; m < MT; ++m) acc[m][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[m], b, acc[m][t], 0, 0, 0);
       }
-      if (!LAST || j + DEPTH < ITER) {
+      if constexpr (F8) {
+        if ((j & 1) && (!LAST || j + DEPTH < ITER)) {  // both k-steps of the slot consumed: the pair DEPTH ahead
+#pragma unroll
+          for (int t = 0; t < NTW; ++t)
+            wr[(j % DEPTH) >> 1][t] = __builtin_nontemporal_load(wp[t] + ((ks + DEPTH) >> 1) * 64);
+        }
+      } else if (!LAST || j + DEPTH < ITER) {
 #pragma unroll
         for (int t = 0; t < NTW; ++t) wr[j % DEPTH][t] = __builtin_nontemporal_load(wp[t] + (ks + DEPTH) * 64);
       }
@@ -292,7 +338,8 @@ __global__ __launch_bounds__(64 * WAVES, 1) void gemm_dec_kernel(
         const int f = tile * 8 + (lane & 7);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const float v = acc[m][t][r] * rs[r];
+          float v = acc[m][t][r] * rs[r];
+          if constexpr (F8) v *= wsc[t];  // the [8 gate | 8 up] interleave permuted the scales with the rows
           const float o = __shfl_xor(v, 8, kWave);
           const int row = m * 16 + (lane >> 4) * 4 + r;
           if ((lane & 8) == 0) {
@@ -308,7 +355,8 @@ __global__ __launch_bounds__(64 * WAVES, 1) void gemm_dec_kernel(
         for (int r = 0; r < 4; ++r) {
           const int row = m * 16 + (lane >> 4) * 4 + r;
           if (row < M) {
-            const float v = acc[m][t][r] * rs[r];
+            float v = acc[m][t][r] * rs[r];
+            if constexpr (F8) v *= wsc[t];
             if constexpr (EPI == DEC_BF16)
               Y[(long)row * ldy + col] = f2bf(v);
             else
@@ -431,34 +479,40 @@ struct DecLaunch {  // what every instantiation is launched with
   int rn_nc;
   float inv_d, rn_eps;
   DecGroup dg;
+  const float* wscale;  // fp8 weights: one scale per packed weight row (else null)
 };
 
 // Launches <mt m-tiles, form F> for 1 <= mt <= MT: the instantiations 1..MT of the form and no
 // others (MT = 0: none).
-template <int F, bool RNW, int MT>
+template <int F, bool RNW, int MT, bool F8 = false>
 bool dec_launch(int mt, const DecLaunch& l) {
   if constexpr (MT == 0) {
     return false;
   } else {
-    if (mt != MT) return dec_launch<F, RNW, MT - 1>(mt, l);
+    if (mt != MT) return dec_launch<F, RNW, MT - 1, F8>(mt, l);
     constexpr DecForm f = kDecForms[F];
-    hipLaunchKernelGGL((gemm_dec_kernel<MT, f.ntw, f.waves, f.epi, f.depth, RNW>), l.grid, l.blk, 0, l.s, l.A, l.W,
-                       l.partial, l.Y, l.ldy, l.M, l.N, l.K, l.kchunk, l.rn_ss, l.rn_nc, l.inv_d, l.rn_eps, l.dg);
+    hipLaunchKernelGGL((gemm_dec_kernel<MT, f.ntw, f.waves, f.epi, f.depth, RNW, F8>), l.grid, l.blk, 0, l.s, l.A,
+                       l.W, l.partial, l.Y, l.ldy, l.M, l.N, l.K, l.kchunk, l.rn_ss, l.rn_nc, l.inv_d, l.rn_eps, l.dg,
+                       l.wscale);
     return true;
   }
 }
 
 // The walk over kDecForms from row F on: false when no row is (epi, ntw, waves, depth) or the row
-// has no instantiation for mt m-tiles (rnw: of the wide deferred-norm form).
-template <int F = 0>
+// has no instantiation for mt m-tiles (rnw: of the wide deferred-norm form; F8: of the fp8-weight
+// form - the rows of kDecF8Forms, narrow norm only).
+template <bool F8 = false, int F = 0>
 bool dec_dispatch(int epi, int ntw, int waves, int depth, bool rnw, int mt, const DecLaunch& l) {
   if constexpr (F == kDecNForms) {
     return false;
   } else {
     constexpr DecForm f = kDecForms[F];
     if (epi != f.epi || ntw != f.ntw || waves != f.waves || depth != f.depth)
-      return dec_dispatch<F + 1>(epi, ntw, waves, depth, rnw, mt, l);
-    return rnw ? dec_launch<F, true, f.wide_norm ? kDecNarrowMaxMT : 0>(mt, l) : dec_launch<F, false, f.max_mt>(mt, l);
+      return dec_dispatch<F8, F + 1>(epi, ntw, waves, depth, rnw, mt, l);
+    if constexpr (F8)
+      return !rnw && dec_launch<F, false, dec_form_f8(F) ? f.max_mt : 0, true>(mt, l);
+    else
+      return rnw ? dec_launch<F, true, f.wide_norm ? kDecNarrowMaxMT : 0>(mt, l) : dec_launch<F, false, f.max_mt>(mt, l);
   }
 }
 
@@ -492,9 +546,42 @@ extern "C" int k8sllm_gemm_dec(const void* A, const void* Wp, float* partial, vo
   if (rnw && (rn_nc % 16 || rn_nc > 16 * kRnWide)) return -1;
   const DecLaunch l{dim3((ntiles + nwg_tiles - 1) / nwg_tiles, splits, experts), dim3(64 * waves), s,
                     (const bf16_t*)A, (const bf16_t*)Wp, partial, (bf16_t*)Y, ldy, M, N, K, kchunk, rn_ss, rn_nc,
-                    inv_d, rn_eps, DecGroup{a_es, w_es, y_es, rw, rw_ld}};
+                    inv_d, rn_eps, DecGroup{a_es, w_es, y_es, rw, rw_ld}, nullptr};
   if (!dec_dispatch(epi, ntw, waves, depth, rnw, MT, l)) return -5;
   return (int)hipGetLastError();
+}
+
+// The same over fp8 weights: Wq e4m3 codes [N/16][K/64][64][16] (ops.pack_skinny_f8), wscale [N]
+// fp32 powers of two in packed row order.  Dense launches only; (epi, ntw, waves, depth) must be a
+// row of kDecForms listed in kDecF8Forms, with ceil(M / 16) <= its max_mt and the narrow deferred
+// norm (rn_nc <= 16).  The same checks and negative codes as k8sllm_gemm_dec.
+extern "C" int k8sllm_gemm_dec_f8(const void* A, const void* Wq, const float* wscale, float* partial, void* Y,
+                                  long ldy, int M, int N, int K, int splits, int epi, int ntw, int waves, int depth,
+                                  const float* rn_ss, int rn_nc, int rn_d, float rn_eps, hipStream_t s) {
+  if (M <= 0) return 0;
+  if (M > kDecMaxM || wscale == nullptr) return -1;
+  if (N % 16 || K % 64 || splits < 1 || K % splits) return -1;
+  const int ntiles = N / 16, nwg_tiles = ntw * waves;
+  if (nwg_tiles < 1) return -5;
+  const int kchunk = K / splits;
+  const int iter = depth > kDecCH ? depth : kDecCH;
+  if (kchunk % 32 || kchunk < 32 * iter || (kchunk / 32) % iter) return -3;
+  if (epi != DEC_SLAB && splits != 1) return -4;
+  const float inv_d = rn_d > 0 ? 1.f / (float)rn_d : 0.f;
+  const int MT = (M + 15) / 16;
+  if (rn_ss != nullptr && rn_nc > 4 * kRnMax) return -1;  // the wide deferred-norm form reads bf16 weights
+  const DecLaunch l{dim3((ntiles + nwg_tiles - 1) / nwg_tiles, splits, 1), dim3(64 * waves), s,
+                    (const bf16_t*)A, (const bf16_t*)Wq, partial, (bf16_t*)Y, ldy, M, N, K, kchunk, rn_ss, rn_nc,
+                    inv_d, rn_eps, DecGroup{0, 0, 0, nullptr, 0}, wscale};
+  if (!dec_dispatch<true>(epi, ntw, waves, depth, false, MT, l)) return -5;
+  return (int)hipGetLastError();
+}
+
+// The indices into kDecForms of the rows with fp8-weight instantiations (kDecF8Forms), at most
+// cap of them into out; returns their count.
+extern "C" int k8sllm_gemm_dec_f8_forms(int* out, int cap) {
+  for (int i = 0; i < kDecNF8Forms && i < cap; ++i) out[i] = kDecF8Forms[i];
+  return kDecNF8Forms;
 }
 
 // The rows of kDecForms as six ints each (epi, ntw, waves, depth, max_mt, wide_norm), at most cap

@@ -8,8 +8,12 @@ reference of the same product first (max |err| / max |ref|).  Above 64 rows (``-
 the 5..8 m-tile instantiations) only gemm_decode.hip has a kernel: the row-major skinny case is
 left out, hipBLASLt stays for the LM head, and configurations without a 65..128-row instantiation
 (ops.dec_form_ok) are reported as errors and skipped.  ``pick`` lines give ops.dec_config's choice per row count.
+``--wdtype fp8`` adds, next to every dec configuration with an fp8 form (ops.DEC_F8_FORMS), the
+same launch over the fp8 encoding of the weights (``f8_`` cases: half the weight bytes; TBps
+counts the bytes actually streamed), checked for bit equality with the bf16 launch over the
+dequantised weights, which the bf16 cases then stream too.  ``--shape 70b_gate_up`` etc.: SHAPES.
 
-    python tools/bench_decode_gemm.py [--ms 1,32,64] [--ops qkv,o,gate_up,down,lm_head] [--rounds 3]
+    python tools/bench_decode_gemm.py [--ms 1,32,64] [--ops qkv,o,gate_up,down,lm_head] [--rounds 3] [--wdtype fp8]
 """
 from __future__ import annotations
 
@@ -27,13 +31,15 @@ from k8s_llm_monitor_amd import ops  # noqa: E402
 from tools.bench_skinny import timeit  # noqa: E402
 
 D, FF, V = 4096, 14336, 128256
-SHAPES = {"qkv": (6144, D, 0), "o": (D, D, 0), "gate_up": (2 * FF, D, 2), "down": (D, FF, 0), "lm_head": (V, D, 1)}
+SHAPES = {"qkv": (6144, D, 0), "o": (D, D, 0), "gate_up": (2 * FF, D, 2), "down": (D, FF, 0), "lm_head": (V, D, 1),
+          "70b_gate_up": (2 * 28672, 8192, 2)}  # Llama-3-70B at TP=1
 CFGS = {  # the sweep list: forms of ops.DEC_FORMS (another form: add its row to the table first)
     "qkv": [(4, 1, 6, 8), (8, 1, 8, 8), (4, 1, 4, 16), (4, 1, 4, 8)],
     "o": [(4, 1, 4, 16), (4, 1, 4, 8), (8, 1, 8, 8), (16, 1, 8, 8)],
     "gate_up": [(1, 1, 7, 16), (1, 1, 7, 8), (1, 1, 8, 16)],
     "down": [(4, 1, 4, 16), (4, 1, 4, 8), (8, 1, 8, 8), (4, 1, 8, 8)],
     "lm_head": [(1, 4, 8, 4), (1, 3, 8, 8), (1, 2, 8, 8)],
+    "70b_gate_up": [(1, 1, 8, 16)],
 }
 
 
@@ -44,6 +50,8 @@ def main() -> None:
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--ops", default="qkv,o,gate_up,down,lm_head")
     ap.add_argument("--cfgs", default=None, help="op:S,NTW,W,D|S,NTW,W,D;... overrides the sweep list")
+    ap.add_argument("--wdtype", default="bf16", choices=["bf16", "fp8"])
+    ap.add_argument("--no-base", action="store_true", help="leave out the row-major skinny / hipBLASLt case")
     a = ap.parse_args()
     dev = "cuda"
     torch.manual_seed(0)
@@ -61,6 +69,14 @@ def main() -> None:
             wdec = [ops.pack_skinny(ops.interleave_gate_up8(w)) for w in canon]
         else:
             wdec = [ops.pack_skinny(w) for w in wrm]
+        wq = ws = None
+        if a.wdtype == "fp8":  # one model, two encodings: the bf16 copies become the dequantised values
+            qs = [ops.quantize_rows_fp8(ops.unpack_skinny(w)) for w in wdec]
+            wdec = [ops.pack_skinny(ops.dequantize_rows_fp8(q, s)) for q, s in qs]
+            wrm = [ops.interleave_gate_up(ops.deinterleave_gate_up8(ops.unpack_skinny(w))) if epi == 2
+                   else ops.unpack_skinny(w) for w in wdec]
+            wq, ws = [ops.pack_skinny_f8(q) for q, _ in qs], [s for _, s in qs]
+            del qs
         gb = N * K * 2 / 1e9
         for M in map(int, a.ms.split(",")):
             x = torch.randn(M, K, device=dev, dtype=torch.bfloat16)
@@ -74,19 +90,20 @@ def main() -> None:
             act = ops.packed_empty(M, N // 2, torch.bfloat16, dev)
             yb = torch.empty(M, N, device=dev, dtype=torch.bfloat16)
 
-            def dec_out(cfg):
+            def dec_out(cfg, w=None, **kw):
+                w = wdec[0] if w is None else w
                 if epi == 0:
-                    s = ops.dec_gemm(xp, wdec[0], 0, M, workspace=wsp, cfg=cfg)
+                    s = ops.dec_gemm(xp, w, 0, M, workspace=wsp, cfg=cfg, **kw)
                     return wsp[: s * M * N].view(s, M, N).sum(0)
                 if epi == 1:
-                    ops.dec_gemm(xp, wdec[0], 1, M, out=yb, cfg=cfg)
+                    ops.dec_gemm(xp, w, 1, M, out=yb, cfg=cfg, **kw)
                     return yb.float()
-                ops.dec_gemm(xp, wdec[0], 2, M, out=act, cfg=cfg)
+                ops.dec_gemm(xp, w, 2, M, out=act, cfg=cfg, **kw)
                 return ops.unpack_skinny(act)[:M].float()
 
             cases = {}
             print(json.dumps({"op": name, "M": M, "pick": ops.dec_config(N, K, epi, rows=M)}), flush=True)
-            if M > ops.SKINNY_MAX_M and epi != 1:
+            if a.no_base or (M > ops.SKINNY_MAX_M and epi != 1):
                 pass  # gemm_skinny stops at 64 rows
             elif epi == 0:
                 cases["rm"] = lambda i: ops.skinny_slabs(xp, wrm[i % ncopy], wsp, 0, rows=M)
@@ -105,15 +122,22 @@ def main() -> None:
                 cases[tag] = (lambda i, cfg=cfg: ops.dec_gemm(xp, wdec[i % ncopy], epi, M, workspace=wsp,
                                                               out=act if epi == 2 else yb, cfg=cfg))
                 print(json.dumps({"op": name, "M": M, "cfg": cfg, "rel_err": round(err, 5)}), flush=True)
+                if wq is not None and ops.dec_form_ok(epi, cfg, M, f8=True):
+                    same = torch.equal(dec_out(cfg).clone(), dec_out(cfg, wq[0], wscale=ws[0]))
+                    cases["f8_" + tag] = (lambda i, cfg=cfg: ops.dec_gemm(xp, wq[i % ncopy], epi, M, workspace=wsp,
+                                                                       out=act if epi == 2 else yb, cfg=cfg,
+                                                                       wscale=ws[i % ncopy]))
+                    print(json.dumps({"op": name, "M": M, "cfg": cfg, "f8_bit_equal_to_bf16": same}), flush=True)
             res: dict = {}
             for _ in range(a.rounds):
                 for tag, fn in cases.items():
                     res.setdefault(tag, []).append(timeit(fn, a.iters))
             for tag, ts in res.items():
                 t = min(ts)
+                b = gb / 2 if tag.startswith("f8_") else gb
                 print(json.dumps({"op": name, "M": M, "impl": tag, "us": round(t, 2),
-                                  "us_all": [round(v, 2) for v in ts], "TBps": round(gb / t * 1e3, 2)}), flush=True)
-        del wrm, wdec
+                                  "us_all": [round(v, 2) for v in ts], "TBps": round(b / t * 1e3, 2)}), flush=True)
+        del wrm, wdec, wq, ws
         torch.cuda.empty_cache()
 
 

@@ -14,6 +14,10 @@ down on 4 split-K slabs instead of 8 (half the bytes add_norm_partial reads) - 6
 rows, 3.78 vs 3.75 at 16: slower, DEC_TABLE unchanged; profiles/r06/decode_step_split4_ab.jsonl.)
 ``rows128`` - CausalLM.DEC_ROWS_MAX 128 vs 64: a 128-row decode step on gemm_decode.hip's 8 m-tile
 kernels vs the generic layer loop (``--rows 64,128``; at 64 rows both sides run the same code).
+``--decode-weights fp8`` builds the engine with the fp8 encoding beside the bf16 weights; ``f8``
+then A/Bs a step streaming fp8 weights (on; the row-complete o projection off, the fp8-mode
+default) against the same engine routed to its bf16 copies with the bf16 defaults (off), and
+``rc`` the row-complete o projection (bf16 o, bf16 wide-norm gate_up) inside fp8 mode.
 """
 from __future__ import annotations
 
@@ -38,8 +42,20 @@ SWITCHES = {"rc": lambda m, on: m.set_decode_fusion(rc=on),
             # decode steps of 65..128 rows on the shared-A decode GEMM (on / reset) vs the routing
             # before it (off: CausalLM.DEC_ROWS_MAX = 64, the generic layer loop on the tile GEMM);
             # run with --rows 64,128
-            "rows128": lambda m, on: setattr(type(m), "DEC_ROWS_MAX", 64 if on is False else 128)}
+            "rows128": lambda m, on: setattr(type(m), "DEC_ROWS_MAX", 64 if on is False else 128),
+            "f8": lambda m, on: _f8(m, on)}
 _DEC_DEFAULT: dict = {}
+_F8_FORMS: list = []
+
+
+def _f8(m, on) -> None:
+    """off: no fp8 form is offered (ops.dec_config(f8=True) answers None, every launch reads the
+    bf16 copy) and the row-complete o projection is back at its bf16 default; on / reset: as built."""
+    ops = _ops()
+    if not _F8_FORMS:
+        _F8_FORMS.append(ops.DEC_F8_FORMS)
+    ops.DEC_F8_FORMS = () if on is False else _F8_FORMS[0]
+    m.set_decode_fusion(rc=m.RC_O_MAX_ROWS if on is False else None)
 
 
 def _dec_table(on, alt: dict) -> None:
@@ -62,12 +78,15 @@ def main() -> None:
     ap.add_argument("--ctx", type=int, default=1700)
     ap.add_argument("--tokens", type=int, default=96)
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--decode-weights", default="bf16", choices=["bf16", "fp8"])
+    ap.add_argument("--layers", type=int, default=0, help="override the model's layer count (0 = all)")
     a = ap.parse_args()
     from k8s_llm_monitor_amd.engine import EngineConfig, LLMEngine, SamplingParams
 
     rows_list = [int(r) for r in a.rows.split(",")]
     eng = LLMEngine(EngineConfig(model=a.model, max_num_seqs=max(rows_list), max_model_len=4096, kv_cache_gb=48.0,
-                                 seed=1), device="cuda")
+                                 seed=1, decode_weights=a.decode_weights,
+                                 model_overrides={"n_layers": a.layers} if a.layers else {}), device="cuda")
     eng.warmup()
     g = torch.Generator().manual_seed(5)
     sp = SamplingParams(max_tokens=a.tokens, temperature=0.0, ignore_eos=True)
@@ -85,7 +104,8 @@ def main() -> None:
                 ms = [m for (n, m, _) in eng.step_samples if n == rows]
                 med = statistics.median(ms) if ms else float("nan")
                 res[on].append(med)
-                print(json.dumps({"switch": a.switch, "rows": rows, "on": on, "round": rnd, "steps": len(ms),
+                print(json.dumps({"switch": a.switch, "decode_weights": a.decode_weights, "rows": rows, "on": on,
+                                  "round": rnd, "steps": len(ms),
                                   "median_step_ms": round(med, 4)}), flush=True)
         print(json.dumps({"switch": a.switch, "rows": rows, "on_ms": [round(x, 4) for x in res[True]],
                           "off_ms": [round(x, 4) for x in res[False]],

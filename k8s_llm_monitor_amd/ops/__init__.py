@@ -1016,17 +1016,9 @@ def _sample_cpu(logits, temperature, top_k, top_p, rng):
         if t <= 0:
             res[b] = int(x.argmax())
             continue
-        x = x / t
-        if top_k is not None and 0 < int(top_k[b]) < x.numel():
-            kth = torch.topk(x, int(top_k[b])).values[-1]
-            x = x.masked_fill(x < kth, float("-inf"))
-        if top_p is not None and float(top_p[b]) < 1.0:
-            p = torch.softmax(x, -1)
-            sp, si = torch.sort(p, descending=True)
-            keep = torch.cumsum(sp, 0) - sp < float(top_p[b])
-            mask = torch.zeros_like(p, dtype=torch.bool)
-            mask[si[keep]] = True
-            x = x.masked_fill(~mask, float("-inf"))
+        keep = ref.sample_keep(logits[b], t, int(top_k[b]) if top_k is not None else 0,
+                               float(top_p[b]) if top_p is not None else 1.0)
+        x = (x / t).masked_fill(~keep, float("-inf"))
         res[b] = int(torch.multinomial(torch.softmax(x, -1), 1, generator=gen))
     return res
 

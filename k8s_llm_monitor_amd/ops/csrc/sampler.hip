@@ -1,8 +1,13 @@
 // Token sampler over logits[B][V].
 //   temperature <= 0        -> greedy argmax (first index on ties, like torch.argmax)
 //   temperature  > 0        -> Gumbel-max over logits/T  (exact sample from softmax(logits/T))
-//   top_k > 0 / top_p < 1   -> the kept set {x >= thr} is found by bisection on the threshold
-//                              (count for top-k, probability mass for top-p); no sort needed.
+//   top_k > 0 / top_p < 1   -> the draw is over a kept set {x >= thr} (ops/reference.py sample_keep):
+//                              top-k first (0 < k < V): thr = the k-th largest x / T, found exactly
+//                              by bisecting its order-preserving integer image on the count;
+//                              then top-p over the top-k survivors: the smallest prefix of their
+//                              renormalised softmax, sorted descending, whose mass reaches p, found
+//                              by bisecting the threshold on the mass.  Ties at either threshold
+//                              are kept; no sort needed.
 // Randomness is a counter hash of (seed, offset, row, index); `rng` lives in device memory so a
 // hipGraph-captured decode step draws fresh numbers on every replay (the engine bumps offset).
 //
@@ -94,6 +99,17 @@ __device__ __forceinline__ ArgMax block_argmax(ArgMax a, float* sv, int* si) {
   return r;
 }
 
+// Order-preserving image of an fp32 value: a < b as floats implies order_key(a) < order_key(b) as
+// unsigned integers (-0 sorts just below +0); -inf -> 0x007fffff, +inf -> 0xff800000.
+__device__ __forceinline__ uint32_t order_key(float f) {
+  const int32_t b = __float_as_int(f);
+  return (uint32_t)(b ^ ((b >> 31) | (int32_t)0x80000000));
+}
+
+__device__ __forceinline__ float order_key_inv(uint32_t u) {
+  return __uint_as_float((u & 0x80000000u) ? (u ^ 0x80000000u) : ~u);
+}
+
 // Whole-row path for rows with top-k / top-p (one workgroup); returns the token on every thread.
 template <typename T>
 __device__ int sample_row_filtered(const T* __restrict__ x, int V, float temp, int k, float p, uint64_t key,
@@ -110,22 +126,28 @@ __device__ int sample_row_filtered(const T* __restrict__ x, int V, float temp, i
   mn = -block_max<kST>(-mn, sv);
   float thr = -INFINITY;
   if (k > 0 && k < V) {
-    float lo = mn, hi = mx;  // invariant: count(x >= lo) >= k
-    for (int it = 0; it < 26; ++it) {
-      const float mid = 0.5f * (lo + hi);
-      float c = 0.f;
-      for (int i = tid; i < V; i += kST) c += (ld<T>(x, i) * itemp >= mid) ? 1.f : 0.f;
+    // the k-th largest value itself: the largest key t with count(key(v) >= t) >= k, built bit by
+    // bit from the top (32 steps, exact for any range of the row, -inf included)
+    uint32_t t = 0u;
+    for (int bit = 31; bit >= 0; --bit) {
+      const uint32_t cand = t | (1u << bit);
+      float c = 0.f;  // V < 2^24: an exact count
+      for (int i = tid; i < V; i += kST) c += (order_key(ld<T>(x, i) * itemp) >= cand) ? 1.f : 0.f;
       c = block_sum<kST>(c, sv);
-      if (c >= (float)k) lo = mid; else hi = mid;
+      if (c >= (float)k) t = cand;
     }
-    thr = lo;
+    thr = order_key_inv(t);
   }
   if (p < 1.f) {
+    // mass over the top-k survivors only (thr = -inf without top-k: the whole row)
     float z = 0.f;
-    for (int i = tid; i < V; i += kST) z += __expf(ld<T>(x, i) * itemp - mx);
+    for (int i = tid; i < V; i += kST) {
+      const float v = ld<T>(x, i) * itemp;
+      z += (v >= thr) ? __expf(v - mx) : 0.f;
+    }
     z = block_sum<kST>(z, sv);
     const float target = p * z;
-    float lo = fmaxf(mn, mx - 80.f), hi = mx;  // invariant: mass(x >= lo) >= target
+    float lo = fmaxf(thr, fmaxf(mn, mx - 80.f)), hi = mx;  // invariant: mass(x >= lo) >= target
     for (int it = 0; it < 26; ++it) {
       const float mid = 0.5f * (lo + hi);
       float s = 0.f;
@@ -171,11 +193,13 @@ __global__ __launch_bounds__(kST) void sample_partial_kernel(float* __restrict__
     if (tid == 0) pi[row * P] = tok;
     return;
   }
-  // parts start on 8-element boundaries so that bf16 rows with an 8-aligned stride are read 16 B
-  // per lane (one load per 8 logits instead of eight dependent 2-byte loads)
+  // parts start on 8-element boundaries so that bf16 rows with an 8-aligned stride and a 16-byte
+  // aligned base are read 16 B per lane (one load per 8 logits instead of eight dependent 2-byte
+  // loads); any other row (a view that starts mid-vector) takes the scalar loop
   const int chunk = ((V + P - 1) / P + 7) & ~7;
   const int lo = min(V, part * chunk), hi = min(V, lo + chunk);
-  const bool vec = std::is_same<T, bf16_t>::value && (stride & 7) == 0;
+  const bool vec = std::is_same<T, bf16_t>::value && (stride & 7) == 0 &&
+                   (reinterpret_cast<uintptr_t>(x + lo) & 15) == 0;
   const int hv = vec ? lo + ((hi - lo) & ~7) : lo;  // [lo, hv) in 8-element vectors, [hv, hi) scalar
   ArgMax a{-INFINITY, 0x7fffffff};
   const bool greedy = !(temp > 0.f);

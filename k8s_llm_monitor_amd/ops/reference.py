@@ -196,6 +196,27 @@ def greedy(logits: torch.Tensor) -> torch.Tensor:
     return logits.float().argmax(-1).to(torch.int32)
 
 
+def sample_keep(logits_row: torch.Tensor, temperature: float, top_k: int, top_p: float) -> torch.Tensor:
+    """bool[V]: the tokens of one row a sampled draw (temperature > 0) may return, in float64.
+
+    Scale by 1/T; top-k keeps {v >= k-th largest v} when 0 < k < V; top-p (p < 1) then takes the
+    softmax of the top-k survivors, sorted descending, and keeps the smallest prefix whose mass
+    reaches p (``cumsum - p_i < p``).  Ties at the last kept value are kept by both filters, the
+    largest value is always kept, and -inf entries never are."""
+    v = logits_row.detach().to(torch.float64) * (1.0 / float(temperature))
+    keep = v > float("-inf")
+    k = int(top_k)
+    if 0 < k < v.numel():
+        keep &= v >= torch.topk(v, k).values[-1]
+    if float(top_p) < 1.0:
+        w = torch.softmax(v.masked_fill(~keep, float("-inf")), -1)
+        sw = torch.sort(w, descending=True).values
+        past = torch.nonzero(~(torch.cumsum(sw, 0) - sw < float(top_p)))
+        n = int(past[0]) if past.numel() else sw.numel()  # length of the kept prefix
+        keep &= w >= sw[max(n, 1) - 1]
+    return keep
+
+
 def moe_route(logits: torch.Tensor, k: int, renorm: bool):
     p = torch.softmax(logits.float(), dim=-1)
     w, ids = torch.topk(p, k, dim=-1)

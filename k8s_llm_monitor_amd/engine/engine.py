@@ -74,6 +74,10 @@ class EngineConfig:
     # model's bf16 weights become the dequantised values and the fp8 copy is kept beside them
     # (resident weights grow by half; prefill still reads bf16; only decode streams fewer bytes)
     decode_weights: str = "bf16"
+    # "bf16" | "fp8": the paged KV cache's encoding.  fp8 stores e4m3 codes with one power-of-two
+    # scale per (token, kv head) for K and for V (ops.quantize_kv): decode streams half the KV bytes
+    # and a kv_cache_gb budget holds ~1.94x the blocks.  GPU: head_dim 128 only
+    kv_cache_dtype: str = "bf16"
 
 
 class _View:
@@ -112,7 +116,8 @@ class LLMEngine:
             load_checkpoint(self.model, cfg.weights)
         self.runner = ModelRunner(self.model, RunnerConfig(
             max_num_seqs=cfg.max_num_seqs, max_model_len=cfg.max_model_len, kv_cache_gb=cfg.kv_cache_gb,
-            num_blocks=cfg.num_blocks, use_graphs=cfg.use_graphs, seed=cfg.seed))
+            num_blocks=cfg.num_blocks, use_graphs=cfg.use_graphs, seed=cfg.seed,
+            kv_cache_dtype=cfg.kv_cache_dtype))
         self.blocks = BlockManager(self.runner.num_blocks, prefix_caching=cfg.prefix_caching)
         self.sched = Scheduler(SchedulerConfig(max_num_seqs=cfg.max_num_seqs,
                                                max_prefill_tokens=cfg.max_prefill_tokens,
@@ -461,7 +466,7 @@ class LLMEngine:
         d.update(self.sched.stats())
         d.update({"model": self.model_cfg.name, "tp_size": self.ps.tp_size, "device": str(self.device),
                   "graph_buckets": sorted(self.runner.graphs), "max_num_seqs": self.cfg.max_num_seqs,
-                  "decode_weights": self.cfg.decode_weights,
+                  "decode_weights": self.cfg.decode_weights, **self.runner.kv_stats(),
                   "resident_weight_bytes": self.model.resident_weight_bytes(),
                   "decode_encodings": self.model.decode_encodings()})
         return d

@@ -25,6 +25,7 @@ from ..models.llama import AttnMeta, CausalLM
 from .sequence import Sequence
 
 BLOCK_SIZE = 16
+KV_CACHE_DTYPES = ("bf16", "fp8")
 DEFAULT_BUCKETS = (1, 2, 4, 8, 16, 24, 32, 40, 48, 56, 64, 80, 96, 112, 128, 160, 192, 224, 256)
 
 
@@ -36,6 +37,7 @@ class RunnerConfig:
     num_blocks: Optional[int] = None  # overrides kv_cache_gb
     use_graphs: bool = True
     seed: int = 0
+    kv_cache_dtype: str = "bf16"  # "fp8": e4m3 codes + per-token scales (ops.kv_cache_alloc)
 
 
 class ModelRunner:
@@ -47,7 +49,14 @@ class ModelRunner:
         self.max_len = min(cfg.max_model_len, c.max_position)
         self.max_blocks_per_seq = (self.max_len + BLOCK_SIZE - 1) // BLOCK_SIZE
         L, hkv, D = c.n_layers, model.hkv, model.D
-        per_block = 2 * L * hkv * D * BLOCK_SIZE * 2  # bytes (K + V, bf16)
+        if cfg.kv_cache_dtype not in KV_CACHE_DTYPES:
+            raise ValueError(f"kv_cache_dtype must be one of {KV_CACHE_DTYPES}, not {cfg.kv_cache_dtype!r}")
+        self.kv_cache_dtype = cfg.kv_cache_dtype
+        fp8 = cfg.kv_cache_dtype == "fp8"
+        if fp8 and self.device.type == "cuda" and D != 128:
+            raise ValueError(f"kv_cache_dtype 'fp8' needs head_dim 128 on the GPU (model has {D})")
+        kv_dtype = torch.float8_e4m3fn if fp8 else model.dtype
+        per_block = ops.kv_bytes_per_block(L, hkv, D, kv_dtype)  # K + V over all layers (+ scales for fp8)
         if cfg.num_blocks:
             nb = cfg.num_blocks
         elif cfg.kv_cache_gb <= 0:  # auto: every admitted sequence can reach max_len (+ one spare block)
@@ -55,9 +64,10 @@ class ModelRunner:
         else:
             nb = max(self.max_blocks_per_seq + 1, int(cfg.kv_cache_gb * (1 << 30) // per_block))
         self.num_blocks = nb
-        self.k_cache = torch.zeros(L, nb, hkv, D // 8, BLOCK_SIZE, 8, dtype=model.dtype, device=self.device)
-        self.v_cache = torch.zeros(L, nb, hkv, D, BLOCK_SIZE, dtype=model.dtype, device=self.device)
-        self.kv = [(self.k_cache[i], self.v_cache[i]) for i in range(L)]
+        self.k_cache, self.v_cache, *sc = ops.kv_cache_alloc(L, nb, hkv, D, kv_dtype, self.device)
+        self.kv_scale = sc[0] if sc else None
+        self.kv_cache_bytes = nb * per_block
+        self.kv = [(self.k_cache[i], self.v_cache[i], self.kv_scale[i] if fp8 else None) for i in range(L)]
         self.is_gpu = self.device.type == "cuda"
         B = cfg.max_num_seqs
         self.B = B
@@ -409,10 +419,13 @@ class ModelRunner:
         handle.event.synchronize()
         return handle.out[: handle.n].tolist()
 
+    def kv_stats(self) -> dict:
+        """The paged cache as allocated: its encoding, blocks and true bytes (codes + scales for fp8)."""
+        return {"kv_cache_dtype": self.kv_cache_dtype, "kv_cache_bytes": self.kv_cache_bytes,
+                "kv_blocks": self.num_blocks, "block_size": BLOCK_SIZE}
+
     def memory_report(self) -> dict:
-        kv = (self.k_cache.numel() + self.v_cache.numel()) * self.k_cache.element_size()
-        return {"kv_cache_bytes": kv, "kv_blocks": self.num_blocks, "block_size": BLOCK_SIZE,
-                "max_model_len": self.max_len, "graph_buckets": sorted(self.graphs)}
+        return {**self.kv_stats(), "max_model_len": self.max_len, "graph_buckets": sorted(self.graphs)}
 
 
 class _Staging:

@@ -391,7 +391,7 @@ class CausalLM:
         or fragment-packed with ``rows`` valid rows), reduced inside rope_and_cache; the attention
         output is then written fragment-packed for the o_proj skinny GEMM."""
         c = self.cfg
-        k_cache, v_cache = kv if kv is not None else (None, None)
+        k_cache, v_cache, kv_scale = (tuple(kv) + (None,))[:3] if kv is not None else (None, None, None)
         partial, ns = None, 0
         roped = False  # q / k already rotated by the qkv GEMM's epilogue
         T = rows if rows is not None else x.shape[0]
@@ -404,7 +404,7 @@ class CausalLM:
                 out = ops.packed_empty(T, self.hq * self.D, self.dtype, self.device)
                 return ops.paged_decode_fused(ws, ns, meta.positions, cs, meta.slot_mapping, k_cache, v_cache,
                                               meta.block_tables, meta.seq_lens, self.hq, self.hkv, self.D, self.scale,
-                                              workspace=meta.decode_ws, out=out)
+                                              workspace=meta.decode_ws, out=out, kv_scale=kv_scale)
             partial = ws
             qkv = torch.empty(T, ops.w_out(L["wqkv"]), dtype=self.dtype, device=self.device)
         elif "bqkv" in L:
@@ -417,7 +417,7 @@ class CausalLM:
             qkv = ops.prefill_linear(x, L["wqkv"])
         ops.rope_and_cache(qkv, meta.positions, cs, k_cache, v_cache,
                            meta.slot_mapping if k_cache is not None else None, self.hq, self.hkv, self.D,
-                           apply_rope=c.arch == "llama" and not roped, partial=partial, nslabs=ns)
+                           apply_rope=c.arch == "llama" and not roped, partial=partial, nslabs=ns, kv_scale=kv_scale)
         if meta.is_prefill:
             qb = (meta.qb_seq, meta.qb_start) if meta.qb_seq is not None else None
             paged = None
@@ -426,19 +426,19 @@ class CausalLM:
             nd = meta.num_decode
             if nd == 0:
                 return ops.flash_prefill(qkv, meta.cu_seqlens, self.hq, self.hkv, self.D, self.scale, qblocks=qb,
-                                         paged=paged)
+                                         paged=paged, kv_scale=kv_scale)
             # mixed step: decode rows through paged_decode, prefill rows through flash prefill
             o = torch.empty(qkv.shape[0], self.hq * self.D, dtype=qkv.dtype, device=qkv.device)
             ops.paged_decode(qkv[:nd], k_cache, v_cache, meta.dec_block_tables, meta.dec_seq_lens, self.hq,
-                             self.hkv, self.D, self.scale, workspace=meta.decode_ws, out=o[:nd])
+                             self.hkv, self.D, self.scale, workspace=meta.decode_ws, out=o[:nd], kv_scale=kv_scale)
             op = ops.flash_prefill(qkv[nd:], meta.cu_seqlens, self.hq, self.hkv, self.D, self.scale, qblocks=qb,
-                                   paged=paged, out=o[nd:])
+                                   paged=paged, out=o[nd:], kv_scale=kv_scale)
             if op.data_ptr() != o[nd:].data_ptr():  # CPU reference paths return a fresh tensor
                 o[nd:] = op
         else:
             out = ops.packed_empty(T, self.hq * self.D, self.dtype, self.device) if slabs is not None else None
             o = ops.paged_decode(qkv, k_cache, v_cache, meta.block_tables, meta.seq_lens, self.hq, self.hkv,
-                                 self.D, self.scale, workspace=meta.decode_ws, out=out)
+                                 self.D, self.scale, workspace=meta.decode_ws, out=out, kv_scale=kv_scale)
         return o
 
     def _mlp(self, L: dict, x: torch.Tensor, meta: AttnMeta) -> torch.Tensor:

@@ -156,6 +156,49 @@ def dequantize_rows_fp8(codes: torch.Tensor, scale: torch.Tensor, dtype=torch.bf
     return (codes.float() * scale.float()[:, None]).to(dtype)
 
 
+# ---- FP8 (e4m3) KV cache.  THE definition of the format; the kernels (csrc/common.h), the CPU
+# references and the engine mirror it.  Codes sit in the bf16 cache's index order, one byte per
+# element; kv_scale [.., NB, Hkv, 2, 16] fp32 holds one power-of-two scale per (token, kv head):
+# [.., 0, t] for K (after RoPE), [.., 1, t] for V of block token t, tokens in sequence order.
+KV_BLOCK = 16
+KV_EXP_MAX = 60  # |e| <= 60: 2^e, 2^-e and every code * 2^e stay normal bf16 / fp32 numbers
+
+
+def quantize_kv(x: torch.Tensor) -> tuple:
+    """[T, Hkv, D] -> (codes [T, Hkv, D] float8_e4m3fn, scale [T, Hkv] fp32): the rule of
+    :func:`quantize_rows_fp8` over the D values of one token and kv head, e = ceil(log2(amax / 448))
+    clamped to [-60, 60] (0 for an all-zero vector), scale = 2^e, code = x / 2^e rounded to e4m3."""
+    xf = x.float()
+    m, ex = torch.frexp(xf.abs().amax(dim=-1) / FP8_MAX)
+    e = torch.where(m == 0.5, ex - 1, ex).clamp(-KV_EXP_MAX, KV_EXP_MAX).to(torch.int32)
+    scale = ((e + 127) << 23).view(torch.float32)
+    return (xf / scale[..., None]).clamp(-FP8_MAX, FP8_MAX).to(torch.float8_e4m3fn), scale
+
+
+def dequantize_kv(codes: torch.Tensor, scale: torch.Tensor, dtype=torch.bfloat16) -> torch.Tensor:
+    """code * 2^e, exact in bf16."""
+    return (codes.float() * scale.float()[..., None]).to(dtype)
+
+
+def kv_cache_alloc(L: int, nb: int, hkv: int, D: int, dtype, device) -> tuple:
+    """The paged KV cache of ``L`` layers and ``nb`` 16-token blocks, zeroed - the single owner of
+    its layout: (k_cache [L, nb, Hkv, D/8, 16, 8], v_cache [L, nb, Hkv, D, 16] with a block's tokens
+    in v_perm order), and for ``dtype=torch.float8_e4m3fn`` also kv_scale [L, nb, Hkv, 2, 16] fp32."""
+    k = torch.zeros(L, nb, hkv, D // 8, KV_BLOCK, 8, dtype=dtype, device=device)
+    v = torch.zeros(L, nb, hkv, D, KV_BLOCK, dtype=dtype, device=device)
+    if dtype != torch.float8_e4m3fn:
+        return k, v
+    return k, v, torch.zeros(L, nb, hkv, 2, KV_BLOCK, dtype=torch.float32, device=device)
+
+
+def kv_bytes_per_block(L: int, hkv: int, D: int, dtype) -> int:
+    """Bytes one 16-token block takes over all layers: K + V elements, plus the scales for fp8."""
+    n = 2 * L * hkv * D * KV_BLOCK * torch.empty(0, dtype=dtype).element_size()
+    if dtype == torch.float8_e4m3fn:
+        n += L * hkv * 2 * KV_BLOCK * 4
+    return n
+
+
 def pack_skinny_f8(q: torch.Tensor) -> torch.Tensor:
     """e4m3 codes [N, K] -> the fragment-packed [N/16, K/64, 64, 16] layout of gemm_dec's fp8 form:
     block (n-tile j, k-step pair p) holds, for lane l = 16 q + r, the 8 codes
@@ -834,22 +877,27 @@ def resolve_ids(ids: torch.Tensor, src: torch.Tensor, prev: torch.Tensor,
 def rope_and_cache(qkv: torch.Tensor, positions: torch.Tensor, cos_sin: torch.Tensor,
                    k_cache: Optional[torch.Tensor], v_cache: Optional[torch.Tensor],
                    slot_mapping: Optional[torch.Tensor], Hq: int, Hkv: int, D: int,
-                   apply_rope: bool = True, partial: Optional[torch.Tensor] = None, nslabs: int = 0) -> None:
+                   apply_rope: bool = True, partial: Optional[torch.Tensor] = None, nslabs: int = 0,
+                   kv_scale: Optional[torch.Tensor] = None) -> None:
     """In place: rotate q and k inside the fused QKV rows; write k, v into the paged cache.
     With ``partial`` (GPU), the QKV values are first reduced from ``nslabs`` fp32 split-K slabs
-    [nslabs, T, (Hq+2Hkv)*D] (skinny_slabs) and the reduced rows are written to ``qkv``."""
+    [nslabs, T, (Hq+2Hkv)*D] (skinny_slabs) and the reduced rows are written to ``qkv``.
+    An e4m3 cache (``kv_scale`` its scales, :func:`kv_cache_alloc`) takes every token quantised
+    from the rotated rows (:func:`quantize_kv`)."""
     if not _gpu(qkv):
         if partial is not None:
             T, n = qkv.shape[0], qkv.shape[1]
             qkv.copy_(partial[: nslabs * T * n].view(nslabs, T, n).sum(0).to(qkv.dtype))
-        ref.rope_and_cache(qkv, positions, cos_sin, k_cache, v_cache, slot_mapping, Hq, Hkv, D, apply_rope)
+        ref.rope_and_cache(qkv, positions, cos_sin, k_cache, v_cache, slot_mapping, Hq, Hkv, D, apply_rope,
+                           kv_scale=kv_scale)
         return
     empty = _empty_i32(qkv.device)
     native().rope_and_cache(qkv, positions, cos_sin,
                             k_cache if k_cache is not None else empty,
                             v_cache if v_cache is not None else empty,
                             slot_mapping if slot_mapping is not None else empty,
-                            Hq, Hkv, D, apply_rope, partial, nslabs)
+                            Hq, Hkv, D, apply_rope, partial, nslabs,
+                            kv_scale if k_cache is not None and slot_mapping is not None else None)
 
 
 _EMPTY = {}
@@ -891,9 +939,9 @@ def decode_workspace(max_batch: int, Hq: int, D: int, max_model_len: int = 0, de
 def paged_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, block_tables: torch.Tensor,
                  seq_lens: torch.Tensor, Hq: int, Hkv: int, D: int, scale: float,
                  workspace: Optional[tuple] = None, out: Optional[torch.Tensor] = None,
-                 splits: Optional[int] = None) -> torch.Tensor:
+                 splits: Optional[int] = None, kv_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     if not _gpu(q):
-        r = cpu_attn.paged_decode(q, k_cache, v_cache, block_tables, seq_lens, Hq, Hkv, D, scale)
+        r = cpu_attn.paged_decode(q, k_cache, v_cache, block_tables, seq_lens, Hq, Hkv, D, scale, kv_scale=kv_scale)
         if out is not None and out.dim() == 4:  # fragment-packed output (gemm_skinny A operand)
             r = pack_activation(r)
         return out.copy_(r) if out is not None else r
@@ -904,7 +952,7 @@ def paged_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, 
         out = torch.empty(B, Hq * D, dtype=q.dtype, device=q.device)
     S = splits or decode_splits(B, Hkv)
     native().paged_decode(out, q, k_cache, v_cache, block_tables, seq_lens, workspace[0], workspace[1],
-                          Hq, Hkv, D, scale, S)
+                          Hq, Hkv, D, scale, S, kv_scale)
     return out
 
 
@@ -912,27 +960,32 @@ def paged_decode_fused(slabs: torch.Tensor, nslabs: int, positions: torch.Tensor
                        slot_mapping: Optional[torch.Tensor], k_cache: torch.Tensor, v_cache: torch.Tensor,
                        block_tables: torch.Tensor, seq_lens: torch.Tensor, Hq: int, Hkv: int, D: int, scale: float,
                        workspace: Optional[tuple] = None, out: Optional[torch.Tensor] = None,
-                       splits: Optional[int] = None) -> torch.Tensor:
+                       splits: Optional[int] = None, kv_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """paged_decode with rope_and_cache folded in: the new token's q / k / v are the sum of the qkv
     projection's ``nslabs`` fp32 split-K slabs [nslabs, B, (Hq + 2 Hkv) * D] (skinny_slabs),
     rounded to the cache dtype, q / k rotated at ``positions``, k / v written to the cache at
-    ``slot_mapping``; attention over the cached tokens plus the new one (D = 128 on the GPU)."""
+    ``slot_mapping``; attention over the cached tokens plus the new one (D = 128 on the GPU).
+    With an e4m3 cache (``kv_scale``) the new token is quantised in the kernel and attended
+    dequantised, as every later step will read it."""
     B = seq_lens.shape[0]
+    act = torch.bfloat16 if is_fp8(k_cache) else k_cache.dtype
     if not _gpu(slabs):
         n = (Hq + 2 * Hkv) * D
-        qkv = slabs[: nslabs * B * n].view(nslabs, B, n).sum(0).to(k_cache.dtype)
-        ref.rope_and_cache(qkv, positions, cos_sin, k_cache, v_cache, slot_mapping, Hq, Hkv, D, True)
-        return paged_decode(qkv, k_cache, v_cache, block_tables, seq_lens, Hq, Hkv, D, scale, out=out)
+        qkv = slabs[: nslabs * B * n].view(nslabs, B, n).sum(0).to(act)
+        ref.rope_and_cache(qkv, positions, cos_sin, k_cache, v_cache, slot_mapping, Hq, Hkv, D, True,
+                           kv_scale=kv_scale)
+        return paged_decode(qkv, k_cache, v_cache, block_tables, seq_lens, Hq, Hkv, D, scale, out=out,
+                            kv_scale=kv_scale)
     if workspace is None:
         workspace = decode_workspace(B, Hq, D, device=slabs.device)
     if out is None:
-        out = torch.empty(B, Hq * D, dtype=k_cache.dtype, device=slabs.device)
+        out = torch.empty(B, Hq * D, dtype=act, device=slabs.device)
     S = splits or decode_splits(B, Hkv)
     merge = workspace[2] if DECODE_MERGE and len(workspace) > 2 else _empty_i32(slabs.device)
     native().paged_decode_fused(out, slabs, nslabs, positions, cos_sin,
                                 slot_mapping if slot_mapping is not None else _empty_i32(slabs.device),
                                 k_cache, v_cache, block_tables, seq_lens, workspace[0], workspace[1], Hq, Hkv, D,
-                                scale, S, merge)
+                                scale, S, merge, kv_scale)
     return out
 
 
@@ -963,14 +1016,17 @@ def prefill_qblocks(cu_seqlens_cpu: list[int], block: int = 128, ctx_starts: Opt
 
 def flash_prefill(qkv: torch.Tensor, cu_seqlens: torch.Tensor, Hq: int, Hkv: int, D: int, scale: float,
                   qblocks: Optional[tuple[torch.Tensor, torch.Tensor]] = None,
-                  out: Optional[torch.Tensor] = None, paged: Optional[tuple] = None) -> torch.Tensor:
+                  out: Optional[torch.Tensor] = None, paged: Optional[tuple] = None,
+                  kv_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Causal varlen attention of the prefill rows.  ``paged = (ctx_start, k_cache, v_cache,
     block_tables)``: each sequence's rows are its NEW tokens at positions ctx_start.. and the
-    keys/values (cached prefix + new) are read from the paged cache."""
+    keys/values (cached prefix + new) are read from the paged cache.  With an e4m3 cache
+    (``kv_scale``) only the cached prefix is read from the cache (dequantised); this step's own
+    tokens are attended unquantised from the qkv rows (the v1 kernel's fp8 form)."""
     if not _gpu(qkv):
         if paged is not None:
             cs, kc, vc, bt = paged
-            return cpu_attn.paged_prefill(qkv, cu_seqlens, cs, kc, vc, bt, Hq, Hkv, D, scale)
+            return cpu_attn.paged_prefill(qkv, cu_seqlens, cs, kc, vc, bt, Hq, Hkv, D, scale, kv_scale=kv_scale)
         return cpu_attn.flash_prefill(qkv, cu_seqlens, Hq, Hkv, D, scale)
     if qblocks is None:
         qs, st = prefill_qblocks(cu_seqlens.tolist())
@@ -980,10 +1036,11 @@ def flash_prefill(qkv: torch.Tensor, cu_seqlens: torch.Tensor, Hq: int, Hkv: int
         out = torch.empty(qkv.shape[0], Hq * D, dtype=qkv.dtype, device=qkv.device)
     if paged is not None:
         cs, kc, vc, bt = paged
-        native().flash_prefill(out, qkv, cu_seqlens, qblocks[0], qblocks[1], Hq, Hkv, D, scale, cs, kc, vc, bt)
+        native().flash_prefill(out, qkv, cu_seqlens, qblocks[0], qblocks[1], Hq, Hkv, D, scale, cs, kc, vc, bt,
+                               kv_scale)
     else:
         native().flash_prefill(out, qkv, cu_seqlens, qblocks[0], qblocks[1], Hq, Hkv, D, scale, None, None, None,
-                               None)
+                               None, None)
     return out
 
 

@@ -28,10 +28,32 @@ def _vperm_index(bs: int, device: torch.device) -> torch.Tensor:
     return t
 
 
-def gather_batch(k_cache: torch.Tensor, v_cache: torch.Tensor, block_tables: torch.Tensor, nb: int):
+def _is_fp8(k_cache: torch.Tensor) -> bool:
+    return k_cache.dtype == torch.float8_e4m3fn
+
+
+def _dequant_blocks(k_cache, v_cache, kv_scale, bt, dtype):
+    """The gathered blocks of an e4m3 cache, dequantised in the cache's own layouts: kb
+    [B, nb, Hkv, D/8, bs, 8], vb [B, nb, Hkv, D, bs] (v_perm order).  Exact in bf16."""
+    bs = k_cache.shape[3]
+    sc = kv_scale[bt]  # [B, nb, Hkv, 2, bs], tokens in sequence order
+    kb = k_cache.view(torch.uint8)[bt].view(torch.float8_e4m3fn).float() * sc[:, :, :, 0, None, :, None]
+    vs = sc[:, :, :, 1].index_select(-1, _vperm_index(bs, sc.device))  # the scale of the token at each position
+    vb = v_cache.view(torch.uint8)[bt].view(torch.float8_e4m3fn).float() * vs[:, :, :, None, :]
+    return kb.to(dtype), vb.to(dtype)
+
+
+def gather_batch(k_cache: torch.Tensor, v_cache: torch.Tensor, block_tables: torch.Tensor, nb: int, kv_scale=None):
     """Keys / values of the first ``nb`` blocks of every row of ``block_tables`` [B, >= nb]:
-    fp32 [B, Hkv, nb * bs, D] each, tokens in sequence order (entries < 0 read block 0; mask them)."""
+    fp32 [B, Hkv, nb * bs, D] each, tokens in sequence order (entries < 0 read block 0; mask them).
+    An e4m3 cache (``kv_scale``) comes back dequantised."""
     bt = block_tables[:, :nb].long().clamp(min=0)
+    if _is_fp8(k_cache):
+        kb, vb = _dequant_blocks(k_cache, v_cache, kv_scale, bt, torch.float32)
+        B, _, hkv, p, bs, _ = kb.shape
+        k = kb.permute(0, 2, 1, 4, 3, 5).reshape(B, hkv, nb * bs, p * 8)
+        vb = vb.index_select(-1, _vperm_index(bs, v_cache.device))
+        return k, vb.permute(0, 2, 1, 4, 3).reshape(B, hkv, nb * bs, -1)
     kb = k_cache[bt]  # [B, nb, Hkv, D/8, bs, 8]
     B, _, hkv, p, bs, _ = kb.shape
     k = kb.permute(0, 2, 1, 4, 3, 5).reshape(B, hkv, nb * bs, p * 8).float()
@@ -41,7 +63,7 @@ def gather_batch(k_cache: torch.Tensor, v_cache: torch.Tensor, block_tables: tor
 
 
 def paged_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, block_tables: torch.Tensor,
-                 seq_lens: torch.Tensor, Hq: int, Hkv: int, D: int, scale: float) -> torch.Tensor:
+                 seq_lens: torch.Tensor, Hq: int, Hkv: int, D: int, scale: float, kv_scale=None) -> torch.Tensor:
     """One query row per sequence (q [B, >= Hq*D]) over its paged cache; [B, Hq*D] in q.dtype.
 
     The blocks are gathered once for the whole batch and used in the cache's own layouts (no
@@ -61,7 +83,10 @@ def paged_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, 
     bs = k_cache.shape[3]
     nb = (lmax + bs - 1) // bs
     bt = block_tables[:, :nb].long().clamp(min=0)
-    kb, vb = k_cache[bt], v_cache[bt]  # [B, nb, Hkv, D/8, bs, 8], [B, nb, Hkv, D, bs]
+    if _is_fp8(k_cache):  # every cached token dequantised, the step's own new token included
+        kb, vb = _dequant_blocks(k_cache, v_cache, kv_scale, bt, q.dtype)
+    else:
+        kb, vb = k_cache[bt], v_cache[bt]  # [B, nb, Hkv, D/8, bs, 8], [B, nb, Hkv, D, bs]
     G = Hq // Hkv
     qv = q[:, : Hq * D].reshape(B, Hkv, G, D // 8, 8).to(kb.dtype)
     s = torch.einsum("bhgpe,bnhpte->bhgnt", qv, kb).float().reshape(B, Hkv, G, nb * bs) * scale
@@ -107,8 +132,10 @@ def flash_prefill(qkv: torch.Tensor, cu_seqlens: torch.Tensor, Hq: int, Hkv: int
 
 def paged_prefill(qkv: torch.Tensor, cu_seqlens: torch.Tensor, ctx_start: torch.Tensor, k_cache: torch.Tensor,
                   v_cache: torch.Tensor, block_tables: torch.Tensor, Hq: int, Hkv: int, D: int,
-                  scale: float) -> torch.Tensor:
-    """Each sequence's new rows (positions ctx_start ..) against its cached prefix + new tokens."""
+                  scale: float, kv_scale=None) -> torch.Tensor:
+    """Each sequence's new rows (positions ctx_start ..) against its cached prefix + new tokens.
+    An e4m3 cache gives only the cached prefix (dequantised); this step's own keys / values are
+    the unquantised qkv rows, as in the cache-less prefill."""
     T = qkv.shape[0]
     out = torch.empty(T, Hq * D, dtype=qkv.dtype, device=qkv.device)
     cu, cs = cu_seqlens.tolist(), ctx_start.tolist()
@@ -118,7 +145,12 @@ def paged_prefill(qkv: torch.Tensor, cu_seqlens: torch.Tensor, ctx_start: torch.
         if b <= a:
             continue
         L = cs[i] + b - a
-        k, v = gather_batch(k_cache, v_cache, block_tables[i:i + 1], (L + bs - 1) // bs)
+        k, v = gather_batch(k_cache, v_cache, block_tables[i:i + 1], (L + bs - 1) // bs, kv_scale)
+        k, v = k[0, :, :L], v[0, :, :L]
+        if _is_fp8(k_cache):
+            x = qkv[a:b].float()
+            k = torch.cat([k[:, :cs[i]], x[:, Hq * D:(Hq + Hkv) * D].reshape(b - a, Hkv, D).transpose(0, 1)], dim=1)
+            v = torch.cat([v[:, :cs[i]], x[:, (Hq + Hkv) * D:(Hq + 2 * Hkv) * D].reshape(b - a, Hkv, D).transpose(0, 1)], dim=1)
         q = qkv[a:b, : Hq * D].view(b - a, Hq, D)
-        out[a:b] = _causal(q, k[0, :, :L], v[0, :, :L], scale, Hq, Hkv).reshape(b - a, -1).to(qkv.dtype)
+        out[a:b] = _causal(q, k, v, scale, Hq, Hkv).reshape(b - a, -1).to(qkv.dtype)
     return out

@@ -20,20 +20,21 @@ int k8sllm_embedding(void* out, const int* ids, const void* weight, long T, int 
 int k8sllm_resolve_ids(int* out, const int* ids, const int* src, const int* prev, int n, hipStream_t s);
 int k8sllm_rope_cache(void* qkv, long qkv_stride, const int* positions, const float* cos_sin, void* k_cache,
                       void* v_cache, const int* slot_mapping, long T, int Hq, int Hkv, int D, int block_size,
-                      int apply_rope, const float* partial, int S, hipStream_t s);
+                      int apply_rope, const float* partial, int S, float* kv_scale, hipStream_t s);
 int k8sllm_paged_decode(void* out, long out_stride, float* part_out, float* part_ml, const void* q, long q_stride,
                         const void* k_cache, const void* v_cache, const int* block_tables, int bt_stride,
-                        const int* seq_lens, int B, int Hq, int Hkv, int D, int S, float scale, hipStream_t s);
+                        const int* seq_lens, int B, int Hq, int Hkv, int D, int S, float scale, const float* kv_scale,
+                        hipStream_t s);
 void k8sllm_decode_tw_force(int tw);
 int k8sllm_paged_decode_fused(void* out, long out_stride, float* part_out, float* part_ml, const float* slabs,
                               int nslabs, const int* positions, const float* cos_sin, const int* slot_mapping,
                               void* k_cache, void* v_cache, const int* block_tables, int bt_stride,
                               const int* seq_lens, int B, int Hq, int Hkv, int D, int S, float scale, int* merge_ctr,
-                              hipStream_t s);
+                              float* kv_scale, hipStream_t s);
 int k8sllm_flash_prefill(void* out, long out_stride, const void* qkv, long qkv_stride, const int* cu_seqlens,
                          const int* qb_seq, const int* qb_start, int n_qblocks, int Hq, int Hkv, int D, float scale,
                          const int* ctx_start, const void* k_cache, const void* v_cache, const int* block_tables,
-                         int bt_stride, hipStream_t s);
+                         int bt_stride, const float* kv_scale, hipStream_t s);
 int k8sllm_sample(int* out, const void* logits, int is_fp32, long B, long stride, int V, const float* temps,
                   const int* top_k, const float* top_p, const int64_t* rng, float* pv, int* pi, int advance, hipStream_t s);
 int k8sllm_sample_parts(long B, int V);
@@ -127,6 +128,32 @@ void fused_add_rms_norm(torch::Tensor out, torch::Tensor x, torch::Tensor residu
         "fused_add_rms_norm");
 }
 
+// The paged KV cache of one layer: bf16 (no scales), or e4m3 codes in the same index order with
+// kv_scale [NB, Hkv, 2, 16] fp32 (ops.kv_cache_alloc; head_dim 128, 16-token blocks).  Returns the
+// scales pointer (nullptr for bf16).
+float* kv_cache_pair(const torch::Tensor& k_cache, const torch::Tensor& v_cache,
+                     const c10::optional<torch::Tensor>& kv_scale, int64_t Hkv, int64_t D) {
+  if (k_cache.scalar_type() != torch::kFloat8_e4m3fn) {
+    dev_bf16(k_cache, "k_cache"); dev_bf16(v_cache, "v_cache");
+    TORCH_CHECK(!kv_scale.has_value(), "kv_scale goes with an e4m3 cache");
+    return nullptr;
+  }
+  TORCH_CHECK(k_cache.is_cuda() && v_cache.is_cuda() && v_cache.scalar_type() == torch::kFloat8_e4m3fn,
+              "fp8 KV cache: k_cache and v_cache must both be e4m3 GPU tensors");
+  TORCH_CHECK(D == 128, "fp8 KV cache: head_dim 128 only");
+  TORCH_CHECK(kv_scale.has_value(), "fp8 KV cache needs kv_scale");
+  TORCH_CHECK(k_cache.is_contiguous() && v_cache.is_contiguous() && k_cache.dim() == 5 && v_cache.dim() == 4 &&
+                  k_cache.size(1) == Hkv && k_cache.size(2) == D / 8 && k_cache.size(3) == 16 && k_cache.size(4) == 8 &&
+                  v_cache.size(0) == k_cache.size(0) && v_cache.size(1) == Hkv && v_cache.size(2) == D &&
+                  v_cache.size(3) == 16,
+              "fp8 KV cache: caches [NB, Hkv, D/8, 16, 8] / [NB, Hkv, D, 16]");
+  TORCH_CHECK(kv_scale->is_cuda() && kv_scale->scalar_type() == torch::kFloat32 && kv_scale->is_contiguous() &&
+                  kv_scale->dim() == 4 && kv_scale->size(0) == k_cache.size(0) && kv_scale->size(1) == Hkv &&
+                  kv_scale->size(2) == 2 && kv_scale->size(3) == 16,
+              "fp8 KV cache: kv_scale [NB, Hkv, 2, 16] fp32");
+  return kv_scale->data_ptr<float>();
+}
+
 void layer_norm(torch::Tensor out, torch::Tensor x, torch::Tensor w, torch::Tensor b, double eps) {
   dev_bf16(out, "out"); dev_bf16(x, "x"); dev_bf16(w, "w"); dev_bf16(b, "b");
   TORCH_CHECK(x.is_contiguous() && out.is_contiguous(), "layer_norm: contiguous");
@@ -172,16 +199,18 @@ void resolve_ids(torch::Tensor out, torch::Tensor ids, torch::Tensor src, torch:
 
 void rope_and_cache(torch::Tensor qkv, torch::Tensor positions, torch::Tensor cos_sin, torch::Tensor k_cache,
                     torch::Tensor v_cache, torch::Tensor slot_mapping, int64_t Hq, int64_t Hkv, int64_t D,
-                    bool apply_rope, c10::optional<torch::Tensor> partial, int64_t S) {
+                    bool apply_rope, c10::optional<torch::Tensor> partial, int64_t S,
+                    c10::optional<torch::Tensor> kv_scale) {
   dev_bf16(qkv, "qkv"); dev_i32(positions, "positions");
   TORCH_CHECK(qkv.stride(-1) == 1 && qkv.dim() == 2, "qkv must be [T, (Hq+2Hkv)*D] with unit inner stride");
   TORCH_CHECK(qkv.size(1) >= (Hq + 2 * Hkv) * D, "qkv width");
   TORCH_CHECK(cos_sin.scalar_type() == torch::kFloat32 && cos_sin.is_contiguous() && cos_sin.size(1) == D, "cos_sin");
   const bool has_cache = slot_mapping.numel() > 0;
   int block_size = 16;
+  float* ksp = nullptr;
   if (has_cache) {
     dev_i32(slot_mapping, "slot_mapping");
-    dev_bf16(k_cache, "k_cache"); dev_bf16(v_cache, "v_cache");
+    ksp = kv_cache_pair(k_cache, v_cache, kv_scale, Hkv, D);
     // k_cache [NB, Hkv, D/8, BS, 8], v_cache [NB, Hkv, D, BS]
     TORCH_CHECK(k_cache.dim() == 5 && k_cache.size(1) == Hkv && k_cache.size(4) == 8, "k_cache layout");
     TORCH_CHECK(v_cache.dim() == 4 && v_cache.size(1) == Hkv && v_cache.size(2) == D, "v_cache layout");
@@ -196,14 +225,16 @@ void rope_and_cache(torch::Tensor qkv, torch::Tensor positions, torch::Tensor co
   check(k8sllm_rope_cache(qkv.data_ptr(), qkv.stride(0), positions.data_ptr<int>(), cos_sin.data_ptr<float>(),
                           has_cache ? k_cache.data_ptr() : nullptr, has_cache ? v_cache.data_ptr() : nullptr,
                           has_cache ? slot_mapping.data_ptr<int>() : nullptr, qkv.size(0), (int)Hq, (int)Hkv, (int)D,
-                          block_size, apply_rope ? 1 : 0, pp, (int)S, cur()),
+                          block_size, apply_rope ? 1 : 0, pp, (int)S, ksp, cur()),
         "rope_and_cache");
 }
 
 void paged_decode(torch::Tensor out, torch::Tensor q, torch::Tensor k_cache, torch::Tensor v_cache,
                   torch::Tensor block_tables, torch::Tensor seq_lens, torch::Tensor part_out, torch::Tensor part_ml,
-                  int64_t Hq, int64_t Hkv, int64_t D, double scale, int64_t splits) {
-  dev_bf16(out, "out"); dev_bf16(q, "q"); dev_bf16(k_cache, "k_cache"); dev_bf16(v_cache, "v_cache");
+                  int64_t Hq, int64_t Hkv, int64_t D, double scale, int64_t splits,
+                  c10::optional<torch::Tensor> kv_scale) {
+  dev_bf16(out, "out"); dev_bf16(q, "q");
+  const float* ksp = kv_cache_pair(k_cache, v_cache, kv_scale, Hkv, D);
   dev_i32(block_tables, "block_tables"); dev_i32(seq_lens, "seq_lens");
   TORCH_CHECK(q.dim() == 2 && q.stride(1) == 1, "q must be [B, >=Hq*D] rows");
   const bool packed = out.dim() == 4;  // fragment-packed [ceil(B/16), Hq*D/32, 64, 8] for gemm_skinny
@@ -224,7 +255,7 @@ void paged_decode(torch::Tensor out, torch::Tensor q, torch::Tensor k_cache, tor
                             part_out.data_ptr<float>(), part_ml.data_ptr<float>(),
                             q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(),
                             block_tables.data_ptr<int>(), (int)block_tables.stride(0), seq_lens.data_ptr<int>(), B,
-                            (int)Hq, (int)Hkv, (int)D, (int)splits, (float)scale, cur()),
+                            (int)Hq, (int)Hkv, (int)D, (int)splits, (float)scale, ksp, cur()),
         "paged_decode");
 }
 
@@ -235,8 +266,10 @@ void paged_decode_fused(torch::Tensor out, torch::Tensor slabs, int64_t nslabs, 
                         torch::Tensor cos_sin, torch::Tensor slot_mapping, torch::Tensor k_cache,
                         torch::Tensor v_cache, torch::Tensor block_tables, torch::Tensor seq_lens,
                         torch::Tensor part_out, torch::Tensor part_ml, int64_t Hq, int64_t Hkv, int64_t D,
-                        double scale, int64_t splits, torch::Tensor merge_ctr) {
-  dev_bf16(out, "out"); dev_bf16(k_cache, "k_cache"); dev_bf16(v_cache, "v_cache");
+                        double scale, int64_t splits, torch::Tensor merge_ctr,
+                        c10::optional<torch::Tensor> kv_scale) {
+  dev_bf16(out, "out");
+  float* ksp = kv_cache_pair(k_cache, v_cache, kv_scale, Hkv, D);
   dev_i32(block_tables, "block_tables"); dev_i32(seq_lens, "seq_lens"); dev_i32(positions, "positions");
   TORCH_CHECK(D == 128, "paged_decode_fused: head_dim 128");
   const int B = (int)seq_lens.size(0);
@@ -275,7 +308,7 @@ void paged_decode_fused(torch::Tensor out, torch::Tensor slabs, int64_t nslabs, 
                                   has_slots ? slot_mapping.data_ptr<int>() : nullptr, k_cache.data_ptr(),
                                   v_cache.data_ptr(), block_tables.data_ptr<int>(), (int)block_tables.stride(0),
                                   seq_lens.data_ptr<int>(), B, (int)Hq, (int)Hkv, (int)D, (int)splits, (float)scale,
-                                  merge ? merge_ctr.data_ptr<int>() : nullptr, cur()),
+                                  merge ? merge_ctr.data_ptr<int>() : nullptr, ksp, cur()),
         "paged_decode_fused");
 }
 
@@ -285,7 +318,8 @@ void paged_decode_fused(torch::Tensor out, torch::Tensor slabs, int64_t nslabs, 
 void flash_prefill(torch::Tensor out, torch::Tensor qkv, torch::Tensor cu_seqlens, torch::Tensor qb_seq,
                    torch::Tensor qb_start, int64_t Hq, int64_t Hkv, int64_t D, double scale,
                    c10::optional<torch::Tensor> ctx_start, c10::optional<torch::Tensor> k_cache,
-                   c10::optional<torch::Tensor> v_cache, c10::optional<torch::Tensor> block_tables) {
+                   c10::optional<torch::Tensor> v_cache, c10::optional<torch::Tensor> block_tables,
+                   c10::optional<torch::Tensor> kv_scale) {
   dev_bf16(out, "out"); dev_bf16(qkv, "qkv");
   dev_i32(cu_seqlens, "cu_seqlens"); dev_i32(qb_seq, "qb_seq"); dev_i32(qb_start, "qb_start");
   TORCH_CHECK(qkv.dim() == 2 && qkv.stride(1) == 1, "qkv rows");
@@ -293,11 +327,12 @@ void flash_prefill(torch::Tensor out, torch::Tensor qkv, torch::Tensor cu_seqlen
   const int* cs = nullptr;
   const void *kc = nullptr, *vc = nullptr;
   const int* bt = nullptr;
+  const float* ksp = nullptr;
   int bts = 0;
   if (ctx_start.has_value()) {
     TORCH_CHECK(k_cache.has_value() && v_cache.has_value() && block_tables.has_value(), "paged prefill needs caches");
     dev_i32(*ctx_start, "ctx_start"); dev_i32(*block_tables, "block_tables");
-    dev_bf16(*k_cache, "k_cache"); dev_bf16(*v_cache, "v_cache");
+    ksp = kv_cache_pair(*k_cache, *v_cache, kv_scale, Hkv, D);
     TORCH_CHECK(k_cache->dim() == 5 && k_cache->size(1) == Hkv && k_cache->size(3) == 16 && k_cache->size(4) == 8,
                 "k_cache layout [NB, Hkv, D/8, 16, 8]");
     TORCH_CHECK(v_cache->dim() == 4 && v_cache->size(1) == Hkv && v_cache->size(2) == D && v_cache->size(3) == 16,
@@ -311,7 +346,7 @@ void flash_prefill(torch::Tensor out, torch::Tensor qkv, torch::Tensor cu_seqlen
   }
   check(k8sllm_flash_prefill(out.data_ptr(), out.stride(0), qkv.data_ptr(), qkv.stride(0), cu_seqlens.data_ptr<int>(),
                              qb_seq.data_ptr<int>(), qb_start.data_ptr<int>(), (int)qb_seq.numel(), (int)Hq, (int)Hkv,
-                             (int)D, (float)scale, cs, kc, vc, bt, bts, cur()),
+                             (int)D, (float)scale, cs, kc, vc, bt, bts, ksp, cur()),
         "flash_prefill");
 }
 

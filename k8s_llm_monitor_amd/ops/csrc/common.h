@@ -69,6 +69,55 @@ __device__ __forceinline__ long act_index(int row, int col, long stride) {
 // LDS-DMA.  Paged decode reads 4-token groups, which v_perm keeps contiguous.
 __device__ __forceinline__ int v_perm(int t) { return (t & ~12) | ((t & 4) << 1) | ((t & 8) >> 1); }
 
+// ---- FP8 (OCP e4m3fn) KV cache: codes in the bf16 cache's index order (one byte per element) and
+// kv_scale [NB][Hkv][2][16] fp32 - [0][t] the K scale, [1][t] the V scale of block token t (sequence
+// order) - one power-of-two scale 2^e per (token, kv head) vector of D values:
+// e = ceil(log2(amax / 448)) clamped to [-60, 60], 0 for an all-zero vector (ops.quantize_kv).
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+
+// e of a vector whose largest magnitude is amax (a bf16 value, finite): amax = 1.f x 2^(E - 127),
+// 448 = 1.75 x 2^8, so amax <= 448 x 2^e first holds at e = E - 135, one more when 1.f > 1.75.
+__device__ __forceinline__ int kv_f8_exp(float amax) {
+  const uint32_t u = __float_as_uint(amax);
+  if (u == 0) return 0;
+  const int e = (int)(u >> 23) - 135 + ((u & 0x7fffffu) > 0x600000u ? 1 : 0);
+  return min(60, max(-60, e));
+}
+__device__ __forceinline__ float kv_f8_pow2(int e) { return __uint_as_float((uint32_t)(e + 127) << 23); }
+
+// two / eight values x inv (= 2^-e, exact) -> e4m3 codes, round to nearest even, first code in the low byte
+__device__ __forceinline__ uint32_t kv_f8_code(float x, float inv) {
+  const float y = fminf(fmaxf(x * inv, -448.f), 448.f);
+  return (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(y, 0.f, 0, false) & 0xffu;
+}
+__device__ __forceinline__ u32x2 kv_f8_code8(const float* f, float inv) {
+  float y[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) y[j] = fminf(fmaxf(f[j] * inv, -448.f), 448.f);
+  int lo = __builtin_amdgcn_cvt_pk_fp8_f32(y[0], y[1], 0, false);
+  lo = __builtin_amdgcn_cvt_pk_fp8_f32(y[2], y[3], lo, true);
+  int hi = __builtin_amdgcn_cvt_pk_fp8_f32(y[4], y[5], 0, false);
+  hi = __builtin_amdgcn_cvt_pk_fp8_f32(y[6], y[7], hi, true);
+  return u32x2{(uint32_t)lo, (uint32_t)hi};
+}
+
+// 8 codes (two dwords) x scale -> the bf16x8 MFMA operand; exact: scale is a power of two and an
+// e4m3 value has 4 significant bits
+__device__ __forceinline__ bf16x8 kv_f8_deq8(u32x2 c, float scale) {
+  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+  const bf16x2 a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c.x, scale, false);
+  const bf16x2 b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c.x, scale, true);
+  const bf16x2 d = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c.y, scale, false);
+  const bf16x2 e = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c.y, scale, true);
+  return bf16x8{a[0], a[1], b[0], b[1], d[0], d[1], e[0], e[1]};
+}
+__device__ __forceinline__ bf16_t kv_f8_deq(uint32_t code, float scale) {
+  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+  const bf16x2 a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(code, scale, false);
+  const __bf16 b = a[0];
+  return __builtin_bit_cast(bf16_t, b);
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);

@@ -42,7 +42,10 @@ __device__ __forceinline__ float xor32_sum(float x) {
   return __uint_as_float(r[0]) + __uint_as_float(r[1]);
 }
 
-template <int D, bool PAGED>
+// F8 (PAGED only): the cache holds e4m3 codes + per-token power-of-two scales (common.h); the
+// cached prefix is dequantised (exactly) while it is staged, this step's own tokens stay the
+// unquantised bf16 qkv rows.
+template <int D, bool PAGED, bool F8 = false>
 __global__ __launch_bounds__(256, 2) void flash_prefill_kernel(bf16_t* __restrict__ out, long out_stride,
                                                                const bf16_t* __restrict__ qkv, long qkv_stride,
                                                                const int* __restrict__ cu_seqlens,
@@ -51,7 +54,8 @@ __global__ __launch_bounds__(256, 2) void flash_prefill_kernel(bf16_t* __restric
                                                                float scale_log2, const int* __restrict__ ctx_start,
                                                                const bf16_t* __restrict__ k_cache,
                                                                const bf16_t* __restrict__ v_cache,
-                                                               const int* __restrict__ block_tables, int bt_stride) {
+                                                               const int* __restrict__ block_tables, int bt_stride,
+                                                               const float* __restrict__ kv_scale) {
   static_assert(D == 128, "prefill kernel is specialised for head_dim 128");
   constexpr int KS = D / 16;  // 8 k-steps over the head dim
   constexpr int DT = D / 32;  // 4 output tiles of 32 dims
@@ -129,6 +133,17 @@ __global__ __launch_bounds__(256, 2) void flash_prefill_kernel(bf16_t* __restric
           const bf16_t* row = base + (long)(kr - cst) * qkv_stride;
           kv = *reinterpret_cast<const uint4*>(row + koff + ch * 8);
           vv = *reinterpret_cast<const uint4*>(row + voff + ch * 8);
+        } else if (F8 && kr < cst) {
+          const long blk = bt[kr >> 4];
+          const uint8_t* kc = reinterpret_cast<const uint8_t*>(k_cache);
+          const uint8_t* vp = reinterpret_cast<const uint8_t*>(v_cache) + ((blk * Hkv + kvh) * D + ch * 8) * 16 + v_perm(kr & 15);
+          const float* sb = kv_scale + (blk * Hkv + kvh) * 32 + (kr & 15);
+          const u32x2 kq = *reinterpret_cast<const u32x2*>(kc + (((blk * Hkv + kvh) * CH + ch) * 16 + (kr & 15)) * 8);
+          u32x2 vq;
+          vq.x = (uint32_t)vp[0] | ((uint32_t)vp[16] << 8) | ((uint32_t)vp[32] << 16) | ((uint32_t)vp[48] << 24);
+          vq.y = (uint32_t)vp[64] | ((uint32_t)vp[80] << 8) | ((uint32_t)vp[96] << 16) | ((uint32_t)vp[112] << 24);
+          kv = __builtin_bit_cast(uint4, kv_f8_deq8(kq, sb[0]));
+          vv = __builtin_bit_cast(uint4, kv_f8_deq8(vq, sb[16]));
         } else if (kr < cst) {
           const long blk = bt[kr >> 4];
           kv = *reinterpret_cast<const uint4*>(k_cache + (((blk * Hkv + kvh) * CH + ch) * 16 + (kr & 15)) * 8);
@@ -520,11 +535,19 @@ using namespace k8sllm;
 extern "C" int k8sllm_flash_prefill(void* out, long out_stride, const void* qkv, long qkv_stride,
                                     const int* cu_seqlens, const int* qb_seq, const int* qb_start, int n_qblocks,
                                     int Hq, int Hkv, int D, float scale, const int* ctx_start, const void* k_cache,
-                                    const void* v_cache, const int* block_tables, int bt_stride, hipStream_t s) {
+                                    const void* v_cache, const int* block_tables, int bt_stride,
+                                    const float* kv_scale, hipStream_t s) {
   if (n_qblocks <= 0) return 0;
   if (D != 128 || Hq % Hkv != 0) return -1;
   const float sl2 = scale * 1.4426950408889634f;
   const int G = Hq / Hkv;
+  if (ctx_start != nullptr && kv_scale != nullptr) {
+    // fp8 cache: v2 stages cache tiles verbatim by LDS-DMA, so every G runs v1 with the fp8 branch
+    hipLaunchKernelGGL((flash_prefill_kernel<128, true, true>), dim3(Hq, n_qblocks), dim3(256), 0, s, (bf16_t*)out,
+                       out_stride, (const bf16_t*)qkv, qkv_stride, cu_seqlens, qb_seq, qb_start, Hq, Hkv, sl2,
+                       ctx_start, (const bf16_t*)k_cache, (const bf16_t*)v_cache, block_tables, bt_stride, kv_scale);
+    return (int)hipGetLastError();
+  }
   // bt_stride = the block-table width = most blocks a sequence can hold: <= 2048 - 3 fit the LDS copy
   if (ctx_start != nullptr && (G == 2 || G == 4 || G == 8) && bt_stride <= 2045) {
     // v2: q-blocks of 128 rows split into 128 / QR workgroups (QR = 256 / G rows each), adjacent in y
@@ -544,11 +567,11 @@ extern "C" int k8sllm_flash_prefill(void* out, long out_stride, const void* qkv,
   if (ctx_start != nullptr) {
     hipLaunchKernelGGL((flash_prefill_kernel<128, true>), dim3(Hq, n_qblocks), dim3(256), 0, s, (bf16_t*)out,
                        out_stride, (const bf16_t*)qkv, qkv_stride, cu_seqlens, qb_seq, qb_start, Hq, Hkv, sl2,
-                       ctx_start, (const bf16_t*)k_cache, (const bf16_t*)v_cache, block_tables, bt_stride);
+                       ctx_start, (const bf16_t*)k_cache, (const bf16_t*)v_cache, block_tables, bt_stride, nullptr);
   } else {
     hipLaunchKernelGGL((flash_prefill_kernel<128, false>), dim3(Hq, n_qblocks), dim3(256), 0, s, (bf16_t*)out,
                        out_stride, (const bf16_t*)qkv, qkv_stride, cu_seqlens, qb_seq, qb_start, Hq, Hkv, sl2,
-                       nullptr, nullptr, nullptr, nullptr, 0);
+                       nullptr, nullptr, nullptr, nullptr, 0, nullptr);
   }
   return (int)hipGetLastError();
 }

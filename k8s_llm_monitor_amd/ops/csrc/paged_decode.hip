@@ -69,11 +69,24 @@ struct DecodeFuse {
   bf16_t* v_cache;
 };
 
+// F8: the cache holds e4m3 codes in the bf16 index order and kv_scale [NB][Hkv][2][16] the per-token
+// power-of-two scales (common.h).  A lane's K operand row is ONE token: its 8 codes are dequantised
+// by the conversion itself (v_cvt_scalef32_pk_bf16_fp8 with that token's scale).  A V operand's 8
+// codes are 8 tokens: they are converted unscaled and P is multiplied by its token's V scale before
+// the bf16 rounding (the 4 tokens of an accumulator's rows are one float4 of scales).  Every scale
+// is a power of two, so both forms are bit-identical to the bf16 kernel over the dequantised cache.
+// FQ + F8: the new token's k / v are quantised in the kernel (codes and scales written to the
+// cache) and the DEQUANTISED values are folded, so this step sees the token as every later one will.
+__device__ __forceinline__ bf16x8 pd_frag(bf16x8 f, float) { return f; }
+__device__ __forceinline__ bf16x8 pd_frag(u32x2 f, float scale) { return kv_f8_deq8(f, scale); }
+template <bool F8> struct PdFrag { typedef bf16x8 type; typedef bf16_t elem; };
+template <> struct PdFrag<true> { typedef u32x2 type; typedef uint8_t elem; };
+
 // TW: tokens per wave per chunk.  TW = 32: two chunk buffers per wave (double-buffered loads,
 // ~240 VGPRs: 2 waves per SIMD) for grids that fill the chip (batch 64: 512 workgroups);
 // TW = 64: one buffer of 64 tokens (~120 VGPRs: up to 4 workgroups per CU) for small, split
 // grids, where residency, not the per-wave pipeline, hides the memory latency.
-template <int D, int G, bool FQ, int TW, bool MERGE = false>
+template <int D, int G, bool FQ, int TW, bool MERGE = false, bool F8 = false>
 __global__ __launch_bounds__(256, TW == 32 ? 2 : 1) void paged_decode_kernel(bf16_t* __restrict__ out, long out_stride,
                                                            float* __restrict__ part_out,  // [B][Hq][S][D]
                                                            float* __restrict__ part_ml,   // [B][Hq][S][2]
@@ -83,7 +96,8 @@ __global__ __launch_bounds__(256, TW == 32 ? 2 : 1) void paged_decode_kernel(bf1
                                                            const int* __restrict__ block_tables, int bt_stride,
                                                            const int* __restrict__ seq_lens, int Hq, int Hkv, int S,
                                                            float scale_log2, DecodeFuse fz,
-                                                           int* __restrict__ merge_ctr) {  // MERGE: [B][Hkv], zero between launches
+                                                           int* __restrict__ merge_ctr,  // MERGE: [B][Hkv], zero between launches
+                                                           float* kv_scale) {  // F8: [NB][Hkv][2][16]
   constexpr int KS = D / 32;  // QK k-steps
   constexpr int DT = D / 16;  // PV output tiles (16 dims each)
   __shared__ float s_max[4][16];
@@ -127,9 +141,15 @@ __global__ __launch_bounds__(256, TW == 32 ? 2 : 1) void paged_decode_kernel(bf1
   // kg hold tokens 16 (kg >> 1) + 4 (kg & 1) + {0..3, 8..11} - in the V cache's v_perm order
   // (common.h) exactly positions 8 (kg & 1) .. + 7 of block 2s + (kg >> 1): ONE 16-byte load per
   // lane, dim tile and step (was two 8-byte loads from two blocks: half the V load instructions).
-  typedef bf16x8 KF[kNI][KS];
-  typedef bf16x8 VF[kNS][DT];
-  auto issue = [&](KF& kf, VF& vf, int c) {
+  typedef typename PdFrag<F8>::type frag_t;  // one lane's operand load: 16 bytes of bf16 / 8 bytes of codes
+  typedef typename PdFrag<F8>::elem elem_t;   // one cache element: bf16 / one code byte
+  typedef frag_t KF[kNI][KS];
+  typedef frag_t VF[kNS][DT];
+  typedef float KSC[F8 ? kNI : 1];  // F8: the K scale of the lane's token row, per K tile
+  typedef f32x4 VSC[F8 ? kNI : 1];  // F8: the V scales of the lane's 4 accumulator-row tokens, per K tile
+  const elem_t* kc = reinterpret_cast<const elem_t*>(k_cache);
+  const elem_t* vc = reinterpret_cast<const elem_t*>(v_cache);
+  auto issue = [&](KF& kf, VF& vf, KSC& ksc, VSC& vsc, int c) {
     const int wtok0 = c * kCH + wave * kTW;
     int phys[kNI];  // the wave's kNI blocks (16 tokens each)
 #pragma unroll
@@ -142,25 +162,34 @@ __global__ __launch_bounds__(256, TW == 32 ? 2 : 1) void paged_decode_kernel(bf1
       const int sp = i >> 1, j = i & 1;  // PV step, tile within it
       const int blk = phys[2 * sp + (col >> 3)];
       const int tok = 8 * j + 4 * ((col >> 2) & 1) + (col & 3);
-      const bf16_t* kb = k_cache + ((long)blk * Hkv + kvh) * head_block + (kg * kBS + tok) * 8;
+      const elem_t* kb = kc + ((long)blk * Hkv + kvh) * head_block + (kg * kBS + tok) * 8;
 #pragma unroll
       for (int s = 0; s < KS; ++s)
-        kf[i][s] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(kb + s * 4 * kBS * 8));
+        kf[i][s] = __builtin_nontemporal_load(reinterpret_cast<const frag_t*>(kb + s * 4 * kBS * 8));
+      if constexpr (F8) {
+        const float* sb = kv_scale + ((long)blk * Hkv + kvh) * (2 * kBS);
+        ksc[i] = sb[tok];
+        // accumulator rows r = 0..3 of tile i: tokens 8 j + 4 (kg & 1) + r of block 2 sp + (kg >> 1)
+        const float* vs = kv_scale + ((long)phys[2 * sp + (kg >> 1)] * Hkv + kvh) * (2 * kBS) + kBS + 8 * j + 4 * (kg & 1);
+        vsc[i] = *reinterpret_cast<const f32x4*>(vs);
+      }
     }
 #pragma unroll
     for (int s = 0; s < kNS; ++s) {
-      const bf16_t* vb = v_cache + ((long)phys[2 * s + (kg >> 1)] * Hkv + kvh) * head_block + col * kBS + 8 * (kg & 1);
+      const elem_t* vb = vc + ((long)phys[2 * s + (kg >> 1)] * Hkv + kvh) * head_block + col * kBS + 8 * (kg & 1);
 #pragma unroll
       for (int dt = 0; dt < DT; ++dt)
-        vf[s][dt] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(vb + 16 * dt * kBS));
+        vf[s][dt] = __builtin_nontemporal_load(reinterpret_cast<const frag_t*>(vb + 16 * dt * kBS));
     }
   };
   KF kf0, kf1;
   VF vf0, vf1;
+  KSC ks0, ks1;
+  VSC vs0, vs1;
   // the first chunks' K/V loads fly while q is loaded (FQ: reduced from the slabs and rotated)
-  issue(kf0, vf0, c0);
+  issue(kf0, vf0, ks0, vs0, c0);
   if constexpr (DB) {
-    if (c0 + 1 < c1) issue(kf1, vf1, c0 + 1);
+    if (c0 + 1 < c1) issue(kf1, vf1, ks1, vs1, c0 + 1);
   }
 
   bf16x8 qf[KS];
@@ -203,6 +232,45 @@ __global__ __launch_bounds__(256, TW == 32 ? 2 : 1) void paged_decode_kernel(bf1
 #pragma unroll
     for (int s = 0; s < KS; ++s) qf[s] = *reinterpret_cast<const bf16x8*>(&s_q[hc][32 * s + 8 * kg]);
     const int slot = fz.slot_mapping != nullptr ? fz.slot_mapping[b] : -1;
+    if constexpr (F8) {
+      // quantise the new token: amax of k and of v over D (one dim per thread of waves 0 and 1,
+      // combined through LDS), codes + scales to the cache, the dequantised values back to s_kv
+      __shared__ float s_amax[2][2];
+      if (owns_new) {  // uniform over the workgroup
+        const int d = threadIdx.x;
+        float kx = 0.f, vx = 0.f;
+        if (d < D) {
+          kx = bf2f(s_kv[0][d]);
+          vx = bf2f(s_kv[1][d]);
+          const float ka = wave_max(fabsf(kx)), va = wave_max(fabsf(vx));
+          if (lane == 0) {
+            s_amax[wave][0] = ka;
+            s_amax[wave][1] = va;
+          }
+        }
+        __syncthreads();
+        if (d < D) {
+          const int ek = kv_f8_exp(fmaxf(s_amax[0][0], s_amax[1][0])), ev = kv_f8_exp(fmaxf(s_amax[0][1], s_amax[1][1]));
+          const float ksc = kv_f8_pow2(ek), vsc = kv_f8_pow2(ev);
+          const uint32_t kq = kv_f8_code(kx, kv_f8_pow2(-ek)), vq = kv_f8_code(vx, kv_f8_pow2(-ev));
+          s_kv[0][d] = kv_f8_deq(kq, ksc);
+          s_kv[1][d] = kv_f8_deq(vq, vsc);
+          if (slot >= 0) {
+            const int blk = slot / kBS, off = slot - blk * kBS;
+            uint8_t* kc = reinterpret_cast<uint8_t*>(fz.k_cache);
+            uint8_t* vc = reinterpret_cast<uint8_t*>(fz.v_cache);
+            kc[(((long)blk * Hkv + kvh) * (D / 8) + (d >> 3)) * (kBS * 8) + off * 8 + (d & 7)] = (uint8_t)kq;
+            vc[(((long)blk * Hkv + kvh) * D + d) * kBS + v_perm(off)] = (uint8_t)vq;
+            if (d == 0) {
+              float* sb = kv_scale + ((long)blk * Hkv + kvh) * (2 * kBS);
+              sb[off] = ksc;
+              sb[kBS + off] = vsc;
+            }
+          }
+        }
+        __syncthreads();  // wave 0 folds the dequantised token from s_kv after the main loop
+      }
+    } else
     if (owns_new && slot >= 0 && threadIdx.x < D) {  // the new token's k / v for the next steps
       const int blk = slot / kBS, off = slot - blk * kBS, d = threadIdx.x;
       fz.k_cache[(((long)blk * Hkv + kvh) * (D / 8) + (d >> 3)) * (kBS * 8) + off * 8 + (d & 7)] = s_kv[0][d];
@@ -220,7 +288,7 @@ __global__ __launch_bounds__(256, TW == 32 ? 2 : 1) void paged_decode_kernel(bf1
 #pragma unroll
   for (int dt = 0; dt < DT; ++dt) oacc[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  auto compute = [&](const KF& kf, const VF& vf, int c) {
+  auto compute = [&](const KF& kf, const VF& vf, const KSC& ksc, const VSC& vsc, int c) {
     const int wtok0 = c * kCH + wave * kTW;
 
     // ---- scores, online softmax (per lane: head `col`)
@@ -230,7 +298,7 @@ __global__ __launch_bounds__(256, TW == 32 ? 2 : 1) void paged_decode_kernel(bf1
       sacc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int s = 0; s < KS; ++s)
-        sacc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[i][s], qf[s], sacc[i], 0, 0, 0);
+        sacc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pd_frag(kf[i][s], ksc[F8 ? i : 0]), qf[s], sacc[i], 0, 0, 0);
     }
     float mx = -INFINITY;
 #pragma unroll
@@ -267,28 +335,34 @@ __global__ __launch_bounds__(256, TW == 32 ? 2 : 1) void paged_decode_kernel(bf1
       bf16x8 pb;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        pb[j] = (__bf16)sacc[2 * s][j];
-        pb[4 + j] = (__bf16)sacc[2 * s + 1][j];
+        if constexpr (F8) {  // P x the V scale of its token (a power of two), then the bf16 rounding
+          pb[j] = (__bf16)(sacc[2 * s][j] * vsc[2 * s][j]);
+          pb[4 + j] = (__bf16)(sacc[2 * s + 1][j] * vsc[2 * s + 1][j]);
+        } else {
+          pb[j] = (__bf16)sacc[2 * s][j];
+          pb[4 + j] = (__bf16)sacc[2 * s + 1][j];
+        }
       }
 #pragma unroll
-      for (int dt = 0; dt < DT; ++dt) oacc[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf[s][dt], pb, oacc[dt], 0, 0, 0);
+      for (int dt = 0; dt < DT; ++dt)
+        oacc[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pd_frag(vf[s][dt], 1.0f), pb, oacc[dt], 0, 0, 0);
     }
   };
   if constexpr (DB) {
     for (int c = c0; c < c1; c += 2) {
-      compute(kf0, vf0, c);
-      if (c + 2 < c1) issue(kf0, vf0, c + 2);
+      compute(kf0, vf0, ks0, vs0, c);
+      if (c + 2 < c1) issue(kf0, vf0, ks0, vs0, c + 2);
       __builtin_amdgcn_sched_barrier(0);  // chunk c + 2's loads go out before chunk c + 1's MFMAs
       if (c + 1 >= c1) break;
-      compute(kf1, vf1, c + 1);
-      if (c + 3 < c1) issue(kf1, vf1, c + 3);
+      compute(kf1, vf1, ks1, vs1, c + 1);
+      if (c + 3 < c1) issue(kf1, vf1, ks1, vs1, c + 3);
       __builtin_amdgcn_sched_barrier(0);
     }
   } else {
     for (int c = c0; c < c1; ++c) {
-      if (c != c0) issue(kf0, vf0, c);  // chunk c0's loads were issued before the q prologue
+      if (c != c0) issue(kf0, vf0, ks0, vs0, c);  // chunk c0's loads were issued before the q prologue
       __builtin_amdgcn_sched_barrier(0);  // keep every load above: none may wait behind an MFMA
-      compute(kf0, vf0, c);
+      compute(kf0, vf0, ks0, vs0, c);
     }
   }
 
@@ -463,11 +537,13 @@ using namespace k8sllm;
 // slabs != nullptr: the fused q/k/v form (D = 128; see DecodeFuse) - q is ignored, the new token's
 // q / k / v come from the qkv projection's nslabs fp32 slabs [nslabs][B][(Hq + 2 Hkv) * D], are
 // rotated at `positions` and k / v written to the cache at `slot_mapping` (nullptr: no write).
+// kv_scale != nullptr: the caches hold e4m3 codes and kv_scale their per-token scales (D = 128).
 extern "C" int k8sllm_paged_decode_fused(void* out, long out_stride, float* part_out, float* part_ml,
                                          const float* slabs, int nslabs, const int* positions, const float* cos_sin,
                                          const int* slot_mapping, void* k_cache, void* v_cache,
                                          const int* block_tables, int bt_stride, const int* seq_lens, int B, int Hq,
-                                         int Hkv, int D, int S, float scale, int* merge_ctr, hipStream_t s);
+                                         int Hkv, int D, int S, float scale, int* merge_ctr, float* kv_scale,
+                                         hipStream_t s);
 
 // Tokens per wave per chunk: the double-buffered 32-token form once the grid fills the chip
 // (>= 384 workgroups, e.g. batch 64 x 8 kv heads), else the single-buffered 64-token form (small
@@ -483,24 +559,37 @@ static int decode_tw(int S, int Hkv, int B) {
 extern "C" int k8sllm_paged_decode(void* out, long out_stride, float* part_out, float* part_ml, const void* q,
                                    long q_stride, const void* k_cache, const void* v_cache, const int* block_tables,
                                    int bt_stride, const int* seq_lens, int B, int Hq, int Hkv, int D, int S,
-                                   float scale, hipStream_t s) {
+                                   float scale, const float* kv_scale, hipStream_t s) {
   if (B <= 0) return 0;
   if (S < 1 || S > 64) return -2;
+  if (kv_scale != nullptr && D != 128) return -3;
   const int G = Hq / Hkv;
   const float sl2 = scale * 1.4426950408889634f;
   const DecodeFuse fz{};
   const int tw = decode_tw(S, Hkv, B);
   dim3 grid(S, Hkv, B), blk(256);
-#define K8S_DEC_T(DD, GG, TWV)                                                                                       \
-  hipLaunchKernelGGL((paged_decode_kernel<DD, GG, false, TWV>), grid, blk, 0, s, (bf16_t*)out, out_stride, part_out, \
-                     part_ml, (const bf16_t*)q, q_stride, (const bf16_t*)k_cache, (const bf16_t*)v_cache,            \
-                     block_tables, bt_stride, seq_lens, Hq, Hkv, S, sl2, fz, nullptr)
-#define K8S_DEC(DD, GG)                                                                                              \
-  if (tw == 32) K8S_DEC_T(DD, GG, 32); else K8S_DEC_T(DD, GG, 64);                                                  \
+#define K8S_DEC_T(DD, GG, TWV, F8V)                                                                                \
+  hipLaunchKernelGGL((paged_decode_kernel<DD, GG, false, TWV, false, F8V>), grid, blk, 0, s, (bf16_t*)out,           \
+                     out_stride, part_out, part_ml, (const bf16_t*)q, q_stride, (const bf16_t*)k_cache,              \
+                     (const bf16_t*)v_cache, block_tables, bt_stride, seq_lens, Hq, Hkv, S, sl2, fz, nullptr,        \
+                     const_cast<float*>(kv_scale))
+#define K8S_DEC_F(DD, GG, F8V)                                                                                       \
+  if (tw == 32) K8S_DEC_T(DD, GG, 32, F8V); else K8S_DEC_T(DD, GG, 64, F8V);                                        \
   if (S > 1)                                                                                                         \
     hipLaunchKernelGGL((paged_decode_reduce_kernel<DD, GG>), dim3(Hkv, B), blk, 0, s, (bf16_t*)out, out_stride,      \
                        part_out, part_ml, seq_lens, Hq, S, 4 * tw);
-  if (D == 128) {
+#define K8S_DEC(DD, GG) K8S_DEC_F(DD, GG, false)
+#define K8S_DEC8(GG) K8S_DEC_F(128, GG, true)
+  if (kv_scale != nullptr) {
+    switch (G) {
+      case 1: K8S_DEC8(1); break;
+      case 2: K8S_DEC8(2); break;
+      case 4: K8S_DEC8(4); break;
+      case 8: K8S_DEC8(8); break;
+      case 16: K8S_DEC8(16); break;
+      default: return -1;
+    }
+  } else if (D == 128) {
     switch (G) {
       case 1: K8S_DEC(128, 1); break;
       case 2: K8S_DEC(128, 2); break;
@@ -520,7 +609,9 @@ extern "C" int k8sllm_paged_decode(void* out, long out_stride, float* part_out, 
   } else {
     return -1;
   }
+#undef K8S_DEC8
 #undef K8S_DEC
+#undef K8S_DEC_F
 #undef K8S_DEC_T
   return (int)hipGetLastError();
 }
@@ -529,7 +620,8 @@ extern "C" int k8sllm_paged_decode_fused(void* out, long out_stride, float* part
                                          const float* slabs, int nslabs, const int* positions, const float* cos_sin,
                                          const int* slot_mapping, void* k_cache, void* v_cache,
                                          const int* block_tables, int bt_stride, const int* seq_lens, int B, int Hq,
-                                         int Hkv, int D, int S, float scale, int* merge_ctr, hipStream_t s) {
+                                         int Hkv, int D, int S, float scale, int* merge_ctr, float* kv_scale,
+                                         hipStream_t s) {
   if (B <= 0) return 0;
   if (S < 1 || S > 64) return -2;
   if (D != 128 || slabs == nullptr || nslabs < 1 || positions == nullptr || cos_sin == nullptr) return -3;
@@ -540,15 +632,21 @@ extern "C" int k8sllm_paged_decode_fused(void* out, long out_stride, float* part
   // merge_ctr (B x Hkv ints, zero): split partials merged in-launch by the last arriving split
   const bool merge = merge_ctr != nullptr && S > 1;
   dim3 grid(S, Hkv, B), blk(256);
-#define K8S_DECF_T(GG, TWV, MG)                                                                                      \
-  hipLaunchKernelGGL((paged_decode_kernel<128, GG, true, TWV, MG>), grid, blk, 0, s, (bf16_t*)out, out_stride,       \
+#define K8S_DECF_T(GG, TWV, MG, F8V)                                                                                 \
+  hipLaunchKernelGGL((paged_decode_kernel<128, GG, true, TWV, MG, F8V>), grid, blk, 0, s, (bf16_t*)out, out_stride,  \
                      part_out, part_ml, nullptr, 0, (const bf16_t*)k_cache, (const bf16_t*)v_cache, block_tables,    \
-                     bt_stride, seq_lens, Hq, Hkv, S, sl2, fz, merge_ctr)
+                     bt_stride, seq_lens, Hq, Hkv, S, sl2, fz, merge_ctr, kv_scale)
+#define K8S_DECF_M(GG, MG)                                                                                           \
+  if (kv_scale != nullptr) {                                                                                         \
+    if (tw == 32) K8S_DECF_T(GG, 32, MG, true); else K8S_DECF_T(GG, 64, MG, true);                                  \
+  } else {                                                                                                           \
+    if (tw == 32) K8S_DECF_T(GG, 32, MG, false); else K8S_DECF_T(GG, 64, MG, false);                                \
+  }
 #define K8S_DECF(GG)                                                                                                 \
   if (merge) {                                                                                                       \
-    if (tw == 32) K8S_DECF_T(GG, 32, true); else K8S_DECF_T(GG, 64, true);                                          \
+    K8S_DECF_M(GG, true)                                                                                             \
   } else {                                                                                                           \
-    if (tw == 32) K8S_DECF_T(GG, 32, false); else K8S_DECF_T(GG, 64, false);                                        \
+    K8S_DECF_M(GG, false)                                                                                            \
     if (S > 1)                                                                                                       \
       hipLaunchKernelGGL((paged_decode_reduce_kernel<128, GG>), dim3(Hkv, B), blk, 0, s, (bf16_t*)out, out_stride,   \
                          part_out, part_ml, seq_lens, Hq, S, 4 * tw);                                                \
@@ -561,6 +659,7 @@ extern "C" int k8sllm_paged_decode_fused(void* out, long out_stride, float* part
     default: return -1;
   }
 #undef K8S_DECF
+#undef K8S_DECF_M
 #undef K8S_DECF_T
   return (int)hipGetLastError();
 }

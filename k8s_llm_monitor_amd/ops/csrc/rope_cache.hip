@@ -32,7 +32,9 @@ __device__ __forceinline__ void slab_sum(const float* __restrict__ p, long slab_
 // SLAB: the qkv values are the sum of S fp32 split-K slabs partial[s][t][col] (the decode qkv
 // projection's launch-boundary reduce); the reduced, rotated q/k are written back to the bf16 qkv
 // row (the attention reads q from there).
-template <int D, bool SLAB>
+// VROW (SLAB only, the fp8 cache's form: launched without slots): the reduced v is written to the
+// bf16 qkv row as well, where kv_cache_write_f8_kernel reads the whole token.
+template <int D, bool SLAB, bool VROW = false>
 __global__ __launch_bounds__(128) void rope_cache_kernel(bf16_t* __restrict__ qkv, long qkv_stride,
                                                          const int* __restrict__ positions,
                                                          const float* __restrict__ cos_sin,  // [max_pos][D]: cos | sin
@@ -103,6 +105,13 @@ __global__ __launch_bounds__(128) void rope_cache_kernel(bf16_t* __restrict__ qk
       const int p2 = HALF + p;
       *reinterpret_cast<uint2*>(kb + ((p2 >> 3) * block_size + off) * 8 + (p2 & 7)) = b;
     }
+  } else if constexpr (VROW) {
+    const int i = w - n_rope;
+    const int vh = i / QPH;
+    const int c = (i - vh * QPH) * 8;
+    float f[8];
+    slab_sum<8>(prow + (Hq + Hkv + vh) * D + c, slab_stride, S, f);
+    *reinterpret_cast<uint4*>(row + (Hq + Hkv + vh) * D + c) = pack8(f);
   } else if (slot >= 0) {
     const int i = w - n_rope;
     const int vh = i / QPH;
@@ -200,28 +209,129 @@ __global__ __launch_bounds__(256) void kv_cache_write_kernel(const bf16_t* __res
   }
 }
 
+// FP8 cache write (common.h: e4m3 codes + one power-of-two scale per token and kv head, for K and
+// for V): every token's k / v comes from the rotated bf16 qkv rows, by the run logic of
+// kv_cache_write_kernel (a single decode token is a run of length 1).  Per run, thread (j, c) =
+// (tid / 16, tid % 16) holds dims 8 c .. 8 c + 7 of token j's k and v: the amax over D is a butterfly
+// over the token's 16 lanes, the 8 K codes are one 8-byte store ([D/8][16][8] bytes), the V codes are
+// transposed through LDS ([D][16] bytes in v_perm order) and leave as one 8-byte store per (dim,
+// 8 positions) where the run covers them, byte stores at a run's ragged ends.  Bytes and scales of
+// tokens outside the run are never touched.  grid = (ceil(T / 16), Hkv), 256 threads.
+template <int D>
+__global__ __launch_bounds__(256) void kv_cache_write_f8_kernel(const bf16_t* __restrict__ qkv, long qkv_stride,
+                                                                const int* __restrict__ slot_mapping,
+                                                                uint8_t* __restrict__ k_cache,
+                                                                uint8_t* __restrict__ v_cache,
+                                                                float* __restrict__ kv_scale, int Hq, int Hkv, int T) {
+  static_assert(D == 128, "16 lanes x 8 dims per token");
+  constexpr int BS = 16;
+  __shared__ int s_slot[33];  // slots of tokens t0 - 1 .. t0 + 31
+  __shared__ __attribute__((aligned(8))) uint8_t s_v[D][BS];  // the run's V codes, [dim][block position]
+  const int t0 = blockIdx.x * 16, h = blockIdx.y, tid = threadIdx.x;
+  if (tid < 33) {
+    const int t = t0 - 1 + tid;
+    s_slot[tid] = (t >= 0 && t < T) ? slot_mapping[t] : -1;
+  }
+  __syncthreads();
+  const long koff = (long)(Hq + h) * D, voff = (long)(Hq + Hkv + h) * D;
+  const int j = tid >> 4, c = tid & 15;
+  for (int i = 0; i < 16 && t0 + i < T; ++i) {  // uniform: every thread reads the same LDS slots
+    const int sl = s_slot[i + 1];
+    if (sl < 0) continue;
+    if (sl % BS != 0 && s_slot[i] == sl - 1) continue;  // not a run start: an earlier window owns it
+    const int off0 = sl % BS;
+    int len = 1;
+    while (len < BS - off0 && i + 1 + len < 33 && s_slot[i + 1 + len] == sl + len) ++len;
+    const long blk = sl / BS;
+    const int ts = t0 + i;
+    float kf[8], vf[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) kf[q] = vf[q] = 0.f;
+    if (j < len) {
+      const bf16_t* row = qkv + (long)(ts + j) * qkv_stride;
+      unpack8(*reinterpret_cast<const uint4*>(row + koff + c * 8), kf);
+      unpack8(*reinterpret_cast<const uint4*>(row + voff + c * 8), vf);
+    }
+    float ka = 0.f, va = 0.f;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      ka = fmaxf(ka, fabsf(kf[q]));
+      va = fmaxf(va, fabsf(vf[q]));
+    }
+#pragma unroll
+    for (int o = 1; o < 16; o <<= 1) {  // the token's 16 lanes
+      ka = fmaxf(ka, __shfl_xor(ka, o, kWave));
+      va = fmaxf(va, __shfl_xor(va, o, kWave));
+    }
+    const int ek = kv_f8_exp(ka), ev = kv_f8_exp(va);
+    const u32x2 kq = kv_f8_code8(kf, kv_f8_pow2(-ek)), vq = kv_f8_code8(vf, kv_f8_pow2(-ev));
+    if (j < len) {
+      const int pos = off0 + j;
+      *reinterpret_cast<u32x2*>(k_cache + (blk * Hkv + h) * (long)(D * BS) + ((long)c * BS + pos) * 8) = kq;
+      if (c == 0) {
+        float* sb = kv_scale + (blk * Hkv + h) * (long)(2 * BS);
+        sb[pos] = kv_f8_pow2(ek);
+        sb[BS + pos] = kv_f8_pow2(ev);
+      }
+      const int vp = v_perm(pos);
+#pragma unroll
+      for (int q = 0; q < 8; ++q) s_v[c * 8 + q][vp] = (uint8_t)((q < 4 ? vq.x >> (8 * q) : vq.y >> (8 * (q - 4))) & 0xffu);
+    }
+    __syncthreads();
+    {
+      const int d = tid >> 1, o0 = (tid & 1) * 8;  // block positions o0 .. o0 + 7 of dim d (D * 2 = 256 items)
+      int have = 0;
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const int jj = v_perm(o0 + q) - off0;  // token of this position, relative to the run
+        have += jj >= 0 && jj < len;
+      }
+      uint8_t* dst = v_cache + (blk * Hkv + h) * (long)(D * BS) + (long)d * BS + o0;
+      if (have == 8) {
+        *reinterpret_cast<u32x2*>(dst) = *reinterpret_cast<const u32x2*>(&s_v[d][o0]);
+      } else if (have > 0) {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+          const int jj = v_perm(o0 + q) - off0;
+          if (jj >= 0 && jj < len) dst[q] = s_v[d][o0 + q];
+        }
+      }
+    }
+    __syncthreads();  // s_v is rewritten by the next run
+  }
+}
+
 }  // namespace k8sllm
 
 using namespace k8sllm;
 
 extern "C" int k8sllm_rope_cache(void* qkv, long qkv_stride, const int* positions, const float* cos_sin, void* k_cache,
                                  void* v_cache, const int* slot_mapping, long T, int Hq, int Hkv, int D,
-                                 int block_size, int apply_rope, const float* partial, int S, hipStream_t s) {
+                                 int block_size, int apply_rope, const float* partial, int S, float* kv_scale,
+                                 hipStream_t s) {
   if (T <= 0) return 0;
   if (D != 128 && D != 64) return -1;
+  // fp8 cache (kv_scale != nullptr): rotate in place (and reduce the slabs, v included, into the
+  // bf16 rows), then every token is quantised and written from the rows by kv_cache_write_f8_kernel
+  const bool f8 = kv_scale != nullptr && slot_mapping != nullptr;
+  if (f8 && (D != 128 || block_size != 16)) return -3;
   // prefill (no slabs, 16-token blocks): rotate in place, then write the cache block-run-wise
-  const bool runs = partial == nullptr && slot_mapping != nullptr && block_size == 16;
+  const bool runs = f8 || (partial == nullptr && slot_mapping != nullptr && block_size == 16);
   const int* rope_slots = runs ? nullptr : slot_mapping;
-  const int items = (Hq + (runs ? 1 : 2) * Hkv) * (D / 8);
+  const int items = (Hq + (runs && partial == nullptr ? 1 : 2) * Hkv) * (D / 8);
   dim3 grid((unsigned)T, (items + 127) / 128);
   // nothing to rotate (q / k rotated by the qkv GEMM epilogue, or a model without RoPE) and the
   // cache written run-wise below: the in-place pass would only copy q / k onto themselves
-  const bool skip_rope = runs && !apply_rope;
+  const bool skip_rope = runs && !apply_rope && partial == nullptr;
 #define K8S_ROPE(DV, SL)                                                                                       \
   hipLaunchKernelGGL((rope_cache_kernel<DV, SL>), grid, dim3(128), 0, s, (bf16_t*)qkv, qkv_stride, positions,  \
                      cos_sin, (bf16_t*)k_cache, (bf16_t*)v_cache, rope_slots, Hq, Hkv, block_size, apply_rope,   \
                      partial, S, (int)T)
   if (skip_rope) {
+  } else if (f8 && partial) {
+    hipLaunchKernelGGL((rope_cache_kernel<128, true, true>), grid, dim3(128), 0, s, (bf16_t*)qkv, qkv_stride,
+                       positions, cos_sin, (bf16_t*)nullptr, (bf16_t*)nullptr, rope_slots, Hq, Hkv, block_size,
+                       apply_rope, partial, S, (int)T);
   } else if (D == 128) {
     if (partial) K8S_ROPE(128, true); else K8S_ROPE(128, false);
   } else if (D == 64) {
@@ -230,7 +340,11 @@ extern "C" int k8sllm_rope_cache(void* qkv, long qkv_stride, const int* position
     return -1;
   }
 #undef K8S_ROPE
-  if (runs) {
+  if (f8) {
+    dim3 g2((unsigned)((T + 15) / 16), Hkv);
+    hipLaunchKernelGGL((kv_cache_write_f8_kernel<128>), g2, dim3(256), 0, s, (const bf16_t*)qkv, qkv_stride,
+                       slot_mapping, (uint8_t*)k_cache, (uint8_t*)v_cache, kv_scale, Hq, Hkv, (int)T);
+  } else if (runs) {
     dim3 g2((unsigned)((T + 15) / 16), Hkv);
     if (D == 128)
       hipLaunchKernelGGL((kv_cache_write_kernel<128>), g2, dim3(256), 0, s, (const bf16_t*)qkv, qkv_stride,

@@ -86,7 +86,8 @@ def apply_rope(x: torch.Tensor, positions: torch.Tensor, cos_sin: torch.Tensor) 
     return torch.cat([x1 * c - x2 * s, x2 * c + x1 * s], dim=-1)
 
 
-def rope_and_cache(qkv, positions, cos_sin, k_cache, v_cache, slot_mapping, Hq, Hkv, D, apply_rope_=True):
+def rope_and_cache(qkv, positions, cos_sin, k_cache, v_cache, slot_mapping, Hq, Hkv, D, apply_rope_=True,
+                   kv_scale=None):
     T = qkv.shape[0]
     q = qkv[:, : Hq * D].view(T, Hq, D)
     k = qkv[:, Hq * D:(Hq + Hkv) * D].view(T, Hkv, D)
@@ -95,7 +96,7 @@ def rope_and_cache(qkv, positions, cos_sin, k_cache, v_cache, slot_mapping, Hq, 
         q.copy_(apply_rope(q, positions, cos_sin).to(qkv.dtype))
         k.copy_(apply_rope(k, positions, cos_sin).to(qkv.dtype))
     if slot_mapping is not None and slot_mapping.numel() > 0:
-        write_kv_cache(k, v, k_cache, v_cache, slot_mapping)
+        write_kv_cache(k, v, k_cache, v_cache, slot_mapping, kv_scale)
 
 
 def v_perm(t):
@@ -103,23 +104,42 @@ def v_perm(t):
     return (t & ~12) | ((t & 4) << 1) | ((t & 8) >> 1)
 
 
-def write_kv_cache(k, v, k_cache, v_cache, slot_mapping):
+def _kv_is_fp8(k_cache) -> bool:
+    return k_cache.dtype == torch.float8_e4m3fn
+
+
+def write_kv_cache(k, v, k_cache, v_cache, slot_mapping, kv_scale=None):
+    """k, v [T, Hkv, D] into the paged cache at ``slot_mapping`` (-1: no write).  An e4m3 cache
+    (``kv_scale`` [NB, Hkv, 2, bs]) takes ops.quantize_kv's codes and scales; nothing else moves."""
     bs = k_cache.shape[3]
     D = v_cache.shape[2]
     sm = slot_mapping.long()
     ok = sm >= 0
     sm, k, v = sm[ok], k[ok], v[ok]
     blk, off = sm // bs, sm % bs
+    if _kv_is_fp8(k_cache):
+        from . import quantize_kv
+        (kq, ks), (vq, vs) = quantize_kv(k), quantize_kv(v)
+        k_cache.view(torch.uint8)[blk, :, :, off, :] = kq.view(torch.uint8).view(k.shape[0], k.shape[1], D // 8, 8)
+        v_cache.view(torch.uint8)[blk, :, :, v_perm(off)] = vq.view(torch.uint8)
+        kv_scale[blk, :, 0, off] = ks
+        kv_scale[blk, :, 1, off] = vs
+        return
     kk = k.view(k.shape[0], k.shape[1], D // 8, 8)
     k_cache[blk, :, :, off, :] = kk
     v_cache[blk, :, :, v_perm(off)] = v
 
 
-def gather_kv(k_cache, v_cache, block_table: torch.Tensor, seq_len: int):
-    """Contiguous [L, Hkv, D] keys and values of one sequence."""
+def gather_kv(k_cache, v_cache, block_table: torch.Tensor, seq_len: int, kv_scale=None):
+    """Contiguous [L, Hkv, D] keys and values of one sequence (an e4m3 cache: dequantised, bf16)."""
     bs = k_cache.shape[3]
     nb = (seq_len + bs - 1) // bs
     blocks = block_table[:nb].long()
+    if _kv_is_fp8(k_cache):
+        from . import dequantize_kv
+        kq, vq = gather_kv(k_cache.view(torch.uint8), v_cache.view(torch.uint8), block_table, seq_len)
+        sc = kv_scale[blocks].permute(2, 0, 3, 1).reshape(2, nb * bs, -1)[:, :seq_len]  # [2, L, Hkv]
+        return (dequantize_kv(kq.view(torch.float8_e4m3fn), sc[0]), dequantize_kv(vq.view(torch.float8_e4m3fn), sc[1]))
     kb = k_cache[blocks]  # [nb, Hkv, D/8, bs, 8]
     nbk, hkv, p, _, _ = kb.shape
     k = kb.permute(0, 3, 1, 2, 4).reshape(nbk * bs, hkv, p * 8)[:seq_len]
@@ -146,7 +166,7 @@ def attention(q, k, v, scale: float, causal: bool) -> torch.Tensor:
     return (p @ vf).transpose(0, 1)
 
 
-def paged_decode(q, k_cache, v_cache, block_tables, seq_lens, Hq, Hkv, D, scale):
+def paged_decode(q, k_cache, v_cache, block_tables, seq_lens, Hq, Hkv, D, scale, kv_scale=None):
     """q [B, >=Hq*D]; returns [B, Hq*D] in q.dtype."""
     B = seq_lens.shape[0]
     out = torch.zeros(B, Hq * D, dtype=q.dtype, device=q.device)
@@ -154,7 +174,7 @@ def paged_decode(q, k_cache, v_cache, block_tables, seq_lens, Hq, Hkv, D, scale)
         L = int(seq_lens[b])
         if L <= 0:
             continue
-        k, v = gather_kv(k_cache, v_cache, block_tables[b], L)
+        k, v = gather_kv(k_cache, v_cache, block_tables[b], L, kv_scale)
         qb = q[b, : Hq * D].view(1, Hq, D)
         out[b] = attention(qb, k, v, scale, causal=False).reshape(-1).to(q.dtype)
     return out
@@ -176,9 +196,10 @@ def flash_prefill(qkv, cu_seqlens, Hq, Hkv, D, scale):
     return out
 
 
-def paged_prefill(qkv, cu_seqlens, ctx_start, k_cache, v_cache, block_tables, Hq, Hkv, D, scale):
+def paged_prefill(qkv, cu_seqlens, ctx_start, k_cache, v_cache, block_tables, Hq, Hkv, D, scale, kv_scale=None):
     """Queries = each sequence's new rows of ``qkv``; keys/values = positions [0, ctx_start + new)
-    from the paged cache (which already holds the new tokens)."""
+    from the paged cache (which already holds the new tokens).  An e4m3 cache gives only the
+    cached prefix (dequantised): this step's own keys / values are the unquantised qkv rows."""
     T = qkv.shape[0]
     out = torch.empty(T, Hq * D, dtype=qkv.dtype, device=qkv.device)
     cu, cs = cu_seqlens.tolist(), ctx_start.tolist()
@@ -186,7 +207,10 @@ def paged_prefill(qkv, cu_seqlens, ctx_start, k_cache, v_cache, block_tables, Hq
         a, b = cu[i], cu[i + 1]
         if b <= a:
             continue
-        k, v = gather_kv(k_cache, v_cache, block_tables[i], cs[i] + b - a)
+        k, v = gather_kv(k_cache, v_cache, block_tables[i], cs[i] + b - a, kv_scale)
+        if _kv_is_fp8(k_cache):
+            k = torch.cat([k[:cs[i]].float(), qkv[a:b, Hq * D:(Hq + Hkv) * D].reshape(b - a, Hkv, D).float()])
+            v = torch.cat([v[:cs[i]].float(), qkv[a:b, (Hq + Hkv) * D:(Hq + 2 * Hkv) * D].reshape(b - a, Hkv, D).float()])
         q = qkv[a:b, : Hq * D].view(b - a, Hq, D)
         out[a:b] = attention(q, k, v, scale, causal=True).reshape(b - a, -1).to(qkv.dtype)
     return out

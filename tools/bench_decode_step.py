@@ -79,13 +79,14 @@ def main() -> None:
     ap.add_argument("--tokens", type=int, default=96)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--decode-weights", default="bf16", choices=["bf16", "fp8"])
+    ap.add_argument("--kv-cache-dtype", default="bf16", choices=["bf16", "fp8"])
     ap.add_argument("--layers", type=int, default=0, help="override the model's layer count (0 = all)")
     a = ap.parse_args()
     from k8s_llm_monitor_amd.engine import EngineConfig, LLMEngine, SamplingParams
 
     rows_list = [int(r) for r in a.rows.split(",")]
     eng = LLMEngine(EngineConfig(model=a.model, max_num_seqs=max(rows_list), max_model_len=4096, kv_cache_gb=48.0,
-                                 seed=1, decode_weights=a.decode_weights,
+                                 seed=1, decode_weights=a.decode_weights, kv_cache_dtype=a.kv_cache_dtype,
                                  model_overrides={"n_layers": a.layers} if a.layers else {}), device="cuda")
     eng.warmup()
     g = torch.Generator().manual_seed(5)
@@ -104,7 +105,8 @@ def main() -> None:
                 ms = [m for (n, m, _) in eng.step_samples if n == rows]
                 med = statistics.median(ms) if ms else float("nan")
                 res[on].append(med)
-                print(json.dumps({"switch": a.switch, "decode_weights": a.decode_weights, "rows": rows, "on": on,
+                print(json.dumps({"switch": a.switch, "decode_weights": a.decode_weights,
+                                  "kv_cache_dtype": a.kv_cache_dtype, "rows": rows, "on": on,
                                   "round": rnd, "steps": len(ms),
                                   "median_step_ms": round(med, 4)}), flush=True)
         print(json.dumps({"switch": a.switch, "rows": rows, "on_ms": [round(x, 4) for x in res[True]],

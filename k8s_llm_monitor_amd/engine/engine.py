@@ -74,6 +74,12 @@ class EngineConfig:
     # model's bf16 weights become the dequantised values and the fp8 copy is kept beside them
     # (resident weights grow by half; prefill still reads bf16; only decode streams fewer bytes)
     decode_weights: str = "bf16"
+    # "bf16" | "fp8" (on top of decode_weights = "fp8" only): what prefill reads
+    # (CausalLM.PREFILL_WEIGHTS).  fp8: the prefill tile GEMM converts the decode codes on the way
+    # into the MFMA (bit-identical results) and the bf16 copy of every dense projection and head
+    # whose decode launches all have an fp8 form is released - dense models at TP = 1; resident
+    # weights then shrink below the bf16 model's instead of growing by half
+    prefill_weights: str = "bf16"
     # "bf16" | "fp8": the paged KV cache's encoding.  fp8 stores e4m3 codes with one power-of-two
     # scale per (token, kv head) for K and for V (ops.quantize_kv): decode streams half the KV bytes
     # and a kv_cache_gb budget holds ~1.94x the blocks.  GPU: head_dim 128 only
@@ -111,7 +117,8 @@ class LLMEngine:
         self.model_cfg = mc
         t0 = time.perf_counter()
         self.model = CausalLM(mc, device=self.device, dtype=getattr(torch, cfg.dtype), seed=cfg.seed, pstate=self.ps,
-                              init="empty" if cfg.weights else "random", dec_weights=cfg.decode_weights)
+                              init="empty" if cfg.weights else "random", dec_weights=cfg.decode_weights,
+                              prefill_weights=cfg.prefill_weights)
         if cfg.weights:
             load_checkpoint(self.model, cfg.weights)
         self.runner = ModelRunner(self.model, RunnerConfig(
@@ -466,9 +473,11 @@ class LLMEngine:
         d.update(self.sched.stats())
         d.update({"model": self.model_cfg.name, "tp_size": self.ps.tp_size, "device": str(self.device),
                   "graph_buckets": sorted(self.runner.graphs), "max_num_seqs": self.cfg.max_num_seqs,
-                  "decode_weights": self.cfg.decode_weights, **self.runner.kv_stats(),
+                  "decode_weights": self.cfg.decode_weights, "prefill_weights": self.cfg.prefill_weights,
+                  **self.runner.kv_stats(),
                   "resident_weight_bytes": self.model.resident_weight_bytes(),
-                  "decode_encodings": self.model.decode_encodings()})
+                  "decode_encodings": self.model.decode_encodings(),
+                  "prefill_encodings": self.model.prefill_encodings()})
         return d
 
     # ----------------------------------------------------------------- tensor parallel

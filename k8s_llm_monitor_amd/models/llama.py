@@ -38,6 +38,11 @@ The four projections of every layer are resident in ONE of three layouts (``Caus
                (w13 paired per 16 rows as [8 gate | 8 up]); prefill's tile GEMM reads it too and
                ``*_d`` / ``*_dg`` are the weights themselves
 
+With ``PREFILL_WEIGHTS = "fp8"`` a PACKED dense projection may be resident as its fp8 encoding
+ONLY: ``L[key]`` is then the packed e4m3 codes ([out/16, in/64, 64, 16], also under ``*_q``) with
+the row scales under ``*_qs`` and no ``*_d`` - prefill's tile GEMM and the decode GEMMs both read
+the codes (``_release_bf16``).
+
 ``to_resident`` / ``to_canonical`` convert one projection between CANONICAL and another layout;
 ``_init_skinny`` / ``_init_dec`` move a model forward, ``begin_load`` takes it out of service
 (LOADING) until the loader's closing ``_init_skinny``.
@@ -106,7 +111,8 @@ CANONICAL, INTERLEAVED, PACKED, LOADING = "canonical", "interleaved", "packed", 
 PROJ = ("wqkv", "wo", "w13", "w2")
 # layer-dict keys with these suffixes are derived from the projections, not parameters: the
 # gemm_skinny views (dense, expert stack), the decode GEMM's packed copies (dense, expert stack)
-# and, with DEC_WEIGHTS = "fp8", the fp8 encoding of a dense projection (packed e4m3 codes, per-row scales)
+# and, with DEC_WEIGHTS = "fp8", the fp8 encoding of a dense projection (packed e4m3 codes, per-row scales;
+# with PREFILL_WEIGHTS = "fp8" the codes may be the projection itself: L[key] is L[key + "_q"], no "_d")
 DERIVED = ("_p", "_pg", "_d", "_dg", "_q", "_qs")
 DEC_COPIES = ("_d", "_dg")  # the decode GEMM's packed bf16 copies among them
 
@@ -123,8 +129,14 @@ def to_resident(w: torch.Tensor, key: str, form: str) -> torch.Tensor:
     return _each(w, ops.interleave_gate_up) if key == "w13" and form == INTERLEAVED else w
 
 
-def to_canonical(w: torch.Tensor, key: str, form: str) -> torch.Tensor:
-    """Projection ``key`` (or its expert stack) resident as ``form``, back to CANONICAL."""
+def to_canonical(w: torch.Tensor, key: str, form: str, scale: Optional[torch.Tensor] = None,
+                 dtype=torch.bfloat16) -> torch.Tensor:
+    """Projection ``key`` (or its expert stack) resident as ``form``, back to CANONICAL.  A
+    projection resident as its fp8 encoding only (packed codes, ``scale`` its row scales in packed
+    row order) is dequantised to ``dtype`` - exactly the bf16 values it was quantised from."""
+    if ops.is_fp8(w):
+        d = ops.dequantize_rows_fp8(ops.unpack_skinny_f8(w), scale, dtype)
+        return ops.deinterleave_gate_up8(d) if key == "w13" else d
     if form == PACKED:
         return _each(w, lambda e: ops.deinterleave_gate_up8(ops.unpack_skinny(e)) if key == "w13"
                      else ops.unpack_skinny(e))
@@ -158,19 +170,32 @@ class CausalLM:
     # decode gets faster).  Per launch the fp8 encoding is used where gemm_decode.hip has an fp8
     # form for the shape and row count (ops.dec_config(f8=True)), the bf16 copy otherwise.
     DEC_WEIGHTS = "bf16"
+    # What prefill reads where DEC_WEIGHTS = "fp8": "bf16" - the bf16 copy beside the codes - or
+    # "fp8": the tile GEMM converts the codes on the way into the MFMA (gemm_tile.hip F8,
+    # bit-identical) and the bf16 copy of every dense projection (and the head) whose decode
+    # launches all have an fp8 form is released: the codes are the only resident copy
+    # (_f8_only_ok; dense, TP = 1, ONE_LAYOUT models - every other projection keeps both copies).
+    PREFILL_WEIGHTS = "bf16"
 
     def __init__(self, cfg: ModelConfig, device: torch.device | str = "cpu", dtype=torch.bfloat16, seed: int = 0,
                  pstate: Optional[ParallelState] = None, init_std: float = 0.02, init: str = "random",
-                 dec_weights: Optional[str] = None):
+                 dec_weights: Optional[str] = None, prefill_weights: Optional[str] = None):
         """``init``: "random" (seeded per tensor name) or "empty" (uninitialised storage, for
         models about to be filled by models/checkpoint.load_checkpoint).  ``dec_weights``: this
-        model's DEC_WEIGHTS ("bf16" | "fp8"; None = the class constant)."""
+        model's DEC_WEIGHTS ("bf16" | "fp8"; None = the class constant); ``prefill_weights``: its
+        PREFILL_WEIGHTS ("bf16" | "fp8", fp8 only on top of fp8 decode weights)."""
         if init not in ("random", "empty"):
             raise ValueError(f"init must be 'random' or 'empty', not {init!r}")
         if dec_weights is not None:
             self.DEC_WEIGHTS = dec_weights
         if self.DEC_WEIGHTS not in ("bf16", "fp8"):
             raise ValueError(f"decode weights must be 'bf16' or 'fp8', not {self.DEC_WEIGHTS!r}")
+        if prefill_weights is not None:
+            self.PREFILL_WEIGHTS = prefill_weights
+        if self.PREFILL_WEIGHTS not in ("bf16", "fp8"):
+            raise ValueError(f"prefill weights must be 'bf16' or 'fp8', not {self.PREFILL_WEIGHTS!r}")
+        if self.PREFILL_WEIGHTS == "fp8" and self.DEC_WEIGHTS != "fp8":
+            raise ValueError("prefill weights 'fp8' need decode weights 'fp8' (the codes prefill reads are decode's)")
         self._empty_init = init == "empty"
         self._f8_defer = self._empty_init  # uninitialised storage is not quantised: the load's closing _init_skinny does
         self.cfg = cfg
@@ -237,9 +262,18 @@ class CausalLM:
         return 8 if self._layout == PACKED else True
 
     @staticmethod
-    def _drop_derived(L: dict) -> None:
-        for k in [k for k in L if k.endswith(DERIVED)]:
+    def _drop_derived(L: dict, every: bool = False) -> None:
+        """Drop the layer's derived tensors - but, unless ``every``, not the codes and scales of a
+        projection that is resident as its fp8 encoding only: those ARE the weight (``_remat``
+        turns it back)."""
+        keep = set() if every else {key + sfx for key in PROJ if ops.is_fp8(L.get(key)) for sfx in ("_q", "_qs")}
+        for k in [k for k in L if k.endswith(DERIVED) and k not in keep]:
             del L[k]
+
+    @staticmethod
+    def _wsc(L: dict, key: str) -> Optional[torch.Tensor]:
+        """The row scales the tile GEMM needs with ``L[key]``: those of an fp8-only projection."""
+        return L[key + "_qs"] if ops.is_fp8(L[key]) else None
 
     def begin_load(self) -> None:
         """Before a loader replaces the weights: the derived tensors (decode copies; under
@@ -250,7 +284,7 @@ class CausalLM:
         self.lm_head_d = self.lm_head_q = self.lm_head_qs = None
         self._f8_defer = False
         for L in self.layers:
-            self._drop_derived(L)
+            self._drop_derived(L, every=True)  # the loader replaces every projection, fp8-only ones too
         self._layout = LOADING
 
     def _rand(self, name: str, shape, std: Optional[float] = None) -> torch.Tensor:
@@ -343,7 +377,7 @@ class CausalLM:
     def resident_weight_bytes(self) -> int:
         """Bytes of every distinct weight tensor this rank holds (parameters, decode-layout copies,
         the LM head's packed copy and the fp8 encodings with their scales; a tensor referenced
-        under two keys counts once)."""
+        under two keys counts once - the codes of an fp8-only projection are its parameter)."""
         seen, n = set(), 0
         ts = [self.embed, self.lm_head, self.lm_head_d, self.lm_head_q, self.lm_head_qs, self.final_norm]
         for L in self.layers:
@@ -378,7 +412,7 @@ class CausalLM:
 
     def _attention(self, L: dict, x: torch.Tensor, meta: AttnMeta, kv) -> torch.Tensor:
         o = self._attn_core(L, x, meta, kv)
-        y = ops.prefill_linear(o, L["wo"]) if "bo" not in L else F.linear(o, L["wo"])
+        y = ops.prefill_linear(o, L["wo"], wscale=self._wsc(L, "wo")) if "bo" not in L else F.linear(o, L["wo"])
         if "bo" in L and self.rank == 0:
             y += L["bo"]
         return tp_all_reduce(y, self.ps)
@@ -412,9 +446,9 @@ class CausalLM:
         elif c.arch == "llama" and self.D == 128 and self.cos_sin is not None:
             # prefill-sized qkv on the tile kernel: RoPE of q / k fused into its epilogue
             qkv, roped = ops.prefill_linear(x, L["wqkv"], rope=(meta.positions, cs, self.hq + self.hkv),
-                                            rowscale=rowscale)
+                                            rowscale=rowscale, wscale=self._wsc(L, "wqkv"))
         else:
-            qkv = ops.prefill_linear(x, L["wqkv"])
+            qkv = ops.prefill_linear(x, L["wqkv"], wscale=self._wsc(L, "wqkv"))
         ops.rope_and_cache(qkv, meta.positions, cs, k_cache, v_cache,
                            meta.slot_mapping if k_cache is not None else None, self.hq, self.hkv, self.D,
                            apply_rope=c.arch == "llama" and not roped, partial=partial, nslabs=ns, kv_scale=kv_scale)
@@ -456,10 +490,10 @@ class CausalLM:
                 return self._moe_a2a_decode(L, x)
             return tp_all_reduce(self._moe(L, x, meta), self.ps)
         if self._w13_il:
-            h = ops.prefill_linear(x, L["w13"], swiglu=self._swg)
+            h = ops.prefill_linear(x, L["w13"], swiglu=self._swg, wscale=self._wsc(L, "w13"))
         else:
             h = ops.silu_mul(F.linear(x, L["w13"]), interleaved=False)
-        return tp_all_reduce(ops.prefill_linear(h, L["w2"]), self.ps)
+        return tp_all_reduce(ops.prefill_linear(h, L["w2"], wscale=self._wsc(L, "w2")), self.ps)
 
     def _moe(self, L: dict, x: torch.Tensor, meta: AttnMeta) -> torch.Tensor:
         """Top-k MoE over this rank's experts [e_lo, e_hi).  Tokens are sorted by expert (moe_align)
@@ -778,12 +812,13 @@ class CausalLM:
         for i, L in enumerate(self.layers):
             kv = kv_caches[i] if kv_caches is not None else None
             o = self._attn_core(L, x, meta, kv, rowscale=(ss, eps) if ss is not None else None)
-            x, ss = ops.gemm_tile_resid(o, L["wo"], residual, L["mlp_norm"])
-            act = ops.prefill_linear(x, L["w13"], swiglu=self._swg, rowscale=(ss, eps))
+            x, ss = ops.gemm_tile_resid(o, L["wo"], residual, L["mlp_norm"], wscale=self._wsc(L, "wo"))
+            act = ops.prefill_linear(x, L["w13"], swiglu=self._swg, rowscale=(ss, eps), wscale=self._wsc(L, "w13"))
             if i + 1 < n:
-                x, ss = ops.gemm_tile_resid(act, L["w2"], residual, self.layers[i + 1]["attn_norm"])
+                x, ss = ops.gemm_tile_resid(act, L["w2"], residual, self.layers[i + 1]["attn_norm"],
+                                            wscale=self._wsc(L, "w2"))
             else:
-                y = ops.prefill_linear(act, L["w2"])
+                y = ops.prefill_linear(act, L["w2"], wscale=self._wsc(L, "w2"))
                 if meta.logits_idx is not None:
                     y = y[meta.logits_idx]
                     residual = residual[meta.logits_idx].contiguous()
@@ -796,19 +831,25 @@ class CausalLM:
         head (``lm_head_d``) up to dec_rows_max() rows at a time (128 for dense TP=1 models, else
         64) go through gemm_decode.hip, one stream of the head per launch - the decode step's and a
         prefill step's last-token logits alike; hipBLASLt otherwise."""
-        hd = self.lm_head_d
-        if x.dim() == 4:  # packed (decode): the decode copy exists by construction
-            logits = torch.empty(rows, hd.shape[0] * 16, dtype=self.dtype, device=self.device)
-            self._dec(x, hd, self.lm_head_q, self.lm_head_qs, 1, rows, out=logits)
-        elif hd is not None and x.is_cuda and x.shape[0] <= self.dec_rows_max():
-            logits = torch.empty(x.shape[0], hd.shape[0] * 16, dtype=self.dtype, device=self.device)
-            self._dec(ops.pack_activation(x), hd, self.lm_head_q, self.lm_head_qs, 1, x.shape[0], out=logits)
-        elif self.lm_head.dim() == 4:  # ONE_LAYOUT: the packed head is the only copy - dec_rows_max()-row chunks
+        hd, hq = self.lm_head_d, self.lm_head_q
+        f8_only = hd is None and hq is not None  # the codes are the head's only decode form (_release_bf16)
+        nv = (hd if hd is not None else hq).shape[0] * 16 if hd is not None or hq is not None else 0
+        if x.dim() == 4:  # packed (decode): the decode copy (or the codes) exists by construction
+            logits = torch.empty(rows, nv, dtype=self.dtype, device=self.device)
+            self._dec(x, hd, hq, self.lm_head_qs, 1, rows, out=logits)
+        elif nv and x.is_cuda and x.shape[0] <= self.dec_rows_max():
+            logits = torch.empty(x.shape[0], nv, dtype=self.dtype, device=self.device)
+            self._dec(ops.pack_activation(x), hd, hq, self.lm_head_qs, 1, x.shape[0], out=logits)
+        elif self.lm_head.dim() == 4 or f8_only:
+            # ONE_LAYOUT: the packed head (or its codes) is the only copy - dec_rows_max()-row chunks
             M, mc = x.shape[0], self.dec_rows_max()
-            logits = torch.empty(M, hd.shape[0] * 16, dtype=self.dtype, device=self.device)
+            logits = torch.empty(M, nv, dtype=self.dtype, device=self.device)
             for i in range(0, M, mc):
                 m = min(mc, M - i)
-                ops.dec_gemm(ops.pack_activation(x[i:i + m]), hd, 1, m, out=logits[i:i + m])
+                if f8_only:
+                    self._dec(ops.pack_activation(x[i:i + m]), None, hq, self.lm_head_qs, 1, m, out=logits[i:i + m])
+                else:
+                    ops.dec_gemm(ops.pack_activation(x[i:i + m]), hd, 1, m, out=logits[i:i + m])
         else:
             logits = F.linear(x, self.lm_head)
         logits = tp_all_gather_last(logits, self.ps)
@@ -834,14 +875,16 @@ class CausalLM:
 
     def _dec_wide_ok(self) -> bool:
         c = self.cfg
-        if self.tp != 1 or c.is_moe or not self.layers or self.lm_head_d is None:
+        if self.tp != 1 or c.is_moe or not self.layers:
             return False
         L = self.layers[0]
-        if not all(k in L for k in ("wqkv_d", "wo_d", "w13_d", "w2_d")):
+        # (decode copy or None, codes or None, epilogue): a projection may hold its codes only
+        ws = [(L.get(k + "_d"), L.get(k + "_q"), 2 if k == "w13" else 0) for k in PROJ]
+        ws.append((self.lm_head_d, self.lm_head_q, 1))
+        if any(wd is None and wq is None for wd, wq, _ in ws):
             return False
-        shapes = [ops.skinny_wdims(L[k]) + (2 if k == "w13_d" else 0,) for k in ("wqkv_d", "wo_d", "w13_d", "w2_d")]
-        shapes.append(ops.skinny_wdims(self.lm_head_d) + (1,))
-        return all(ops.dec_available(N, K, epi, rows=ops.DEC_MAX_M) for N, K, epi in shapes)
+        return all(ops.dec_config(*ops.skinny_wdims(wd if wd is not None else wq), epi, rows=ops.DEC_MAX_M,
+                                  f8=wd is None) is not None for wd, wq, epi in ws)
 
     def _use_skinny(self, meta: AttnMeta, h: torch.Tensor) -> bool:
         """Llama-family decode steps of up to dec_rows_max() rows (128 for dense TP=1 models on the
@@ -871,23 +914,26 @@ class CausalLM:
         On the CPU the same ops run as fp32 references with the kernels' split-K slicing, so the
         control flow (and TP over gloo) is covered by the CPU tests."""
         c = self.cfg
+        if self.lm_head.dim() == 4:  # before the head's scales go: an fp8-only head dequantises with them
+            self.lm_head = self.canonical_head().contiguous()
         self._skinny_ws = self.lm_head_d = self.lm_head_q = self.lm_head_qs = None
         self._rc_o, self._dec_wide, self._attn_rope = 0, False, False
-        if self.lm_head.dim() == 4:
-            self.lm_head = self.canonical_head().contiguous()
         ff = c.ffn_dim if c.is_moe else self.f_local  # experts are sharded by count (EP), not by F
         old = CANONICAL if self._layout == LOADING else self._layout
         new = INTERLEAVED if c.arch == "llama" and ff % 64 == 0 else CANONICAL
+        d, nq = c.d_model, (self.hq + 2 * self.hkv) * self.D
+        dec = (c.arch == "llama" and self.SKINNY_DECODE and new == INTERLEAVED
+               and not (d % 64 or nq % 64 or (self.hq * self.D) % 32))
         for L in self.layers:
+            if not dec:  # no _init_dec below: fp8-only projections back to bf16 here (else there, layer by layer)
+                self._remat(L, new)
             self._drop_derived(L)
             if old != new:
                 for key in PROJ:
-                    L[key] = relayout(L[key], key, old, new).contiguous()
+                    if not ops.is_fp8(L[key]):
+                        L[key] = relayout(L[key], key, old, new).contiguous()
         self._layout = new
-        if c.arch != "llama" or not self.SKINNY_DECODE or new != INTERLEAVED:
-            return
-        d, nq = c.d_model, (self.hq + 2 * self.hkv) * self.D
-        if d % 64 or nq % 64 or (self.hq * self.D) % 32:
+        if not dec:
             return
         # (In-launch split-K epilogues - RoPE + KV write in the qkv GEMM, residual add + norm
         # producer in the o / down GEMMs, reduced by each tile's last-arriving workgroup - measured
@@ -900,6 +946,8 @@ class CausalLM:
         self.skinny_layout = "rowmajor" if rowmajor else "packed"
         for L in self.layers:
             for key in PROJ:  # MoE: stacked per local expert for the grouped (grid.z = expert) launches
+                if ops.is_fp8(L[key]):  # fp8-only so far: _init_dec's _remat makes its view
+                    continue
                 sfx = "_pg" if L[key].dim() == 3 else "_p"
                 L[key + sfx] = L[key] if rowmajor else _each(L[key], ops.pack_skinny)
         split = ops.SKINNY_SPLITS_FORCE  # 0: the launcher picks per call (kernel and batch dependent)
@@ -922,7 +970,8 @@ class CausalLM:
         c, split = self.cfg, self._split_qkv
         d, nq, no = c.d_model, (self.hq + 2 * self.hkv) * self.D, self.hq * self.D
         dec_rows = ops.DEC_MAX_M if self._dec_wide else ops.SKINNY_MAX_M
-        dec_copies = bool(self.layers) and any(k.endswith(DEC_COPIES) for k in self.layers[0])
+        # decode copies, or - where a projection is fp8-only - its codes
+        dec_copies = bool(self.layers) and any(k.endswith(DEC_COPIES + ("_q",)) for k in self.layers[0])
         f8 = bool(self.layers) and any(k.endswith("_q") for k in self.layers[0])
 
         def most(N: int, K: int) -> int:
@@ -959,6 +1008,9 @@ class CausalLM:
         phase behind a grid seam - neutral to slower - and the down projection row-complete -
         0.2-4.5 % slower at 4-32 rows; profiles/r05/README.md.)"""
         c = self.cfg
+        if rc is True and self.layers and any(ops.is_fp8(self.layers[0][k]) for k in ("wo", "w13")):
+            raise ValueError("the row-complete o projection reads bf16 weights: wo / w13 are resident as fp8 only "
+                             "(prefill_weights=fp8)")
         ok = (self.tp == 1 and not c.is_moe and bool(self.layers) and "w13_d" in self.layers[0]
               and c.d_model % 512 == 0)
         # fp8 decode weights: the row-complete kernel reads bf16 and leaves the gate_up GEMM the wide
@@ -1010,9 +1062,9 @@ class CausalLM:
                     continue
                 rc = self._norm_tail(residual, ws, ns, L["mlp_norm"], rows=M)
             xw, rn = rc  # the dense MLP's input, from either form of the o projection
-            if "w13_d" in L:
+            if "w13_d" in L or "w13_q" in L:
                 act = ops.packed_empty(M, self.f_local, self.dtype, self.device)
-                self._dec(xw, L["w13_d"], L.get("w13_q"), L.get("w13_qs"), 2, M, out=act, rownorm=rn)
+                self._dec(xw, L.get("w13_d"), L.get("w13_q"), L.get("w13_qs"), 2, M, out=act, rownorm=rn)
             else:
                 act = ops.skinny_swiglu(xw, L["w13_p"], rows=M, packed_out=True, rownorm=rn)
             ns = self._proj_slabs(L, "w2", act, M, self._split_d)
@@ -1020,7 +1072,7 @@ class CausalLM:
                 xw, rn = self._norm_tail(residual, ws, ns, self.layers[i + 1]["attn_norm"], rows=M)
         # final norm feeds the LM head: fragment-packed for the decode GEMM (gemm_decode.hip), or
         # complete and row-major for hipBLASLt where no decode copy of the head exists
-        packed = self.lm_head_d is not None
+        packed = self.lm_head_d is not None or self.lm_head_q is not None
         x = self._tp_tail(ws, ns, residual, self.final_norm, packed=packed)
         if x is None:
             y = self._row_parallel_sum(ws, ns, M, residual)
@@ -1071,10 +1123,9 @@ class CausalLM:
         """Split-K slabs of a decode projection into the shared workspace: the shared-A decode
         GEMM over the packed copy ``L[key + "_d"]`` where one exists, else gemm_skinny over
         ``L[key + "_p"]``.  Returns the slab count."""
-        wd = L.get(key + "_d")
-        if wd is not None:
-            return self._dec(x, wd, L.get(key + "_q"), L.get(key + "_qs"), 0, rows, workspace=self._skinny_ws,
-                             rownorm=rownorm)
+        wd, wq = L.get(key + "_d"), L.get(key + "_q")
+        if wd is not None or wq is not None:  # wd None: the codes are the only copy
+            return self._dec(x, wd, wq, L.get(key + "_qs"), 0, rows, workspace=self._skinny_ws, rownorm=rownorm)
         return ops.skinny_slabs(x, L[key + "_p"], self._skinny_ws, split, rows=rows, rownorm=rownorm)
 
     @staticmethod
@@ -1083,12 +1134,22 @@ class CausalLM:
         """ops.dec_gemm over the fp8 encoding (``wq``, ``wqs``) of a weight where one exists and
         gemm_decode.hip has an fp8 form for the shape at ``rows`` rows with this deferred norm (the
         wide form of the row-complete o projection's sums reads bf16), else over the bf16 copy
-        ``wd`` - the same values either way, so the choice is one of speed only."""
-        if wq is not None and not (rownorm is not None and rownorm[0].shape[1] > 16):
+        ``wd`` - the same values either way, so the choice is one of speed only.  ``wd`` None: the
+        weight is resident as its codes only (_f8_only_ok made sure every launch has an fp8 form;
+        one without raises in ops.dec_gemm)."""
+        if wq is not None and (wd is None or not (rownorm is not None and rownorm[0].shape[1] > 16)):
             N, K = ops.skinny_wdims(wq)
-            if ops.dec_config(N, K, epi, rows=rows, f8=True) is not None:
+            if wd is None or ops.dec_config(N, K, epi, rows=rows, f8=True) is not None:
                 return ops.dec_gemm(x, wq, epi, rows, rownorm=rownorm, wscale=wqs, **kw)
         return ops.dec_gemm(x, wd, epi, rows, rownorm=rownorm, **kw)
+
+    def prefill_encodings(self) -> dict:
+        """What prefill reads each dense projection and the head from: "fp8" where the codes are
+        the only resident copy (the bf16 copy is released), "bf16" otherwise; layer 0 speaks for all."""
+        L = self.layers[0] if self.layers else {}
+        enc = {k: "fp8" if ops.is_fp8(L[k]) else "bf16" for k in PROJ if k in L}
+        enc["head"] = "fp8" if self.lm_head_q is not None and self.lm_head_d is None else "bf16"
+        return enc
 
     def decode_encodings(self) -> dict:
         """Which encoding each decode projection streams from ("fp8" | "bf16" per key of wqkv, wo,
@@ -1155,13 +1216,15 @@ class CausalLM:
     def canonical_head(self) -> torch.Tensor:
         """The LM head as row-major [vocab shard, d] (ONE_LAYOUT keeps only its packed copy)."""
         h = self.lm_head
+        if ops.is_fp8(h):  # the codes are the only copy: the bf16 values they were quantised from
+            return ops.dequantize_rows_fp8(ops.unpack_skinny_f8(h), self.lm_head_qs, self.dtype)
         return ops.unpack_skinny(h) if h.dim() == 4 else h
 
     def canonical(self, L: dict, key: str) -> torch.Tensor:
         """A dense projection as the row-major [out, in] weight of the reference / the checkpoint
         format (w13 as [gate; up]), whatever its resident layout (row-major, gate/up interleaved
         per 128 rows, or the one fragment-packed copy)."""
-        return to_canonical(L[key], key, self._layout)
+        return to_canonical(L[key], key, self._layout, L.get(key + "_qs"), self.dtype)
 
     @torch.no_grad()
     def copy_weights_from(self, src: "CausalLM") -> None:
@@ -1172,7 +1235,12 @@ class CausalLM:
         self.embed.copy_(src.embed)
         if self.lm_head is not self.embed:
             h = src.canonical_head().to(self.lm_head.device)
-            self.lm_head.copy_(ops.pack_skinny(h) if self.lm_head.dim() == 4 else h)
+            if ops.is_fp8(self.lm_head):  # fp8-only head: straight to codes and scales
+                q, qs = ops.quantize_rows_fp8(h.to(self.dtype))
+                self.lm_head.copy_(ops.pack_skinny_f8(q))
+                self.lm_head_qs.copy_(qs)
+            else:
+                self.lm_head.copy_(ops.pack_skinny(h) if self.lm_head.dim() == 4 else h)
         for a, b in zip(self.final_norm if isinstance(self.final_norm, tuple) else (self.final_norm,),
                         src.final_norm if isinstance(src.final_norm, tuple) else (src.final_norm,)):
             a.copy_(b)
@@ -1181,6 +1249,14 @@ class CausalLM:
             for k, v in Ld.items():
                 if k.endswith(DERIVED):
                     derived = True
+                elif k in PROJ and ops.is_fp8(v):
+                    # fp8-only here: the source's canonical values straight to codes and scales, one
+                    # projection's bf16 at a time
+                    q, qs = self._codes(src.canonical(Ls, k).to(device=v.device, dtype=self.dtype), k)
+                    v.copy_(q)
+                    Ld[k + "_qs"].copy_(qs)
+                elif k in PROJ and ops.is_fp8(Ls[k]):
+                    v.copy_(to_resident(src.canonical(Ls, k), k, self._layout))
                 elif k in PROJ:
                     v.copy_(relayout(Ls[k], k, src._layout, self._layout))
                 elif isinstance(v, tuple):
@@ -1213,13 +1289,28 @@ class CausalLM:
         overwritten with the dequantised values (so the packed copy, prefill and the checkpoint
         hold exactly what the fp8 kernel computes with; a tied embedding table with them), and its
         codes and scales kept as ``*_q`` / ``*_qs`` in the packed copy's row order - layer by
-        layer, so peak memory stays the model plus one layer.  MoE expert stacks stay bf16."""
+        layer, so peak memory stays the model plus one layer.  MoE expert stacks stay bf16.
+
+        ``PREFILL_WEIGHTS`` = "fp8" on top: each ONE_LAYOUT layer then releases the packed bf16
+        tensor of every projection ``_f8_only_ok`` accepts - the codes become ``L[key]`` itself
+        (``_release_bf16``) - before the next layer is touched, and so does the head.  A model that
+        already holds fp8-only projections (a second ``_init_skinny``, a weight copy) turns each
+        layer's back to bf16 first (``_remat``), one layer at a time."""
+        if self.layers:
+            self._remat(self.layers[0], self._layout)  # layer 0's shapes decide below
         parts, one = self._want_dec(), self._one_layout_wanted()
         f8 = self.DEC_WEIGHTS == "fp8" and not self._f8_defer
         if f8 and self.cfg.is_moe:
             log.info("%s: decode_weights=fp8 leaves the MoE expert stacks on bf16 (grouped launches have no fp8 form)",
                      self.cfg.name)
+        f8_only = f8 and self.PREFILL_WEIGHTS == "fp8"
+        why = None  # why nothing can be fp8-only, if so
+        if f8_only and (self.cfg.is_moe or self.tp != 1 or not one):
+            why = "MoE" if self.cfg.is_moe else "TP > 1" if self.tp != 1 else "not ONE_LAYOUT-packed"
+        ceil = self._dec_row_ceiling(parts) if f8_only and why is None else 0
+        stayed: dict = {}
         for L in self.layers:
+            self._remat(L, self._layout)
             for key in ("wqkv", "wo", "w2", "w13"):  # w13 (three passes of temporaries) last: a fixed allocation order
                 w = L[key]
                 if w.dim() == 3:  # an [E, ...] stack for the grouped launches: both projections or neither
@@ -1235,6 +1326,13 @@ class CausalLM:
                     L[key + sfx] = relayout(w, key, self._layout, PACKED)
             if one:
                 self._adopt_packed(L)
+            if f8_only:
+                for key in PROJ:
+                    r = why or self._f8_only_why(L.get(key + "_q"), 2 if key == "w13" else 0, ceil)
+                    if r is None:
+                        self._release_bf16(L, key)
+                    else:
+                        stayed[key] = r
         N, K = self.lm_head.shape
         if "head" in parts and N % 16 == 0 and K % 32 == 0 and ops.dec_available(N, K, 1):
             if f8 and self._f8_shape_ok(N, K, 1):
@@ -1242,11 +1340,75 @@ class CausalLM:
                 self.lm_head.copy_(ops.dequantize_rows_fp8(q, self.lm_head_qs, self.dtype))  # tied: the embedding too
                 self.lm_head_q = ops.pack_skinny_f8(q)
                 del q
-            self.lm_head_d = ops.pack_skinny(self.lm_head)
-            if one and self.lm_head is not self.embed:
-                self.lm_head = self.lm_head_d  # ONE_LAYOUT: the packed head is the only copy too
+            r = (why or self._f8_only_why(self.lm_head_q, 1, ceil)) if f8_only else "off"
+            if r is None:
+                # the codes are the head's only copy: an untied bf16 head goes; a tied one stays as
+                # what it also is, the embedding table, and only its packed decode copy is not made
+                if self.lm_head is not self.embed:
+                    self.lm_head = self.lm_head_q
+            else:
+                if f8_only:
+                    stayed["head"] = r
+                self.lm_head_d = ops.pack_skinny(self.lm_head)
+                if one and self.lm_head is not self.embed:
+                    self.lm_head = self.lm_head_d  # ONE_LAYOUT: the packed head is the only copy too
+        elif f8_only:
+            stayed["head"] = why or "no decode copy of the head"
         if one:
             self._layout = PACKED
+        if stayed:
+            log.info("%s: prefill_weights=fp8 keeps the bf16 copy of %s", self.cfg.name,
+                     ", ".join(f"{k} ({r})" for k, r in stayed.items()))
+
+    def _dec_row_ceiling(self, parts: set) -> int:
+        """The most rows a decode step of this model will have once built (dec_rows_max's ceiling):
+        DEC_MAX_M where every projection and the head have a decode configuration at that many
+        rows (what _dec_wide_ok will find), else SKINNY_MAX_M.  From the shapes, before any layer
+        is packed."""
+        L = self.layers[0]
+        shapes = [tuple(L[k].shape) + (2 if k == "w13" else 0,) for k in PROJ if L[k].dim() == 2]
+        N, K = self.lm_head.shape
+        wide = (len(shapes) == 4 and "head" in parts and N % 16 == 0 and K % 32 == 0
+                and all(ops.dec_available(n, k, e, rows=ops.DEC_MAX_M) for n, k, e in shapes + [(N, K, 1)]))
+        return ops.DEC_MAX_M if wide else ops.SKINNY_MAX_M
+
+    @staticmethod
+    def _f8_only_why(wq: Optional[torch.Tensor], epi: int, ceil: int) -> Optional[str]:
+        """None when the weight with the codes ``wq`` may be resident as fp8 only, else why not:
+        it needs an fp8 encoding, an fp8 decode form in every row class up to the model's row
+        ceiling (nothing may ever ask for the bf16 copy) and the tile GEMM's fp8-W form."""
+        if wq is None:
+            return "no fp8 encoding"
+        N, K = ops.skinny_wdims(wq)
+        if not all(ops.dec_config(N, K, epi, rows=r, f8=True) is not None for r in ops.dec_row_classes() if r <= ceil):
+            return "no fp8 decode form in some row class"
+        return None if ops.tile_f8_ok(N, K) else "no fp8 form of the prefill GEMM for the shape"
+
+    @staticmethod
+    def _release_bf16(L: dict, key: str) -> None:
+        """PACKED layer: the codes of ``key`` become the resident weight; its packed bf16 tensor
+        (``L[key]`` and ``*_d``, one tensor) is released."""
+        L[key] = L[key + "_q"]
+        del L[key + "_d"]
+
+    def _codes(self, w: torch.Tensor, key: str) -> tuple:
+        """(packed codes, scales in packed row order) of the CANONICAL weight ``w`` of ``key``."""
+        q, s = ops.quantize_rows_fp8(w)
+        if key == "w13":
+            q = ops.interleave_gate_up8(q.view(torch.uint8)).view(torch.float8_e4m3fn)
+            s = ops.interleave_gate_up8(s[:, None])[:, 0]
+        return ops.pack_skinny_f8(q), s.contiguous()
+
+    def _remat(self, L: dict, form: str) -> None:
+        """Every fp8-only projection of the layer back to a bf16 tensor in the row-major layout
+        ``form`` (the dequantised values - what it was quantised from), its codes dropped, with the
+        gemm_skinny view ``*_p`` the other projections got in _init_skinny."""
+        for key in PROJ:
+            if ops.is_fp8(L.get(key)):
+                w = to_resident(self.canonical(L, key), key, form).contiguous()
+                L[key] = w
+                del L[key + "_q"], L[key + "_qs"]
+                L[key + "_p"] = w if self.skinny_layout == "rowmajor" else ops.pack_skinny(w)
 
     @staticmethod
     def _f8_shape_ok(N: int, K: int, epi: int) -> bool:

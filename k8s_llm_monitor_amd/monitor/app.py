@@ -71,7 +71,8 @@ def engine_config(cfg: Config):
                         tp_size=cfg.llm.tp_size, dtype=torch_dtype_name(cfg.llm.dtype),
                         max_prefill_tokens=cfg.llm.max_prefill_tokens, chunked_prefill=cfg.llm.chunked_prefill,
                         prefix_caching=cfg.llm.prefix_caching, weights=cfg.llm.weights or None,
-                        decode_weights=cfg.llm.decode_weights, kv_cache_dtype=cfg.llm.kv_cache_dtype)
+                        decode_weights=cfg.llm.decode_weights, prefill_weights=cfg.llm.prefill_weights,
+                        kv_cache_dtype=cfg.llm.kv_cache_dtype)
 
 
 def make_llm_backend(cfg: Config, pstate=None, device: Optional[str] = None):

@@ -9,7 +9,7 @@ keys are ignored.  A missing file is an error, like ``viper.ReadInConfig``.
 New engine knobs live under ``llm`` next to the reference's keys: ``provider: local-rocm`` selects
 the in-process MI355X engine (``openai`` keeps the reference's remote semantics: no local model),
 plus ``tp_size``, ``dp_replicas``, ``max_batch``, ``kv_cache_gb``, ``max_model_len``, ``dtype``,
-``seed``, ``use_graphs``, ``decode_weights``, ``kv_cache_dtype``.
+``seed``, ``use_graphs``, ``decode_weights``, ``prefill_weights``, ``kv_cache_dtype``.
 """
 from __future__ import annotations
 
@@ -61,6 +61,9 @@ class LLMConfig:
     # from (fp8: e4m3 codes per weight row with a power-of-two scale, kept beside the bf16 weights -
     # resident weights grow by half, prefill still reads bf16; docs/engine.md)
     decode_weights: str = "bf16"
+    # "bf16" | "fp8" (with decode_weights: fp8 only): prefill reads the fp8 codes too and the bf16
+    # copy of every dense projection / head that decode never needs is released (dense, TP = 1)
+    prefill_weights: str = "bf16"
     # "bf16" | "fp8": the paged KV cache's encoding (fp8: e4m3 codes + one power-of-two scale per
     # token and kv head - half the KV bytes per decode step, ~1.94x the tokens per kv_cache_gb)
     kv_cache_dtype: str = "bf16"

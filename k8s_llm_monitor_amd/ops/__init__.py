@@ -1165,7 +1165,7 @@ def moe_grouped_gemm(x: torch.Tensor, w: torch.Tensor, offsets: torch.Tensor, sw
 
 def gemm_tile(x: torch.Tensor, w: torch.Tensor, offsets: Optional[torch.Tensor] = None, swiglu: bool = False,
               out: Optional[torch.Tensor] = None, algo: int = 0, rope: Optional[tuple] = None,
-              rowscale: Optional[tuple] = None) -> torch.Tensor:
+              rowscale: Optional[tuple] = None, wscale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Prefill-sized ``x @ w^T`` on the 256 x 256 MFMA tile kernel (csrc/gemm_tile.hip).
 
     Dense: ``w`` [N, K].  Grouped: ``w`` [E, N, K] and ``offsets`` [E + 1] int32 device offsets of
@@ -1182,8 +1182,17 @@ def gemm_tile(x: torch.Tensor, w: torch.Tensor, offsets: Optional[torch.Tensor] 
     ``w`` may also be fragment-packed (pack_skinny: [N/16, K/32, 64, 8], grouped [E, ...]): the
     decode GEMMs' layout, consumed as is (every W DMA piece one contiguous 1-KiB block).
     ``swiglu=8``: the gate/up rows are interleaved per 16 (interleave_gate_up8, the decode GEMMs'
-    SwiGLU copy) instead of per 128 - prefill and decode then share one weight."""
+    SwiGLU copy) instead of per 128 - prefill and decode then share one weight.
+    ``w`` may be the fp8 decode encoding (pack_skinny_f8 codes [N/16, K/64, 64, 16]) with ``wscale``
+    its [N] fp32 row scales in packed row order: the codes are converted on the way into the MFMA,
+    bit-identical to the packed bf16 form over the dequantised weight.  Compiled for dense
+    launches on schedule 1 with K >= 192 (tile_f8_ok), plain / ``swiglu=8`` / ``rope`` with or
+    without ``rowscale``; any other form raises."""
     M = x.shape[0]
+    f8 = is_fp8(w)
+    if f8:
+        _tile_f8_check(w, wscale, "grouped" if offsets is not None else "swiglu=1 (per-128 pairing)"
+                       if swiglu and swiglu != 8 else None, algo)
     packed = w.dim() == (5 if offsets is not None else 4)
     N = w.shape[-4] * 16 if packed else w.shape[-2]
     if out is None:
@@ -1194,7 +1203,9 @@ def gemm_tile(x: torch.Tensor, w: torch.Tensor, offsets: Optional[torch.Tensor] 
     if rowscale is not None and (offsets is not None or not (swiglu or rope is not None)):
         raise ValueError("gemm_tile: the row scale is for the dense fused consumers (SwiGLU or RoPE)")
     if not _gpu(x):
-        if packed:
+        if f8:  # the dequantised values: exactly the bf16 encoding's
+            w = dequantize_rows_fp8(unpack_skinny_f8(w), wscale, x.dtype)
+        elif packed:
             w = (torch.stack([unpack_skinny(e) for e in w]) if offsets is not None else unpack_skinny(w))
         inv = None
         if rowscale is not None:
@@ -1231,30 +1242,60 @@ def gemm_tile(x: torch.Tensor, w: torch.Tensor, offsets: Optional[torch.Tensor] 
         raise ValueError("gemm_tile: the row scale needs schedule 1")
     if rope is not None:
         pos, cs, heads = rope
-        native().gemm_tile(out, x.contiguous(), w, None, False, algo, pos, cs, heads, rs_part, rs_eps)
+        native().gemm_tile(out, x.contiguous(), w, None, False, algo, pos, cs, heads, rs_part, rs_eps, wscale=wscale)
     elif rowscale is not None:
-        native().gemm_tile(out, x.contiguous(), w, None, int(swiglu), algo, None, None, 0, rs_part, rs_eps)
+        native().gemm_tile(out, x.contiguous(), w, None, int(swiglu), algo, None, None, 0, rs_part, rs_eps,
+                           wscale=wscale)
     else:
         native().gemm_tile(out, x.contiguous(), w, offsets.contiguous() if offsets is not None else None,
-                           int(swiglu), algo)
+                           int(swiglu), algo, wscale=wscale)
     return out
 
 
+def tile_f8_ok(N: int, K: int) -> bool:
+    """gemm_tile has an fp8-W form for a dense weight [N, K]: whole 16-row blocks and 64-deep
+    k-tiles, at least three of them (schedule 1's peeled ring tail; no schedule 0 form), and 32-bit
+    DMA byte offsets within the weight."""
+    return N % 16 == 0 and K % 64 == 0 and K >= 192 and N * K < (1 << 31)
+
+
+def _tile_f8_check(w: torch.Tensor, wscale: Optional[torch.Tensor], form: Optional[str], algo: int) -> None:
+    """An fp8 W of gemm_tile: only the compiled forms, no silent other path."""
+    if form is not None:
+        raise ValueError(f"gemm_tile: the fp8-W form is not compiled for {form} launches")
+    if w.dim() != 4 or w.shape[-2:] != (64, 16):
+        raise ValueError("gemm_tile: an fp8 w is pack_skinny_f8's [N/16, K/64, 64, 16]")
+    N, K = skinny_wdims(w)
+    if wscale is None or wscale.numel() != N or wscale.dtype != torch.float32:
+        raise ValueError(f"gemm_tile: an fp8 weight needs its [{N}] fp32 scale vector")
+    if algo != 1:
+        raise ValueError("gemm_tile: the fp8-W form is compiled for schedule 1 (algo=1) only, not schedule 0")
+    if not tile_f8_ok(N, K):
+        raise ValueError(f"gemm_tile: no fp8-W form for N={N} K={K} (K >= 192, K % 64 == 0, N * K < 2^31)")
+
+
 def gemm_tile_resid(x: torch.Tensor, w: torch.Tensor, resid: torch.Tensor, norm_w: torch.Tensor,
-                    hw: Optional[torch.Tensor] = None, ss: Optional[torch.Tensor] = None) -> tuple:
+                    hw: Optional[torch.Tensor] = None, ss: Optional[torch.Tensor] = None,
+                    wscale: Optional[torch.Tensor] = None) -> tuple:
     """A residual-producing prefill projection with the next RMSNorm's pass fused into its epilogue
     (csrc/gemm_tile.hip TILE_EPI_RESID; dense, N % 128 == 0): ``resid`` [M, N] <- bf16(resid +
     bf16(x @ w^T)) in place; returns ``(hw, ss)`` - hw = bf16(resid * norm_w) [M, N] and ss [M, N / 128]
     fp32 partial sums of resid^2 over each 128 columns, the operands of the consumer's row scale
-    (``gemm_tile(hw, ..., rowscale=(ss, eps))`` = the projection of rms_norm(resid) * norm_w)."""
+    (``gemm_tile(hw, ..., rowscale=(ss, eps))`` = the projection of rms_norm(resid) * norm_w).
+    ``w`` row-major, fragment-packed, or the fp8 encoding with ``wscale`` (see gemm_tile)."""
     M = x.shape[0]
+    f8 = is_fp8(w)
+    if f8:
+        _tile_f8_check(w, wscale, None, 1)
     N = w.shape[0] * 16 if w.dim() == 4 else w.shape[0]  # row-major or fragment-packed W
     if N % 128 or resid.shape != (M, N):
         raise ValueError("gemm_tile_resid: N % 128 == 0 and resid [M, N]")
     hw = hw if hw is not None else torch.empty_like(resid)
     ss = ss if ss is not None else torch.empty(M, N // 128, dtype=torch.float32, device=resid.device)
     if not _gpu(x):
-        if w.dim() == 4:
+        if f8:
+            w = dequantize_rows_fp8(unpack_skinny_f8(w), wscale, x.dtype)
+        elif w.dim() == 4:
             w = unpack_skinny(w)
         y = torch.nn.functional.linear(x.float(), w.float()).to(x.dtype)
         h = (y.float() + resid.float()).to(resid.dtype)
@@ -1263,7 +1304,7 @@ def gemm_tile_resid(x: torch.Tensor, w: torch.Tensor, resid: torch.Tensor, norm_
         ss.copy_((h.float() ** 2).view(M, N // 128, 128).sum(2))
         return hw, ss
     native().gemm_tile(resid, x.contiguous(), w, None, False, TILE_ALGO, None, None, 0, None, 1e-5, resid, hw,
-                       norm_w.contiguous(), ss)
+                       norm_w.contiguous(), ss, wscale=wscale)
     return hw, ss
 
 
@@ -1302,19 +1343,19 @@ def fused_norm_ok(M: int, d: int, n_qkv: int, n_o_in: int, n_13: int, f: int) ->
 
 
 def w_out(w: torch.Tensor) -> int:
-    """Output features of a dense projection weight: row-major [N, K] or fragment-packed
-    [N/16, K/32, 64, 8] (pack_skinny)."""
+    """Output features of a dense projection weight: row-major [N, K], fragment-packed
+    [N/16, K/32, 64, 8] (pack_skinny) or the fp8 encoding [N/16, K/64, 64, 16] (pack_skinny_f8)."""
     return w.shape[0] * 16 if w.dim() == 4 else w.shape[0]
 
 
 def w_in(w: torch.Tensor) -> int:
-    """Input features (K) of a row-major or fragment-packed dense projection weight."""
-    return w.shape[1] * 32 if w.dim() == 4 else w.shape[1]
+    """Input features (K) of a row-major, fragment-packed or fp8-encoded dense projection weight."""
+    return skinny_wdims(w)[1]
 
 
 def prefill_linear(x: torch.Tensor, w: torch.Tensor, swiglu: bool = False,
                    out: Optional[torch.Tensor] = None, rope: Optional[tuple] = None,
-                   rowscale: Optional[tuple] = None) -> torch.Tensor:
+                   rowscale: Optional[tuple] = None, wscale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``x @ w^T`` for a prefill-sized ``x`` [M, K] and row-major ``w`` [N, K]; ``swiglu``: ``w`` is
     gate/up-interleaved (interleave_gate_up) and the result is silu(gate) * up [M, N / 2] - fused
     into the tile kernel's epilogue, or F.linear + silu_mul on the library path.
@@ -1323,12 +1364,14 @@ def prefill_linear(x: torch.Tensor, w: torch.Tensor, swiglu: bool = False,
     library took the GEMM (the caller then applies RoPE itself).
     A fragment-packed ``w`` (pack_skinny, the ONE_LAYOUT resident form; ``swiglu=8`` with the
     interleave_gate_up8 pairing) always takes the tile kernel, whatever the row count - hipBLASLt
-    cannot read it; on the CPU gemm_tile unpacks it for the fp32 reference."""
+    cannot read it; on the CPU gemm_tile unpacks it for the fp32 reference.  So does the fp8
+    encoding of a weight (pack_skinny_f8 codes with ``wscale``, where the model keeps no bf16 copy)."""
     M, K = x.shape
     if w.dim() == 4:
+        ws = wscale if is_fp8(w) else None
         if rope is not None:
-            return gemm_tile(x, w, out=out, algo=TILE_ALGO, rope=rope, rowscale=rowscale), True
-        return gemm_tile(x, w, swiglu=swiglu, out=out, algo=TILE_ALGO, rowscale=rowscale)
+            return gemm_tile(x, w, out=out, algo=TILE_ALGO, rope=rope, rowscale=rowscale, wscale=ws), True
+        return gemm_tile(x, w, swiglu=swiglu, out=out, algo=TILE_ALGO, rowscale=rowscale, wscale=ws)
     N = w.shape[0]
     mode = PREFILL_GEMM
     tile_ok = _gpu(x) and tile_shape_ok(M, N, K, swiglu)

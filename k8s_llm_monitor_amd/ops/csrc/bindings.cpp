@@ -50,7 +50,7 @@ int k8sllm_gather_rows(void* out, const void* x, const int* idx, long n, int d, 
 int k8sllm_gemm_tile(const void* X, const void* W, void* Y, int M, int N, int K, const int* offsets, int E, long w_es,
                      int epi, int algo, const int* rope_pos, const float* rope_cs, int rope_heads,
                      const float* rs_part, int rs_np, float rs_eps, void* resid, void* hw, const void* norm_w,
-                     float* ss_out, int wpk, hipStream_t s);
+                     float* ss_out, int wpk, const float* wscale, hipStream_t s);
 int k8sllm_moe_grouped_gemm(const void* X, const void* W, void* Y, const int* offsets, int E, long rows, int N, int K,
                             long w_es, int epi, hipStream_t s);
 int k8sllm_gemm_skinny(const void* A, long lda, const void* Wp, float* partial, void* Y, long ldy, int M, int N, int K,
@@ -446,18 +446,38 @@ void gemm_tile(torch::Tensor y, torch::Tensor x, torch::Tensor w, c10::optional<
                int64_t algo, c10::optional<torch::Tensor> rope_pos, c10::optional<torch::Tensor> rope_cs,
                int64_t rope_heads, c10::optional<torch::Tensor> rs_part, double rs_eps,
                c10::optional<torch::Tensor> resid, c10::optional<torch::Tensor> hw,
-               c10::optional<torch::Tensor> norm_w, c10::optional<torch::Tensor> ss_out) {
-  dev_bf16(y, "y"); dev_bf16(x, "x"); dev_bf16(w, "w");
+               c10::optional<torch::Tensor> norm_w, c10::optional<torch::Tensor> ss_out,
+               c10::optional<torch::Tensor> wscale) {
+  dev_bf16(y, "y"); dev_bf16(x, "x");
+  // fp8 W: e4m3 codes fragment-packed [N/16, K/64, 64, 16] (pack_skinny_f8) + wscale [N] fp32 in packed row order
+  const bool f8 = w.scalar_type() == torch::kFloat8_e4m3fn;
+  if (f8) {
+    TORCH_CHECK(w.is_cuda(), "w must be a GPU tensor");
+  } else {
+    dev_bf16(w, "w");
+  }
   TORCH_CHECK(x.dim() == 2 && x.is_contiguous() && w.is_contiguous() && y.is_contiguous(),
               "gemm_tile: x [M, K], w contiguous, y contiguous");
   const bool grouped = offsets.has_value();
   // w row-major [N, K] / [E, N, K], or fragment-packed [N/16, K/32, 64, 8] / [E, ...] (pack_skinny)
   const bool wpk = w.dim() == (grouped ? 5 : 4);
-  TORCH_CHECK(w.dim() == (grouped ? 3 : 2) || (wpk && w.size(-2) == 64 && w.size(-1) == 8),
+  if (f8) {
+    TORCH_CHECK(!grouped, "gemm_tile: the fp8-W form is not compiled for grouped launches");
+    TORCH_CHECK(w.dim() == 4 && w.size(-2) == 64 && w.size(-1) == 16, "gemm_tile: fp8 w must be [N/16, K/64, 64, 16]");
+    TORCH_CHECK(wscale.has_value() && wscale->is_cuda() && wscale->scalar_type() == torch::kFloat32 &&
+                    wscale->is_contiguous() && wscale->numel() == w.size(0) * 16,
+                "gemm_tile: an fp8 w needs its [N] fp32 scale vector");
+    TORCH_CHECK(w.size(1) * 64 >= 192, "gemm_tile: the fp8-W form needs K >= 192 (schedule 1 only)");
+    TORCH_CHECK(algo == 1, "gemm_tile: the fp8-W form is compiled for schedule 1 (algo=1) only");
+    TORCH_CHECK(swiglu != 1, "gemm_tile: the fp8-W form has no per-128 SwiGLU pairing (swiglu=8 only)");
+  } else {
+    TORCH_CHECK(!wscale.has_value(), "gemm_tile: wscale goes with an fp8 w");
+  }
+  TORCH_CHECK(f8 || w.dim() == (grouped ? 3 : 2) || (wpk && w.size(-2) == 64 && w.size(-1) == 8),
               "gemm_tile: w [N, K] (dense) or [E, N, K] (grouped), or their fragment-packed forms");
   const int E = grouped ? (int)w.size(0) : 1;
   const int N = wpk ? (int)w.size(w.dim() - 4) * 16 : (int)w.size(w.dim() - 2);
-  const int K = wpk ? (int)w.size(w.dim() - 3) * 32 : (int)w.size(w.dim() - 1);
+  const int K = wpk ? (int)w.size(w.dim() - 3) * (f8 ? 64 : 32) : (int)w.size(w.dim() - 1);
   const int M = (int)x.size(0);
   TORCH_CHECK(x.size(1) == K, "gemm_tile: K mismatch");
   TORCH_CHECK(algo >= 0 && algo <= 1, "gemm_tile: algo 0 (one barrier per k-tile) or 1 (two)");
@@ -513,7 +533,7 @@ void gemm_tile(torch::Tensor y, torch::Tensor x, torch::Tensor w, c10::optional<
                          (long)N * K, epi, (int)algo, rp, rc, (int)rope_heads, rsp, rs_np, (float)rs_eps,
                          rsd ? resid->data_ptr() : nullptr, rsd ? hw->data_ptr() : nullptr,
                          rsd ? norm_w->data_ptr() : nullptr, rsd ? ss_out->data_ptr<float>() : nullptr, wpk ? 1 : 0,
-                         cur()),
+                         f8 ? wscale->data_ptr<float>() : nullptr, cur()),
         "gemm_tile");
 }
 
@@ -1065,7 +1085,7 @@ PYBIND11_MODULE(_k8sllm_ops, m) {
         py::arg("algo") = 1, py::arg("rope_pos") = py::none(), py::arg("rope_cs") = py::none(),
         py::arg("rope_heads") = 0, py::arg("rs_part") = py::none(), py::arg("rs_eps") = 1e-5,
         py::arg("resid") = py::none(), py::arg("hw") = py::none(), py::arg("norm_w") = py::none(),
-        py::arg("ss_out") = py::none());
+        py::arg("ss_out") = py::none(), py::arg("wscale") = py::none());
   m.def("gelu_tanh", &gelu_tanh);
   m.def("embedding", &embedding);
   m.def("resolve_ids", &resolve_ids);

@@ -53,6 +53,22 @@
 // than the DMA issue), the same tile on v_mfma_f32_32x32x16_bf16 (1-5 % slower), unswizzled rows
 // (bank conflicts, 10-15 % slower), L1-bypass / nt cache policies and staggered per-wave issue
 // (within 1 %).
+//
+// F8 (dense, schedule 1): W is the decode GEMMs' fp8 encoding - e4m3 codes fragment-packed
+// [N/16][K/64][64][16] (ops.pack_skinny_f8) and one power-of-two scale per row - so a model needs no
+// bf16 copy of a projection for prefill.  Block (n-tile j, k-tile) is one contiguous 1 KiB whose
+// lane l holds its 8 codes of k sub-step 0, then of sub-step 1:
+//  * a B half-tile is 16 KiB = 4 DMA pieces per wave (piece p = block 4p + wave of the tile), in
+//    the first half of its 32 KiB half-slot.  The ring keeps its five 32 KiB half-slots (A and B
+//    rotate through the same slots); the 16 KiB a B half-tile leaves free is not used.
+//  * while sub-step s computes, a wave reads the 8 bytes of sub-step s+1's codes of each of its 8
+//    blocks (ds_read_b64 at lane * 16 + 8 ks: lanes l and l + 16 share banks, so a read costs the
+//    4 LDS cycles of the bf16 kernel's ds_read_b128 - the same LDS time per k-tile as there; one
+//    16-B read for both sub-steps would halve it, but its 32 registers held across the k-tile
+//    spilled) and converts them: v_cvt_scalef32_pk_bf16_fp8 with the scale of row
+//    16 j + (lane & 15), two per MFMA shadow, 32 per sub-step.  code * 2^e is exact in bf16, so
+//    the fragment registers hold exactly the bf16 weight: the MFMA sequence and every epilogue are
+//    those of the bf16 kernel, and the result is bit-identical to it over the dequantised weight.
 #include <type_traits>
 
 #include "common.h"
@@ -70,11 +86,12 @@ __device__ __forceinline__ void vm_wait_n() {
 __device__ __forceinline__ void lgkm_wait0() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 }  // namespace
 
-template <int EPI, bool GROUPED, int SCH, bool RS = false>
+template <int EPI, bool GROUPED, int SCH, bool RS = false, bool F8 = false>
 __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ W,
                                                          bf16_t* __restrict__ Y, const int* __restrict__ offsets,
                                                          int E, int M, int N, int K, long w_es, int n_mt, int n_nt,
-                                                         TileEpi ep, int wpk) {
+                                                         TileEpi ep, int wpk, const float* __restrict__ wscale) {
+  static_assert(!F8 || (SCH == 1 && !GROUPED), "the fp8-W form is dense, schedule 1");
   constexpr int HS = 32768;  // one half-slot: 256 rows x 128 B
   __shared__ __attribute__((aligned(16))) char smem[5 * HS];
   const int lane = threadIdx.x & 63;
@@ -125,12 +142,21 @@ __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(const bf16_t* __restric
     const int cl = (lane & 7) ^ ((rl >> 1) & 7);
     soff[0][p] = (uint32_t)(((long)min(rl, mrows - 1) * K + cl * 8) * 2);  // rows past the end: clamped, never stored
     soff[1][p] = (uint32_t)(((long)min(rl, nrows - 1) * K + cl * 8) * 2);
-    if (wpk) {  // W fragment-packed [N/16][K/32][64][8]: piece = one contiguous 1-KiB block (n-tile, k-step)
+    if constexpr (F8) {  // e4m3 codes [N/16][K/64][64][16]: piece p < 4 = the 1-KiB block (n-tile 4 p + wave, k-tile):
+      // the block's offset is wave-uniform (sB below, in the soffset); the lane part is lane * 16
+      soff[1][p] = (uint32_t)(lane * 16);
+    } else if (wpk) {  // W fragment-packed [N/16][K/32][64][8]: piece = one contiguous 1-KiB block (n-tile, k-step)
       const int blk = p * 4 + wave, j = min(blk >> 1, (nrows >> 4) - 1);
       soff[1][p] = (uint32_t)(((long)j * (K >> 5) + (blk & 1)) * 1024 + lane * 16);
     }
   }
-  const int kstrB = wpk ? 2048 : 128;  // bytes of W per k-tile step, in the piece's soffset
+  // F8: byte offset of piece p's block row (n-tile 4 p + wave; the ragged last n-tile clamps, those
+  // rows are never stored) in this tile's W range - scalar
+  uint32_t sB[4];
+#pragma unroll
+  for (int p = 0; p < 4; ++p) sB[p] = F8 ? (uint32_t)(min(p * 4 + wave, (nrows >> 4) - 1) * (K >> 6)) * 1024u : 0u;
+  const int kstrB = F8 ? 1024 : wpk ? 2048 : 128;  // bytes of W per k-tile step, in the piece's soffset
+  constexpr int WB = F8 ? 1 : 2;                    // bytes per W element
   // buffer descriptors over this tile's X rows / W rows, built from wave-uniform values only so
   // hipcc keeps them in SGPRs (no waterfall loops, cdna_hip_programming.md T20)
   auto rsrc = [](const void* base, long bytes) {
@@ -140,7 +166,7 @@ __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(const bf16_t* __restric
     return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((uint64_t)hi << 32) | lo), 0, nb, 0x00020000);
   };
   const __amdgpu_buffer_rsrc_t xr = rsrc(reinterpret_cast<const char*>(X) + (long)row0 * K * 2, (long)mrows * K * 2);
-  const __amdgpu_buffer_rsrc_t wr = rsrc(reinterpret_cast<const char*>(Wt) + (long)n0 * K * 2, (long)nrows * K * 2);
+  const __amdgpu_buffer_rsrc_t wr = rsrc(reinterpret_cast<const char*>(Wt) + (long)n0 * K * WB, (long)nrows * K * WB);
   const int nk = K >> 6;
 
   // piece p of half-tile (operand o, k-tile kt) into half-slot `slot`; k-tiles past the end re-read
@@ -149,13 +175,13 @@ __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(const bf16_t* __restric
   auto piece = [&](int o, int p, int kt, int slot) {
     char* dst = smem + slot * HS + (p * 4 + wave) * 1024;
     if (o)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(wr, (lds_void_t*)dst, 16, soff[1][p], min(kt, nk - 1) * kstrB, 0, 0);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(wr, (lds_void_t*)dst, 16, soff[1][p], min(kt, nk - 1) * kstrB + sB[p & 3], 0, 0);
     else
       __builtin_amdgcn_raw_ptr_buffer_load_lds(xr, (lds_void_t*)dst, 16, soff[0][p], min(kt, nk - 1) * 128, 0, 0);
   };
   auto issue_half = [&](int o, int kt) {
 #pragma unroll
-    for (int p = 0; p < 8; ++p) piece(o, p, kt, (2 * kt + o) % 5);
+    for (int p = 0; p < (F8 && o ? 4 : 8); ++p) piece(o, p, kt, (2 * kt + o) % 5);
   };
 
   // fragment read: lane row lane & 15 of a 16-row block, 16-B chunk 4 ks + (lane >> 4)
@@ -178,8 +204,21 @@ __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(const bf16_t* __restric
 #pragma unroll
     for (int j = 0; j < 8; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  bf16x8 fa0[8], fb0[8], fa1[8], fb1[8];
   typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+  // F8: the B fragments are built a dword (two bf16) at a time, so they are held as dwords
+  using fragb_t = std::conditional_t<F8, u32x4, bf16x8>;
+  bf16x8 fa0[8], fa1[8];
+  fragb_t fb0[8], fb1[8];
+  // F8: the next sub-step's 8 codes of each of the wave's 8 blocks as read from LDS, and the scale
+  // of this lane's row of each block
+  u32x2 raw[F8 ? 8 : 1];
+  float wsc[F8 ? 8 : 1];
+  // 4 codes (one dword) x the row scale -> dwords 2 h, 2 h + 1 of a fragment; exact (common.h kv_f8_deq8)
+  auto cvt4 = [](u32x4& d, uint32_t c, float sc, int h) {
+    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+    d[2 * h] = __builtin_bit_cast(uint32_t, (bf16x2)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c, sc, false));
+    d[2 * h + 1] = __builtin_bit_cast(uint32_t, (bf16x2)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c, sc, true));
+  };
   // RESID: this lane's first 16 residual chunks (rows rr + 4b of the wave's 128, 16 B at column
   // chunk cc), issued during the last k-tile's second half so they land behind its MFMAs
   u32x4 resq[EPI == TILE_EPI_RESID ? 16 : 1];
@@ -193,16 +232,20 @@ __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(const bf16_t* __restric
     auto rd16 = [&](uint32_t base, int blk) -> bf16x8 {
       return *reinterpret_cast<const bf16x8*>(smem + base + blk * 2048);
     };
+    const uint32_t fbR = (uint32_t)(lane * 16 + wn * 8192);  // F8: block blk of the wave's 8, 1 KiB each
+    auto rdraw = [&](uint32_t base, int blk) -> u32x2 {
+      return *reinterpret_cast<const u32x2*>(smem + base + blk * 1024);
+    };
     auto pc = [&](int o, int p, int kt, uint32_t slot_bytes) {
       char* dst = smem + slot_bytes + (p * 4 + wave) * 1024;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(o ? wr : xr, (lds_void_t*)dst, 16, soff[o][p], min(kt, nk - 1) * (o ? kstrB : 128),
-                                               0, 0);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(o ? wr : xr, (lds_void_t*)dst, 16, soff[o][p],
+                                               min(kt, nk - 1) * (o ? kstrB : 128) + (o ? sB[p & 3] : 0u), 0, 0);
     };
     // PM (the ring tail, peeled): 0 = B_{t+2} and A_{t+3} refills; 1 = B_{t+2} only (A_{t+3} is
     // past the end); 2 = no refill; 3 = no refill and, in (t, 1), no reads of tile t+1 (there is
     // none).  The tail issues no dummy pieces (a re-read of the last k-tile kept the counts fixed:
     // 40 of every tile's 1064 pieces per wave, ~4 % of the DMA issue at K = 4096).
-    auto sub = [&](auto ph, auto pm, bf16x8 (&ca)[8], bf16x8 (&cb)[8], bf16x8 (&na)[8], bf16x8 (&nb)[8],
+    auto sub = [&](auto ph, auto pm, bf16x8 (&ca)[8], fragb_t (&cb)[8], bf16x8 (&na)[8], fragb_t (&nb)[8],
                    uint32_t sa, uint32_t sb, uint32_t da, uint32_t db, int t) {
       constexpr int PH = decltype(ph)::value, PM = decltype(pm)::value;
       constexpr bool READS = !(PH == 1 && PM == 3);
@@ -214,8 +257,34 @@ __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(const bf16_t* __restric
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           const int n = g * 8 + j;
-          acc[g][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cb[j], ca[g], acc[g][j], 0, 0, 0);
-          if (n < 8) {
+          acc[g][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, cb[j]), ca[g], acc[g][j], 0, 0, 0);
+          if constexpr (F8) {
+            // One instruction group per MFMA shadow, as below.  B_{t+2} is 4 pieces (MFMAs 22, 34,
+            // 46, 58 of (t, 0)) and A_{t+3}'s 8 ride MFMAs 19, 24, .., 54 of (t, 1).  MFMAs 0-7 read
+            // the next sub-step's codes of the 8 blocks, 8-15 its A fragments; behind them the 16
+            // conversion units (unit u: fragment u >> 1, code dword u & 1 -> fragment dwords
+            // 2 (u & 1), + 1: two v_cvt) take the non-piece MFMAs from 20 on - (t, 0): 20 .. 37
+            // without 22, 34, after the barrier's wait for the reads; (t, 1): 20 .. 38 without 24,
+            // 29, 34.  nb was the previous sub-step's cb: all of its MFMAs have issued (in order)
+            // long before the first unit, and an MFMA reads its A / B operands when it issues.
+            const int cu = n < 20 ? -1
+                           : PH == 0 ? (n <= 37 && n != 22 && n != 34 ? (n - 20) - (n > 22) - (n > 34) : -1)
+                                     : (n < 39 && (n - 19) % 5 != 0 ? (n - 20) - (n - 19) / 5 : -1);
+            if (n < 8) {
+              if constexpr (READS) raw[n] = rdraw(sb + fbR + (PH == 0 ? 8 : 0), n);
+            } else if (n < 16) {
+              if constexpr (READS) na[n - 8] = rd16(ba, n - 8);
+            } else if (cu >= 0) {
+              if constexpr (READS) cvt4(nb[cu >> 1], raw[cu >> 1][cu & 1], wsc[cu >> 1], cu & 1);
+            } else if (PH == 0 && PM <= 1 && n == 19) {  // frees tile t's half-slots for the refills
+              lgkm_wait0();
+              __builtin_amdgcn_s_barrier();
+            } else if (PH == 0 && PM <= 1 && n >= 22 && (n - 22) % 12 == 0) {
+              pc(1, (n - 22) / 12, t + 2, da);
+            } else if (PH == 1 && PM == 0 && n >= 19 && (n - 19) % 5 == 0 && (n - 19) / 5 < 8) {
+              pc(0, (n - 19) / 5, t + 3, db);
+            }
+          } else if (n < 8) {
             if constexpr (READS) nb[n] = rd16(bb, n);
           } else if (n < 16) {
             if constexpr (READS) na[n - 8] = rd16(ba, n - 8);
@@ -247,12 +316,17 @@ __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(const bf16_t* __restric
 #pragma unroll
       for (int j = 0; j < 16; ++j) rsq[j] = *reinterpret_cast<const f32x4*>(rp + min(4 * j, ep.rs_np - 4));
     }
+    if constexpr (F8) {  // scale of row 16 j + (lane & 15) of the wave's 8 blocks (past N: clamped, never stored)
+#pragma unroll
+      for (int g = 0; g < 8; ++g) wsc[g] = wscale[min(n0 + (wn * 8 + g) * 16 + (lane & 15), N - 1)];
+    }
     issue_half(0, 0);
     issue_half(1, 0);
     issue_half(0, 1);
     issue_half(1, 1);
     issue_half(0, 2);
-    vm_wait_n<24>();
+    // tile 0 landed: younger are A_1 B_1 A_2 = 8 + 8 + 8 pieces; F8 (B = 4 pieces): 8 + 4 + 8
+    if constexpr (F8) vm_wait_n<20>(); else vm_wait_n<24>();
     __builtin_amdgcn_s_barrier();
     if constexpr (RS) {
       float sum = 0.f;
@@ -260,11 +334,20 @@ __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(const bf16_t* __restric
       for (int j = 0; j < 16; ++j)
         if (4 * j < ep.rs_np) sum += (rsq[j][0] + rsq[j][1]) + (rsq[j][2] + rsq[j][3]);
       rs_inv = rsqrtf(sum / (float)K + ep.rs_eps);
+      // F8: pin the sum here (the compiler otherwise sinks it behind the k loop and keeps the 64
+      // partial-sum registers alive across it, which with the raw codes no longer fit)
+      if constexpr (F8) asm volatile("" : "+v"(rs_inv));
     }
 #pragma unroll
     for (int g = 0; g < 8; ++g) {
       fa0[g] = frag(0, 0, 0, g);
-      fb0[g] = frag(1, 0, 1, g);
+      if constexpr (F8) {
+        raw[g] = rdraw(HS + fbR, g);
+        cvt4(fb0[g], raw[g][0], wsc[g], 0);
+        cvt4(fb0[g], raw[g][1], wsc[g], 1);
+      } else {
+        fb0[g] = frag(1, 0, 1, g);
+      }
     }
     // half-slot bytes of tile t: S0 = (2t % 5) HS (A_t), S1 = ((2t + 1) % 5) HS (B_t), S2 / S3 =
     // tile t+1's.  Tile t+1: S0' = S2, S1' = S3, S2' = ((2t + 4) % 5) HS, S3' = S0.
@@ -277,11 +360,13 @@ __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(const bf16_t* __restric
       S3 = s0;
     };
     // vmcnt at the mid-tile wait: B_{t+1} must have landed; younger are A_{t+2} (8) + B_{t+2}'s
-    // first 7 pieces (15) in the steady state and at t = nk - 3, nothing from t = nk - 2 on
+    // first 7 pieces (15) in the steady state and at t = nk - 3, nothing from t = nk - 2 on.
+    // F8: A_{t+2} (8) + all 4 pieces of B_{t+2}, issued in (t, 0) (12)
+    constexpr int MIDW = F8 ? 12 : 15;
     for (int t = 0; t < nk - 3; ++t) {
       __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): the previous sub-step's reads, explicitly
       sub(P0{}, P0{}, fa0, fb0, fa1, fb1, S0, S1, S0, S1, t);
-      vm_wait_n<15>();
+      vm_wait_n<MIDW>();
       __builtin_amdgcn_s_barrier();
       sub(P1{}, P0{}, fa1, fb1, fa0, fb0, S2, S3, S0, S1, t);
       rotate();
@@ -290,7 +375,7 @@ __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(const bf16_t* __restric
       const int t = nk - 3;
       __builtin_amdgcn_s_waitcnt(0xc07f);
       sub(P0{}, P1{}, fa0, fb0, fa1, fb1, S0, S1, S0, S1, t);
-      vm_wait_n<15>();
+      vm_wait_n<MIDW>();
       __builtin_amdgcn_s_barrier();
       sub(P1{}, P1{}, fa1, fb1, fa0, fb0, S2, S3, S0, S1, t);
       rotate();
@@ -386,7 +471,12 @@ __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(const bf16_t* __restric
   const int ml = lane & 15, nq = 4 * (lane >> 4);
   const int rr = lane >> 4, cc = lane & 15;
   uint4 nwv{};
-  if constexpr (EPI == TILE_EPI_RESID) nwv = *reinterpret_cast<const uint4*>(ep.norm_w + n0 + wn * 128 + cc * 8);
+  // RESID (N % 128 == 0): the wave's 128 columns are all inside N or, in a last n-tile of 128
+  // columns, all past it - then it stores nothing (its offsets would alias the next row): branch-free,
+  // its norm weights are read from the tile's first quarter and its offsets are out of range
+  [[maybe_unused]] const bool quarter_in = nrows - wn * 128 >= 128;
+  if constexpr (EPI == TILE_EPI_RESID)
+    nwv = *reinterpret_cast<const uint4*>(ep.norm_w + n0 + (quarter_in ? wn * 128 : 0) + cc * 8);
   // RS: each thread's row scale through LDS (after the staging area) to the lanes holding the row
   float sc[8];
 #pragma unroll
@@ -451,7 +541,7 @@ __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(const bf16_t* __restric
     // lane (rr, cc): row rr + 4b, columns cc*8 .. +7 of the wave's quarter; N % 128 == 0 (host)
     const __amdgpu_buffer_rsrc_t rres = rsrc(ep.resid + (long)row0 * N, (long)mrows * N * 2);
     const __amdgpu_buffer_rsrc_t rhw = rsrc(ep.hw + (long)row0 * N, (long)mrows * N * 2);
-    const uint32_t ro = (uint32_t)(((wm * 128 + rr) * N + n0 + wn * 128 + cc * 8) * 2);
+    const uint32_t ro = quarter_in ? (uint32_t)(((wm * 128 + rr) * N + n0 + wn * 128 + cc * 8) * 2) : 0x80000000u;
     float wf[8];
     unpack8(nwv, wf);
     const int ss_np = N >> 7, ssc = (n0 + wn * 128) >> 7;
@@ -477,7 +567,7 @@ __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(const bf16_t* __restric
       __builtin_amdgcn_raw_buffer_store_b128(u32x4{wq.x, wq.y, wq.z, wq.w}, rhw, off, 0, 0);
       ss = row16_sum(ss);
       const int grow = wm * 128 + r;
-      if (cc == 0 && grow < mrows) ep.ss_out[(long)(row0 + grow) * ss_np + ssc] = ss;
+      if (cc == 0 && grow < mrows && quarter_in) ep.ss_out[(long)(row0 + grow) * ss_np + ssc] = ss;
     }
     return;
   }
@@ -545,11 +635,17 @@ using namespace k8sllm;
 // Shapes: N % 16 == 0 (SwiGLU: N % 256 == 0), K % 64 == 0.  algo: the refill schedule (0 or 1).
 // wpk: W is fragment-packed ([E][N/16][K/32][64][8], ops.pack_skinny - the decode GEMMs' layout)
 // instead of row-major: every W DMA piece is one contiguous 1-KiB block, read lane-linear from LDS.
+// wscale != nullptr: W is the fp8 encoding - e4m3 codes [N/16][K/64][64][16] (ops.pack_skinny_f8) with
+// wscale [N] fp32 row scales in packed row order.  Compiled forms: dense, schedule 1 (K >= 192), the
+// BF16 / SWIGLU8 / ROPE / RESID epilogues and the row-scaled SWIGLU8 / ROPE; any other returns -4.
 extern "C" int k8sllm_gemm_tile(const void* X, const void* W, void* Y, int M, int N, int K, const int* offsets, int E,
                                 long w_es, int epi, int algo, const int* rope_pos, const float* rope_cs,
                                 int rope_heads, const float* rs_part, int rs_np, float rs_eps, void* resid, void* hw,
-                                const void* norm_w, float* ss_out, int wpk, hipStream_t s) {
+                                const void* norm_w, float* ss_out, int wpk, const float* wscale, hipStream_t s) {
   if (M <= 0) return 0;
+  const bool f8 = wscale != nullptr;
+  // fp8 W: only the forms a packed dense layer launches are compiled - no silent other schedule
+  if (f8 && (offsets != nullptr || algo != 1 || K < 192 || epi == TILE_EPI_SWIGLU)) return -4;
   const bool grouped = offsets != nullptr;
   const bool rs = rs_part != nullptr;
   if (grouped && (E < 1 || E > 256)) return -1;
@@ -571,15 +667,16 @@ extern "C" int k8sllm_gemm_tile(const void* X, const void* W, void* Y, int M, in
   const TileEpi ep{rope_pos, rope_cs, rope_heads, rs_part, rs_np, rs_eps, (bf16_t*)resid, (bf16_t*)hw,
                    (const bf16_t*)norm_w, ss_out};
   // 32-bit DMA offsets (X: relative to the tile's first row; W: within one expert / n-tile)
-  if ((long)N * K * 2 >= (1L << 31) || 256L * K * 2 >= (1L << 31)) return -3;
+  if ((long)N * K * (f8 ? 1 : 2) >= (1L << 31) || 256L * K * 2 >= (1L << 31)) return -3;
   if (epi == TILE_EPI_RESID && 256L * N * 2 >= (1L << 31)) return -3;
   const int n_mt = (M + 255) / 256 + (grouped ? E : 0), n_nt = (N + 255) / 256;
   const long nwg = (long)n_mt * n_nt;
   if (nwg > (1L << 30)) return -2;
   const dim3 grid((unsigned)nwg);
-#define K8_TILE_LAUNCH(EPI_, G_, SCH_, RS_)                                                                          \
-  hipLaunchKernelGGL((gemm_w4_kernel<EPI_, G_, SCH_, RS_>), grid, dim3(256), 0, s, (const bf16_t*)X,                \
-                     (const bf16_t*)W, (bf16_t*)Y, offsets, E, M, N, K, w_es, n_mt, n_nt, ep, wpk)
+#define K8_TILE_LAUNCH_F(EPI_, G_, SCH_, RS_, F8_)                                                                   \
+  hipLaunchKernelGGL((gemm_w4_kernel<EPI_, G_, SCH_, RS_, F8_>), grid, dim3(256), 0, s, (const bf16_t*)X,           \
+                     (const bf16_t*)W, (bf16_t*)Y, offsets, E, M, N, K, w_es, n_mt, n_nt, ep, wpk, wscale)
+#define K8_TILE_LAUNCH(EPI_, G_, SCH_, RS_) K8_TILE_LAUNCH_F(EPI_, G_, SCH_, RS_, false)
 #define K8_TILE_SCH(SCH_)                                                                                            \
   if (grouped) {                                                                                                     \
     if (epi == TILE_EPI_SWIGLU) K8_TILE_LAUNCH(TILE_EPI_SWIGLU, true, SCH_, false);                                  \
@@ -591,7 +688,14 @@ extern "C" int k8sllm_gemm_tile(const void* X, const void* W, void* Y, int M, in
     else if (epi == TILE_EPI_ROPE) K8_TILE_LAUNCH(TILE_EPI_ROPE, false, SCH_, false);                                \
     else K8_TILE_LAUNCH(TILE_EPI_BF16, false, SCH_, false);                                                          \
   }
-  if (epi == TILE_EPI_RESID) {
+  if (f8) {
+    if (epi == TILE_EPI_RESID) K8_TILE_LAUNCH_F(TILE_EPI_RESID, false, 1, false, true);
+    else if (epi == TILE_EPI_SWIGLU8 && rs) K8_TILE_LAUNCH_F(TILE_EPI_SWIGLU8, false, 1, true, true);
+    else if (epi == TILE_EPI_SWIGLU8) K8_TILE_LAUNCH_F(TILE_EPI_SWIGLU8, false, 1, false, true);
+    else if (epi == TILE_EPI_ROPE && rs) K8_TILE_LAUNCH_F(TILE_EPI_ROPE, false, 1, true, true);
+    else if (epi == TILE_EPI_ROPE) K8_TILE_LAUNCH_F(TILE_EPI_ROPE, false, 1, false, true);
+    else K8_TILE_LAUNCH_F(TILE_EPI_BF16, false, 1, false, true);
+  } else if (epi == TILE_EPI_RESID) {
     K8_TILE_LAUNCH(TILE_EPI_RESID, false, 1, false);
   } else if (rs) {
     if (epi == TILE_EPI_SWIGLU) K8_TILE_LAUNCH(TILE_EPI_SWIGLU, false, 1, true);
@@ -604,5 +708,6 @@ extern "C" int k8sllm_gemm_tile(const void* X, const void* W, void* Y, int M, in
   }
 #undef K8_TILE_SCH
 #undef K8_TILE_LAUNCH
+#undef K8_TILE_LAUNCH_F
   return (int)hipGetLastError();
 }

@@ -4,6 +4,12 @@ Mixtral-8x7B grouped expert shapes (top-2 of 8).  Random operands, interleaved r
 replay of back-to-back calls; the SwiGLU rows compare the fused epilogue with F.linear + silu_mul.
 
     python tools/bench_gemm_tile.py [--tokens 16384] [--rounds 3]
+
+``--f8``: the fp8-W form (prefill_weights: fp8 - e4m3 codes converted on the way into the MFMA)
+against the packed bf16 form of the same weights, in one process, interleaved, on the four
+Llama-3-8B projections with the epilogues the fused-norm prefill layer launches: qkv RoPE + row
+scale, o residual, gate_up SwiGLU8 + row scale, down residual.  Also checks that the two forms
+give the same bits.
 """
 from __future__ import annotations
 
@@ -22,6 +28,64 @@ from tools.bench_skinny import timeit  # noqa: E402
 F_ = torch.nn.functional
 
 
+def f8_cases(T: int, dev: str) -> list:
+    from k8s_llm_monitor_amd.ops import reference as ref
+
+    d, F = 4096, 14336
+    x = torch.randn(T, d, device=dev, dtype=torch.bfloat16)
+    xf = torch.randn(T, F, device=dev, dtype=torch.bfloat16)
+    cs = ref.rope_cos_sin(8192, 128, 500000.0).to(dev).float().contiguous()
+    pos = (torch.arange(T, device=dev) % 8192).to(torch.int32)
+    ssq = (torch.rand(T, d // 128, device=dev) * 128 + 64).contiguous()
+    resid = torch.randn(T, d, device=dev, dtype=torch.bfloat16)
+    hwb = torch.empty(T, d, device=dev, dtype=torch.bfloat16)
+    ssb = torch.empty(T, d // 128, device=dev, dtype=torch.float32)
+    nwv = torch.ones(d, device=dev, dtype=torch.bfloat16)
+
+    def enc(N, K, il=False):
+        w = (torch.randn(N, K, device=dev) * 0.02).to(torch.bfloat16)
+        q, s = ops.quantize_rows_fp8(ops.interleave_gate_up8(w) if il else w)
+        return ops.pack_skinny(ops.dequantize_rows_fp8(q, s)), ops.pack_skinny_f8(q), s.contiguous()
+
+    cases = []
+    wb, wq, ws = enc(6144, d)
+    yq = torch.empty(T, 6144, device=dev, dtype=torch.bfloat16)
+    kw = dict(out=yq, algo=1, rope=(pos, cs, 40), rowscale=(ssq, 1e-5))
+    assert torch.equal(ops.gemm_tile(x, wb, **kw).clone(), ops.gemm_tile(x, wq, wscale=ws, **kw))
+    cases.append(("qkv+rope_rs", 2 * T * 6144 * d, {
+        "bf16": (lambda i, wb=wb, kw=kw: ops.gemm_tile(x, wb, **kw)),
+        "fp8": (lambda i, wq=wq, ws=ws, kw=kw: ops.gemm_tile(x, wq, wscale=ws, **kw))}))
+    for name, K, xin in (("o_resid", d, x), ("down_resid", F, xf)):
+        wb, wq, ws = enc(d, K)
+        cases.append((name, 2 * T * d * K, {
+            "bf16": (lambda i, wb=wb, xin=xin: ops.gemm_tile_resid(xin, wb, resid, nwv, hw=hwb, ss=ssb)),
+            "fp8": (lambda i, wq=wq, ws=ws, xin=xin: ops.gemm_tile_resid(xin, wq, resid, nwv, hw=hwb, ss=ssb, wscale=ws))}))
+    wb, wq, ws = enc(2 * F, d, il=True)
+    act = torch.empty(T, F, device=dev, dtype=torch.bfloat16)
+    kw2 = dict(swiglu=8, out=act, algo=1, rowscale=(ssq, 1e-5))
+    assert torch.equal(ops.gemm_tile(x, wb, **kw2).clone(), ops.gemm_tile(x, wq, wscale=ws, **kw2))
+    cases.append(("gate_up+swiglu8_rs", 2 * T * 2 * F * d, {
+        "bf16": (lambda i, wb=wb: ops.gemm_tile(x, wb, **kw2)),
+        "fp8": (lambda i, wq=wq, ws=ws: ops.gemm_tile(x, wq, wscale=ws, **kw2))}))
+    return cases
+
+
+def run_cases(cases: list, a, T: int) -> None:
+    for name, flops, impls in cases:
+        if a.only and name not in a.only.split(","):
+            continue
+        res: dict = {}
+        for _ in range(a.rounds):
+            for tag, fn in impls.items():
+                if a.impl and tag not in a.impl.split(","):
+                    continue
+                res.setdefault(tag, []).append(timeit(fn, a.iters, per_graph=4))
+        for tag, ts in res.items():
+            t = min(ts)
+            print(json.dumps({"op": name, "tokens": T, "impl": tag, "us": round(t, 1),
+                              "us_all": [round(v, 1) for v in ts], "PFps": round(flops / t / 1e9, 3)}), flush=True)
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--tokens", type=int, default=16384)
@@ -29,10 +93,14 @@ def main() -> None:
     ap.add_argument("--iters", type=int, default=16)
     ap.add_argument("--only", default="")
     ap.add_argument("--impl", default="", help="comma list of implementations to time (default all)")
+    ap.add_argument("--f8", action="store_true", help="the fp8-W form against the packed bf16 form (see above)")
     a = ap.parse_args()
     dev = "cuda"
     T = a.tokens
     torch.manual_seed(0)
+    if a.f8:
+        run_cases(f8_cases(T, dev), a, T)
+        return
     cases = []
     d, F = 4096, 14336
     x = torch.randn(T, d, device=dev, dtype=torch.bfloat16)
@@ -134,19 +202,7 @@ def main() -> None:
         "moe_gemm128": (lambda i: ops.moe_grouped_gemm(hs, we2, offsets, out=ys)),
         "hipblaslt_loop": loop2,
     }))
-    for name, flops, impls in cases:
-        if a.only and name not in a.only.split(","):
-            continue
-        res: dict = {}
-        for _ in range(a.rounds):
-            for tag, fn in impls.items():
-                if a.impl and tag not in a.impl.split(","):
-                    continue
-                res.setdefault(tag, []).append(timeit(fn, a.iters, per_graph=4))
-        for tag, ts in res.items():
-            t = min(ts)
-            print(json.dumps({"op": name, "tokens": T, "impl": tag, "us": round(t, 1),
-                              "us_all": [round(v, 1) for v in ts], "PFps": round(flops / t / 1e9, 3)}), flush=True)
+    run_cases(cases, a, T)
 
 
 if __name__ == "__main__":

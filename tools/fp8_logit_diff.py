@@ -6,6 +6,9 @@ rms logit difference, the logit scale, and how many of the rows keep their argma
 
     python tools/fp8_logit_diff.py [--model llama-3-8b --layers 2 --prompts 8]
 
+(``prefill_weights: fp8`` needs no numbers of its own: it releases the bf16 copy of weights whose
+values stay exactly these dequantised ones, and its prefill GEMM is bit-identical.)
+
 ``--kv-cache-dtype fp8`` measures the e4m3 KV cache instead: both engines keep bf16 weights, one
 on a bf16 and one on an fp8 cache; the first half of each prompt is prefilled into the engine's own
 paged cache and the second half decoded through it one teacher-forced token at a time, so every

@@ -69,10 +69,12 @@ class EngineConfig:
     # a Hugging Face model directory (config.json, *.safetensors, optional tokenizer.json): real
     # weights instead of the seeded random init (models/checkpoint.py); None = random init
     weights: Optional[str] = None
-    # "bf16" | "fp8": the encoding the decode GEMMs stream the dense projections and the LM head from
+    # "bf16" | "fp8" | "mxfp4": the encoding the decode GEMMs stream the dense projections and the LM head from
     # (CausalLM.DEC_WEIGHTS).  fp8 quantises each weight row to e4m3 with a power-of-two scale; the
     # model's bf16 weights become the dequantised values and the fp8 copy is kept beside them
-    # (resident weights grow by half; prefill still reads bf16; only decode streams fewer bytes)
+    # (resident weights grow by half; prefill still reads bf16; only decode streams fewer bytes).
+    # mxfp4: the same design over OCP MXFP4 (e2m1 codes, one e8m0 scale per 32 elements along K;
+    # resident weights grow by 17/64; round-to-nearest, visibly less accurate than fp8)
     decode_weights: str = "bf16"
     # "bf16" | "fp8" (on top of decode_weights = "fp8" only): what prefill reads
     # (CausalLM.PREFILL_WEIGHTS).  fp8: the prefill tile GEMM converts the decode codes on the way

@@ -113,6 +113,8 @@ PROJ = ("wqkv", "wo", "w13", "w2")
 # gemm_skinny views (dense, expert stack), the decode GEMM's packed copies (dense, expert stack)
 # and, with DEC_WEIGHTS = "fp8", the fp8 encoding of a dense projection (packed e4m3 codes, per-row scales;
 # with PREFILL_WEIGHTS = "fp8" the codes may be the projection itself: L[key] is L[key + "_q"], no "_d")
+# or, with DEC_WEIGHTS = "mxfp4", its mxfp4 encoding under the same two keys (ops.pack_skinny_f4's
+# codes and block scales; ops.is_mxfp4 / ops.is_fp8 tell the two apart)
 DERIVED = ("_p", "_pg", "_d", "_dg", "_q", "_qs")
 DEC_COPIES = ("_d", "_dg")  # the decode GEMM's packed bf16 copies among them
 
@@ -169,6 +171,10 @@ class CausalLM:
     # read them unchanged) and the fp8 copy sits beside them (resident weights grow by half; only
     # decode gets faster).  Per launch the fp8 encoding is used where gemm_decode.hip has an fp8
     # form for the shape and row count (ops.dec_config(f8=True)), the bf16 copy otherwise.
+    # "mxfp4" - the same two-copy design over OCP MXFP4 (ops.quantize_mxfp4: e2m1 codes with one
+    # e8m0 scale per 32 elements along K): the bf16 weights are the dequantised values, the codes
+    # and block scales sit beside them under the same ``*_q`` / ``*_qs`` keys (resident weights
+    # grow by 17/64), and a launch streams them where ops.dec_config(f4=True) has a form.
     DEC_WEIGHTS = "bf16"
     # What prefill reads where DEC_WEIGHTS = "fp8": "bf16" - the bf16 copy beside the codes - or
     # "fp8": the tile GEMM converts the codes on the way into the MFMA (gemm_tile.hip F8,
@@ -182,14 +188,14 @@ class CausalLM:
                  dec_weights: Optional[str] = None, prefill_weights: Optional[str] = None):
         """``init``: "random" (seeded per tensor name) or "empty" (uninitialised storage, for
         models about to be filled by models/checkpoint.load_checkpoint).  ``dec_weights``: this
-        model's DEC_WEIGHTS ("bf16" | "fp8"; None = the class constant); ``prefill_weights``: its
+        model's DEC_WEIGHTS ("bf16" | "fp8" | "mxfp4"; None = the class constant); ``prefill_weights``: its
         PREFILL_WEIGHTS ("bf16" | "fp8", fp8 only on top of fp8 decode weights)."""
         if init not in ("random", "empty"):
             raise ValueError(f"init must be 'random' or 'empty', not {init!r}")
         if dec_weights is not None:
             self.DEC_WEIGHTS = dec_weights
-        if self.DEC_WEIGHTS not in ("bf16", "fp8"):
-            raise ValueError(f"decode weights must be 'bf16' or 'fp8', not {self.DEC_WEIGHTS!r}")
+        if self.DEC_WEIGHTS not in ("bf16", "fp8", "mxfp4"):
+            raise ValueError(f"decode weights must be 'bf16', 'fp8' or 'mxfp4', not {self.DEC_WEIGHTS!r}")
         if prefill_weights is not None:
             self.PREFILL_WEIGHTS = prefill_weights
         if self.PREFILL_WEIGHTS not in ("bf16", "fp8"):
@@ -977,8 +983,8 @@ class CausalLM:
         def most(N: int, K: int) -> int:
             s = split if split else max(ops.skinny_auto_splits(m, N, K) for m in (1, 33, 64))
             for r in (r for r in ops.dec_row_classes() if dec_copies and r <= dec_rows):
-                for enc in ((False, True) if f8 else (False,)):  # the fp8 encoding may pick another split
-                    cfg = ops.dec_config(N, K, 0, rows=r, f8=enc)
+                for enc in (({}, self._enc_kw()) if f8 else ({},)):  # the fp8 / mxfp4 encoding may pick another split
+                    cfg = ops.dec_config(N, K, 0, rows=r, **enc)
                     s = max(s, cfg[0] if cfg else 1)
             return s
 
@@ -1131,7 +1137,7 @@ class CausalLM:
     @staticmethod
     def _dec(x: torch.Tensor, wd: torch.Tensor, wq: Optional[torch.Tensor], wqs: Optional[torch.Tensor], epi: int,
              rows: int, rownorm: Optional[tuple] = None, **kw) -> int:
-        """ops.dec_gemm over the fp8 encoding (``wq``, ``wqs``) of a weight where one exists and
+        """ops.dec_gemm over the fp8 or mxfp4 encoding (``wq``, ``wqs``) of a weight where one exists and
         gemm_decode.hip has an fp8 form for the shape at ``rows`` rows with this deferred norm (the
         wide form of the row-complete o projection's sums reads bf16), else over the bf16 copy
         ``wd`` - the same values either way, so the choice is one of speed only.  ``wd`` None: the
@@ -1139,7 +1145,8 @@ class CausalLM:
         one without raises in ops.dec_gemm)."""
         if wq is not None and (wd is None or not (rownorm is not None and rownorm[0].shape[1] > 16)):
             N, K = ops.skinny_wdims(wq)
-            if wd is None or ops.dec_config(N, K, epi, rows=rows, f8=True) is not None:
+            enc = dict(f4=True) if ops.is_mxfp4(wq) else dict(f8=True)  # the codes say which encoding they are
+            if wd is None or ops.dec_config(N, K, epi, rows=rows, **enc) is not None:
                 return ops.dec_gemm(x, wq, epi, rows, rownorm=rownorm, wscale=wqs, **kw)
         return ops.dec_gemm(x, wd, epi, rows, rownorm=rownorm, **kw)
 
@@ -1152,12 +1159,17 @@ class CausalLM:
         return enc
 
     def decode_encodings(self) -> dict:
-        """Which encoding each decode projection streams from ("fp8" | "bf16" per key of wqkv, wo,
-        w13, w2, head) where the decode GEMM has both; layer 0 speaks for all."""
+        """Which encoding each decode projection streams from ("fp8" | "mxfp4" | "bf16" per key of
+        wqkv, wo, w13, w2, head) where the decode GEMM has both; layer 0 speaks for all."""
         L = self.layers[0] if self.layers else {}
-        enc = {k: "fp8" if k + "_q" in L else "bf16" for k in PROJ if k in L}
-        enc["head"] = "fp8" if self.lm_head_q is not None else "bf16"
+        name = lambda wq: "bf16" if wq is None else "mxfp4" if ops.is_mxfp4(wq) else "fp8"  # noqa: E731
+        enc = {k: name(L.get(k + "_q")) for k in PROJ if k in L}
+        enc["head"] = name(self.lm_head_q)
         return enc
+
+    def _enc_kw(self) -> dict:
+        """dec_config's keyword for this model's quantised decode encoding."""
+        return dict(f4=True) if self.DEC_WEIGHTS == "mxfp4" else dict(f8=True)
 
     def _want_dec(self) -> set:
         """Which projections gemm_decode.hip gets in its fragment-packed form (``DECODE_GEMM`` =
@@ -1267,7 +1279,7 @@ class CausalLM:
         # what is derived from the copied weights is stale now: under PACKED the layers' derived keys
         # ARE the weights and only a tied head keeps a separate packed copy (of the embedding)
         # (an fp8-decoding model requantises: its bf16 weights become the new dequantised values)
-        if self.DEC_WEIGHTS == "fp8":
+        if self.DEC_WEIGHTS in ("fp8", "mxfp4"):
             self._f8_defer = False  # the weights are real now, whatever the model was built with
             self._init_skinny()
         elif self._packed and self.lm_head_d is not None and self.lm_head_d is not self.lm_head:
@@ -1290,6 +1302,9 @@ class CausalLM:
         hold exactly what the fp8 kernel computes with; a tied embedding table with them), and its
         codes and scales kept as ``*_q`` / ``*_qs`` in the packed copy's row order - layer by
         layer, so peak memory stays the model plus one layer.  MoE expert stacks stay bf16.
+        ``DEC_WEIGHTS`` = "mxfp4": the same with ops.quantize_mxfp4 (one scale per row and block of
+        32 along K, so the [8 gate | 8 up] row interleave carries codes and block scales along
+        unchanged), the packed codes and block scales (ops.pack_skinny_f4) under the same two keys.
 
         ``PREFILL_WEIGHTS`` = "fp8" on top: each ONE_LAYOUT layer then releases the packed bf16
         tensor of every projection ``_f8_only_ok`` accepts - the codes become ``L[key]`` itself
@@ -1299,10 +1314,11 @@ class CausalLM:
         if self.layers:
             self._remat(self.layers[0], self._layout)  # layer 0's shapes decide below
         parts, one = self._want_dec(), self._one_layout_wanted()
-        f8 = self.DEC_WEIGHTS == "fp8" and not self._f8_defer
+        f8 = self.DEC_WEIGHTS in ("fp8", "mxfp4") and not self._f8_defer
+        f4 = f8 and self.DEC_WEIGHTS == "mxfp4"
         if f8 and self.cfg.is_moe:
-            log.info("%s: decode_weights=fp8 leaves the MoE expert stacks on bf16 (grouped launches have no fp8 form)",
-                     self.cfg.name)
+            log.info("%s: decode_weights=%s leaves the MoE expert stacks on bf16 (grouped launches have no such form)",
+                     self.cfg.name, self.DEC_WEIGHTS)
         f8_only = f8 and self.PREFILL_WEIGHTS == "fp8"
         why = None  # why nothing can be fp8-only, if so
         if f8_only and (self.cfg.is_moe or self.tp != 1 or not one):
@@ -1335,7 +1351,12 @@ class CausalLM:
                         stayed[key] = r
         N, K = self.lm_head.shape
         if "head" in parts and N % 16 == 0 and K % 32 == 0 and ops.dec_available(N, K, 1):
-            if f8 and self._f8_shape_ok(N, K, 1):
+            if f4 and self._f8_shape_ok(N, K, 1):
+                q, qs = ops.quantize_mxfp4(self.lm_head)
+                self.lm_head.copy_(ops.dequantize_mxfp4(q, qs, self.dtype))  # tied: the embedding too
+                self.lm_head_q, self.lm_head_qs = ops.pack_skinny_f4(q, qs)
+                del q, qs
+            elif f8 and self._f8_shape_ok(N, K, 1):
                 q, self.lm_head_qs = ops.quantize_rows_fp8(self.lm_head)
                 self.lm_head.copy_(ops.dequantize_rows_fp8(q, self.lm_head_qs, self.dtype))  # tied: the embedding too
                 self.lm_head_q = ops.pack_skinny_f8(q)
@@ -1410,10 +1431,10 @@ class CausalLM:
                 del L[key + "_q"], L[key + "_qs"]
                 L[key + "_p"] = w if self.skinny_layout == "rowmajor" else ops.pack_skinny(w)
 
-    @staticmethod
-    def _f8_shape_ok(N: int, K: int, epi: int) -> bool:
-        """gemm_decode.hip has an fp8 form for the weight [N, K] in some row class."""
-        return any(ops.dec_config(N, K, epi, rows=r, f8=True) is not None for r in ops.dec_row_classes())
+    def _f8_shape_ok(self, N: int, K: int, epi: int) -> bool:
+        """gemm_decode.hip has a form over this model's quantised encoding (fp8 or mxfp4) for the
+        weight [N, K] in some row class."""
+        return any(ops.dec_config(N, K, epi, rows=r, **self._enc_kw()) is not None for r in ops.dec_row_classes())
 
     def _quantize_fp8(self, L: dict, key: str) -> None:
         """The fp8 encoding of the dense projection ``L[key]`` (resident row-major, INTERLEAVED or
@@ -1424,6 +1445,18 @@ class CausalLM:
         w = L[key]
         N, K = w.shape
         if not self._f8_shape_ok(N, K, 2 if key == "w13" else 0):
+            return
+        if self.DEC_WEIGHTS == "mxfp4":
+            # block scales run along K, so the row order is free: quantise the canonical rows,
+            # permute codes and scales together into the packed copy's row order
+            q, s = ops.quantize_mxfp4(to_canonical(w, key, self._layout))
+            w.copy_(to_resident(ops.dequantize_mxfp4(q, s, self.dtype), key, self._layout))
+            p = L.get(key + "_p")
+            if p is not None and p is not w:
+                L[key + "_p"] = ops.pack_skinny(w)
+            if key == "w13":
+                q, s = ops.interleave_gate_up8(q), ops.interleave_gate_up8(s)
+            L[key + "_q"], L[key + "_qs"] = ops.pack_skinny_f4(q, s)
             return
         q, s = ops.quantize_rows_fp8(to_canonical(w, key, self._layout))
         w.copy_(to_resident(ops.dequantize_rows_fp8(q, s, self.dtype), key, self._layout))

@@ -57,9 +57,11 @@ class LLMConfig:
     dtype: str = "bf16"
     seed: int = 0
     use_graphs: bool = True
-    # "bf16" | "fp8": the encoding the decode GEMMs stream the dense projections and the LM head
+    # "bf16" | "fp8" | "mxfp4": the encoding the decode GEMMs stream the dense projections and the LM head
     # from (fp8: e4m3 codes per weight row with a power-of-two scale, kept beside the bf16 weights -
-    # resident weights grow by half, prefill still reads bf16; docs/engine.md)
+    # resident weights grow by half, prefill still reads bf16; mxfp4: e2m1 codes with one e8m0
+    # scale per 32 elements along K, a quarter of the bf16 bytes beside the bf16 weights, less
+    # accurate than fp8; docs/engine.md)
     decode_weights: str = "bf16"
     # "bf16" | "fp8" (with decode_weights: fp8 only): prefill reads the fp8 codes too and the bf16
     # copy of every dense projection / head that decode never needs is released (dense, TP = 1)

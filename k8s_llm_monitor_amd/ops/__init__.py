@@ -116,14 +116,19 @@ def dec_row_classes() -> tuple:
 
 
 def dec_form_ok(epi: int, cfg: tuple, rows: int, grouped: bool = False, wide_norm: bool = False,
-                f8: bool = False) -> bool:
+                f8: bool = False, f4: bool = False, K: int = 0) -> bool:
     """Whether gemm_decode.hip has an instantiation for ``cfg = (splits, ntw, waves, depth)`` at
     ``rows`` rows: a DEC_FORMS row with that many m-tiles; ``grouped`` launches and the
     ``wide_norm`` form (which the row must have) stop at DEC_NARROW_MAX_M rows.  ``f8``: over fp8
-    weights - a row listed in DEC_F8_FORMS, dense launches with the narrow deferred norm only."""
-    if (grouped or wide_norm) and (f8 or rows > DEC_NARROW_MAX_M):
+    weights - a row listed in DEC_F8_FORMS, dense launches with the narrow deferred norm only.
+    ``f4``: over mxfp4 weights - a row listed in DEC_F4_FORMS, the same limits; with ``K`` given,
+    every split-K slice must also hold whole 256-deep A chunks (so whole 128-deep code groups)."""
+    if (grouped or wide_norm) and (f8 or f4 or rows > DEC_NARROW_MAX_M):
         return False
-    forms = [DEC_FORMS[i] for i in DEC_F8_FORMS] if f8 else DEC_FORMS
+    if f4:
+        if dec_f4_depth(epi, cfg) == 0 or (K and (K % cfg[0] or (K // cfg[0]) % 256)):
+            return False
+    forms = [DEC_FORMS[i] for i in DEC_F8_FORMS] if f8 else [DEC_FORMS[i] for i, _ in DEC_F4_FORMS] if f4 else DEC_FORMS
     return any(f[:4] == (epi,) + tuple(cfg[1:]) and rows <= 16 * f[4] and (f[5] or not wide_norm) for f in forms)
 
 
@@ -221,6 +226,104 @@ def is_fp8(w: Optional[torch.Tensor]) -> bool:
     return w is not None and w.dtype == torch.float8_e4m3fn
 
 
+# ---------------------------------------------------------------- MXFP4 decode weights
+# The OCP microscaling format: e2m1 elements (sign in bit 3, grid {0, 0.5, 1, 1.5, 2, 3, 4, 6}), one
+# e8m0 power-of-two scale 2^(b - 127) per block of 32 along K, 4.25 bits per weight.  As with e4m3
+# every dequantised value code * 2^e is a bf16 value, so the bf16 tensors of an mxfp4-decoding
+# model hold exactly what the mxfp4 kernel computes with.
+
+# the DEC_FORMS rows that gemm_decode.hip also instantiates over mxfp4 weights, as (index, F4 ring
+# depth in k-steps at <= 16 rows - 8 above, and where it does not divide the K slice): kDecF4Forms
+# in csrc/gemm_dec_forms.h, reported by native().gemm_dec_f4_forms()
+DEC_F4_FORMS: tuple = ((0, 16), (1, 16), (4, 16), (7, 8), (9, 16))
+# test / tool override: the F4 ring depth of every mxfp4 launch (0 = the launcher's choice)
+DEC_F4_DEPTH_FORCE = 0
+MXFP4_MAX = 6.0  # largest e2m1 magnitude
+MXFP4_BLOCK = 32  # elements along K that share a scale
+MXFP4_EXP_MAX = 60  # |e| <= 60: 2^e and every code * 2^e stay normal bf16 / fp32 numbers
+_MXFP4_CHUNK = 1 << 25  # elements quantised / dequantised at a time
+_E2M1_GRID = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+
+
+def dec_f4_depth(epi: int, cfg: tuple) -> int:
+    """The one-m-tile F4 ring depth (k-steps) of the DEC_F4_FORMS row of
+    ``cfg = (splits, ntw, waves, depth)``, 0 where the form has no mxfp4 instantiation."""
+    for i, d4 in DEC_F4_FORMS:
+        if DEC_FORMS[i][:4] == (epi,) + tuple(cfg[1:]):
+            return d4
+    return 0
+
+
+def quantize_mxfp4(w: torch.Tensor) -> tuple:
+    """Row-major weight [N, K] -> (codes [N, K/2] uint8, scales [N, K/32] uint8).  Per (row, block of
+    32 along K) the scale 2^e with e = ceil(log2(amax / 6)) clamped to +-60 (0 for a block of zeros),
+    stored as the e8m0 byte e + 127; element = w / 2^e rounded to the nearest e2m1 value, ties to
+    the even mantissa, sign in bit 3 (-0 stays -0).  |w / 2^e| <= 6, so nothing clips.  Element 2i
+    sits in the low nibble of byte i."""
+    N, K = w.shape
+    if K % MXFP4_BLOCK:
+        raise ValueError(f"quantize_mxfp4: [{N}, {K}] needs K % 32 == 0")
+    rows = max(1, _MXFP4_CHUNK // K)
+    if N > rows:  # an LM head: row chunks keep the fp32 / index temporaries small
+        parts = [quantize_mxfp4(w[i:i + rows]) for i in range(0, N, rows)]
+        return torch.cat([c for c, _ in parts]), torch.cat([s for _, s in parts])
+    wf = w.float().reshape(N, K // MXFP4_BLOCK, MXFP4_BLOCK)
+    # amax = m 2^x, m in [0.5, 1): amax <= 6 * 2^e = 0.75 * 2^(e + 3) first holds at e = x - 3 for
+    # m <= 0.75 and at x - 2 above (exact: no division); frexp(0) = (0, 0) gives the clamp's -3 -> 0
+    m, x = torch.frexp(wf.abs().amax(dim=-1))
+    e = torch.where(m > 0.75, x - 2, x - 3)
+    e = torch.where(m == 0, torch.zeros_like(e), e).clamp(-MXFP4_EXP_MAX, MXFP4_EXP_MAX).to(torch.int32)
+    scale = ((e + 127) << 23).view(torch.float32)  # 2^e exactly
+    a = (wf / scale[..., None]).abs().clamp(max=MXFP4_MAX)  # a power-of-two division: exact
+    # the grid's step is 0.5 below 2, 1 below 4, 2 above; torch.round takes ties to the even
+    # multiple of the step, which is the even mantissa
+    q = torch.where(a < 2, torch.round(a * 2) / 2, torch.where(a < 4, torch.round(a), torch.round(a / 2) * 2))
+    lut = torch.tensor([0, 1, 2, 3, 4, 0, 5, 0, 6, 0, 0, 0, 7], dtype=torch.uint8, device=w.device)  # 2 value -> code
+    c = lut[(q * 2).long()] | (torch.signbit(wf).to(torch.uint8) << 3)
+    c = c.reshape(N, K // 2, 2)
+    return c[..., 0] | (c[..., 1] << 4), (e + 127).to(torch.uint8)
+
+
+def dequantize_mxfp4(codes: torch.Tensor, scales: torch.Tensor, dtype=torch.bfloat16) -> torch.Tensor:
+    """(codes [N, K/2], scales [N, K/32]) -> [N, K]: code * 2^(scale - 127), exact in bf16 (an e2m1
+    value has 2 significant bits)."""
+    N, K = codes.shape[0], codes.shape[1] * 2
+    rows = max(1, _MXFP4_CHUNK // K)
+    if N > rows:
+        return torch.cat([dequantize_mxfp4(codes[i:i + rows], scales[i:i + rows], dtype) for i in range(0, N, rows)])
+    c = torch.stack((codes & 15, codes >> 4), dim=-1).reshape(N, K).long()
+    grid = torch.tensor(_E2M1_GRID + tuple(-v for v in _E2M1_GRID), dtype=torch.float32, device=codes.device)
+    scale = (scales.to(torch.int32) << 23).view(torch.float32)
+    return (grid[c].reshape(N, K // MXFP4_BLOCK, MXFP4_BLOCK) * scale[..., None]).reshape(N, K).to(dtype)
+
+
+def pack_skinny_f4(codes: torch.Tensor, scales: torch.Tensor) -> tuple:
+    """quantize_mxfp4's (codes [N, K/2], scales [N, K/32]) -> the layout gemm_dec's mxfp4 form
+    streams: codes [N/16, K/128, 64, 16] bytes - block (n-tile j, k-step quad g) holds, for lane
+    l = 16 q + r, four dwords, dword s the 8 codes W[16 j + r, 128 g + 32 s + 8 q : +8] (k-step
+    4g + s, pack_skinny's fragment order): 1 KiB contiguous per block, four k-steps - and scales
+    [N/16, K/128, 16, 4] bytes, dword (j, g, r) the e8m0 bytes of row 16 j + r for k-steps
+    4g .. 4g + 3, the first in the low byte."""
+    N, K = codes.shape[0], codes.shape[1] * 2
+    if N % 16 or K % 128 or scales.shape != (N, K // MXFP4_BLOCK):
+        raise ValueError(f"pack_skinny_f4: [{N}, {K}] needs N % 16 == 0, K % 128 == 0 and scales [N, K/32]")
+    b = codes.contiguous().reshape(N // 16, 16, K // 128, 4, 4, 4).permute(0, 2, 4, 1, 3, 5)
+    sp = scales.contiguous().reshape(N // 16, 16, K // 128, 4).permute(0, 2, 1, 3)
+    return b.reshape(N // 16, K // 128, 64, 16).contiguous(), sp.contiguous()
+
+
+def unpack_skinny_f4(cp: torch.Tensor, sp: torch.Tensor) -> tuple:
+    nt, kg = cp.shape[0], cp.shape[1]
+    b = cp.contiguous().reshape(nt, kg, 4, 16, 4, 4).permute(0, 3, 1, 4, 2, 5)
+    s = sp.contiguous().reshape(nt, kg, 16, 4).permute(0, 2, 1, 3)
+    return b.reshape(nt * 16, kg * 64).contiguous(), s.reshape(nt * 16, kg * 4).contiguous()
+
+
+def is_mxfp4(w: Optional[torch.Tensor]) -> bool:
+    """A weight in pack_skinny_f4's code layout (the only 4-d uint8 weight there is)."""
+    return w is not None and w.dtype == torch.uint8 and w.dim() == 4
+
+
 def pack_skinny(w: torch.Tensor) -> torch.Tensor:
     """Row-major weight [N, K] -> the fragment-packed [N/16, K/32, 64, 8] layout of gemm_skinny:
     block (n-tile j, k-step s) holds, for lane l = 16 q + r, elements W[16 j + r, 32 s + 8 q : +8]
@@ -298,15 +401,17 @@ def skinny_nslabs(K: int, S: int, rm: bool = False) -> int:
 def skinny_wdims(wp: torch.Tensor) -> tuple:
     """(N, K) of a skinny-GEMM weight: fragment-packed [N/16, K/32, 64, 8] or row-major [N, K]
     (the single resident copy, read by gemm_skinny_rm_kernel), or the fp8 decode encoding
-    [N/16, K/64, 64, 16] (pack_skinny_f8)."""
+    [N/16, K/64, 64, 16] (pack_skinny_f8), or the mxfp4 one [N/16, K/128, 64, 16] (pack_skinny_f4)."""
     if wp.dim() == 4:
-        return wp.shape[0] * 16, wp.shape[1] * (64 if is_fp8(wp) else 32)
+        return wp.shape[0] * 16, wp.shape[1] * (128 if is_mxfp4(wp) else 64 if is_fp8(wp) else 32)
     return wp.shape[0], wp.shape[1]
 
 
 def _cpu_w(wp: torch.Tensor, wscale: Optional[torch.Tensor] = None) -> torch.Tensor:
     if is_fp8(wp):  # the dequantised values, exactly the bf16 encoding's
         return unpack_skinny_f8(wp).float() * wscale.float()[:, None]
+    if is_mxfp4(wp):
+        return dequantize_mxfp4(*unpack_skinny_f4(wp, wscale), dtype=torch.float32)
     return (unpack_skinny(wp) if wp.dim() == 4 else wp).float()
 
 
@@ -525,8 +630,13 @@ DEC_TABLE_M128: dict = {
 # bf16 pick was the fastest in every row class, 1.13-2.05x over bf16 (profiles/r08/README.md).
 DEC_TABLE_F8: dict = {}
 
+# mxfp4 weights: the same, for the shapes that measure better on another pick of DEC_F4_FORMS or
+# (None) on the bf16 copy.
+DEC_TABLE_F4: dict = {}
 
-def dec_config(N: int, K: int, epi: int, experts: int = 1, rows: int = 0, f8: bool = False) -> Optional[tuple]:
+
+def dec_config(N: int, K: int, epi: int, experts: int = 1, rows: int = 0, f8: bool = False,
+               f4: bool = False) -> Optional[tuple]:
     """Launch configuration of gemm_dec for a weight [N, K]: (splits, ntw, waves, depth) or None
     when no configuration tiles the shape (the caller keeps gemm_skinny).  The candidates are the
     DEC_FORMS rows of the epilogue that serve ``rows``, in list order (the first of two equal
@@ -539,17 +649,25 @@ def dec_config(N: int, K: int, epi: int, experts: int = 1, rows: int = 0, f8: bo
     DEC_MAX_M): the pick among the forms instantiated with 5..8 m-tiles; ``rows`` <= 64 (or not
     given) never changes the answer.  ``f8``: the configuration over the fp8 encoding of the
     weight (dense launches, K a multiple of 64) - the same tables and candidates restricted to
-    DEC_F8_FORMS, DEC_TABLE_F8 first; None where the shape decodes from bf16."""
+    DEC_F8_FORMS, DEC_TABLE_F8 first; None where the shape decodes from bf16.  ``f4``: the same over
+    the mxfp4 encoding (K a multiple of 128, DEC_F4_FORMS, DEC_TABLE_F4; every K slice whole
+    256-deep A chunks)."""
     wide = rows > DEC_NARROW_MAX_M
     if wide and (experts != 1 or rows > DEC_MAX_M):
         return None
     if f8 and (experts != 1 or K % 64):
         return None
-    compiled = [DEC_FORMS[i] for i in DEC_F8_FORMS] if f8 else DEC_FORMS
+    if f4 and (f8 or experts != 1 or K % 128):
+        return None
+    compiled = ([DEC_FORMS[i] for i in DEC_F8_FORMS] if f8 else
+                [DEC_FORMS[i] for i, _ in DEC_F4_FORMS] if f4 else DEC_FORMS)
     if f8 and (N, K, epi, 128 if wide else 64) in DEC_TABLE_F8:
         return DEC_TABLE_F8[(N, K, epi, 128 if wide else 64)]
+    if f4 and (N, K, epi, 128 if wide else 64) in DEC_TABLE_F4:
+        return DEC_TABLE_F4[(N, K, epi, 128 if wide else 64)]
     hit = (DEC_TABLE_M128 if wide else DEC_TABLE).get((N, K, epi)) if experts == 1 else None
-    if hit is not None and (not f8 or dec_form_ok(epi, hit, rows, f8=True)):
+    if hit is not None and (not f8 or dec_form_ok(epi, hit, rows, f8=True)) and (
+            not f4 or dec_form_ok(epi, hit, rows, f4=True, K=K)):
         return hit
     ntiles, ksteps = N // 16, K // 32
     forms = [f[1:4] for f in compiled
@@ -559,7 +677,7 @@ def dec_config(N: int, K: int, epi: int, experts: int = 1, rows: int = 0, f8: bo
     for s, ntw, w, d in cands:
         if experts > 1 and s > 1:  # grouped: the per-expert slabs are the split (workspace E x M x N)
             continue
-        it = max(d, 8)
+        it = 8 if f4 else max(d, 8)  # mxfp4: the launcher fits the ring depth to the slice
         if (epi == 0 and ntiles % (ntw * w)) or K % s or (ksteps // s) % it or ksteps % s:
             continue
         wgs = -(-ntiles // (ntw * w)) * s * experts
@@ -588,17 +706,21 @@ def dec_gemm(a: torch.Tensor, wp: torch.Tensor, epi: int, rows: int, workspace: 
     the 5..8 m-tile instantiations).  ``wp`` may be the fp8 encoding (pack_skinny_f8 codes) with
     ``wscale`` its per-row scales in packed row order: the same launch over half the weight
     bytes, bit-identical to the bf16 launch of the same configuration over the dequantised
-    weights; a form without an fp8 instantiation raises.  CPU: the fp32 reference with the same
+    weights; a form without an fp8 instantiation raises.  Or the mxfp4 encoding (pack_skinny_f4's
+    codes, ``wscale`` its packed block scales), under the same contract.
+    CPU: the fp32 reference with the same
     split-K slicing (over the dequantised values)."""
     N, K = skinny_wdims(wp)
     M = rows
-    f8 = is_fp8(wp)
+    f8, f4 = is_fp8(wp), is_mxfp4(wp)
     if f8 and (wscale is None or wscale.numel() != N):
         raise ValueError(f"gemm_dec: an fp8 weight needs its [{N}] scale vector")
+    if f4 and (wscale is None or wscale.dtype != torch.uint8 or tuple(wscale.shape) != (N // 16, K // 128, 16, 4)):
+        raise ValueError(f"gemm_dec: an mxfp4 weight needs its packed block scales [{N // 16}, {K // 128}, 16, 4] uint8")
     if M > DEC_MAX_M:
         raise ValueError(f"gemm_dec: at most {DEC_MAX_M} rows, got {M}")
     if cfg is None:
-        cfg = dec_config(N, K, epi, rows=M, f8=f8)
+        cfg = dec_config(N, K, epi, rows=M, f8=f8, f4=f4)
     if cfg is None:
         raise ValueError(f"gemm_dec: no configuration for N={N} K={K} epi={epi} rows={M}")
     S, ntw, waves, depth = cfg
@@ -626,10 +748,13 @@ def dec_gemm(a: torch.Tensor, wp: torch.Tensor, epi: int, rows: int, workspace: 
     rn = (None, 0.0) if rownorm is None else (rownorm[0], float(rownorm[1]))
     # more than 16 partial sums per row: gemm_dec_rc's per-16-column sums, the wide-norm form
     wn = rownorm is not None and rownorm[0].shape[1] > 16
-    if not dec_form_ok(epi, cfg, M, wide_norm=wn, f8=f8):
+    if not dec_form_ok(epi, cfg, M, wide_norm=wn, f8=f8, f4=f4, K=K):
         raise RuntimeError(f"gemm_dec: form (epi, ntw, waves, depth) = {(epi,) + tuple(cfg[1:])} not compiled for "
-                           f"{M} rows" + (" with the wide deferred norm" if wn else "") + (" over fp8 weights" if f8 else ""))
-    if f8:
+                           f"{M} rows" + (" with the wide deferred norm" if wn else "") +
+                           (" over fp8 weights" if f8 else f" over mxfp4 weights in {S} K slices" if f4 else ""))
+    if f4:
+        r = native().gemm_dec_f4(a, wp, wscale, workspace, out, S, epi, ntw, waves, depth, M, *rn, DEC_F4_DEPTH_FORCE)
+    elif f8:
         r = native().gemm_dec_f8(a, wp, wscale, workspace, out, S, epi, ntw, waves, depth, M, *rn)
     else:
         r = native().gemm_dec(a, wp, workspace, out, S, epi, ntw, waves, depth, M, *rn)
@@ -647,6 +772,8 @@ def dec_gemm_grouped(a: torch.Tensor, wp: torch.Tensor, epi: int, rows: int, wor
     epi 2: ``out`` [E, ceil(M/16), F/32, 64, 8] packed SwiGLU; epi 0: fp32 slabs [E * S, M, N] in
     ``workspace`` scaled by ``row_w`` [M, E] (routing weights, 0 where a row skipped the expert),
     returns E * S - the residual-add kernel's slab sum is the expert combine."""
+    if wp.dtype == torch.uint8:
+        raise ValueError("gemm_dec_grouped: grouped launches have no mxfp4 form (expert stacks stay bf16)")
     E = wp.shape[0]
     N, K = wp.shape[1] * 16, wp.shape[2] * 32
     M = rows

@@ -65,6 +65,10 @@ int k8sllm_gemm_dec_f8(const void* A, const void* Wq, const float* wscale, float
                        int N, int K, int splits, int epi, int ntw, int waves, int depth, const float* rn_ss, int rn_nc,
                        int rn_d, float rn_eps, hipStream_t s);
 int k8sllm_gemm_dec_f8_forms(int* out, int cap);
+int k8sllm_gemm_dec_f4(const void* A, const void* Wq, const void* wscale, float* partial, void* Y, long ldy, int M,
+                       int N, int K, int splits, int epi, int ntw, int waves, int depth, int f4_depth,
+                       const float* rn_ss, int rn_nc, int rn_d, float rn_eps, hipStream_t s);
+int k8sllm_gemm_dec_f4_forms(int* out, int cap);
 int k8sllm_gemm_dec_rc(const void* A, const void* Wp, void* resid, const void* nw, void* xw, float* ss, int M, int N,
                        int K, hipStream_t s);
 int k8sllm_add_norm_partial(void* out, long out_stride, void* residual, const float* partial, int S, int M,
@@ -750,6 +754,67 @@ std::vector<int64_t> gemm_dec_f8_forms() {
   return std::vector<int64_t>(v.begin(), v.end());
 }
 
+// gemm_dec over MXFP4 weights: wq e2m1 codes fragment-packed [N/16, K/128, 64, 16] bytes and wscale
+// the e8m0 block scales [N/16, K/128, 16, 4] bytes (ops.pack_skinny_f4; for epi 2 over the
+// [8 gate | 8 up] row order).  Everything else as gemm_dec; only the forms of kDecF4Forms, the
+// narrow deferred norm.  f4_depth: the F4 ring depth (8 / 16 k-steps), 0 = the launcher's choice.
+int64_t gemm_dec_f4(torch::Tensor a, torch::Tensor wq, torch::Tensor wscale, c10::optional<torch::Tensor> partial,
+                    c10::optional<torch::Tensor> y, int64_t splits, int64_t epi, int64_t ntw, int64_t waves,
+                    int64_t depth, int64_t rows, c10::optional<torch::Tensor> rn_ss, double rn_eps,
+                    int64_t f4_depth) {
+  dev_bf16(a, "a");
+  TORCH_CHECK(wq.is_cuda() && wq.scalar_type() == torch::kUInt8 && wq.dim() == 4 && wq.is_contiguous() &&
+                  wq.size(2) == 64 && wq.size(3) == 16,
+              "gemm_dec_f4: wq must be uint8, fragment-packed [N/16, K/128, 64, 16]");
+  const int N = (int)wq.size(0) * 16, K = (int)wq.size(1) * 128, M = (int)rows;
+  TORCH_CHECK(wscale.is_cuda() && wscale.scalar_type() == torch::kUInt8 && wscale.is_contiguous() &&
+                  wscale.dim() == 4 && wscale.size(0) == wq.size(0) && wscale.size(1) == wq.size(1) &&
+                  wscale.size(2) == 16 && wscale.size(3) == 4,
+              "gemm_dec_f4: wscale must be uint8 [N/16, K/128, 16, 4]");
+  TORCH_CHECK(a.dim() == 4 && a.is_contiguous() && a.size(1) * 32 == K && a.size(2) == 64 && a.size(3) == 8,
+              "gemm_dec_f4: a must be fragment-packed [ceil(M/16), K/32, 64, 8]");
+  TORCH_CHECK(M > 0 && M <= k8sllm::kDecMaxM && (M + 15) / 16 <= a.size(0), "gemm_dec_f4: 1..", k8sllm::kDecMaxM,
+              " rows within the packed a");
+  float* pp = nullptr;
+  void* yp = nullptr;
+  long ldy = 0;
+  if (epi == 0) {
+    pp = slab_buffer(partial, splits * M * N, "gemm_dec_f4");
+  } else {
+    TORCH_CHECK(splits == 1, "gemm_dec_f4: bf16 / SwiGLU epilogues need splits == 1");
+    if (epi == 2) {
+      yp = swiglu_packed_out(y, 0, M, N, "gemm_dec_f4");
+    } else {
+      TORCH_CHECK(y.has_value(), "gemm_dec_f4: output tensor required");
+      dev_bf16(*y, "y");
+      TORCH_CHECK(y->dim() == 2 && y->size(0) >= M && y->size(1) == N && y->stride(1) == 1, "gemm_dec_f4: y [M, N]");
+      ldy = y->stride(0);
+      yp = y->data_ptr();
+    }
+  }
+  const float* rp = nullptr;
+  int rn_nc = 0;
+  rownorm_args(rn_ss, M, K, rp, rn_nc);
+  const int rc = k8sllm_gemm_dec_f4(a.data_ptr(), wq.data_ptr(), wscale.data_ptr(), pp, yp, ldy, M, N, K,
+                                    (int)splits, (int)epi, (int)ntw, (int)waves, (int)depth, (int)f4_depth, rp,
+                                    rn_nc, K, (float)rn_eps, cur());
+  if (rc < 0) return -1;
+  check(rc, "gemm_dec_f4");
+  return epi == 0 ? splits : 1;
+}
+
+// The rows of kDecForms with mxfp4-weight instantiations (kDecF4Forms): (index into
+// gemm_dec_forms(), F4 ring depth at one m-tile) each.
+std::vector<std::vector<int64_t>> gemm_dec_f4_forms() {
+  std::vector<int> v(2 * k8sllm::kDecNF4Forms);
+  const int n = k8sllm_gemm_dec_f4_forms(v.data(), k8sllm::kDecNF4Forms);
+  TORCH_CHECK(n == k8sllm::kDecNF4Forms, "gemm_dec_f4_forms: ", n, " rows compiled, ", k8sllm::kDecNF4Forms,
+              " in the header");
+  std::vector<std::vector<int64_t>> out;
+  for (int i = 0; i < n; ++i) out.push_back({v[2 * i], v[2 * i + 1]});
+  return out;
+}
+
 // Grouped decode GEMM over the local experts of a MoE layer (grid.z = expert): wp [E, N/16, K/32,
 // 64, 8]; a packed [ceil(M/16), K/32, 64, 8] shared by every expert (gate_up) or [E, ceil(M/16),
 // K/32, 64, 8] per expert (down).  epi 2: y [E, ceil(M/16), N/64, 64, 8] packed SwiGLU per expert;
@@ -1113,6 +1178,8 @@ PYBIND11_MODULE(_k8sllm_ops, m) {
   m.def("gemm_dec_forms", &gemm_dec_forms);
   m.def("gemm_dec_f8", &gemm_dec_f8);
   m.def("gemm_dec_f8_forms", &gemm_dec_f8_forms);
+  m.def("gemm_dec_f4", &gemm_dec_f4);
+  m.def("gemm_dec_f4_forms", &gemm_dec_f4_forms);
   m.def("gemm_dec_rc", &gemm_dec_rc);
   m.def("reduce_add_rms_norm", &reduce_add_rms_norm);
   m.def("reduce_slabs", &reduce_slabs);

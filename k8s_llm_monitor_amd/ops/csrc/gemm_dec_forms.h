@@ -9,6 +9,7 @@
 namespace k8sllm {
 
 enum { DEC_SLAB = 0, DEC_BF16 = 1, DEC_SWIGLU8 = 2 };
+enum { DEC_W_BF16 = 0, DEC_W_F8 = 1, DEC_W_F4 = 2 };  // the weight format of an instantiation
 
 // One row = the instantiations <1..max_mt m-tiles, ntw, waves, epi, depth> (16 rows per m-tile:
 // max_mt 4 serves <= 64 rows, 8 <= 128; above 4 the A chunks are max_mt * 8 KiB in the 2-slot LDS
@@ -49,6 +50,27 @@ constexpr bool dec_form_f8(int form) {
   for (int i : kDecF8Forms)
     if (i == form) return true;
   return false;
+}
+
+// The rows of kDecForms that also have the MXFP4-weight instantiations (k8sllm_gemm_dec_f4: e2m1
+// codes [N/16][K/128][64][16] plus the e8m0 block scales [N/16][K/128][16] dwords; dense launches,
+// narrow deferred norm, 1..max_mt m-tiles): every pick of ops.DEC_TABLE / DEC_TABLE_M128.  The F4
+// ring depth (k-steps in flight per n-tile, four per load) replaces the row's own: 8 at every row
+// count, and at one m-tile (<= 16 rows) the `depth` given here where it divides the K slice's
+// k-steps - 16 measured 1-4 % faster than 8 at 1 row and 3-10 % slower at 64 and 128; 32 gained
+// nothing and spills at 8 m-tiles (profiles/r13/README.md).  A slice need only hold whole 256-deep
+// A chunks.  Four n-tiles per wave stay at 8 (16 spills at 4 m-tiles and was not tried at one).
+// k8sllm_gemm_dec_f4_forms reports the list and ops.DEC_F4_FORMS mirrors it.
+struct DecF4Form {
+  int form, depth;
+};
+constexpr DecF4Form kDecF4Forms[] = {{0, 16}, {1, 16}, {4, 16}, {7, 8}, {9, 16}};
+constexpr int kDecNF4Forms = sizeof(kDecF4Forms) / sizeof(kDecF4Forms[0]);
+
+constexpr int dec_form_f4_depth(int form) {  // the row's F4 ring depth at one m-tile; 0: no mxfp4 instantiation
+  for (const DecF4Form& f : kDecF4Forms)
+    if (f.form == form) return f.depth;
+  return 0;
 }
 
 constexpr int dec_max_mt() {

@@ -71,6 +71,19 @@ __device__ __forceinline__ bf16x8 dec_f8x8(uint32_t lo, uint32_t hi) {
   return bf16x8{a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
 }
 
+// 8 e2m1 codes (one dword: element 2i in the low nibble of byte i) times the block scale (an fp32
+// power of two) -> the bf16x8 MFMA operand: four v_cvt_scalef32_pk_bf16_fp4, one per byte.  Exact:
+// code * 2^e is a bf16 value for |e| <= 60.
+__device__ __forceinline__ bf16x8 dec_f4x8(uint32_t q, float scale) {
+  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+  const bf16x2 a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q, scale, 0);
+  const bf16x2 b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q, scale, 1);
+  const bf16x2 c = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q, scale, 2);
+  const bf16x2 d = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q, scale, 3);
+  return bf16x8{a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
+}
+
+// WF, the weight format: DEC_W_BF16, DEC_W_F8 or DEC_W_F4.
 // F8: W holds e4m3 codes [N/16][K/64][64][16] (pack_skinny_f8: lane l's 16 bytes are its 8 codes of
 // k-step 2j, then its 8 of k-step 2j + 1, in the bf16 layout's fragment order), so one 1-KiB wave
 // load feeds two k-steps and the ring holds DEPTH / 2 loads per n-tile.  A fragment is converted
@@ -79,12 +92,23 @@ __device__ __forceinline__ bf16x8 dec_f8x8(uint32_t lo, uint32_t hi) {
 // epilogue (after the deferred-norm row scale, before any bf16 rounding), which commutes with
 // every rounding: bit-identical to the bf16 launch over the dequantised weights.  Dense launches
 // with the narrow deferred norm only.
-template <int MT, int NTW, int WAVES, int EPI, int DEPTH, bool RNW = false, bool F8 = false>
+// F4: W holds MXFP4 (e2m1) codes [N/16][K/128][64][16] (pack_skinny_f4: lane l's dword s is its 8
+// codes of k-step 4g + s, in the bf16 layout's fragment order), so one 1-KiB wave load feeds four
+// k-steps and the ring holds DEPTH / 4 loads per n-tile (DEPTH here is the F4 ring depth the
+// launcher chose - 8, or at one m-tile the F4 table's 16 - not the form's).  The block scales
+// ride beside them: wscale is [N/16][K/128][16] dwords, dword (tile, g, r) the four e8m0 bytes of
+// row r for k-steps 4g .. 4g + 3 (byte b is the fp32 b << 23); one 64-byte wave load per ring
+// slot, issued with the slot's code load.  A fragment is converted
+// once per (k-step, n-tile) WITH its block scale and runs the bf16 MFMA sequence in the bf16
+// order; the epilogue is the bf16 one.  Dense launches with the narrow deferred norm only.
+template <int MT, int NTW, int WAVES, int EPI, int DEPTH, bool RNW = false, int WF = DEC_W_BF16>
 __global__ __launch_bounds__(64 * WAVES, 1) void gemm_dec_kernel(
     const bf16_t* __restrict__ A, const bf16_t* __restrict__ W, float* __restrict__ partial,
     bf16_t* __restrict__ Y, long ldy, int M, int N, int K, int kchunk, const float* __restrict__ rn_ss, int rn_nc,
     float rn_inv_d, float rn_eps, DecGroup grp, const float* __restrict__ wscale) {
+  constexpr bool F8 = WF == DEC_W_F8, F4 = WF == DEC_W_F4;
   static_assert(!F8 || (!RNW && DEPTH % 2 == 0), "fp8 weights: narrow deferred norm, whole k-step pairs in the ring");
+  static_assert(!F4 || (!RNW && DEPTH % 4 == 0), "mxfp4 weights: narrow deferred norm, whole k-step quads in the ring");
   using G = DecGeom<MT, WAVES>;
   const int ex = blockIdx.z;  // expert of a grouped launch (0 otherwise)
   A += ex * grp.a_es;
@@ -103,8 +127,10 @@ __global__ __launch_bounds__(64 * WAVES, 1) void gemm_dec_kernel(
   // ---- weight stream: DEPTH k-steps x NTW fragments in flight per wave, filled after chunk 0's
   // staging loads (below)
   // (F8: one load = a pair of k-steps; kb and DEPTH are even, so pairs never straddle a slice)
-  constexpr int RING = F8 ? DEPTH / 2 : DEPTH;
-  const int wsteps = F8 ? ksteps >> 1 : ksteps, wkb = F8 ? kb >> 1 : kb;
+  // (F4: one load = four k-steps; kb and DEPTH are multiples of 4)
+  constexpr int WSH = F4 ? 2 : F8 ? 1 : 0;
+  constexpr int RING = DEPTH >> WSH;
+  const int wsteps = ksteps >> WSH, wkb = kb >> WSH;
   const u32x4* wp[NTW];
 #pragma unroll
   for (int t = 0; t < NTW; ++t)
@@ -116,12 +142,23 @@ __global__ __launch_bounds__(64 * WAVES, 1) void gemm_dec_kernel(
 #pragma unroll
     for (int t = 0; t < NTW; ++t) wsc[t] = wscale[min(tile0 + t, (N >> 4) - 1) * 16 + (lane & 15)];
   }
+  // F4: the block scales of the ring's slots, a dword (four k-steps of row lane & 15) per slot
+  const uint32_t* sp[F4 ? NTW : 1];
+  if constexpr (F4) {
+#pragma unroll
+    for (int t = 0; t < NTW; ++t)
+      sp[t] = reinterpret_cast<const uint32_t*>(wscale) + ((long)min(tile0 + t, (N >> 4) - 1) * wsteps + wkb) * 16 + (lane & 15);
+  }
   u32x4 wr[RING][NTW];
+  uint32_t wsr[F4 ? RING : 1][F4 ? NTW : 1];
   auto ring_fill = [&]() {
 #pragma unroll
     for (int d = 0; d < RING; ++d)
 #pragma unroll
-      for (int t = 0; t < NTW; ++t) wr[d][t] = __builtin_nontemporal_load(wp[t] + d * 64);
+      for (int t = 0; t < NTW; ++t) {
+        wr[d][t] = __builtin_nontemporal_load(wp[t] + d * 64);
+        if constexpr (F4) wsr[d][t] = __builtin_nontemporal_load(sp[t] + d * 16);
+      }
   };
 
   // ---- the A rows' partial sums of squares (deferred RMSNorm), 4 threads per row, loaded first so
@@ -298,6 +335,10 @@ __global__ __launch_bounds__(64 * WAVES, 1) void gemm_dec_kernel(
         if constexpr (F8) {
           const u32x4 q = wr[(j % DEPTH) >> 1][t];
           b = (j & 1) ? dec_f8x8(q[2], q[3]) : dec_f8x8(q[0], q[1]);
+        } else if constexpr (F4) {
+          // the slot's code load and scale load are consumed together: one counted wait per slot
+          const uint32_t e8 = (wsr[(j % DEPTH) >> 2][t] >> (8 * (j & 3))) & 0xffu;
+          b = dec_f4x8(wr[(j % DEPTH) >> 2][t][j & 3], __uint_as_float(e8 << 23));
         } else {
           b = __builtin_bit_cast(bf16x8, wr[j % DEPTH][t]);
         }
@@ -309,6 +350,14 @@ __global__ __launch_bounds__(64 * WAVES, 1) void gemm_dec_kernel(
 #pragma unroll
           for (int t = 0; t < NTW; ++t)
             wr[(j % DEPTH) >> 1][t] = __builtin_nontemporal_load(wp[t] + ((ks + DEPTH) >> 1) * 64);
+        }
+      } else if constexpr (F4) {
+        if ((j & 3) == 3 && (!LAST || j + DEPTH < ITER)) {  // the slot's four k-steps consumed: the quad DEPTH ahead
+#pragma unroll
+          for (int t = 0; t < NTW; ++t) {
+            wr[(j % DEPTH) >> 2][t] = __builtin_nontemporal_load(wp[t] + ((ks + DEPTH) >> 2) * 64);
+            wsr[(j % DEPTH) >> 2][t] = __builtin_nontemporal_load(sp[t] + ((ks + DEPTH) >> 2) * 16);
+          }
         }
       } else if (!LAST || j + DEPTH < ITER) {
 #pragma unroll
@@ -479,19 +528,22 @@ struct DecLaunch {  // what every instantiation is launched with
   int rn_nc;
   float inv_d, rn_eps;
   DecGroup dg;
-  const float* wscale;  // fp8 weights: one scale per packed weight row (else null)
+  const float* wscale;  // fp8 weights: one scale per packed weight row; mxfp4: the packed block scales (else null)
+  int d4 = 0;           // mxfp4: the ring depth in k-steps (8 or 16)
 };
 
 // Launches <mt m-tiles, form F> for 1 <= mt <= MT: the instantiations 1..MT of the form and no
 // others (MT = 0: none).
-template <int F, bool RNW, int MT, bool F8 = false>
+// (D4: the mxfp4 ring depth, which replaces the form's own)
+template <int F, bool RNW, int MT, int WF = DEC_W_BF16, int D4 = 0>
 bool dec_launch(int mt, const DecLaunch& l) {
   if constexpr (MT == 0) {
     return false;
   } else {
-    if (mt != MT) return dec_launch<F, RNW, MT - 1, F8>(mt, l);
+    if (mt != MT) return dec_launch<F, RNW, MT - 1, WF, D4>(mt, l);
     constexpr DecForm f = kDecForms[F];
-    hipLaunchKernelGGL((gemm_dec_kernel<MT, f.ntw, f.waves, f.epi, f.depth, RNW, F8>), l.grid, l.blk, 0, l.s, l.A,
+    constexpr int depth = WF == DEC_W_F4 ? D4 : f.depth;
+    hipLaunchKernelGGL((gemm_dec_kernel<MT, f.ntw, f.waves, f.epi, depth, RNW, WF>), l.grid, l.blk, 0, l.s, l.A,
                        l.W, l.partial, l.Y, l.ldy, l.M, l.N, l.K, l.kchunk, l.rn_ss, l.rn_nc, l.inv_d, l.rn_eps, l.dg,
                        l.wscale);
     return true;
@@ -499,18 +551,25 @@ bool dec_launch(int mt, const DecLaunch& l) {
 }
 
 // The walk over kDecForms from row F on: false when no row is (epi, ntw, waves, depth) or the row
-// has no instantiation for mt m-tiles (rnw: of the wide deferred-norm form; F8: of the fp8-weight
-// form - the rows of kDecF8Forms, narrow norm only).
-template <bool F8 = false, int F = 0>
+// has no instantiation for mt m-tiles (rnw: of the wide deferred-norm form; WF: of the fp8- or
+// mxfp4-weight form - the rows of kDecF8Forms / kDecF4Forms, narrow norm only).
+template <int WF = DEC_W_BF16, int F = 0>
 bool dec_dispatch(int epi, int ntw, int waves, int depth, bool rnw, int mt, const DecLaunch& l) {
   if constexpr (F == kDecNForms) {
     return false;
   } else {
     constexpr DecForm f = kDecForms[F];
     if (epi != f.epi || ntw != f.ntw || waves != f.waves || depth != f.depth)
-      return dec_dispatch<F8, F + 1>(epi, ntw, waves, depth, rnw, mt, l);
-    if constexpr (F8)
-      return !rnw && dec_launch<F, false, dec_form_f8(F) ? f.max_mt : 0, true>(mt, l);
+      return dec_dispatch<WF, F + 1>(epi, ntw, waves, depth, rnw, mt, l);
+    if constexpr (WF == DEC_W_F8)
+      return !rnw && dec_launch<F, false, dec_form_f8(F) ? f.max_mt : 0, DEC_W_F8>(mt, l);
+    else if constexpr (WF == DEC_W_F4) {
+      // ring depth 8 at 1..max_mt m-tiles, and 16 at one m-tile where kDecF4Forms says so (0: no row)
+      constexpr int d1 = dec_form_f4_depth(F);
+      if (rnw) return false;
+      if (l.d4 == 16) return dec_launch<F, false, d1 >= 16 ? 1 : 0, DEC_W_F4, 16>(mt, l);
+      return l.d4 == 8 && dec_launch<F, false, d1 >= 8 ? f.max_mt : 0, DEC_W_F4, 8>(mt, l);
+    }
     else
       return rnw ? dec_launch<F, true, f.wide_norm ? kDecNarrowMaxMT : 0>(mt, l) : dec_launch<F, false, f.max_mt>(mt, l);
   }
@@ -573,7 +632,7 @@ extern "C" int k8sllm_gemm_dec_f8(const void* A, const void* Wq, const float* ws
   const DecLaunch l{dim3((ntiles + nwg_tiles - 1) / nwg_tiles, splits, 1), dim3(64 * waves), s,
                     (const bf16_t*)A, (const bf16_t*)Wq, partial, (bf16_t*)Y, ldy, M, N, K, kchunk, rn_ss, rn_nc,
                     inv_d, rn_eps, DecGroup{0, 0, 0, nullptr, 0}, wscale};
-  if (!dec_dispatch<true>(epi, ntw, waves, depth, false, MT, l)) return -5;
+  if (!dec_dispatch<DEC_W_F8>(epi, ntw, waves, depth, false, MT, l)) return -5;
   return (int)hipGetLastError();
 }
 
@@ -582,6 +641,55 @@ extern "C" int k8sllm_gemm_dec_f8(const void* A, const void* Wq, const float* ws
 extern "C" int k8sllm_gemm_dec_f8_forms(int* out, int cap) {
   for (int i = 0; i < kDecNF8Forms && i < cap; ++i) out[i] = kDecF8Forms[i];
   return kDecNF8Forms;
+}
+
+// The same over MXFP4 weights: Wq e2m1 codes [N/16][K/128][64][16] and wscale the e8m0 block scales
+// [N/16][K/128][16] dwords (ops.pack_skinny_f4).  Dense launches only; (epi, ntw, waves, depth)
+// must be a row of kDecForms listed in kDecF4Forms, with ceil(M / 16) <= its max_mt and the narrow
+// deferred norm; every K slice holds whole 256-deep A chunks (so whole 128-deep code groups).
+// f4_depth: the ring depth in k-steps - 0: the launcher's rule (the row's one-m-tile depth at
+// <= 16 rows where it divides the slice's k-steps, else 8); 8 or 16: forced, within that rule's
+// range.  The same negative codes as k8sllm_gemm_dec.
+extern "C" int k8sllm_gemm_dec_f4(const void* A, const void* Wq, const void* wscale, float* partial, void* Y,
+                                  long ldy, int M, int N, int K, int splits, int epi, int ntw, int waves, int depth,
+                                  int f4_depth, const float* rn_ss, int rn_nc, int rn_d, float rn_eps,
+                                  hipStream_t s) {
+  if (M <= 0) return 0;
+  if (M > kDecMaxM || wscale == nullptr) return -1;
+  if (N % 16 || K % 128 || splits < 1 || K % splits) return -1;
+  const int ntiles = N / 16, nwg_tiles = ntw * waves;
+  if (nwg_tiles < 1) return -5;
+  int dmax = 0;
+  for (int i = 0; i < kDecNForms; ++i) {
+    const DecForm& f = kDecForms[i];
+    if (f.epi == epi && f.ntw == ntw && f.waves == waves && f.depth == depth) dmax = dec_form_f4_depth(i);
+  }
+  if (dmax == 0) return -5;
+  const int kchunk = K / splits;
+  if (kchunk % 128 || kchunk < 32 * kDecCH || (kchunk / 32) % kDecCH) return -3;
+  const int MT = (M + 15) / 16;
+  if (MT > 1) dmax = 8;
+  int d4 = f4_depth;
+  if (d4 == 0) d4 = dmax >= 16 && (kchunk / 32) % 16 == 0 ? 16 : 8;
+  if ((d4 != 8 && d4 != 16) || d4 > dmax || (kchunk / 32) % d4) return -3;
+  if (epi != DEC_SLAB && splits != 1) return -4;
+  const float inv_d = rn_d > 0 ? 1.f / (float)rn_d : 0.f;
+  if (rn_ss != nullptr && rn_nc > 4 * kRnMax) return -1;  // the wide deferred-norm form reads bf16 weights
+  const DecLaunch l{dim3((ntiles + nwg_tiles - 1) / nwg_tiles, splits, 1), dim3(64 * waves), s,
+                    (const bf16_t*)A, (const bf16_t*)Wq, partial, (bf16_t*)Y, ldy, M, N, K, kchunk, rn_ss, rn_nc,
+                    inv_d, rn_eps, DecGroup{0, 0, 0, nullptr, 0}, (const float*)wscale, d4};
+  if (!dec_dispatch<DEC_W_F4>(epi, ntw, waves, depth, false, MT, l)) return -5;
+  return (int)hipGetLastError();
+}
+
+// The rows of kDecForms with mxfp4-weight instantiations (kDecF4Forms) as two ints each (index
+// into kDecForms, F4 ring depth at one m-tile), at most cap rows into out; returns the row count.
+extern "C" int k8sllm_gemm_dec_f4_forms(int* out, int cap) {
+  for (int i = 0; i < kDecNF4Forms && i < cap; ++i) {
+    out[2 * i] = kDecF4Forms[i].form;
+    out[2 * i + 1] = kDecF4Forms[i].depth;
+  }
+  return kDecNF4Forms;
 }
 
 // The rows of kDecForms as six ints each (epi, ntw, waves, depth, max_mt, wide_norm), at most cap

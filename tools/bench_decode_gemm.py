@@ -11,7 +11,12 @@ left out, hipBLASLt stays for the LM head, and configurations without a 65..128-
 ``--wdtype fp8`` adds, next to every dec configuration with an fp8 form (ops.DEC_F8_FORMS), the
 same launch over the fp8 encoding of the weights (``f8_`` cases: half the weight bytes; TBps
 counts the bytes actually streamed), checked for bit equality with the bf16 launch over the
-dequantised weights, which the bf16 cases then stream too.  ``--shape 70b_gate_up`` etc.: SHAPES.
+dequantised weights, which the bf16 cases then stream too.  ``--wdtype mxfp4`` does the same for
+the MXFP4 encoding (``f4_`` cases, ops.DEC_F4_FORMS: 17/64 of the bytes), ``--wdtype fp8,mxfp4``
+both in one session (each checked against the bf16 launch over its own dequantised weights;
+the timed bf16 cases stream the last encoding's).  ``--f4-depths 8,16`` times the mxfp4 cases
+once per forced F4 ring depth (ops.DEC_F4_DEPTH_FORCE; 0 = the launcher's choice) where the
+launcher takes it.  ``--shape 70b_gate_up`` etc.: SHAPES.
 
     python tools/bench_decode_gemm.py [--ms 1,32,64] [--ops qkv,o,gate_up,down,lm_head] [--rounds 3] [--wdtype fp8]
 """
@@ -50,9 +55,14 @@ def main() -> None:
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--ops", default="qkv,o,gate_up,down,lm_head")
     ap.add_argument("--cfgs", default=None, help="op:S,NTW,W,D|S,NTW,W,D;... overrides the sweep list")
-    ap.add_argument("--wdtype", default="bf16", choices=["bf16", "fp8"])
+    ap.add_argument("--wdtype", default="bf16", help="bf16, fp8, mxfp4 or fp8,mxfp4")
+    ap.add_argument("--f4-depths", default="0", help="F4 ring depths to time the mxfp4 cases at (0 = automatic)")
     ap.add_argument("--no-base", action="store_true", help="leave out the row-major skinny / hipBLASLt case")
     a = ap.parse_args()
+    encs = [e for e in a.wdtype.split(",") if e != "bf16"]
+    if any(e not in ("fp8", "mxfp4") for e in encs):
+        ap.error("--wdtype: bf16, fp8, mxfp4 or fp8,mxfp4")
+    f4_depths = [int(d) for d in a.f4_depths.split(",")]
     dev = "cuda"
     torch.manual_seed(0)
     cfgs = dict(CFGS)
@@ -70,13 +80,24 @@ def main() -> None:
         else:
             wdec = [ops.pack_skinny(w) for w in wrm]
         wq = ws = None
-        if a.wdtype == "fp8":  # one model, two encodings: the bf16 copies become the dequantised values
-            qs = [ops.quantize_rows_fp8(ops.unpack_skinny(w)) for w in wdec]
-            wdec = [ops.pack_skinny(ops.dequantize_rows_fp8(q, s)) for q, s in qs]
-            wrm = [ops.interleave_gate_up(ops.deinterleave_gate_up8(ops.unpack_skinny(w))) if epi == 2
-                   else ops.unpack_skinny(w) for w in wdec]
-            wq, ws = [ops.pack_skinny_f8(q) for q, _ in qs], [s for _, s in qs]
+        quant: dict = {}  # encoding -> (codes per copy, scales per copy, packed bf16 dequantised values of copy 0)
+        for enc in encs:  # one model, two encodings: the bf16 copies become the dequantised values
+            if enc == "fp8":
+                qs = [ops.quantize_rows_fp8(ops.unpack_skinny(w)) for w in wdec]
+                dq = [ops.pack_skinny(ops.dequantize_rows_fp8(q, s)) for q, s in qs]
+                quant[enc] = ([ops.pack_skinny_f8(q) for q, _ in qs], [s for _, s in qs], dq[0])
+            else:
+                qs = [ops.quantize_mxfp4(ops.unpack_skinny(w)) for w in wdec]
+                dq = [ops.pack_skinny(ops.dequantize_mxfp4(q, s)) for q, s in qs]
+                pk = [ops.pack_skinny_f4(q, s) for q, s in qs]
+                quant[enc] = ([c for c, _ in pk], [s for _, s in pk], dq[0])
+                del pk
             del qs
+            if enc == encs[-1]:
+                wdec = dq
+                wrm = [ops.interleave_gate_up(ops.deinterleave_gate_up8(ops.unpack_skinny(w))) if epi == 2
+                       else ops.unpack_skinny(w) for w in wdec]
+            del dq
         gb = N * K * 2 / 1e9
         for M in map(int, a.ms.split(",")):
             x = torch.randn(M, K, device=dev, dtype=torch.bfloat16)
@@ -122,22 +143,38 @@ def main() -> None:
                 cases[tag] = (lambda i, cfg=cfg: ops.dec_gemm(xp, wdec[i % ncopy], epi, M, workspace=wsp,
                                                               out=act if epi == 2 else yb, cfg=cfg))
                 print(json.dumps({"op": name, "M": M, "cfg": cfg, "rel_err": round(err, 5)}), flush=True)
-                if wq is not None and ops.dec_form_ok(epi, cfg, M, f8=True):
-                    same = torch.equal(dec_out(cfg).clone(), dec_out(cfg, wq[0], wscale=ws[0]))
-                    cases["f8_" + tag] = (lambda i, cfg=cfg: ops.dec_gemm(xp, wq[i % ncopy], epi, M, workspace=wsp,
-                                                                       out=act if epi == 2 else yb, cfg=cfg,
-                                                                       wscale=ws[i % ncopy]))
-                    print(json.dumps({"op": name, "M": M, "cfg": cfg, "f8_bit_equal_to_bf16": same}), flush=True)
+                for enc, (wq, ws, wchk) in quant.items():
+                    pre, kw = ("f8_", dict(f8=True)) if enc == "fp8" else ("f4_", dict(f4=True, K=K))
+                    if not ops.dec_form_ok(epi, cfg, M, **kw):
+                        continue
+                    same = torch.equal(dec_out(cfg, wchk).clone(), dec_out(cfg, wq[0], wscale=ws[0]))
+                    print(json.dumps({"op": name, "M": M, "cfg": cfg, pre + "bit_equal_to_bf16": same}), flush=True)
+
+                    def run(i, cfg=cfg, wq=wq, ws=ws, depth=0):
+                        ops.DEC_F4_DEPTH_FORCE = depth
+                        try:
+                            return ops.dec_gemm(xp, wq[i % ncopy], epi, M, workspace=wsp, out=act if epi == 2 else yb,
+                                                cfg=cfg, wscale=ws[i % ncopy])
+                        finally:
+                            ops.DEC_F4_DEPTH_FORCE = 0
+
+                    for d in (f4_depths if enc == "mxfp4" else [0]):
+                        fn = (lambda i, run=run, d=d: run(i, depth=d))
+                        try:
+                            fn(0)  # a forced depth the launcher does not take for this slice: left out
+                        except RuntimeError:
+                            continue
+                        cases[pre + (f"ring{d}_" if d else "") + tag] = fn
             res: dict = {}
             for _ in range(a.rounds):
                 for tag, fn in cases.items():
                     res.setdefault(tag, []).append(timeit(fn, a.iters))
             for tag, ts in res.items():
                 t = min(ts)
-                b = gb / 2 if tag.startswith("f8_") else gb
+                b = gb / 2 if tag.startswith("f8_") else gb * 17 / 64 if tag.startswith("f4_") else gb
                 print(json.dumps({"op": name, "M": M, "impl": tag, "us": round(t, 2),
                                   "us_all": [round(v, 2) for v in ts], "TBps": round(b / t * 1e3, 2)}), flush=True)
-        del wrm, wdec, wq, ws
+        del wrm, wdec, wq, ws, quant
         torch.cuda.empty_cache()
 
 

@@ -18,6 +18,8 @@ kernels vs the generic layer loop (``--rows 64,128``; at 64 rows both sides run 
 then A/Bs a step streaming fp8 weights (on; the row-complete o projection off, the fp8-mode
 default) against the same engine routed to its bf16 copies with the bf16 defaults (off), and
 ``rc`` the row-complete o projection (bf16 o, bf16 wide-norm gate_up) inside fp8 mode.
+``--decode-weights mxfp4``: the same with the MXFP4 encoding (``f8`` then switches its forms,
+ops.DEC_F4_FORMS, off and on); every line also carries the engine's ``resident_weight_bytes``.
 """
 from __future__ import annotations
 
@@ -49,12 +51,13 @@ _F8_FORMS: list = []
 
 
 def _f8(m, on) -> None:
-    """off: no fp8 form is offered (ops.dec_config(f8=True) answers None, every launch reads the
-    bf16 copy) and the row-complete o projection is back at its bf16 default; on / reset: as built."""
+    """off: no fp8 / mxfp4 form is offered (ops.dec_config(f8=True) / (f4=True) answers None, every
+    launch reads the bf16 copy) and the row-complete o projection is back at its bf16 default;
+    on / reset: as built."""
     ops = _ops()
     if not _F8_FORMS:
-        _F8_FORMS.append(ops.DEC_F8_FORMS)
-    ops.DEC_F8_FORMS = () if on is False else _F8_FORMS[0]
+        _F8_FORMS.append((ops.DEC_F8_FORMS, ops.DEC_F4_FORMS))
+    ops.DEC_F8_FORMS, ops.DEC_F4_FORMS = ((), ()) if on is False else _F8_FORMS[0]
     m.set_decode_fusion(rc=m.RC_O_MAX_ROWS if on is False else None)
 
 
@@ -78,7 +81,7 @@ def main() -> None:
     ap.add_argument("--ctx", type=int, default=1700)
     ap.add_argument("--tokens", type=int, default=96)
     ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--decode-weights", default="bf16", choices=["bf16", "fp8"])
+    ap.add_argument("--decode-weights", default="bf16", choices=["bf16", "fp8", "mxfp4"])
     ap.add_argument("--kv-cache-dtype", default="bf16", choices=["bf16", "fp8"])
     ap.add_argument("--layers", type=int, default=0, help="override the model's layer count (0 = all)")
     a = ap.parse_args()
@@ -108,6 +111,7 @@ def main() -> None:
                 print(json.dumps({"switch": a.switch, "decode_weights": a.decode_weights,
                                   "kv_cache_dtype": a.kv_cache_dtype, "rows": rows, "on": on,
                                   "round": rnd, "steps": len(ms),
+                                  "resident_weight_bytes": eng.model.resident_weight_bytes(),
                                   "median_step_ms": round(med, 4)}), flush=True)
         print(json.dumps({"switch": a.switch, "rows": rows, "on_ms": [round(x, 4) for x in res[True]],
                           "off_ms": [round(x, 4) for x in res[False]],

@@ -6,6 +6,10 @@ rms logit difference, the logit scale, and how many of the rows keep their argma
 
     python tools/fp8_logit_diff.py [--model llama-3-8b --layers 2 --prompts 8]
 
+``--decode-weights mxfp4`` (or ``fp8,mxfp4``: one line each against the same unquantised engine)
+measures the MXFP4 encoding (ops.quantize_mxfp4: round-to-nearest e2m1, one e8m0 scale per 32
+weights) the same way.
+
 (``prefill_weights: fp8`` needs no numbers of its own: it releases the bf16 copy of weights whose
 values stay exactly these dequantised ones, and its prefill GEMM is bit-identical.)
 
@@ -33,8 +37,12 @@ def main() -> None:
     ap.add_argument("--prompts", type=int, default=8)
     ap.add_argument("--seed", type=int, default=5)
     ap.add_argument("--kv-cache-dtype", default="bf16", choices=["bf16", "fp8"])
+    ap.add_argument("--decode-weights", default="fp8", help="the weight encodings to measure: fp8, mxfp4 or fp8,mxfp4")
     a = ap.parse_args()
     kv_mode = a.kv_cache_dtype == "fp8"
+    encs = a.decode_weights.split(",")
+    if any(e not in ("fp8", "mxfp4") for e in encs) or (kv_mode and encs != ["fp8"]):
+        ap.error("--decode-weights: fp8, mxfp4 or fp8,mxfp4 (without --kv-cache-dtype fp8)")
     from k8s_llm_monitor_amd.engine import EngineConfig, LLMEngine
     from k8s_llm_monitor_amd.models import AttnMeta
 
@@ -60,33 +68,40 @@ def main() -> None:
             out.append(e.model.forward(i32(ids[t:t + 1]), meta, e.runner.kv).float())
         return torch.cat(out)
 
-    engs = {dw: engine(dw) for dw in ("bf16", "fp8")}
+    def logits(e, ids):
+        t = torch.tensor(ids, dtype=torch.int32, device="cuda")
+        k = len(ids)
+        meta = AttnMeta(is_prefill=True, positions=torch.arange(k, dtype=torch.int32, device="cuda"),
+                        slot_mapping=torch.full((k,), -1, dtype=torch.int32, device="cuda"),
+                        cu_seqlens=torch.tensor([0, k], dtype=torch.int32, device="cuda"),
+                        logits_idx=torch.arange(k, device="cuda"))
+        with torch.no_grad():
+            return through_cache(e, ids) if kv_mode else e.model.forward(t, meta, None).float()
+
+    base = engine("bf16")
     prompts = [f"a node-{i:03d} CPU={30 + i % 60}% pod payments-{i} restarts={i % 7} 为什么我的pod频繁重启？"
                for i in range(a.prompts)]
-    d2 = n = same = rows = 0
-    dmax = scale = 0.0
-    for p in prompts:
-        ids = engs["bf16"].tokenizer.encode(p)
-        lg = {}
-        for dw, e in engs.items():
-            t = torch.tensor(ids, dtype=torch.int32, device="cuda")
-            k = len(ids)
-            meta = AttnMeta(is_prefill=True, positions=torch.arange(k, dtype=torch.int32, device="cuda"),
-                            slot_mapping=torch.full((k,), -1, dtype=torch.int32, device="cuda"),
-                            cu_seqlens=torch.tensor([0, k], dtype=torch.int32, device="cuda"),
-                            logits_idx=torch.arange(k, device="cuda"))
-            with torch.no_grad():
-                lg[dw] = through_cache(e, ids) if kv_mode else e.model.forward(t, meta, None).float()
-        diff = lg["fp8"] - lg["bf16"]
-        d2 += float(diff.pow(2).sum())
-        n += diff.numel()
-        dmax = max(dmax, float(diff.abs().max()))
-        scale = max(scale, float(lg["bf16"].abs().max()))
-        same += int((lg["fp8"].argmax(-1) == lg["bf16"].argmax(-1)).sum())
-        rows += diff.shape[0]
-    print(json.dumps({"model": a.model, "layers": a.layers, "quantised": "kv_cache" if kv_mode else "weights", "prompts": a.prompts, "rows": rows,
-                      "logit_scale": round(scale, 4), "max_diff": round(dmax, 4),
-                      "rms_diff": round((d2 / n) ** 0.5, 5), "argmax_kept": same}), flush=True)
+    ids_all = [base.tokenizer.encode(p) for p in prompts]
+    ref = [logits(base, ids) for ids in ids_all]
+    for enc in encs:
+        e = engine(enc)
+        d2 = n = same = rows = 0
+        dmax = scale = 0.0
+        for ids, lb in zip(ids_all, ref):
+            lq = logits(e, ids)
+            diff = lq - lb
+            d2 += float(diff.pow(2).sum())
+            n += diff.numel()
+            dmax = max(dmax, float(diff.abs().max()))
+            scale = max(scale, float(lb.abs().max()))
+            same += int((lq.argmax(-1) == lb.argmax(-1)).sum())
+            rows += diff.shape[0]
+        print(json.dumps({"model": a.model, "layers": a.layers, "quantised": "kv_cache" if kv_mode else "weights",
+                          "encoding": enc, "prompts": a.prompts, "rows": rows,
+                          "logit_scale": round(scale, 4), "max_diff": round(dmax, 4),
+                          "rms_diff": round((d2 / n) ** 0.5, 5), "argmax_kept": same}), flush=True)
+        del e
+        torch.cuda.empty_cache()
 
 
 if __name__ == "__main__":

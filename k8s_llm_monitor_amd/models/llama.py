@@ -115,6 +115,7 @@ PROJ = ("wqkv", "wo", "w13", "w2")
 # with PREFILL_WEIGHTS = "fp8" the codes may be the projection itself: L[key] is L[key + "_q"], no "_d")
 # or, with DEC_WEIGHTS = "mxfp4", its mxfp4 encoding under the same two keys (ops.pack_skinny_f4's
 # codes and block scales; ops.is_mxfp4 / ops.is_fp8 tell the two apart)
+# (MoE expert stacks: the same two keys hold 5-d [E, ...] stacks of per-expert codes and scales)
 DERIVED = ("_p", "_pg", "_d", "_dg", "_q", "_qs")
 DEC_COPIES = ("_d", "_dg")  # the decode GEMM's packed bf16 copies among them
 
@@ -175,6 +176,10 @@ class CausalLM:
     # e8m0 scale per 32 elements along K): the bf16 weights are the dequantised values, the codes
     # and block scales sit beside them under the same ``*_q`` / ``*_qs`` keys (resident weights
     # grow by 17/64), and a launch streams them where ops.dec_config(f4=True) has a form.
+    # MoE expert stacks are quantised under either encoding too (5-d ``w13_q`` / ``w2_q`` stacks
+    # beside the bf16 stacks, _quantize_experts) and the grouped launches of up to 64 rows stream
+    # them (ops.dec_grouped_q_config, _dec_grouped); prefill and the routed > 64-row decode path
+    # read the bf16 stacks, which hold the dequantised values.
     DEC_WEIGHTS = "bf16"
     # What prefill reads where DEC_WEIGHTS = "fp8": "bf16" - the bf16 copy beside the codes - or
     # "fp8": the tile GEMM converts the codes on the way into the MFMA (gemm_tile.hip F8,
@@ -655,8 +660,8 @@ class CausalLM:
             for c0 in range(0, R, ops.SKINNY_MAX_M):
                 mc = min(ops.SKINNY_MAX_M, R - c0)
                 act = torch.empty((E, -(-mc // 16), L["w13_dg"].shape[1] // 4, 64, 8), dtype=x.dtype, device=x.device)
-                ops.dec_gemm_grouped(ops.pack_activation(rows[c0:c0 + mc]), L["w13_dg"], 2, mc, out=act)
-                ns = ops.dec_gemm_grouped(act, L["w2_dg"], 0, mc, workspace=ws, row_w=onehot[c0:c0 + mc].contiguous())
+                self._dec_grouped(L, "w13", ops.pack_activation(rows[c0:c0 + mc]), 2, mc, out=act)
+                ns = self._dec_grouped(L, "w2", act, 0, mc, workspace=ws, row_w=onehot[c0:c0 + mc].contiguous())
                 ops.reduce_slabs(ws, ns, mc, d, dtype=x.dtype, out=y[c0:c0 + mc])
         elif ws is not None and "w13_pg" in L:
             y = torch.empty(R, d, dtype=x.dtype, device=x.device)
@@ -1118,9 +1123,8 @@ class CausalLM:
         if "w13_dg" in L and M <= ops.SKINNY_MAX_M:  # shared-A decode GEMM over the packed expert copies
             E = L["w13_dg"].shape[0]
             act = torch.empty((E, -(-M // 16), L["w13_dg"].shape[1] // 4, 64, 8), dtype=self.dtype, device=self.device)
-            ops.dec_gemm_grouped(xp, L["w13_dg"], 2, M, out=act)
-            return ops.dec_gemm_grouped(act, L["w2_dg"], 0, M, workspace=ws,
-                                        row_w=wd[:, self.e_lo:self.e_hi].contiguous())
+            self._dec_grouped(L, "w13", xp, 2, M, out=act)
+            return self._dec_grouped(L, "w2", act, 0, M, workspace=ws, row_w=wd[:, self.e_lo:self.e_hi].contiguous())
         act = ops.skinny_grouped_swiglu(xp, L["w13_pg"], rows=M)
         return ops.skinny_grouped_slabs(act, L["w2_pg"], ws, M, wd[:, self.e_lo:self.e_hi].contiguous(), splits=1)
 
@@ -1301,7 +1305,10 @@ class CausalLM:
         overwritten with the dequantised values (so the packed copy, prefill and the checkpoint
         hold exactly what the fp8 kernel computes with; a tied embedding table with them), and its
         codes and scales kept as ``*_q`` / ``*_qs`` in the packed copy's row order - layer by
-        layer, so peak memory stays the model plus one layer.  MoE expert stacks stay bf16.
+        layer, so peak memory stays the model plus one layer.  MoE expert stacks that get packed
+        copies are quantised too, expert by expert (``_quantize_experts``: 5-d stacks of codes and
+        scales under ``w13_q`` / ``w13_qs`` / ``w2_q`` / ``w2_qs``), where the grouped launch has a
+        form over the encoding for both projections (ops.dec_grouped_q_config); else they stay bf16.
         ``DEC_WEIGHTS`` = "mxfp4": the same with ops.quantize_mxfp4 (one scale per row and block of
         32 along K, so the [8 gate | 8 up] row interleave carries codes and block scales along
         unchanged), the packed codes and block scales (ops.pack_skinny_f4) under the same two keys.
@@ -1316,9 +1323,7 @@ class CausalLM:
         parts, one = self._want_dec(), self._one_layout_wanted()
         f8 = self.DEC_WEIGHTS in ("fp8", "mxfp4") and not self._f8_defer
         f4 = f8 and self.DEC_WEIGHTS == "mxfp4"
-        if f8 and self.cfg.is_moe:
-            log.info("%s: decode_weights=%s leaves the MoE expert stacks on bf16 (grouped launches have no such form)",
-                     self.cfg.name, self.DEC_WEIGHTS)
+        bf16_experts = None  # why the expert stacks stay on bf16, where they do
         f8_only = f8 and self.PREFILL_WEIGHTS == "fp8"
         why = None  # why nothing can be fp8-only, if so
         if f8_only and (self.cfg.is_moe or self.tp != 1 or not one):
@@ -1333,6 +1338,10 @@ class CausalLM:
                     E, F2, d = L["w13"].shape
                     sfx, ok = "_dg", "experts" in parts and all(
                         ops.dec_config(n, k, epi, experts=E) is not None for n, k, epi in ((F2, d, 2), (d, F2 // 2, 0)))
+                    if f8:  # the codes beside the packed stack: both projections or neither, as for _dg
+                        bf16_experts = "no packed expert copies" if not ok else self._experts_q_why(E, F2, d)
+                        if bf16_experts is None:
+                            self._quantize_experts(L, key)
                 else:
                     sfx, ok = "_d", (("attn" if key in ("wqkv", "wo") else "mlp") in parts
                                      and ops.dec_available(*w.shape, 2 if key == "w13" else 0))
@@ -1377,6 +1386,9 @@ class CausalLM:
             stayed["head"] = why or "no decode copy of the head"
         if one:
             self._layout = PACKED
+        if bf16_experts:
+            log.info("%s: decode_weights=%s leaves the MoE expert stacks on bf16 (%s)", self.cfg.name,
+                     self.DEC_WEIGHTS, bf16_experts)
         if stayed:
             log.info("%s: prefill_weights=fp8 keeps the bf16 copy of %s", self.cfg.name,
                      ", ".join(f"{k} ({r})" for k, r in stayed.items()))
@@ -1467,6 +1479,69 @@ class CausalLM:
             q = ops.interleave_gate_up8(q.view(torch.uint8)).view(torch.float8_e4m3fn)
             s = ops.interleave_gate_up8(s[:, None])[:, 0]
         L[key + "_q"], L[key + "_qs"] = ops.pack_skinny_f8(q), s.contiguous()
+
+    def _experts_q_why(self, E: int, F2: int, d: int) -> Optional[str]:
+        """None when the grouped decode GEMM has a form over this model's quantised encoding for
+        both expert projections ([E, F2, d] gate_up and [E, d, F2 / 2] down), else why not."""
+        for name, (n, k, epi) in (("gate_up", (F2, d, 2)), ("down", (d, F2 // 2, 0))):
+            if ops.dec_grouped_q_config(n, k, epi, E, **self._enc_kw()) is None:
+                return f"no {self.DEC_WEIGHTS} grouped form, or none faster than bf16, for {name} [{E}, {n}, {k}]"
+        return None
+
+    def _quantize_experts(self, L: dict, key: str) -> None:
+        """The fp8 / mxfp4 encoding of the expert stack ``L[key]`` ([E, out, in], row-major,
+        INTERLEAVED or CANONICAL), one expert at a time (the fp32 temporaries stay one expert's):
+        each expert's rows are overwritten in place with the dequantised values (a row-major
+        ``*_pg`` view aliases them; a packed ``*_pg`` copy is refreshed) and ``*_q`` / ``*_qs``
+        hold the stacks of packed codes [E, out/16, in/64 | in/128, 64, 16] and of scales ([E, out]
+        fp32 | [E, out/16, in/128, 16, 4] uint8) in the row order of the packed copy ``*_dg``
+        (w13: [8 gate | 8 up] per 16 rows, the scales permuted with the rows).  The codes kept are
+        those of the dequantised values: where a row's (block's) largest element rounded down to
+        half the code range, the first pass's scale is one step coarser than the one the values
+        themselves ask for - the same values on either, but only the second is what a checkpoint
+        load, a weight copy or a second ``_init_skinny`` will find, so those reproduce the codes."""
+        w = L[key]
+        f4 = self.DEC_WEIGHTS == "mxfp4"
+        Q = S = None  # the [E, ...] stacks, allocated from expert 0's shapes
+        pg = L.get(key + "_pg")
+        for e in range(w.shape[0]):
+            c = to_canonical(w[e], key, self._layout)
+            if f4:
+                deq = ops.dequantize_mxfp4(*ops.quantize_mxfp4(c), self.dtype)
+                q, s = ops.quantize_mxfp4(deq)  # of the dequantised values: see the docstring
+                if key == "w13":
+                    q, s = ops.interleave_gate_up8(q), ops.interleave_gate_up8(s)
+                q, s = ops.pack_skinny_f4(q, s)
+            else:
+                deq = ops.dequantize_rows_fp8(*ops.quantize_rows_fp8(c), self.dtype)
+                q, s = ops.quantize_rows_fp8(deq)
+                if key == "w13":
+                    q = ops.interleave_gate_up8(q.view(torch.uint8)).view(torch.float8_e4m3fn)
+                    s = ops.interleave_gate_up8(s[:, None])[:, 0]
+                q, s = ops.pack_skinny_f8(q), s.contiguous()
+            w[e].copy_(to_resident(deq, key, self._layout))
+            if pg is not None and pg is not w:
+                pg[e].copy_(ops.pack_skinny(w[e]))
+            if Q is None:
+                Q, S = (torch.empty((w.shape[0],) + t.shape, dtype=t.dtype, device=t.device) for t in (q, s))
+            Q[e].copy_(q)
+            S[e].copy_(s)
+            del c, deq, q, s
+        L[key + "_q"], L[key + "_qs"] = Q, S
+
+    @staticmethod
+    def _dec_grouped(L: dict, key: str, a: torch.Tensor, epi: int, rows: int, **kw) -> int:
+        """The grouped (grid.z = expert) decode GEMM of the expert stack ``key``: over its fp8 or
+        mxfp4 codes (``*_q`` / ``*_qs``) where the layer holds them and ops.dec_grouped_q_config
+        has a form for the stack, else over the packed bf16 stack ``*_dg`` - the same values
+        either way, so the choice is one of speed only (the grouped analogue of ``_dec``)."""
+        wq = L.get(key + "_q")
+        if wq is not None:
+            E, N, K = ops.grouped_q_wdims(wq)
+            enc = dict(f4=True) if ops.is_mxfp4(wq) else dict(f8=True)  # the codes say which encoding they are
+            if ops.dec_grouped_q_config(N, K, epi, E, **enc) is not None:
+                return ops.dec_gemm_grouped_q(a, wq, L[key + "_qs"], epi, rows, **kw)
+        return ops.dec_gemm_grouped(a, L[key + "_dg"], epi, rows, **kw)
 
     @staticmethod
     def _adopt_packed(L: dict) -> None:

@@ -320,8 +320,9 @@ def unpack_skinny_f4(cp: torch.Tensor, sp: torch.Tensor) -> tuple:
 
 
 def is_mxfp4(w: Optional[torch.Tensor]) -> bool:
-    """A weight in pack_skinny_f4's code layout (the only 4-d uint8 weight there is)."""
-    return w is not None and w.dtype == torch.uint8 and w.dim() == 4
+    """A weight in pack_skinny_f4's code layout (the only 4-d uint8 weight there is), or an
+    [E, ...] stack of such (the only 5-d one)."""
+    return w is not None and w.dtype == torch.uint8 and w.dim() in (4, 5)
 
 
 def pack_skinny(w: torch.Tensor) -> torch.Tensor:
@@ -651,19 +652,27 @@ def dec_config(N: int, K: int, epi: int, experts: int = 1, rows: int = 0, f8: bo
     weight (dense launches, K a multiple of 64) - the same tables and candidates restricted to
     DEC_F8_FORMS, DEC_TABLE_F8 first; None where the shape decodes from bf16.  ``f4``: the same over
     the mxfp4 encoding (K a multiple of 128, DEC_F4_FORMS, DEC_TABLE_F4; every K slice whole
-    256-deep A chunks)."""
+    256-deep A chunks).  Grouped launches over a quantised stack have a rule of their own,
+    dec_grouped_q_config: ``f8`` / ``f4`` with ``experts`` != 1 answers None here."""
+    if (f8 or f4) and experts != 1:  # the quantised grouped launches answer to dec_grouped_q_config
+        return None
+    return _dec_pick(N, K, epi, experts, rows, f8, f4)
+
+
+def _dec_pick(N: int, K: int, epi: int, experts: int, rows: int, f8: bool, f4: bool) -> Optional[tuple]:
+    """dec_config's rule (tables, then the candidate walk), whatever the expert count."""
     wide = rows > DEC_NARROW_MAX_M
     if wide and (experts != 1 or rows > DEC_MAX_M):
         return None
-    if f8 and (experts != 1 or K % 64):
+    if f8 and K % 64:
         return None
-    if f4 and (f8 or experts != 1 or K % 128):
+    if f4 and (f8 or K % 128):
         return None
     compiled = ([DEC_FORMS[i] for i in DEC_F8_FORMS] if f8 else
                 [DEC_FORMS[i] for i, _ in DEC_F4_FORMS] if f4 else DEC_FORMS)
-    if f8 and (N, K, epi, 128 if wide else 64) in DEC_TABLE_F8:
+    if f8 and experts == 1 and (N, K, epi, 128 if wide else 64) in DEC_TABLE_F8:
         return DEC_TABLE_F8[(N, K, epi, 128 if wide else 64)]
-    if f4 and (N, K, epi, 128 if wide else 64) in DEC_TABLE_F4:
+    if f4 and experts == 1 and (N, K, epi, 128 if wide else 64) in DEC_TABLE_F4:
         return DEC_TABLE_F4[(N, K, epi, 128 if wide else 64)]
     hit = (DEC_TABLE_M128 if wide else DEC_TABLE).get((N, K, epi)) if experts == 1 else None
     if hit is not None and (not f8 or dec_form_ok(epi, hit, rows, f8=True)) and (
@@ -799,6 +808,95 @@ def dec_gemm_grouped(a: torch.Tensor, wp: torch.Tensor, epi: int, rows: int, wor
     r = native().gemm_dec_grouped(a, wp, workspace, out, S, epi, ntw, waves, depth, M, row_w)
     if r < 0:
         raise RuntimeError(f"gemm_dec_grouped: configuration {cfg} not compiled for N={N} K={K} epi={epi}")
+    return r
+
+
+# Quantised grouped launches: (N, K, epi, experts, "fp8" | "mxfp4") -> a pick that differs from the
+# rule's, or None to route the projection of that many local experts to the bf16 stacks
+# (dec_grouped_q_config answers None: not faster than bf16).  Measurements: profiles/r14/README.md.
+DEC_TABLE_GROUPED_Q: dict = {}
+
+
+def dec_grouped_q_config(N: int, K: int, epi: int, experts: int, f8: bool = False, f4: bool = False) -> Optional[tuple]:
+    """Launch configuration (splits, ntw, waves, depth) of a grouped gemm_dec (grid.z = expert,
+    <= DEC_NARROW_MAX_M rows) over the fp8 (``f8``) or mxfp4 (``f4``) encoding of an expert stack
+    [experts, N, K], or None where the stack decodes from bf16: dec_config's rule with the
+    candidates restricted to DEC_F8_FORMS / DEC_F4_FORMS - splits 1 when ``experts`` > 1 (the expert
+    slabs are the split), K a multiple of 64 (fp8) or of 128 with whole 256-deep K slices (mxfp4) -
+    behind DEC_TABLE_GROUPED_Q.  SLAB and SWIGLU8 epilogues only."""
+    if f8 == f4 or experts < 1 or epi not in (DEC_SLAB, DEC_SWIGLU8):
+        return None
+    key = (N, K, epi, experts, "mxfp4" if f4 else "fp8")
+    if key in DEC_TABLE_GROUPED_Q:
+        return DEC_TABLE_GROUPED_Q[key]
+    return _dec_pick(N, K, epi, experts, 0, f8, f4)
+
+
+def dec_grouped_q_form_ok(epi: int, cfg: tuple, rows: int, f8: bool = False, f4: bool = False, K: int = 0) -> bool:
+    """Whether gemm_decode.hip has an instantiation for a grouped launch of
+    ``cfg = (splits, ntw, waves, depth)`` at ``rows`` rows over fp8 (``f8``) or mxfp4 (``f4``)
+    codes: a SLAB or SWIGLU8 row of DEC_F8_FORMS / DEC_F4_FORMS, at most DEC_NARROW_MAX_M rows; mxfp4
+    with ``K`` given: every K slice whole 256-deep A chunks."""
+    if f8 == f4 or rows > DEC_NARROW_MAX_M or epi not in (DEC_SLAB, DEC_SWIGLU8):
+        return False
+    return dec_form_ok(epi, cfg, rows, f8=f8, f4=f4, K=K)
+
+
+def grouped_q_wdims(wq: torch.Tensor) -> tuple:
+    """(E, N, K) of a quantised expert stack: fp8 codes [E, N/16, K/64, 64, 16] or mxfp4 codes
+    [E, N/16, K/128, 64, 16]."""
+    if wq.dim() != 5 or not (is_fp8(wq) or is_mxfp4(wq)) or tuple(wq.shape[3:]) != (64, 16):
+        raise ValueError("a quantised expert stack is float8_e4m3fn [E, N/16, K/64, 64, 16] or uint8 "
+                         f"[E, N/16, K/128, 64, 16], not {wq.dtype} {tuple(wq.shape)}")
+    return wq.shape[0], wq.shape[1] * 16, wq.shape[2] * (128 if is_mxfp4(wq) else 64)
+
+
+def dec_gemm_grouped_q(a: torch.Tensor, wq: torch.Tensor, wqs: torch.Tensor, epi: int, rows: int,
+                       workspace: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                       row_w: Optional[torch.Tensor] = None, cfg: Optional[tuple] = None) -> int:
+    """dec_gemm_grouped over the quantised encoding of the expert stack: ``wq`` the fp8 codes
+    [E, N/16, K/64, 64, 16] with ``wqs`` [E, N] fp32 row scales in packed row order (pack_skinny_f8 /
+    quantize_rows_fp8 per expert), or the mxfp4 codes [E, N/16, K/128, 64, 16] with ``wqs`` the packed
+    block scales [E, N/16, K/128, 16, 4] uint8 (pack_skinny_f4 per expert).  ``a``, ``out``,
+    ``workspace`` and ``row_w`` as dec_gemm_grouped; the configuration is dec_grouped_q_config's.
+    One launch over half (a quarter of) the weight bytes, bit-identical to dec_gemm_grouped of the
+    same configuration over the dequantised stack.  CPU: the per-expert dec_gemm loop over
+    ``(wq[e], wqs[e])`` with the routing weights applied as dec_gemm_grouped applies them."""
+    E, N, K = grouped_q_wdims(wq)
+    f4 = is_mxfp4(wq)
+    want = (E, N // 16, K // 128, 16, 4) if f4 else (E, N)
+    if wqs is None or tuple(wqs.shape) != want or wqs.dtype != (torch.uint8 if f4 else torch.float32):
+        raise ValueError(f"gemm_dec_grouped_q: the {'mxfp4' if f4 else 'fp8'} stack needs its scales "
+                         f"{list(want)} {'uint8' if f4 else 'fp32'}")
+    M = rows
+    if M > DEC_NARROW_MAX_M:
+        raise ValueError(f"gemm_dec_grouped_q: at most {DEC_NARROW_MAX_M} rows, got {M}")
+    if epi not in (DEC_SLAB, DEC_SWIGLU8):
+        raise ValueError("gemm_dec_grouped_q: only the slab and SwiGLU epilogues")
+    if cfg is None:
+        cfg = dec_grouped_q_config(N, K, epi, E, f8=not f4, f4=f4)
+    if cfg is None:
+        raise ValueError(f"gemm_dec_grouped_q: no configuration for N={N} K={K} epi={epi} experts={E}")
+    S, ntw, waves, depth = cfg
+    if not _gpu(a):
+        for e in range(E):
+            ae = a[e] if a.dim() == 5 else a
+            if epi == 2:
+                dec_gemm(ae, wq[e], 2, M, out=out[e], cfg=cfg, wscale=wqs[e])
+            else:
+                ws = workspace[e * S * M * N: (e + 1) * S * M * N]
+                dec_gemm(ae, wq[e], 0, M, workspace=ws, cfg=cfg, wscale=wqs[e])
+                if row_w is not None:
+                    ws.view(S, M, N).mul_(row_w[:M, e].float().view(1, M, 1))
+        return E * S if epi == 0 else 1
+    if not dec_grouped_q_form_ok(epi, cfg, M, f8=not f4, f4=f4, K=K):
+        raise RuntimeError(f"gemm_dec_grouped_q: form (epi, ntw, waves, depth) = {(epi,) + tuple(cfg[1:])} not "
+                           f"compiled for {M} rows of a grouped launch over {'mxfp4' if f4 else 'fp8'} weights"
+                           + (f" in {S} K slices" if f4 else ""))
+    r = native().gemm_dec_grouped_q(a, wq, wqs, workspace, out, S, epi, ntw, waves, depth, M, row_w,
+                                    DEC_F4_DEPTH_FORCE if f4 else 0)
+    if r < 0:
+        raise RuntimeError(f"gemm_dec_grouped_q: configuration {cfg} not compiled for N={N} K={K} epi={epi}")
     return r
 
 

@@ -59,7 +59,11 @@ int k8sllm_gemm_skinny(const void* A, long lda, const void* Wp, float* partial, 
                        const float* row_w, int row_w_ld, int w_rm, hipStream_t s);
 int k8sllm_gemm_dec(const void* A, const void* Wp, float* partial, void* Y, long ldy, int M, int N, int K, int splits,
                     int epi, int ntw, int waves, int depth, const float* rn_ss, int rn_nc, int rn_d, float rn_eps,
-                    int experts, long a_es, long w_es, long y_es, const float* rw, int rw_ld, hipStream_t s);
+                    int experts, long a_es, long w_eb, long y_es, const float* rw, int rw_ld, hipStream_t s);
+int k8sllm_gemm_dec_grouped_q(const void* A, const void* Wq, const void* wscale, int wf, float* partial, void* Y, int M,
+                              int N, int K, int splits, int epi, int ntw, int waves, int depth, int f4_depth,
+                              int experts, long a_es, long w_eb, long s_eb, long y_es, const float* rw, int rw_ld,
+                              hipStream_t s);
 int k8sllm_gemm_dec_forms(int* out, int cap);
 int k8sllm_gemm_dec_f8(const void* A, const void* Wq, const float* wscale, float* partial, void* Y, long ldy, int M,
                        int N, int K, int splits, int epi, int ntw, int waves, int depth, const float* rn_ss, int rn_nc,
@@ -836,7 +840,7 @@ int64_t gemm_dec_grouped(torch::Tensor a, torch::Tensor wp, c10::optional<torch:
                                           : (a.dim() == 4 && a.size(0) >= MT && a.size(1) * 32 == K &&
                                              a.size(2) == 64 && a.size(3) == 8)),
               "gemm_dec_grouped: a packed [ceil(M/16), K/32, 64, 8] or [E, ...]");
-  const long a_es = per_e ? a.stride(0) : 0, w_es = wp.stride(0);
+  const long a_es = per_e ? a.stride(0) : 0, w_eb = wp.stride(0) * wp.element_size();  // the kernel strides W in bytes
   float* pp = nullptr;
   void* yp = nullptr;
   long y_es = 0;
@@ -857,9 +861,74 @@ int64_t gemm_dec_grouped(torch::Tensor a, torch::Tensor wp, c10::optional<torch:
     y_es = y->stride(0);
   }
   const int rc = k8sllm_gemm_dec(a.data_ptr(), wp.data_ptr(), pp, yp, 0, M, N, K, (int)splits, (int)epi, (int)ntw,
-                                 (int)waves, (int)depth, nullptr, 0, K, 0.f, E, a_es, w_es, y_es, rw, rw_ld, cur());
+                                 (int)waves, (int)depth, nullptr, 0, K, 0.f, E, a_es, w_eb, y_es, rw, rw_ld, cur());
   if (rc < 0) return -1;
   check(rc, "gemm_dec_grouped");
+  return epi == 0 ? (int64_t)E * splits : 1;
+}
+
+// gemm_dec_grouped over a quantised expert stack.  fp8: wq float8_e4m3fn [E, N/16, K/64, 64, 16]
+// (ops.pack_skinny_f8 per expert), wscale [E, N] fp32 row scales in packed row order.  mxfp4: wq
+// uint8 [E, N/16, K/128, 64, 16], wscale uint8 [E, N/16, K/128, 16, 4] (ops.pack_skinny_f4 per
+// expert).  a, y, partial and row_w as gemm_dec_grouped; only the forms of kDecF8Forms /
+// kDecF4Forms.  f4_depth: the mxfp4 ring depth (8 / 16 k-steps), 0 = the launcher's choice.
+int64_t gemm_dec_grouped_q(torch::Tensor a, torch::Tensor wq, torch::Tensor wscale,
+                           c10::optional<torch::Tensor> partial, c10::optional<torch::Tensor> y, int64_t splits,
+                           int64_t epi, int64_t ntw, int64_t waves, int64_t depth, int64_t rows,
+                           c10::optional<torch::Tensor> row_w, int64_t f4_depth) {
+  dev_bf16(a, "a");
+  const bool f4 = wq.scalar_type() == torch::kUInt8;
+  TORCH_CHECK(wq.is_cuda() && (f4 || wq.scalar_type() == torch::kFloat8_e4m3fn) && wq.dim() == 5 &&
+                  wq.is_contiguous() && wq.size(3) == 64 && wq.size(4) == 16,
+              "gemm_dec_grouped_q: wq must be float8_e4m3fn [E, N/16, K/64, 64, 16] or uint8 [E, N/16, K/128, 64, 16]");
+  const int E = (int)wq.size(0), N = (int)wq.size(1) * 16, K = (int)wq.size(2) * (f4 ? 128 : 64), M = (int)rows;
+  if (f4) {
+    TORCH_CHECK(wscale.is_cuda() && wscale.scalar_type() == torch::kUInt8 && wscale.is_contiguous() &&
+                    wscale.dim() == 5 && wscale.size(0) == E && wscale.size(1) == wq.size(1) &&
+                    wscale.size(2) == wq.size(2) && wscale.size(3) == 16 && wscale.size(4) == 4,
+                "gemm_dec_grouped_q: mxfp4 wscale must be uint8 [E, N/16, K/128, 16, 4]");
+  } else {
+    TORCH_CHECK(wscale.is_cuda() && wscale.scalar_type() == torch::kFloat32 && wscale.is_contiguous() &&
+                    wscale.dim() == 2 && wscale.size(0) == E && wscale.size(1) == N,
+                "gemm_dec_grouped_q: fp8 wscale must be [E, N] fp32");
+  }
+  const int MT = (M + 15) / 16;
+  TORCH_CHECK(M > 0 && M <= k8sllm::kDecNarrowMaxM && E >= 1, "gemm_dec_grouped_q: 1..", k8sllm::kDecNarrowMaxM,
+              " rows, >= 1 expert");
+  const bool per_e = a.dim() == 5;
+  TORCH_CHECK(a.is_contiguous() && (per_e ? (a.size(0) == E && a.size(1) >= MT && a.size(2) * 32 == K &&
+                                             a.size(3) == 64 && a.size(4) == 8)
+                                          : (a.dim() == 4 && a.size(0) >= MT && a.size(1) * 32 == K &&
+                                             a.size(2) == 64 && a.size(3) == 8)),
+              "gemm_dec_grouped_q: a packed [ceil(M/16), K/32, 64, 8] or [E, ...]");
+  const long a_es = per_e ? a.stride(0) : 0;
+  const long w_eb = wq.stride(0) * wq.element_size(), s_eb = wscale.stride(0) * wscale.element_size();
+  float* pp = nullptr;
+  void* yp = nullptr;
+  long y_es = 0;
+  const float* rw = nullptr;
+  int rw_ld = 0;
+  if (epi == 0) {
+    TORCH_CHECK(splits >= 1, "gemm_dec_grouped_q: splits >= 1");
+    pp = slab_buffer(partial, (int64_t)E * splits * M * N, "gemm_dec_grouped_q");
+    if (row_w.has_value()) {
+      TORCH_CHECK(row_w->is_cuda() && row_w->scalar_type() == torch::kFloat32 && row_w->dim() == 2 &&
+                      row_w->size(0) >= M && row_w->size(1) == E && row_w->stride(1) == 1,
+                  "gemm_dec_grouped_q: row_w [M, E] fp32");
+      rw = row_w->data_ptr<float>();
+      rw_ld = (int)row_w->stride(0);
+    }
+  } else {
+    TORCH_CHECK(epi == 2 && splits == 1, "gemm_dec_grouped_q: only the SwiGLU output, with splits 1");
+    yp = swiglu_packed_out(y, E, M, N, "gemm_dec_grouped_q");
+    y_es = y->stride(0);
+  }
+  const int rc = k8sllm_gemm_dec_grouped_q(a.data_ptr(), wq.data_ptr(), wscale.data_ptr(),
+                                           f4 ? k8sllm::DEC_W_F4 : k8sllm::DEC_W_F8, pp, yp, M, N, K, (int)splits,
+                                           (int)epi, (int)ntw, (int)waves, (int)depth, (int)f4_depth, E, a_es, w_eb,
+                                           s_eb, y_es, rw, rw_ld, cur());
+  if (rc < 0) return -1;
+  check(rc, "gemm_dec_grouped_q");
   return epi == 0 ? (int64_t)E * splits : 1;
 }
 
@@ -1175,6 +1244,7 @@ PYBIND11_MODULE(_k8sllm_ops, m) {
   m.attr("SKINNY_GROUPED_MAX_M") = k8sllm::kSkinnyGroupedMaxM;
   m.def("gemm_dec", &gemm_dec);
   m.def("gemm_dec_grouped", &gemm_dec_grouped);
+  m.def("gemm_dec_grouped_q", &gemm_dec_grouped_q);
   m.def("gemm_dec_forms", &gemm_dec_forms);
   m.def("gemm_dec_f8", &gemm_dec_f8);
   m.def("gemm_dec_f8_forms", &gemm_dec_f8_forms);

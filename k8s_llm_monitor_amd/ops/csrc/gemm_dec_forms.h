@@ -42,7 +42,9 @@ constexpr int kDecNForms = sizeof(kDecForms) / sizeof(kDecForms[0]);
 // codes [N/16][K/64][64][16] plus one fp32 power-of-two scale per packed weight row; dense
 // launches, narrow deferred norm, 1..max_mt m-tiles): the Llama-3-8B picks of ops.DEC_TABLE /
 // DEC_TABLE_M128 and the 70B TP=1 gate_up form.  k8sllm_gemm_dec_f8_forms reports the list and
-// ops.DEC_F8_FORMS mirrors it.
+// ops.DEC_F8_FORMS mirrors it.  The SLAB and SWIGLU8 rows also serve the grouped launches over a
+// quantised expert stack (k8sllm_gemm_dec_grouped_q, <= kDecNarrowMaxM rows: the same
+// instantiations, the expert strides being run-time arguments); so do those of kDecF4Forms.
 constexpr int kDecF8Forms[] = {0, 1, 4, 6, 7, 9};
 constexpr int kDecNF8Forms = sizeof(kDecF8Forms) / sizeof(kDecF8Forms[0]);
 

@@ -36,8 +36,13 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 // a per-expert stride; SLAB partials land in slab e * S + split, scaled by the routing weight
 // rw[row * rw_ld + e] (0 where the row did not pick the expert), so the residual-add kernel's slab
 // sum IS the expert combine.  Dense launches: all strides 0, rw null, grid.z 1.
+// The weight stride is in BYTES: the stack holds bf16 (2 B per element), e4m3 codes (1 B) or
+// packed e2m1 codes (1/2 B), and the scales of a quantised stack ride beside it with a byte
+// stride of their own (fp8: N fp32 row scales per expert; mxfp4: (N/16)(K/128) 16 block-scale
+// dwords).
 struct DecGroup {
-  long a_es, w_es, y_es;  // elements between experts' A / W / SWIGLU8 outputs
+  long a_es, y_es;  // elements between experts' A / SWIGLU8 outputs
+  long w_eb, s_eb;  // bytes between experts' weights / their scales (s_eb: quantised stacks)
   const float* rw;        // [M][rw_ld] routing weights (SLAB epilogue) or null
   int rw_ld;
 };
@@ -89,9 +94,9 @@ __device__ __forceinline__ bf16x8 dec_f4x8(uint32_t q, float scale) {
 // load feeds two k-steps and the ring holds DEPTH / 2 loads per n-tile.  A fragment is converted
 // once per (k-step, n-tile), unscaled, and runs the bf16 MFMA sequence in the bf16 order; the
 // weight row's power-of-two scale wscale[packed row] multiplies the fp32 accumulator in the
-// epilogue (after the deferred-norm row scale, before any bf16 rounding), which commutes with
-// every rounding: bit-identical to the bf16 launch over the dequantised weights.  Dense launches
-// with the narrow deferred norm only.
+// epilogue (after the deferred-norm row scale, before the routing weight of a grouped launch and
+// before any bf16 rounding), which commutes with every rounding: bit-identical to the bf16 launch
+// over the dequantised weights.  The narrow deferred norm only.
 // F4: W holds MXFP4 (e2m1) codes [N/16][K/128][64][16] (pack_skinny_f4: lane l's dword s is its 8
 // codes of k-step 4g + s, in the bf16 layout's fragment order), so one 1-KiB wave load feeds four
 // k-steps and the ring holds DEPTH / 4 loads per n-tile (DEPTH here is the F4 ring depth the
@@ -100,7 +105,7 @@ __device__ __forceinline__ bf16x8 dec_f4x8(uint32_t q, float scale) {
 // row r for k-steps 4g .. 4g + 3 (byte b is the fp32 b << 23); one 64-byte wave load per ring
 // slot, issued with the slot's code load.  A fragment is converted
 // once per (k-step, n-tile) WITH its block scale and runs the bf16 MFMA sequence in the bf16
-// order; the epilogue is the bf16 one.  Dense launches with the narrow deferred norm only.
+// order; the epilogue is the bf16 one.  The narrow deferred norm only.
 template <int MT, int NTW, int WAVES, int EPI, int DEPTH, bool RNW = false, int WF = DEC_W_BF16>
 __global__ __launch_bounds__(64 * WAVES, 1) void gemm_dec_kernel(
     const bf16_t* __restrict__ A, const bf16_t* __restrict__ W, float* __restrict__ partial,
@@ -112,7 +117,8 @@ __global__ __launch_bounds__(64 * WAVES, 1) void gemm_dec_kernel(
   using G = DecGeom<MT, WAVES>;
   const int ex = blockIdx.z;  // expert of a grouped launch (0 otherwise)
   A += ex * grp.a_es;
-  W += ex * grp.w_es;
+  W = reinterpret_cast<const bf16_t*>(reinterpret_cast<const char*>(W) + ex * grp.w_eb);
+  if constexpr (F8 || F4) wscale = reinterpret_cast<const float*>(reinterpret_cast<const char*>(wscale) + ex * grp.s_eb);
   if constexpr (EPI == DEC_SWIGLU8) Y += ex * grp.y_es;
   constexpr int ITER = DEPTH > kDecCH ? DEPTH : kDecCH;  // k-steps per unrolled main-loop iteration
   __shared__ __attribute__((aligned(16))) char sA[2 * G::SLOT];
@@ -583,11 +589,12 @@ bool dec_dispatch(int epi, int ntw, int waves, int depth, bool rnw, int mt, cons
 // weight k-steps in flight per wave.
 // (epi, ntw, waves, depth) must be a row of kDecForms (gemm_dec_forms.h) with ceil(M / 16) <= its
 // max_mt; grouped launches (experts > 1 or rw) and the wide deferred-norm form take M <= kDecNarrowMaxM.
+// a_es / y_es: elements between experts' A / SWIGLU8 outputs; w_eb: BYTES between their weights.
 // Returns 0, or a negative code when the shape / configuration is not supported (the caller then
 // uses gemm_skinny).
 extern "C" int k8sllm_gemm_dec(const void* A, const void* Wp, float* partial, void* Y, long ldy, int M, int N, int K,
                                int splits, int epi, int ntw, int waves, int depth, const float* rn_ss, int rn_nc,
-                               int rn_d, float rn_eps, int experts, long a_es, long w_es,
+                               int rn_d, float rn_eps, int experts, long a_es, long w_eb,
                                long y_es, const float* rw, int rw_ld, hipStream_t s) {
   if (M <= 0) return 0;
   if (experts < 1 || (rw != nullptr && epi != DEC_SLAB)) return -1;
@@ -605,7 +612,7 @@ extern "C" int k8sllm_gemm_dec(const void* A, const void* Wp, float* partial, vo
   if (rnw && (rn_nc % 16 || rn_nc > 16 * kRnWide)) return -1;
   const DecLaunch l{dim3((ntiles + nwg_tiles - 1) / nwg_tiles, splits, experts), dim3(64 * waves), s,
                     (const bf16_t*)A, (const bf16_t*)Wp, partial, (bf16_t*)Y, ldy, M, N, K, kchunk, rn_ss, rn_nc,
-                    inv_d, rn_eps, DecGroup{a_es, w_es, y_es, rw, rw_ld}, nullptr};
+                    inv_d, rn_eps, DecGroup{a_es, y_es, w_eb, 0, rw, rw_ld}, nullptr};
   if (!dec_dispatch(epi, ntw, waves, depth, rnw, MT, l)) return -5;
   return (int)hipGetLastError();
 }
@@ -631,7 +638,7 @@ extern "C" int k8sllm_gemm_dec_f8(const void* A, const void* Wq, const float* ws
   if (rn_ss != nullptr && rn_nc > 4 * kRnMax) return -1;  // the wide deferred-norm form reads bf16 weights
   const DecLaunch l{dim3((ntiles + nwg_tiles - 1) / nwg_tiles, splits, 1), dim3(64 * waves), s,
                     (const bf16_t*)A, (const bf16_t*)Wq, partial, (bf16_t*)Y, ldy, M, N, K, kchunk, rn_ss, rn_nc,
-                    inv_d, rn_eps, DecGroup{0, 0, 0, nullptr, 0}, wscale};
+                    inv_d, rn_eps, DecGroup{0, 0, 0, 0, nullptr, 0}, wscale};
   if (!dec_dispatch<DEC_W_F8>(epi, ntw, waves, depth, false, MT, l)) return -5;
   return (int)hipGetLastError();
 }
@@ -677,8 +684,56 @@ extern "C" int k8sllm_gemm_dec_f4(const void* A, const void* Wq, const void* wsc
   if (rn_ss != nullptr && rn_nc > 4 * kRnMax) return -1;  // the wide deferred-norm form reads bf16 weights
   const DecLaunch l{dim3((ntiles + nwg_tiles - 1) / nwg_tiles, splits, 1), dim3(64 * waves), s,
                     (const bf16_t*)A, (const bf16_t*)Wq, partial, (bf16_t*)Y, ldy, M, N, K, kchunk, rn_ss, rn_nc,
-                    inv_d, rn_eps, DecGroup{0, 0, 0, nullptr, 0}, (const float*)wscale, d4};
+                    inv_d, rn_eps, DecGroup{0, 0, 0, 0, nullptr, 0}, (const float*)wscale, d4};
   if (!dec_dispatch<DEC_W_F4>(epi, ntw, waves, depth, false, MT, l)) return -5;
+  return (int)hipGetLastError();
+}
+
+// Grouped launch (grid.z = expert) over a quantised expert stack: wf DEC_W_F8 - Wq e4m3 codes
+// [E][N/16][K/64][64][16], wscale [E][N] fp32 row scales in packed row order - or DEC_W_F4 - Wq e2m1
+// codes [E][N/16][K/128][64][16], wscale the e8m0 block scales [E][N/16][K/128][16] dwords.  w_eb /
+// s_eb: bytes between experts' codes / scales; a_es / y_es: elements between their A / SWIGLU8
+// outputs (a_es 0: A shared).  SLAB (slabs [E * splits][M][N], scaled by rw [M][rw_ld] where given)
+// and SWIGLU8 epilogues, M <= kDecNarrowMaxM, no deferred norm; the forms of kDecF8Forms /
+// kDecF4Forms, and for mxfp4 the ring-depth rule of k8sllm_gemm_dec_f4 (f4_depth as there).  The
+// same negative codes as k8sllm_gemm_dec.
+extern "C" int k8sllm_gemm_dec_grouped_q(const void* A, const void* Wq, const void* wscale, int wf, float* partial,
+                                         void* Y, int M, int N, int K, int splits, int epi, int ntw, int waves,
+                                         int depth, int f4_depth, int experts, long a_es, long w_eb, long s_eb,
+                                         long y_es, const float* rw, int rw_ld, hipStream_t s) {
+  if (M <= 0) return 0;
+  if ((wf != DEC_W_F8 && wf != DEC_W_F4) || wscale == nullptr) return -1;
+  if (experts < 1 || M > kDecNarrowMaxM || (epi != DEC_SLAB && epi != DEC_SWIGLU8)) return -1;
+  if (rw != nullptr && epi != DEC_SLAB) return -1;
+  if (N % 16 || K % (wf == DEC_W_F4 ? 128 : 64) || splits < 1 || K % splits) return -1;
+  const int ntiles = N / 16, nwg_tiles = ntw * waves;
+  if (nwg_tiles < 1) return -5;
+  const int kchunk = K / splits;
+  const int MT = (M + 15) / 16;
+  int d4 = 0;
+  if (wf == DEC_W_F4) {
+    int dmax = 0;
+    for (int i = 0; i < kDecNForms; ++i) {
+      const DecForm& f = kDecForms[i];
+      if (f.epi == epi && f.ntw == ntw && f.waves == waves && f.depth == depth) dmax = dec_form_f4_depth(i);
+    }
+    if (dmax == 0) return -5;
+    if (kchunk % 128 || kchunk < 32 * kDecCH || (kchunk / 32) % kDecCH) return -3;
+    if (MT > 1) dmax = 8;
+    d4 = f4_depth;
+    if (d4 == 0) d4 = dmax >= 16 && (kchunk / 32) % 16 == 0 ? 16 : 8;
+    if ((d4 != 8 && d4 != 16) || d4 > dmax || (kchunk / 32) % d4) return -3;
+  } else {
+    const int iter = depth > kDecCH ? depth : kDecCH;
+    if (kchunk % 32 || kchunk < 32 * iter || (kchunk / 32) % iter) return -3;
+  }
+  if (epi != DEC_SLAB && splits != 1) return -4;
+  const DecLaunch l{dim3((ntiles + nwg_tiles - 1) / nwg_tiles, splits, experts), dim3(64 * waves), s,
+                    (const bf16_t*)A, (const bf16_t*)Wq, partial, (bf16_t*)Y, 0, M, N, K, kchunk, nullptr, 0,
+                    0.f, 0.f, DecGroup{a_es, y_es, w_eb, s_eb, rw, rw_ld}, (const float*)wscale, d4};
+  const bool ok = wf == DEC_W_F4 ? dec_dispatch<DEC_W_F4>(epi, ntw, waves, depth, false, MT, l)
+                                 : dec_dispatch<DEC_W_F8>(epi, ntw, waves, depth, false, MT, l);
+  if (!ok) return -5;
   return (int)hipGetLastError();
 }
 

@@ -17,6 +17,10 @@ both in one session (each checked against the bf16 launch over its own dequantis
 the timed bf16 cases stream the last encoding's).  ``--f4-depths 8,16`` times the mxfp4 cases
 once per forced F4 ring depth (ops.DEC_F4_DEPTH_FORCE; 0 = the launcher's choice) where the
 launcher takes it.  ``--shape 70b_gate_up`` etc.: SHAPES.
+``--experts E``: the grouped (grid.z = expert) launches of a Mixtral-8x7B MoE layer over E local
+experts instead - gate_up and down (``--ops``), bf16 stacks on ops.dec_config's pick against the
+``--wdtype`` code stacks on ops.dec_grouped_q_config's (and the bf16 stacks on that pick where it
+differs), each quantised launch checked for bit equality with the bf16 launch of its configuration.
 
     python tools/bench_decode_gemm.py [--ms 1,32,64] [--ops qkv,o,gate_up,down,lm_head] [--rounds 3] [--wdtype fp8]
 """
@@ -48,6 +52,80 @@ CFGS = {  # the sweep list: forms of ops.DEC_FORMS (another form: add its row to
 }
 
 
+def grouped(a, encs: list) -> None:
+    """--experts: one MoE layer's grouped launches, bf16 against the quantised stacks."""
+    dev, E = "cuda", a.experts
+    for name in [n for n in a.ops.split(",") if n in ("gate_up", "down")]:
+        N, K, epi = SHAPES[name]
+        ncopy = max(2, (512 << 20) // (E * N * K * 2) + 1)
+        enc_kw = {"fp8": dict(f8=True), "mxfp4": dict(f4=True)}
+        picks = {"bf16": ops.dec_config(N, K, epi, experts=E)}
+        picks.update({enc: ops.dec_grouped_q_config(N, K, epi, E, **enc_kw[enc]) for enc in encs})
+        print(json.dumps({"op": name, "experts": E, "picks": picks}), flush=True)
+        # encoding -> (code stacks per copy, scale stacks per copy, packed bf16 stack of copy 0's dequantised values);
+        # the timed bf16 stacks hold the last encoding's dequantised values (one model, two encodings)
+        stacks: dict = {enc: ([], [], None) for enc in encs}
+        wdec = []
+        for i in range(ncopy):
+            ws = [torch.randn(N, K, device=dev, dtype=torch.bfloat16) * 0.02 for _ in range(E)]
+            for enc in encs:
+                if enc == "fp8":
+                    qs = [ops.quantize_rows_fp8(w) for w in ws]
+                    dq = [ops.dequantize_rows_fp8(q, sc) for q, sc in qs]
+                    pk = [(ops.pack_skinny_f8(q), sc) for q, sc in qs]
+                else:
+                    qs = [ops.quantize_mxfp4(w) for w in ws]
+                    dq = [ops.dequantize_mxfp4(q, sc) for q, sc in qs]
+                    pk = [ops.pack_skinny_f4(q, sc) for q, sc in qs]
+                stacks[enc][0].append(torch.stack([q for q, _ in pk]))
+                stacks[enc][1].append(torch.stack([sc for _, sc in pk]))
+                if i == 0:
+                    stacks[enc] = stacks[enc][:2] + (torch.stack([ops.pack_skinny(w) for w in dq]),)
+                if enc == encs[-1]:
+                    ws = dq
+                del qs, dq, pk
+            wdec.append(torch.stack([ops.pack_skinny(w) for w in ws]))
+            del ws
+        gb = E * N * K * 2 / 1e9
+        for M in map(int, a.ms.split(",")):
+            MT = -(-M // 16)
+            if epi == 2:
+                xa = ops.pack_activation(torch.randn(M, K, device=dev, dtype=torch.bfloat16))
+                out = dict(out=torch.empty((E, MT, N // 64, 64, 8), device=dev, dtype=torch.bfloat16))
+            else:
+                xa = torch.stack([ops.pack_activation(torch.randn(M, K, device=dev, dtype=torch.bfloat16)) for _ in range(E)])
+                rw = torch.rand(M, E, device=dev)
+                out = dict(workspace=torch.empty(E * M * N, device=dev, dtype=torch.float32), row_w=rw)
+            res_t = out["out"] if epi == 2 else out["workspace"]
+            cases = {}
+            for cfg in dict.fromkeys(c for c in picks.values() if c is not None):
+                cases["bf16_" + "_".join(map(str, cfg))] = (
+                    lambda i, cfg=cfg: ops.dec_gemm_grouped(xa, wdec[i % ncopy], epi, M, cfg=cfg, **out))
+            for enc in encs:
+                cfg = picks[enc]
+                if cfg is None:
+                    continue
+                ops.dec_gemm_grouped(xa, stacks[enc][2], epi, M, cfg=cfg, **out)
+                want = res_t.clone()
+                ops.dec_gemm_grouped_q(xa, stacks[enc][0][0], stacks[enc][1][0], epi, M, cfg=cfg, **out)
+                print(json.dumps({"op": name, "experts": E, "M": M, "cfg": cfg,
+                                  enc + "_bit_equal_to_bf16": torch.equal(want, res_t)}), flush=True)
+                cases[enc + "_" + "_".join(map(str, cfg))] = (
+                    lambda i, cfg=cfg, enc=enc: ops.dec_gemm_grouped_q(xa, stacks[enc][0][i % ncopy],
+                                                                       stacks[enc][1][i % ncopy], epi, M, cfg=cfg, **out))
+            res: dict = {}
+            for _ in range(a.rounds):
+                for tag, fn in cases.items():
+                    res.setdefault(tag, []).append(timeit(fn, a.iters))
+            for tag, ts in res.items():
+                t = min(ts)
+                b = gb / 2 if tag.startswith("fp8_") else gb * 17 / 64 if tag.startswith("mxfp4_") else gb
+                print(json.dumps({"op": name, "experts": E, "M": M, "impl": tag, "us": round(t, 2),
+                                  "us_all": [round(v, 2) for v in ts], "TBps": round(b / t * 1e3, 2)}), flush=True)
+        del wdec, stacks
+        torch.cuda.empty_cache()
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=320)
@@ -58,6 +136,7 @@ def main() -> None:
     ap.add_argument("--wdtype", default="bf16", help="bf16, fp8, mxfp4 or fp8,mxfp4")
     ap.add_argument("--f4-depths", default="0", help="F4 ring depths to time the mxfp4 cases at (0 = automatic)")
     ap.add_argument("--no-base", action="store_true", help="leave out the row-major skinny / hipBLASLt case")
+    ap.add_argument("--experts", type=int, default=0, help="E > 0: the grouped launches of a Mixtral MoE layer")
     a = ap.parse_args()
     encs = [e for e in a.wdtype.split(",") if e != "bf16"]
     if any(e not in ("fp8", "mxfp4") for e in encs):
@@ -65,6 +144,8 @@ def main() -> None:
     f4_depths = [int(d) for d in a.f4_depths.split(",")]
     dev = "cuda"
     torch.manual_seed(0)
+    if a.experts:
+        return grouped(a, encs)
     cfgs = dict(CFGS)
     if a.cfgs:
         for item in a.cfgs.split(";"):

@@ -20,6 +20,9 @@ default) against the same engine routed to its bf16 copies with the bf16 default
 ``rc`` the row-complete o projection (bf16 o, bf16 wide-norm gate_up) inside fp8 mode.
 ``--decode-weights mxfp4``: the same with the MXFP4 encoding (``f8`` then switches its forms,
 ops.DEC_F4_FORMS, off and on); every line also carries the engine's ``resident_weight_bytes``.
+``--model mixtral-8x7b --decode-weights fp8|mxfp4 --switch f8``: the MoE step with the grouped expert
+launches over the code stacks (on) against the same engine on its bf16 stacks (off); ``--layers``
+where the box is short of memory or time (a step's time is linear in the layer count).
 """
 from __future__ import annotations
 
@@ -96,7 +99,8 @@ def main() -> None:
     sp = SamplingParams(max_tokens=a.tokens, temperature=0.0, ignore_eos=True)
     set_sw = SWITCHES[a.switch]
     for rows in rows_list:
-        prompts = [torch.randint(100, 120000, (a.ctx + (i * 37) % 200,), generator=g).tolist() for i in range(rows)]
+        hi = min(120000, eng.model.cfg.vocab_size)  # Mixtral's vocabulary is 32000
+        prompts = [torch.randint(100, hi, (a.ctx + (i * 37) % 200,), generator=g).tolist() for i in range(rows)]
         res: dict = {True: [], False: []}
         for rnd in range(a.rounds):
             for on in (True, False):

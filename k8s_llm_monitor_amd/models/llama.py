@@ -1149,8 +1149,7 @@ class CausalLM:
         one without raises in ops.dec_gemm)."""
         if wq is not None and (wd is None or not (rownorm is not None and rownorm[0].shape[1] > 16)):
             N, K = ops.skinny_wdims(wq)
-            enc = dict(f4=True) if ops.is_mxfp4(wq) else dict(f8=True)  # the codes say which encoding they are
-            if wd is None or ops.dec_config(N, K, epi, rows=rows, **enc) is not None:
+            if wd is None or ops.dec_config(N, K, epi, rows=rows, **ops.enc_kw(wq)) is not None:
                 return ops.dec_gemm(x, wq, epi, rows, rownorm=rownorm, wscale=wqs, **kw)
         return ops.dec_gemm(x, wd, epi, rows, rownorm=rownorm, **kw)
 
@@ -1173,7 +1172,7 @@ class CausalLM:
 
     def _enc_kw(self) -> dict:
         """dec_config's keyword for this model's quantised decode encoding."""
-        return dict(f4=True) if self.DEC_WEIGHTS == "mxfp4" else dict(f8=True)
+        return ops.enc_kw(self.DEC_WEIGHTS)
 
     def _want_dec(self) -> set:
         """Which projections gemm_decode.hip gets in its fragment-packed form (``DECODE_GEMM`` =
@@ -1252,8 +1251,8 @@ class CausalLM:
         if self.lm_head is not self.embed:
             h = src.canonical_head().to(self.lm_head.device)
             if ops.is_fp8(self.lm_head):  # fp8-only head: straight to codes and scales
-                q, qs = ops.quantize_rows_fp8(h.to(self.dtype))
-                self.lm_head.copy_(ops.pack_skinny_f8(q))
+                _, q, qs = ops.encode_weight(h.to(self.dtype), "fp8")
+                self.lm_head.copy_(q)
                 self.lm_head_qs.copy_(qs)
             else:
                 self.lm_head.copy_(ops.pack_skinny(h) if self.lm_head.dim() == 4 else h)
@@ -1322,7 +1321,6 @@ class CausalLM:
             self._remat(self.layers[0], self._layout)  # layer 0's shapes decide below
         parts, one = self._want_dec(), self._one_layout_wanted()
         f8 = self.DEC_WEIGHTS in ("fp8", "mxfp4") and not self._f8_defer
-        f4 = f8 and self.DEC_WEIGHTS == "mxfp4"
         bf16_experts = None  # why the expert stacks stay on bf16, where they do
         f8_only = f8 and self.PREFILL_WEIGHTS == "fp8"
         why = None  # why nothing can be fp8-only, if so
@@ -1360,16 +1358,10 @@ class CausalLM:
                         stayed[key] = r
         N, K = self.lm_head.shape
         if "head" in parts and N % 16 == 0 and K % 32 == 0 and ops.dec_available(N, K, 1):
-            if f4 and self._f8_shape_ok(N, K, 1):
-                q, qs = ops.quantize_mxfp4(self.lm_head)
-                self.lm_head.copy_(ops.dequantize_mxfp4(q, qs, self.dtype))  # tied: the embedding too
-                self.lm_head_q, self.lm_head_qs = ops.pack_skinny_f4(q, qs)
-                del q, qs
-            elif f8 and self._f8_shape_ok(N, K, 1):
-                q, self.lm_head_qs = ops.quantize_rows_fp8(self.lm_head)
-                self.lm_head.copy_(ops.dequantize_rows_fp8(q, self.lm_head_qs, self.dtype))  # tied: the embedding too
-                self.lm_head_q = ops.pack_skinny_f8(q)
-                del q
+            if f8 and self._f8_shape_ok(N, K, 1):
+                deq, self.lm_head_q, self.lm_head_qs = ops.encode_weight(self.lm_head, self.DEC_WEIGHTS)
+                self.lm_head.copy_(deq)  # tied: the embedding too
+                del deq
             r = (why or self._f8_only_why(self.lm_head_q, 1, ceil)) if f8_only else "off"
             if r is None:
                 # the codes are the head's only copy: an untied bf16 head goes; a tied one stays as
@@ -1426,11 +1418,7 @@ class CausalLM:
 
     def _codes(self, w: torch.Tensor, key: str) -> tuple:
         """(packed codes, scales in packed row order) of the CANONICAL weight ``w`` of ``key``."""
-        q, s = ops.quantize_rows_fp8(w)
-        if key == "w13":
-            q = ops.interleave_gate_up8(q.view(torch.uint8)).view(torch.float8_e4m3fn)
-            s = ops.interleave_gate_up8(s[:, None])[:, 0]
-        return ops.pack_skinny_f8(q), s.contiguous()
+        return ops.encode_weight(w, "fp8", key == "w13")[1:]
 
     def _remat(self, L: dict, form: str) -> None:
         """Every fp8-only projection of the layer back to a bf16 tensor in the row-major layout
@@ -1458,27 +1446,14 @@ class CausalLM:
         N, K = w.shape
         if not self._f8_shape_ok(N, K, 2 if key == "w13" else 0):
             return
-        if self.DEC_WEIGHTS == "mxfp4":
-            # block scales run along K, so the row order is free: quantise the canonical rows,
-            # permute codes and scales together into the packed copy's row order
-            q, s = ops.quantize_mxfp4(to_canonical(w, key, self._layout))
-            w.copy_(to_resident(ops.dequantize_mxfp4(q, s, self.dtype), key, self._layout))
-            p = L.get(key + "_p")
-            if p is not None and p is not w:
-                L[key + "_p"] = ops.pack_skinny(w)
-            if key == "w13":
-                q, s = ops.interleave_gate_up8(q), ops.interleave_gate_up8(s)
-            L[key + "_q"], L[key + "_qs"] = ops.pack_skinny_f4(q, s)
-            return
-        q, s = ops.quantize_rows_fp8(to_canonical(w, key, self._layout))
-        w.copy_(to_resident(ops.dequantize_rows_fp8(q, s, self.dtype), key, self._layout))
+        # (block scales run along K and row scales with their rows, so the row order is free: the
+        # canonical rows are quantised, codes and scales permuted into the packed copy's row order)
+        deq, L[key + "_q"], L[key + "_qs"] = ops.encode_weight(to_canonical(w, key, self._layout), self.DEC_WEIGHTS,
+                                                               key == "w13")
+        w.copy_(to_resident(deq, key, self._layout))
         p = L.get(key + "_p")
         if p is not None and p is not w:
             L[key + "_p"] = ops.pack_skinny(w)
-        if key == "w13":
-            q = ops.interleave_gate_up8(q.view(torch.uint8)).view(torch.float8_e4m3fn)
-            s = ops.interleave_gate_up8(s[:, None])[:, 0]
-        L[key + "_q"], L[key + "_qs"] = ops.pack_skinny_f8(q), s.contiguous()
 
     def _experts_q_why(self, E: int, F2: int, d: int) -> Optional[str]:
         """None when the grouped decode GEMM has a form over this model's quantised encoding for
@@ -1501,24 +1476,11 @@ class CausalLM:
         themselves ask for - the same values on either, but only the second is what a checkpoint
         load, a weight copy or a second ``_init_skinny`` will find, so those reproduce the codes."""
         w = L[key]
-        f4 = self.DEC_WEIGHTS == "mxfp4"
         Q = S = None  # the [E, ...] stacks, allocated from expert 0's shapes
         pg = L.get(key + "_pg")
         for e in range(w.shape[0]):
             c = to_canonical(w[e], key, self._layout)
-            if f4:
-                deq = ops.dequantize_mxfp4(*ops.quantize_mxfp4(c), self.dtype)
-                q, s = ops.quantize_mxfp4(deq)  # of the dequantised values: see the docstring
-                if key == "w13":
-                    q, s = ops.interleave_gate_up8(q), ops.interleave_gate_up8(s)
-                q, s = ops.pack_skinny_f4(q, s)
-            else:
-                deq = ops.dequantize_rows_fp8(*ops.quantize_rows_fp8(c), self.dtype)
-                q, s = ops.quantize_rows_fp8(deq)
-                if key == "w13":
-                    q = ops.interleave_gate_up8(q.view(torch.uint8)).view(torch.float8_e4m3fn)
-                    s = ops.interleave_gate_up8(s[:, None])[:, 0]
-                q, s = ops.pack_skinny_f8(q), s.contiguous()
+            deq, q, s = ops.encode_weight(c, self.DEC_WEIGHTS, key == "w13", settle=True)  # see the docstring
             w[e].copy_(to_resident(deq, key, self._layout))
             if pg is not None and pg is not w:
                 pg[e].copy_(ops.pack_skinny(w[e]))
@@ -1538,8 +1500,7 @@ class CausalLM:
         wq = L.get(key + "_q")
         if wq is not None:
             E, N, K = ops.grouped_q_wdims(wq)
-            enc = dict(f4=True) if ops.is_mxfp4(wq) else dict(f8=True)  # the codes say which encoding they are
-            if ops.dec_grouped_q_config(N, K, epi, E, **enc) is not None:
+            if ops.dec_grouped_q_config(N, K, epi, E, **ops.enc_kw(wq)) is not None:
                 return ops.dec_gemm_grouped_q(a, wq, L[key + "_qs"], epi, rows, **kw)
         return ops.dec_gemm_grouped(a, L[key + "_dg"], epi, rows, **kw)
 

@@ -325,6 +325,32 @@ def is_mxfp4(w: Optional[torch.Tensor]) -> bool:
     return w is not None and w.dtype == torch.uint8 and w.dim() in (4, 5)
 
 
+def encode_weight(w: torch.Tensor, enc: str, gate_up8: bool = False, settle: bool = False) -> tuple:
+    """THE encoding of a decode projection: the canonical row-major weight ``w`` [N, K] ->
+    (the dequantised values [N, K] in ``w``'s dtype and row order, the packed codes, the packed
+    scales) in the encoding ``enc`` ("fp8": quantize_rows_fp8 / pack_skinny_f8, scales [N] fp32;
+    "mxfp4": quantize_mxfp4 / pack_skinny_f4).  ``gate_up8``: codes and scales in the
+    [8 gate | 8 up] row order of the packed gate_up copy (interleave_gate_up8 - a row permutation,
+    which per-row scales and per-row block scales follow).  ``settle``: the codes returned are those
+    of the dequantised values, which is what encoding those values again reproduces: where a row's
+    (block's) largest element rounded down to half the code range, the first pass's scale is one
+    step coarser than the one the values themselves ask for - the same values on either."""
+    if enc not in ("fp8", "mxfp4"):
+        raise ValueError(f"encode_weight: encoding {enc!r}")
+    f4 = enc == "mxfp4"
+    quant, dequant = (quantize_mxfp4, dequantize_mxfp4) if f4 else (quantize_rows_fp8, dequantize_rows_fp8)
+    q, s = quant(w)
+    deq = dequant(q, s, w.dtype)
+    if settle:
+        q, s = quant(deq)
+    if gate_up8 and f4:
+        q, s = interleave_gate_up8(q), interleave_gate_up8(s)
+    elif gate_up8:  # the row permutation moves bytes: through the uint8 view, the scales as a column
+        q = interleave_gate_up8(q.view(torch.uint8)).view(torch.float8_e4m3fn)
+        s = interleave_gate_up8(s[:, None])[:, 0]
+    return (deq,) + (pack_skinny_f4(q, s) if f4 else (pack_skinny_f8(q), s.contiguous()))
+
+
 def pack_skinny(w: torch.Tensor) -> torch.Tensor:
     """Row-major weight [N, K] -> the fragment-packed [N/16, K/32, 64, 8] layout of gemm_skinny:
     block (n-tile j, k-step s) holds, for lane l = 16 q + r, elements W[16 j + r, 32 s + 8 q : +8]
@@ -703,114 +729,6 @@ def dec_available(N: int, K: int, epi: int, rows: int = 0) -> bool:
     return dec_config(N, K, epi, rows=rows) is not None
 
 
-def dec_gemm(a: torch.Tensor, wp: torch.Tensor, epi: int, rows: int, workspace: Optional[torch.Tensor] = None,
-             out: Optional[torch.Tensor] = None, rownorm: Optional[tuple] = None,
-             cfg: Optional[tuple] = None, wscale: Optional[torch.Tensor] = None) -> int:
-    """gemm_dec over a fragment-packed activation ``a`` and packed weight ``wp`` (pack_skinny: under
-    ONE_LAYOUT the model's only copy, which prefill's tile GEMM reads too; else a copy for decode).
-    epi 0: fp32 split-K slabs into ``workspace`` [S, M, N], returns S; epi 1: ``out`` [M, N] bf16;
-    epi 2: ``out`` packed SwiGLU [ceil(M/16), F/32, 64, 8] over an interleave_gate_up8 weight.
-    ``rownorm = (ss_part, eps)``: deferred RMSNorm of the A rows (add_norm_partial).  Up to
-    DEC_MAX_M = 128 rows; the configuration is dec_config's for that row count (65..128 rows run
-    the 5..8 m-tile instantiations).  ``wp`` may be the fp8 encoding (pack_skinny_f8 codes) with
-    ``wscale`` its per-row scales in packed row order: the same launch over half the weight
-    bytes, bit-identical to the bf16 launch of the same configuration over the dequantised
-    weights; a form without an fp8 instantiation raises.  Or the mxfp4 encoding (pack_skinny_f4's
-    codes, ``wscale`` its packed block scales), under the same contract.
-    CPU: the fp32 reference with the same
-    split-K slicing (over the dequantised values)."""
-    N, K = skinny_wdims(wp)
-    M = rows
-    f8, f4 = is_fp8(wp), is_mxfp4(wp)
-    if f8 and (wscale is None or wscale.numel() != N):
-        raise ValueError(f"gemm_dec: an fp8 weight needs its [{N}] scale vector")
-    if f4 and (wscale is None or wscale.dtype != torch.uint8 or tuple(wscale.shape) != (N // 16, K // 128, 16, 4)):
-        raise ValueError(f"gemm_dec: an mxfp4 weight needs its packed block scales [{N // 16}, {K // 128}, 16, 4] uint8")
-    if M > DEC_MAX_M:
-        raise ValueError(f"gemm_dec: at most {DEC_MAX_M} rows, got {M}")
-    if cfg is None:
-        cfg = dec_config(N, K, epi, rows=M, f8=f8, f4=f4)
-    if cfg is None:
-        raise ValueError(f"gemm_dec: no configuration for N={N} K={K} epi={epi} rows={M}")
-    S, ntw, waves, depth = cfg
-    if not _gpu(a):
-        x = _cpu_a(a, rows).float()
-        w = _cpu_w(wp, wscale)
-        sc = _rn_scale(rownorm, M, K)
-        if epi == 0:
-            kc = K // S
-            slabs = workspace[: S * M * N].view(S, M, N)
-            for s in range(S):
-                y = x[:, s * kc:(s + 1) * kc] @ w[:, s * kc:(s + 1) * kc].t()
-                slabs[s] = y * sc if sc is not None else y
-            return S
-        y = x @ w.t()
-        if sc is not None:
-            y = y * sc
-        if epi == 1:
-            out[:M].copy_(y.to(out.dtype))
-            return 1
-        gu = deinterleave_gate_up8(y.to(a.dtype).float().t()).t()
-        g, u = gu[:, : N // 2], gu[:, N // 2:]
-        out.copy_(pack_activation((torch.nn.functional.silu(g) * u).to(a.dtype)))
-        return 1
-    rn = (None, 0.0) if rownorm is None else (rownorm[0], float(rownorm[1]))
-    # more than 16 partial sums per row: gemm_dec_rc's per-16-column sums, the wide-norm form
-    wn = rownorm is not None and rownorm[0].shape[1] > 16
-    if not dec_form_ok(epi, cfg, M, wide_norm=wn, f8=f8, f4=f4, K=K):
-        raise RuntimeError(f"gemm_dec: form (epi, ntw, waves, depth) = {(epi,) + tuple(cfg[1:])} not compiled for "
-                           f"{M} rows" + (" with the wide deferred norm" if wn else "") +
-                           (" over fp8 weights" if f8 else f" over mxfp4 weights in {S} K slices" if f4 else ""))
-    if f4:
-        r = native().gemm_dec_f4(a, wp, wscale, workspace, out, S, epi, ntw, waves, depth, M, *rn, DEC_F4_DEPTH_FORCE)
-    elif f8:
-        r = native().gemm_dec_f8(a, wp, wscale, workspace, out, S, epi, ntw, waves, depth, M, *rn)
-    else:
-        r = native().gemm_dec(a, wp, workspace, out, S, epi, ntw, waves, depth, M, *rn)
-    if r < 0:
-        raise RuntimeError(f"gemm_dec: configuration {cfg} not compiled for N={N} K={K} epi={epi}")
-    return r
-
-
-def dec_gemm_grouped(a: torch.Tensor, wp: torch.Tensor, epi: int, rows: int, workspace: Optional[torch.Tensor] = None,
-                     out: Optional[torch.Tensor] = None, row_w: Optional[torch.Tensor] = None,
-                     cfg: Optional[tuple] = None) -> int:
-    """gemm_dec over every local expert of a MoE layer in ONE launch (grid.z = expert): ``wp``
-    [E, N/16, K/32, 64, 8] (packed per expert, gate/up interleave_gate_up8 for epi 2); ``a`` packed
-    [ceil(M/16), K/32, 64, 8] shared by the experts (gate_up) or [E, ...] per expert (down).
-    epi 2: ``out`` [E, ceil(M/16), F/32, 64, 8] packed SwiGLU; epi 0: fp32 slabs [E * S, M, N] in
-    ``workspace`` scaled by ``row_w`` [M, E] (routing weights, 0 where a row skipped the expert),
-    returns E * S - the residual-add kernel's slab sum is the expert combine."""
-    if wp.dtype == torch.uint8:
-        raise ValueError("gemm_dec_grouped: grouped launches have no mxfp4 form (expert stacks stay bf16)")
-    E = wp.shape[0]
-    N, K = wp.shape[1] * 16, wp.shape[2] * 32
-    M = rows
-    if cfg is None:
-        cfg = dec_config(N, K, epi, experts=E)
-    if cfg is None:
-        raise ValueError(f"gemm_dec_grouped: no configuration for N={N} K={K} epi={epi}")
-    S, ntw, waves, depth = cfg
-    if not _gpu(a):
-        for e in range(E):
-            ae = a[e] if a.dim() == 5 else a
-            if epi == 2:
-                dec_gemm(ae, wp[e], 2, M, out=out[e], cfg=cfg)
-            else:
-                ws = workspace[e * S * M * N: (e + 1) * S * M * N]
-                dec_gemm(ae, wp[e], 0, M, workspace=ws, cfg=cfg)
-                if row_w is not None:
-                    ws.view(S, M, N).mul_(row_w[:M, e].float().view(1, M, 1))
-        return E * S if epi == 0 else 1
-    if not dec_form_ok(epi, cfg, M, grouped=True):
-        raise RuntimeError(f"gemm_dec_grouped: form (epi, ntw, waves, depth) = {(epi,) + tuple(cfg[1:])} not "
-                           f"compiled for {M} rows of a grouped launch")
-    r = native().gemm_dec_grouped(a, wp, workspace, out, S, epi, ntw, waves, depth, M, row_w)
-    if r < 0:
-        raise RuntimeError(f"gemm_dec_grouped: configuration {cfg} not compiled for N={N} K={K} epi={epi}")
-    return r
-
-
 # Quantised grouped launches: (N, K, epi, experts, "fp8" | "mxfp4") -> a pick that differs from the
 # rule's, or None to route the projection of that many local experts to the bf16 stacks
 # (dec_grouped_q_config answers None: not faster than bf16).  Measurements: profiles/r14/README.md.
@@ -851,6 +769,118 @@ def grouped_q_wdims(wq: torch.Tensor) -> tuple:
     return wq.shape[0], wq.shape[1] * 16, wq.shape[2] * (128 if is_mxfp4(wq) else 64)
 
 
+def enc_kw(x) -> dict:
+    """dec_config's / dec_form_ok's keyword for a quantised encoding: ``x`` its name ("fp8" |
+    "mxfp4") or a codes tensor, which says which encoding it is."""
+    if x == "mxfp4" or (isinstance(x, torch.Tensor) and is_mxfp4(x)):
+        return {"f4": True}
+    if x == "fp8" or (isinstance(x, torch.Tensor) and is_fp8(x)):
+        return {"f8": True}
+    raise ValueError(f"not a quantised decode encoding: {x if isinstance(x, str) else x.dtype}")
+
+
+def _dec_gemm(name: str, a: torch.Tensor, w: torch.Tensor, wscale: Optional[torch.Tensor], epi: int, rows: int,
+              workspace: Optional[torch.Tensor], out: Optional[torch.Tensor], rownorm: Optional[tuple],
+              row_w: Optional[torch.Tensor], cfg: Optional[tuple], E: int) -> int:
+    """The one body of dec_gemm (``E`` = 0), dec_gemm_grouped and dec_gemm_grouped_q (``E`` experts,
+    ``w`` and ``wscale`` [E, ...] stacks): checks, configuration, the CPU reference - one per-expert
+    loop with the kernel's split-K slicing over the dequantised values - and the one native launch."""
+    f8, f4 = is_fp8(w), is_mxfp4(w)
+    enc = "mxfp4" if f4 else "fp8" if f8 else None
+    N, K = skinny_wdims(w[0] if E else w)
+    M = rows
+    lead = (E,) if E else ()
+    want = lead + ((N // 16, K // 128, 16, 4) if f4 else (N,))
+    if enc and (wscale is None or (wscale.numel() != N if f8 and not E else
+                                   tuple(wscale.shape) != want or wscale.dtype != (torch.uint8 if f4 else torch.float32))):
+        raise ValueError(f"{name}: the {enc} {'stack' if E else 'weight'} needs its scales {list(want)} "
+                         + ("uint8 (the packed block scales)" if f4 else "fp32"))
+    limit = DEC_NARROW_MAX_M if E and enc else DEC_MAX_M
+    if M > limit and (enc or not E or not _gpu(a)):  # (a bf16 stack on the GPU: the form check below refuses)
+        raise ValueError(f"{name}: at most {limit} rows, got {M}")
+    if E and enc and epi not in (DEC_SLAB, DEC_SWIGLU8):
+        raise ValueError(f"{name}: only the slab and SwiGLU epilogues")
+    if cfg is None:
+        cfg = (dec_grouped_q_config(N, K, epi, E, **enc_kw(w)) if E and enc else
+               dec_config(N, K, epi, experts=E) if E else dec_config(N, K, epi, rows=M, f8=f8, f4=f4))
+    if cfg is None:
+        raise ValueError(f"{name}: no configuration for N={N} K={K} epi={epi} " + (f"experts={E}" if E else f"rows={M}"))
+    S, ntw, waves, depth = cfg
+    if not _gpu(a):
+        sc = _rn_scale(rownorm, M, K)
+        for e in range(max(E, 1)):
+            x = _cpu_a(a[e] if a.dim() == 5 else a, rows).float()
+            wf = _cpu_w(w[e], wscale[e] if enc else None) if E else _cpu_w(w, wscale)
+            if epi == 0:
+                kc = K // S
+                slabs = workspace[e * S * M * N: (e + 1) * S * M * N].view(S, M, N)
+                for s in range(S):
+                    y = x[:, s * kc:(s + 1) * kc] @ wf[:, s * kc:(s + 1) * kc].t()
+                    slabs[s] = y * sc if sc is not None else y
+                if row_w is not None:
+                    slabs.mul_(row_w[:M, e].float().view(1, M, 1))
+                continue
+            y = x @ wf.t()
+            if sc is not None:
+                y = y * sc
+            o = out[e] if E else out
+            if epi == 1:
+                o[:M].copy_(y.to(o.dtype))
+            else:
+                gu = deinterleave_gate_up8(y.to(a.dtype).float().t()).t()
+                g, u = gu[:, : N // 2], gu[:, N // 2:]
+                o.copy_(pack_activation((torch.nn.functional.silu(g) * u).to(a.dtype)))
+        return max(E, 1) * S if epi == 0 else 1
+    rn = (None, 0.0) if rownorm is None else (rownorm[0], float(rownorm[1]))
+    # more than 16 partial sums per row: gemm_dec_rc's per-16-column sums, the wide-norm form
+    wn = rownorm is not None and rownorm[0].shape[1] > 16
+    ok = (dec_grouped_q_form_ok(epi, cfg, M, K=K, **enc_kw(w)) if E and enc else
+          dec_form_ok(epi, cfg, M, grouped=E > 0, wide_norm=wn, f8=f8, f4=f4, K=K))
+    if not ok:
+        raise RuntimeError(f"{name}: form (epi, ntw, waves, depth) = {(epi,) + tuple(cfg[1:])} not compiled for "
+                           f"{M} rows" + (" of a grouped launch" if E else "") +
+                           (" with the wide deferred norm" if wn else "") +
+                           (" over fp8 weights" if f8 else f" over mxfp4 weights in {S} K slices" if f4 else ""))
+    r = native().gemm_dec(a, w, wscale if enc else None, workspace, out, S, epi, ntw, waves, depth, M, *rn,
+                          row_w if E else None, DEC_F4_DEPTH_FORCE if f4 else 0)
+    if r < 0:
+        raise RuntimeError(f"{name}: configuration {cfg} not compiled for N={N} K={K} epi={epi}")
+    return r
+
+
+def dec_gemm(a: torch.Tensor, wp: torch.Tensor, epi: int, rows: int, workspace: Optional[torch.Tensor] = None,
+             out: Optional[torch.Tensor] = None, rownorm: Optional[tuple] = None,
+             cfg: Optional[tuple] = None, wscale: Optional[torch.Tensor] = None) -> int:
+    """gemm_dec over a fragment-packed activation ``a`` and packed weight ``wp`` (pack_skinny: under
+    ONE_LAYOUT the model's only copy, which prefill's tile GEMM reads too; else a copy for decode).
+    epi 0: fp32 split-K slabs into ``workspace`` [S, M, N], returns S; epi 1: ``out`` [M, N] bf16;
+    epi 2: ``out`` packed SwiGLU [ceil(M/16), F/32, 64, 8] over an interleave_gate_up8 weight.
+    ``rownorm = (ss_part, eps)``: deferred RMSNorm of the A rows (add_norm_partial).  Up to
+    DEC_MAX_M = 128 rows; the configuration is dec_config's for that row count (65..128 rows run
+    the 5..8 m-tile instantiations).  ``wp`` may be the fp8 encoding (pack_skinny_f8 codes) with
+    ``wscale`` its per-row scales in packed row order: the same launch over half the weight
+    bytes, bit-identical to the bf16 launch of the same configuration over the dequantised
+    weights; a form without an fp8 instantiation raises.  Or the mxfp4 encoding (pack_skinny_f4's
+    codes, ``wscale`` its packed block scales), under the same contract.
+    CPU: the fp32 reference with the same split-K slicing (over the dequantised values)."""
+    return _dec_gemm("gemm_dec", a, wp, wscale, epi, rows, workspace, out, rownorm, None, cfg, 0)
+
+
+def dec_gemm_grouped(a: torch.Tensor, wp: torch.Tensor, epi: int, rows: int, workspace: Optional[torch.Tensor] = None,
+                     out: Optional[torch.Tensor] = None, row_w: Optional[torch.Tensor] = None,
+                     cfg: Optional[tuple] = None) -> int:
+    """gemm_dec over every local expert of a MoE layer in ONE launch (grid.z = expert): ``wp``
+    [E, N/16, K/32, 64, 8] (packed per expert, gate/up interleave_gate_up8 for epi 2); ``a`` packed
+    [ceil(M/16), K/32, 64, 8] shared by the experts (gate_up) or [E, ...] per expert (down).
+    epi 2: ``out`` [E, ceil(M/16), F/32, 64, 8] packed SwiGLU; epi 0: fp32 slabs [E * S, M, N] in
+    ``workspace`` scaled by ``row_w`` [M, E] (routing weights, 0 where a row skipped the expert),
+    returns E * S - the residual-add kernel's slab sum is the expert combine."""
+    if wp.dtype == torch.uint8:
+        raise ValueError("gemm_dec_grouped: grouped launches have no mxfp4 form here (dec_gemm_grouped_q takes the "
+                         "codes with their scales)")
+    return _dec_gemm("gemm_dec_grouped", a, wp, None, epi, rows, workspace, out, None, row_w, cfg, wp.shape[0])
+
+
 def dec_gemm_grouped_q(a: torch.Tensor, wq: torch.Tensor, wqs: torch.Tensor, epi: int, rows: int,
                        workspace: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
                        row_w: Optional[torch.Tensor] = None, cfg: Optional[tuple] = None) -> int:
@@ -860,44 +890,9 @@ def dec_gemm_grouped_q(a: torch.Tensor, wq: torch.Tensor, wqs: torch.Tensor, epi
     block scales [E, N/16, K/128, 16, 4] uint8 (pack_skinny_f4 per expert).  ``a``, ``out``,
     ``workspace`` and ``row_w`` as dec_gemm_grouped; the configuration is dec_grouped_q_config's.
     One launch over half (a quarter of) the weight bytes, bit-identical to dec_gemm_grouped of the
-    same configuration over the dequantised stack.  CPU: the per-expert dec_gemm loop over
-    ``(wq[e], wqs[e])`` with the routing weights applied as dec_gemm_grouped applies them."""
-    E, N, K = grouped_q_wdims(wq)
-    f4 = is_mxfp4(wq)
-    want = (E, N // 16, K // 128, 16, 4) if f4 else (E, N)
-    if wqs is None or tuple(wqs.shape) != want or wqs.dtype != (torch.uint8 if f4 else torch.float32):
-        raise ValueError(f"gemm_dec_grouped_q: the {'mxfp4' if f4 else 'fp8'} stack needs its scales "
-                         f"{list(want)} {'uint8' if f4 else 'fp32'}")
-    M = rows
-    if M > DEC_NARROW_MAX_M:
-        raise ValueError(f"gemm_dec_grouped_q: at most {DEC_NARROW_MAX_M} rows, got {M}")
-    if epi not in (DEC_SLAB, DEC_SWIGLU8):
-        raise ValueError("gemm_dec_grouped_q: only the slab and SwiGLU epilogues")
-    if cfg is None:
-        cfg = dec_grouped_q_config(N, K, epi, E, f8=not f4, f4=f4)
-    if cfg is None:
-        raise ValueError(f"gemm_dec_grouped_q: no configuration for N={N} K={K} epi={epi} experts={E}")
-    S, ntw, waves, depth = cfg
-    if not _gpu(a):
-        for e in range(E):
-            ae = a[e] if a.dim() == 5 else a
-            if epi == 2:
-                dec_gemm(ae, wq[e], 2, M, out=out[e], cfg=cfg, wscale=wqs[e])
-            else:
-                ws = workspace[e * S * M * N: (e + 1) * S * M * N]
-                dec_gemm(ae, wq[e], 0, M, workspace=ws, cfg=cfg, wscale=wqs[e])
-                if row_w is not None:
-                    ws.view(S, M, N).mul_(row_w[:M, e].float().view(1, M, 1))
-        return E * S if epi == 0 else 1
-    if not dec_grouped_q_form_ok(epi, cfg, M, f8=not f4, f4=f4, K=K):
-        raise RuntimeError(f"gemm_dec_grouped_q: form (epi, ntw, waves, depth) = {(epi,) + tuple(cfg[1:])} not "
-                           f"compiled for {M} rows of a grouped launch over {'mxfp4' if f4 else 'fp8'} weights"
-                           + (f" in {S} K slices" if f4 else ""))
-    r = native().gemm_dec_grouped_q(a, wq, wqs, workspace, out, S, epi, ntw, waves, depth, M, row_w,
-                                    DEC_F4_DEPTH_FORCE if f4 else 0)
-    if r < 0:
-        raise RuntimeError(f"gemm_dec_grouped_q: configuration {cfg} not compiled for N={N} K={K} epi={epi}")
-    return r
+    same configuration over the dequantised stack."""
+    E = grouped_q_wdims(wq)[0]  # raises for anything but a stack of codes
+    return _dec_gemm("gemm_dec_grouped_q", a, wq, wqs, epi, rows, workspace, out, None, row_w, cfg, E)
 
 
 def dec_gemm_rc(a: torch.Tensor, wp: torch.Tensor, rows: int, residual: torch.Tensor, norm_w: torch.Tensor,

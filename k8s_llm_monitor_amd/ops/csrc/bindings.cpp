@@ -57,21 +57,12 @@ int k8sllm_gemm_skinny(const void* A, long lda, const void* Wp, float* partial, 
                        int S, int epi, int nt_tiles, int a_packed, const float* rn_ss, int rn_nc, int rn_d,
                        float rn_eps, int waves, int experts, long w_es, long a_es, long y_es,
                        const float* row_w, int row_w_ld, int w_rm, hipStream_t s);
-int k8sllm_gemm_dec(const void* A, const void* Wp, float* partial, void* Y, long ldy, int M, int N, int K, int splits,
-                    int epi, int ntw, int waves, int depth, const float* rn_ss, int rn_nc, int rn_d, float rn_eps,
-                    int experts, long a_es, long w_eb, long y_es, const float* rw, int rw_ld, hipStream_t s);
-int k8sllm_gemm_dec_grouped_q(const void* A, const void* Wq, const void* wscale, int wf, float* partial, void* Y, int M,
-                              int N, int K, int splits, int epi, int ntw, int waves, int depth, int f4_depth,
-                              int experts, long a_es, long w_eb, long s_eb, long y_es, const float* rw, int rw_ld,
-                              hipStream_t s);
+int k8sllm_gemm_dec(const void* A, const void* W, const void* wscale, int wf, float* partial, void* Y, long ldy, int M,
+                    int N, int K, int splits, int epi, int ntw, int waves, int depth, int f4_depth, const float* rn_ss,
+                    int rn_nc, int rn_d, float rn_eps, int experts, long a_es, long w_eb, long s_eb, long y_es,
+                    const float* rw, int rw_ld, hipStream_t s);
 int k8sllm_gemm_dec_forms(int* out, int cap);
-int k8sllm_gemm_dec_f8(const void* A, const void* Wq, const float* wscale, float* partial, void* Y, long ldy, int M,
-                       int N, int K, int splits, int epi, int ntw, int waves, int depth, const float* rn_ss, int rn_nc,
-                       int rn_d, float rn_eps, hipStream_t s);
 int k8sllm_gemm_dec_f8_forms(int* out, int cap);
-int k8sllm_gemm_dec_f4(const void* A, const void* Wq, const void* wscale, float* partial, void* Y, long ldy, int M,
-                       int N, int K, int splits, int epi, int ntw, int waves, int depth, int f4_depth,
-                       const float* rn_ss, int rn_nc, int rn_d, float rn_eps, hipStream_t s);
 int k8sllm_gemm_dec_f4_forms(int* out, int cap);
 int k8sllm_gemm_dec_rc(const void* A, const void* Wp, void* resid, const void* nw, void* xw, float* ss, int M, int N,
                        int K, hipStream_t s);
@@ -658,95 +649,113 @@ int64_t gemm_skinny(torch::Tensor a, torch::Tensor wp, c10::optional<torch::Tens
   return p.slabs;
 }
 
-// Decode GEMM over a fragment-packed weight copy with A shared through LDS (gemm_decode.hip):
-// a packed [ceil(M/16), K/32, 64, 8] (`rows` valid), wp packed [N/16, K/32, 64, 8] (for epi 2 the
-// rows interleaved per 16-row n-tile as [8 gate | 8 up]).  epi 0: fp32 slabs partial[S][M][N],
-// returns S = splits; epi 1: y [M, N] bf16 (row stride y.stride(0)); epi 2: packed SwiGLU
-// y [ceil(M/16), N/64, 64, 8].  Up to kDecMaxM rows on the forms of gemm_dec_forms.h that have
-// that many m-tiles.  Returns the slab count (1 for epi 1/2); -1 if the configuration
-// is not available (the caller falls back to gemm_skinny).
-int64_t gemm_dec(torch::Tensor a, torch::Tensor wp, c10::optional<torch::Tensor> partial, c10::optional<torch::Tensor> y,
-                 int64_t splits, int64_t epi, int64_t ntw, int64_t waves, int64_t depth, int64_t rows,
-                 c10::optional<torch::Tensor> rn_ss, double rn_eps) {
-  dev_bf16(a, "a"); dev_bf16(wp, "wp");
-  TORCH_CHECK(wp.dim() == 4 && wp.is_contiguous() && wp.size(2) == 64 && wp.size(3) == 8,
-              "gemm_dec: wp must be fragment-packed [N/16, K/32, 64, 8]");
-  const int N = (int)wp.size(0) * 16, K = (int)wp.size(1) * 32, M = (int)rows;
-  TORCH_CHECK(a.dim() == 4 && a.is_contiguous() && a.size(1) * 32 == K && a.size(2) == 64 && a.size(3) == 8,
-              "gemm_dec: a must be fragment-packed [ceil(M/16), K/32, 64, 8]");
-  TORCH_CHECK(M > 0 && M <= k8sllm::kDecMaxM && (M + 15) / 16 <= a.size(0), "gemm_dec: 1..", k8sllm::kDecMaxM,
-              " rows within the packed a");
-  float* pp = nullptr;
-  void* yp = nullptr;
-  long ldy = 0;
-  if (epi == 0) {
-    pp = slab_buffer(partial, splits * M * N, "gemm_dec");
-  } else {
-    TORCH_CHECK(splits == 1, "gemm_dec: bf16 / SwiGLU epilogues need splits == 1");
-    if (epi == 2) {
-      yp = swiglu_packed_out(y, 0, M, N, "gemm_dec");
-    } else {
-      TORCH_CHECK(y.has_value(), "gemm_dec: output tensor required");
-      dev_bf16(*y, "y");
-      TORCH_CHECK(y->dim() == 2 && y->size(0) >= M && y->size(1) == N && y->stride(1) == 1, "gemm_dec: y [M, N]");
-      ldy = y->stride(0);
-      yp = y->data_ptr();
-    }
+// Decode GEMM with A shared through LDS (gemm_decode.hip), every weight format, dense or grouped;
+// the tensors say which.  w.dtype: bf16 - fragment-packed [N/16, K/32, 64, 8] (ops.pack_skinny);
+// float8_e4m3fn - codes [N/16, K/64, 64, 16] (ops.pack_skinny_f8) with wscale [N] fp32, one
+// power-of-two scale per packed weight row; uint8 - mxfp4 codes [N/16, K/128, 64, 16] with wscale
+// the e8m0 block scales [N/16, K/128, 16, 4] uint8 (ops.pack_skinny_f4).  For epi 2 the weight rows
+// are interleaved per 16-row n-tile as [8 gate | 8 up].  One more leading dimension E on w (and
+// wscale): a grouped launch over the local experts of a MoE layer (grid.z = expert).
+// a packed [ceil(M/16), K/32, 64, 8] (`rows` valid); grouped: shared by every expert (gate_up) or
+// [E, ceil(M/16), K/32, 64, 8] per expert (down).
+// epi 0: fp32 slabs partial [S, M, N] ([E * S, M, N], scaled by row_w [M, E], the routing weights
+// of these experts, where given); epi 1 (dense): y [M, N] bf16 (row stride y.stride(0)); epi 2:
+// packed SwiGLU y [ceil(M/16), N/64, 64, 8] ([E, ...] per expert).  rn_ss: deferred RMSNorm of the
+// A rows (dense).  f4_depth: the mxfp4 ring depth (8 / 16 k-steps), 0 = the launcher's choice.
+// Row limit, slicing and forms are dec_plan's (gemm_dec_forms.h).  Returns the slab count (1 for
+// epi 1 / 2); -1 if the configuration is not available (the caller falls back to gemm_skinny).
+int64_t gemm_dec(torch::Tensor a, torch::Tensor w, c10::optional<torch::Tensor> wscale,
+                 c10::optional<torch::Tensor> partial, c10::optional<torch::Tensor> y, int64_t splits, int64_t epi,
+                 int64_t ntw, int64_t waves, int64_t depth, int64_t rows, c10::optional<torch::Tensor> rn_ss,
+                 double rn_eps, c10::optional<torch::Tensor> row_w, int64_t f4_depth) {
+  dev_bf16(a, "a");
+  const auto wt = w.scalar_type();
+  const int wf = wt == torch::kFloat8_e4m3fn ? k8sllm::DEC_W_F8 : wt == torch::kUInt8 ? k8sllm::DEC_W_F4 : k8sllm::DEC_W_BF16;
+  const int g = w.dim() == 5 ? 1 : 0;  // grouped: leading expert dimension
+  const int kq = wf == k8sllm::DEC_W_F4 ? 128 : wf == k8sllm::DEC_W_F8 ? 64 : 32, wl = wf == k8sllm::DEC_W_BF16 ? 8 : 16;
+  const std::string whats = std::string("gemm_dec (") + (wf == k8sllm::DEC_W_F4 ? "mxfp4" : wf == k8sllm::DEC_W_F8 ? "fp8" : "bf16") +
+                            (g ? ", grouped)" : ")");
+  const char* what = whats.c_str();
+  TORCH_CHECK(w.is_cuda() && (wf != k8sllm::DEC_W_BF16 || wt == torch::kBFloat16) && w.dim() == 4 + g &&
+                  w.is_contiguous() && w.size(g + 2) == 64 && w.size(g + 3) == wl,
+              what, ": w must be bf16 [N/16, K/32, 64, 8], float8_e4m3fn [N/16, K/64, 64, 16] or uint8 [N/16, K/128, "
+                    "64, 16], fragment-packed, or an [E, ...] stack of such");
+  const int E = g ? (int)w.size(0) : 0, N = (int)w.size(g) * 16, K = (int)w.size(g + 1) * kq, M = (int)rows;
+  const void* sp = nullptr;
+  if (wf == k8sllm::DEC_W_F8) {
+    TORCH_CHECK(wscale.has_value() && wscale->is_cuda() && wscale->scalar_type() == torch::kFloat32 &&
+                    wscale->is_contiguous() && (g ? wscale->dim() == 2 && wscale->size(0) == E && wscale->size(1) == N
+                                                  : wscale->numel() == N),
+                what, ": wscale must be [N] fp32 ([E, N] for a stack)");
+    sp = wscale->data_ptr();
+  } else if (wf == k8sllm::DEC_W_F4) {
+    TORCH_CHECK(wscale.has_value() && wscale->is_cuda() && wscale->scalar_type() == torch::kUInt8 &&
+                    wscale->is_contiguous() && wscale->dim() == 4 + g && (!g || wscale->size(0) == E) &&
+                    wscale->size(g) == w.size(g) && wscale->size(g + 1) == w.size(g + 1) &&
+                    wscale->size(g + 2) == 16 && wscale->size(g + 3) == 4,
+                what, ": wscale must be uint8 [N/16, K/128, 16, 4] ([E, ...] for a stack)");
+    sp = wscale->data_ptr();
   }
+  TORCH_CHECK(g || !row_w.has_value(), what, ": routing weights go with an [E, ...] stack");
+  TORCH_CHECK(!g || !rn_ss.has_value(), what, ": a grouped launch takes no deferred norm");
+  TORCH_CHECK(!g || epi == 0 || epi == 2, what, ": only the slab and SwiGLU outputs");
   const float* rp = nullptr;
   int rn_nc = 0;
   rownorm_args(rn_ss, M, K, rp, rn_nc);
-  const int rc = k8sllm_gemm_dec(a.data_ptr(), wp.data_ptr(), pp, yp, ldy, M, N, K, (int)splits, (int)epi, (int)ntw,
-                                 (int)waves, (int)depth, rp, rn_nc, K, (float)rn_eps, 1, 0, 0, 0, nullptr, 0, cur());
+  const bool scaled = epi == 0 && row_w.has_value();  // (other epilogues have always ignored row_w)
+  const k8sllm::DecPlan p = k8sllm::dec_plan(wf, M, N, K, (int)splits, (int)epi, (int)ntw, (int)waves, (int)depth,
+                                             (int)f4_depth, E, scaled, rn_nc);
+  const int MT = (M + 15) / 16;
+  TORCH_CHECK(M > 0 && M <= p.max_m && (!g || E >= 1), what, ": 1..", p.max_m, " rows", g ? ", >= 1 expert" : "");
+  const bool per_e = g && a.dim() == 5;
+  const int ag = per_e ? 1 : 0;
+  TORCH_CHECK(a.is_contiguous() && a.dim() == 4 + ag && (!per_e || a.size(0) == E) && a.size(ag) >= MT &&
+                  a.size(ag + 1) * 32 == K && a.size(ag + 2) == 64 && a.size(ag + 3) == 8,
+              what, ": a must be fragment-packed [ceil(M/16), K/32, 64, 8]", g ? " or [E, ...]" : "");
+  if (p.err < 0) return -1;
+  float* pp = nullptr;
+  void* yp = nullptr;
+  long ldy = 0, y_es = 0;
+  const float* rw = nullptr;
+  int rw_ld = 0;
+  if (epi == 0) {
+    pp = slab_buffer(partial, (int64_t)p.slabs * M * N, what);
+    if (scaled) {
+      TORCH_CHECK(row_w->is_cuda() && row_w->scalar_type() == torch::kFloat32 && row_w->dim() == 2 &&
+                      row_w->size(0) >= M && row_w->size(1) == E && row_w->stride(1) == 1,
+                  what, ": row_w [M, E] fp32");
+      rw = row_w->data_ptr<float>();
+      rw_ld = (int)row_w->stride(0);
+    }
+  } else if (epi == 2) {
+    yp = swiglu_packed_out(y, E, M, N, what);
+    y_es = g ? y->stride(0) : 0;
+  } else {
+    TORCH_CHECK(y.has_value(), what, ": output tensor required");
+    dev_bf16(*y, "y");
+    TORCH_CHECK(y->dim() == 2 && y->size(0) >= M && y->size(1) == N && y->stride(1) == 1, what, ": y [M, N]");
+    ldy = y->stride(0);
+    yp = y->data_ptr();
+  }
+  // the kernel strides W and the scales in bytes
+  const long a_es = per_e ? a.stride(0) : 0, w_eb = g ? w.stride(0) * w.element_size() : 0;
+  const long s_eb = g && sp ? wscale->stride(0) * wscale->element_size() : 0;
+  const int rc = k8sllm_gemm_dec(a.data_ptr(), w.data_ptr(), sp, wf, pp, yp, ldy, M, N, K, (int)splits, (int)epi,
+                                 (int)ntw, (int)waves, (int)depth, (int)f4_depth, rp, rn_nc, K, (float)rn_eps, E,
+                                 a_es, w_eb, s_eb, y_es, rw, rw_ld, cur());
   if (rc < 0) return -1;
-  check(rc, "gemm_dec");
-  return epi == 0 ? splits : 1;
+  check(rc, what);
+  return p.slabs;
 }
 
-// gemm_dec over fp8 weights: wq e4m3 codes fragment-packed [N/16, K/64, 64, 16] (ops.pack_skinny_f8;
-// for epi 2 over the [8 gate | 8 up] row order), wscale [N] fp32, one power-of-two scale per packed
-// weight row.  Everything else as gemm_dec; only the forms of kDecF8Forms, the narrow deferred norm.
-int64_t gemm_dec_f8(torch::Tensor a, torch::Tensor wq, torch::Tensor wscale, c10::optional<torch::Tensor> partial,
-                    c10::optional<torch::Tensor> y, int64_t splits, int64_t epi, int64_t ntw, int64_t waves,
-                    int64_t depth, int64_t rows, c10::optional<torch::Tensor> rn_ss, double rn_eps) {
-  dev_bf16(a, "a");
-  TORCH_CHECK(wq.is_cuda() && wq.scalar_type() == torch::kFloat8_e4m3fn && wq.dim() == 4 && wq.is_contiguous() &&
-                  wq.size(2) == 64 && wq.size(3) == 16,
-              "gemm_dec_f8: wq must be float8_e4m3fn, fragment-packed [N/16, K/64, 64, 16]");
-  const int N = (int)wq.size(0) * 16, K = (int)wq.size(1) * 64, M = (int)rows;
-  TORCH_CHECK(wscale.is_cuda() && wscale.scalar_type() == torch::kFloat32 && wscale.is_contiguous() &&
-                  wscale.numel() == N,
-              "gemm_dec_f8: wscale must be [N] fp32");
-  TORCH_CHECK(a.dim() == 4 && a.is_contiguous() && a.size(1) * 32 == K && a.size(2) == 64 && a.size(3) == 8,
-              "gemm_dec_f8: a must be fragment-packed [ceil(M/16), K/32, 64, 8]");
-  TORCH_CHECK(M > 0 && M <= k8sllm::kDecMaxM && (M + 15) / 16 <= a.size(0), "gemm_dec_f8: 1..", k8sllm::kDecMaxM,
-              " rows within the packed a");
-  float* pp = nullptr;
-  void* yp = nullptr;
-  long ldy = 0;
-  if (epi == 0) {
-    pp = slab_buffer(partial, splits * M * N, "gemm_dec_f8");
-  } else {
-    TORCH_CHECK(splits == 1, "gemm_dec_f8: bf16 / SwiGLU epilogues need splits == 1");
-    if (epi == 2) {
-      yp = swiglu_packed_out(y, 0, M, N, "gemm_dec_f8");
-    } else {
-      TORCH_CHECK(y.has_value(), "gemm_dec_f8: output tensor required");
-      dev_bf16(*y, "y");
-      TORCH_CHECK(y->dim() == 2 && y->size(0) >= M && y->size(1) == N && y->stride(1) == 1, "gemm_dec_f8: y [M, N]");
-      ldy = y->stride(0);
-      yp = y->data_ptr();
-    }
-  }
-  const float* rp = nullptr;
-  int rn_nc = 0;
-  rownorm_args(rn_ss, M, K, rp, rn_nc);
-  const int rc = k8sllm_gemm_dec_f8(a.data_ptr(), wq.data_ptr(), wscale.data_ptr<float>(), pp, yp, ldy, M, N, K,
-                                    (int)splits, (int)epi, (int)ntw, (int)waves, (int)depth, rp, rn_nc, K,
-                                    (float)rn_eps, cur());
-  if (rc < 0) return -1;
-  check(rc, "gemm_dec_f8");
-  return epi == 0 ? splits : 1;
+// dec_plan (gemm_dec_forms.h), what a launch with these arguments does: (err, m-tiles, kchunk,
+// mxfp4 ring depth, wide-norm, grid x, y, z, slabs, row limit).  experts 0: a dense launch.  No launch.
+std::vector<int64_t> gemm_dec_plan(int64_t wf, int64_t M, int64_t N, int64_t K, int64_t splits, int64_t epi, int64_t ntw,
+                                   int64_t waves, int64_t depth, int64_t f4_depth, int64_t experts, bool has_row_w,
+                                   int64_t rn_nc) {
+  const k8sllm::DecPlan p = k8sllm::dec_plan((int)wf, (int)M, (int)N, (int)K, (int)splits, (int)epi, (int)ntw,
+                                             (int)waves, (int)depth, (int)f4_depth, (int)experts, has_row_w, (int)rn_nc);
+  return {p.err, p.mt, p.kchunk, p.d4, p.rnw, p.gx, p.gy, p.gz, p.slabs, p.max_m};
 }
 
 // The rows of kDecForms with fp8-weight instantiations (kDecF8Forms), as indices into gemm_dec_forms().
@@ -756,55 +765,6 @@ std::vector<int64_t> gemm_dec_f8_forms() {
   TORCH_CHECK(n == k8sllm::kDecNF8Forms, "gemm_dec_f8_forms: ", n, " rows compiled, ", k8sllm::kDecNF8Forms,
               " in the header");
   return std::vector<int64_t>(v.begin(), v.end());
-}
-
-// gemm_dec over MXFP4 weights: wq e2m1 codes fragment-packed [N/16, K/128, 64, 16] bytes and wscale
-// the e8m0 block scales [N/16, K/128, 16, 4] bytes (ops.pack_skinny_f4; for epi 2 over the
-// [8 gate | 8 up] row order).  Everything else as gemm_dec; only the forms of kDecF4Forms, the
-// narrow deferred norm.  f4_depth: the F4 ring depth (8 / 16 k-steps), 0 = the launcher's choice.
-int64_t gemm_dec_f4(torch::Tensor a, torch::Tensor wq, torch::Tensor wscale, c10::optional<torch::Tensor> partial,
-                    c10::optional<torch::Tensor> y, int64_t splits, int64_t epi, int64_t ntw, int64_t waves,
-                    int64_t depth, int64_t rows, c10::optional<torch::Tensor> rn_ss, double rn_eps,
-                    int64_t f4_depth) {
-  dev_bf16(a, "a");
-  TORCH_CHECK(wq.is_cuda() && wq.scalar_type() == torch::kUInt8 && wq.dim() == 4 && wq.is_contiguous() &&
-                  wq.size(2) == 64 && wq.size(3) == 16,
-              "gemm_dec_f4: wq must be uint8, fragment-packed [N/16, K/128, 64, 16]");
-  const int N = (int)wq.size(0) * 16, K = (int)wq.size(1) * 128, M = (int)rows;
-  TORCH_CHECK(wscale.is_cuda() && wscale.scalar_type() == torch::kUInt8 && wscale.is_contiguous() &&
-                  wscale.dim() == 4 && wscale.size(0) == wq.size(0) && wscale.size(1) == wq.size(1) &&
-                  wscale.size(2) == 16 && wscale.size(3) == 4,
-              "gemm_dec_f4: wscale must be uint8 [N/16, K/128, 16, 4]");
-  TORCH_CHECK(a.dim() == 4 && a.is_contiguous() && a.size(1) * 32 == K && a.size(2) == 64 && a.size(3) == 8,
-              "gemm_dec_f4: a must be fragment-packed [ceil(M/16), K/32, 64, 8]");
-  TORCH_CHECK(M > 0 && M <= k8sllm::kDecMaxM && (M + 15) / 16 <= a.size(0), "gemm_dec_f4: 1..", k8sllm::kDecMaxM,
-              " rows within the packed a");
-  float* pp = nullptr;
-  void* yp = nullptr;
-  long ldy = 0;
-  if (epi == 0) {
-    pp = slab_buffer(partial, splits * M * N, "gemm_dec_f4");
-  } else {
-    TORCH_CHECK(splits == 1, "gemm_dec_f4: bf16 / SwiGLU epilogues need splits == 1");
-    if (epi == 2) {
-      yp = swiglu_packed_out(y, 0, M, N, "gemm_dec_f4");
-    } else {
-      TORCH_CHECK(y.has_value(), "gemm_dec_f4: output tensor required");
-      dev_bf16(*y, "y");
-      TORCH_CHECK(y->dim() == 2 && y->size(0) >= M && y->size(1) == N && y->stride(1) == 1, "gemm_dec_f4: y [M, N]");
-      ldy = y->stride(0);
-      yp = y->data_ptr();
-    }
-  }
-  const float* rp = nullptr;
-  int rn_nc = 0;
-  rownorm_args(rn_ss, M, K, rp, rn_nc);
-  const int rc = k8sllm_gemm_dec_f4(a.data_ptr(), wq.data_ptr(), wscale.data_ptr(), pp, yp, ldy, M, N, K,
-                                    (int)splits, (int)epi, (int)ntw, (int)waves, (int)depth, (int)f4_depth, rp,
-                                    rn_nc, K, (float)rn_eps, cur());
-  if (rc < 0) return -1;
-  check(rc, "gemm_dec_f4");
-  return epi == 0 ? splits : 1;
 }
 
 // The rows of kDecForms with mxfp4-weight instantiations (kDecF4Forms): (index into
@@ -817,119 +777,6 @@ std::vector<std::vector<int64_t>> gemm_dec_f4_forms() {
   std::vector<std::vector<int64_t>> out;
   for (int i = 0; i < n; ++i) out.push_back({v[2 * i], v[2 * i + 1]});
   return out;
-}
-
-// Grouped decode GEMM over the local experts of a MoE layer (grid.z = expert): wp [E, N/16, K/32,
-// 64, 8]; a packed [ceil(M/16), K/32, 64, 8] shared by every expert (gate_up) or [E, ceil(M/16),
-// K/32, 64, 8] per expert (down).  epi 2: y [E, ceil(M/16), N/64, 64, 8] packed SwiGLU per expert;
-// epi 0: fp32 slabs [E * splits, M, N] scaled by row_w [M, E] (the routing weights of these
-// experts).  Returns the slab count (epi 0) or 1; -1 for a shape / configuration it does not take.
-int64_t gemm_dec_grouped(torch::Tensor a, torch::Tensor wp, c10::optional<torch::Tensor> partial,
-                         c10::optional<torch::Tensor> y, int64_t splits, int64_t epi, int64_t ntw, int64_t waves,
-                         int64_t depth, int64_t rows, c10::optional<torch::Tensor> row_w) {
-  dev_bf16(a, "a"); dev_bf16(wp, "wp");
-  TORCH_CHECK(wp.dim() == 5 && wp.is_contiguous() && wp.size(3) == 64 && wp.size(4) == 8,
-              "gemm_dec_grouped: wp must be [E, N/16, K/32, 64, 8]");
-  const int E = (int)wp.size(0), N = (int)wp.size(1) * 16, K = (int)wp.size(2) * 32, M = (int)rows;
-  const int MT = (M + 15) / 16;
-  TORCH_CHECK(M > 0 && M <= k8sllm::kDecNarrowMaxM && E >= 1, "gemm_dec_grouped: 1..", k8sllm::kDecNarrowMaxM,
-              " rows, >= 1 expert");
-  const bool per_e = a.dim() == 5;
-  TORCH_CHECK(a.is_contiguous() && (per_e ? (a.size(0) == E && a.size(1) >= MT && a.size(2) * 32 == K &&
-                                             a.size(3) == 64 && a.size(4) == 8)
-                                          : (a.dim() == 4 && a.size(0) >= MT && a.size(1) * 32 == K &&
-                                             a.size(2) == 64 && a.size(3) == 8)),
-              "gemm_dec_grouped: a packed [ceil(M/16), K/32, 64, 8] or [E, ...]");
-  const long a_es = per_e ? a.stride(0) : 0, w_eb = wp.stride(0) * wp.element_size();  // the kernel strides W in bytes
-  float* pp = nullptr;
-  void* yp = nullptr;
-  long y_es = 0;
-  const float* rw = nullptr;
-  int rw_ld = 0;
-  if (epi == 0) {
-    pp = slab_buffer(partial, (int64_t)E * splits * M * N, "gemm_dec_grouped");
-    if (row_w.has_value()) {
-      TORCH_CHECK(row_w->is_cuda() && row_w->scalar_type() == torch::kFloat32 && row_w->dim() == 2 &&
-                      row_w->size(0) >= M && row_w->size(1) == E && row_w->stride(1) == 1,
-                  "gemm_dec_grouped: row_w [M, E] fp32");
-      rw = row_w->data_ptr<float>();
-      rw_ld = (int)row_w->stride(0);
-    }
-  } else {
-    TORCH_CHECK(epi == 2 && splits == 1, "gemm_dec_grouped: only the SwiGLU output, with splits 1");
-    yp = swiglu_packed_out(y, E, M, N, "gemm_dec_grouped");
-    y_es = y->stride(0);
-  }
-  const int rc = k8sllm_gemm_dec(a.data_ptr(), wp.data_ptr(), pp, yp, 0, M, N, K, (int)splits, (int)epi, (int)ntw,
-                                 (int)waves, (int)depth, nullptr, 0, K, 0.f, E, a_es, w_eb, y_es, rw, rw_ld, cur());
-  if (rc < 0) return -1;
-  check(rc, "gemm_dec_grouped");
-  return epi == 0 ? (int64_t)E * splits : 1;
-}
-
-// gemm_dec_grouped over a quantised expert stack.  fp8: wq float8_e4m3fn [E, N/16, K/64, 64, 16]
-// (ops.pack_skinny_f8 per expert), wscale [E, N] fp32 row scales in packed row order.  mxfp4: wq
-// uint8 [E, N/16, K/128, 64, 16], wscale uint8 [E, N/16, K/128, 16, 4] (ops.pack_skinny_f4 per
-// expert).  a, y, partial and row_w as gemm_dec_grouped; only the forms of kDecF8Forms /
-// kDecF4Forms.  f4_depth: the mxfp4 ring depth (8 / 16 k-steps), 0 = the launcher's choice.
-int64_t gemm_dec_grouped_q(torch::Tensor a, torch::Tensor wq, torch::Tensor wscale,
-                           c10::optional<torch::Tensor> partial, c10::optional<torch::Tensor> y, int64_t splits,
-                           int64_t epi, int64_t ntw, int64_t waves, int64_t depth, int64_t rows,
-                           c10::optional<torch::Tensor> row_w, int64_t f4_depth) {
-  dev_bf16(a, "a");
-  const bool f4 = wq.scalar_type() == torch::kUInt8;
-  TORCH_CHECK(wq.is_cuda() && (f4 || wq.scalar_type() == torch::kFloat8_e4m3fn) && wq.dim() == 5 &&
-                  wq.is_contiguous() && wq.size(3) == 64 && wq.size(4) == 16,
-              "gemm_dec_grouped_q: wq must be float8_e4m3fn [E, N/16, K/64, 64, 16] or uint8 [E, N/16, K/128, 64, 16]");
-  const int E = (int)wq.size(0), N = (int)wq.size(1) * 16, K = (int)wq.size(2) * (f4 ? 128 : 64), M = (int)rows;
-  if (f4) {
-    TORCH_CHECK(wscale.is_cuda() && wscale.scalar_type() == torch::kUInt8 && wscale.is_contiguous() &&
-                    wscale.dim() == 5 && wscale.size(0) == E && wscale.size(1) == wq.size(1) &&
-                    wscale.size(2) == wq.size(2) && wscale.size(3) == 16 && wscale.size(4) == 4,
-                "gemm_dec_grouped_q: mxfp4 wscale must be uint8 [E, N/16, K/128, 16, 4]");
-  } else {
-    TORCH_CHECK(wscale.is_cuda() && wscale.scalar_type() == torch::kFloat32 && wscale.is_contiguous() &&
-                    wscale.dim() == 2 && wscale.size(0) == E && wscale.size(1) == N,
-                "gemm_dec_grouped_q: fp8 wscale must be [E, N] fp32");
-  }
-  const int MT = (M + 15) / 16;
-  TORCH_CHECK(M > 0 && M <= k8sllm::kDecNarrowMaxM && E >= 1, "gemm_dec_grouped_q: 1..", k8sllm::kDecNarrowMaxM,
-              " rows, >= 1 expert");
-  const bool per_e = a.dim() == 5;
-  TORCH_CHECK(a.is_contiguous() && (per_e ? (a.size(0) == E && a.size(1) >= MT && a.size(2) * 32 == K &&
-                                             a.size(3) == 64 && a.size(4) == 8)
-                                          : (a.dim() == 4 && a.size(0) >= MT && a.size(1) * 32 == K &&
-                                             a.size(2) == 64 && a.size(3) == 8)),
-              "gemm_dec_grouped_q: a packed [ceil(M/16), K/32, 64, 8] or [E, ...]");
-  const long a_es = per_e ? a.stride(0) : 0;
-  const long w_eb = wq.stride(0) * wq.element_size(), s_eb = wscale.stride(0) * wscale.element_size();
-  float* pp = nullptr;
-  void* yp = nullptr;
-  long y_es = 0;
-  const float* rw = nullptr;
-  int rw_ld = 0;
-  if (epi == 0) {
-    TORCH_CHECK(splits >= 1, "gemm_dec_grouped_q: splits >= 1");
-    pp = slab_buffer(partial, (int64_t)E * splits * M * N, "gemm_dec_grouped_q");
-    if (row_w.has_value()) {
-      TORCH_CHECK(row_w->is_cuda() && row_w->scalar_type() == torch::kFloat32 && row_w->dim() == 2 &&
-                      row_w->size(0) >= M && row_w->size(1) == E && row_w->stride(1) == 1,
-                  "gemm_dec_grouped_q: row_w [M, E] fp32");
-      rw = row_w->data_ptr<float>();
-      rw_ld = (int)row_w->stride(0);
-    }
-  } else {
-    TORCH_CHECK(epi == 2 && splits == 1, "gemm_dec_grouped_q: only the SwiGLU output, with splits 1");
-    yp = swiglu_packed_out(y, E, M, N, "gemm_dec_grouped_q");
-    y_es = y->stride(0);
-  }
-  const int rc = k8sllm_gemm_dec_grouped_q(a.data_ptr(), wq.data_ptr(), wscale.data_ptr(),
-                                           f4 ? k8sllm::DEC_W_F4 : k8sllm::DEC_W_F8, pp, yp, M, N, K, (int)splits,
-                                           (int)epi, (int)ntw, (int)waves, (int)depth, (int)f4_depth, E, a_es, w_eb,
-                                           s_eb, y_es, rw, rw_ld, cur());
-  if (rc < 0) return -1;
-  check(rc, "gemm_dec_grouped_q");
-  return epi == 0 ? (int64_t)E * splits : 1;
 }
 
 // The compiled forms of gemm_dec (kDecForms): (epi, ntw, waves, depth, max m-tiles, wide-norm) per row.
@@ -1240,15 +1087,12 @@ PYBIND11_MODULE(_k8sllm_ops, m) {
   m.def("gemm_skinny_grouped", &gemm_skinny_grouped);
   m.def("gemm_skinny_forms", &gemm_skinny_forms);
   m.def("gemm_skinny_plan", &gemm_skinny_plan);
+  m.def("gemm_dec_plan", &gemm_dec_plan);
   m.attr("SKINNY_MAX_M") = k8sllm::kSkinnyMaxM;
   m.attr("SKINNY_GROUPED_MAX_M") = k8sllm::kSkinnyGroupedMaxM;
   m.def("gemm_dec", &gemm_dec);
-  m.def("gemm_dec_grouped", &gemm_dec_grouped);
-  m.def("gemm_dec_grouped_q", &gemm_dec_grouped_q);
   m.def("gemm_dec_forms", &gemm_dec_forms);
-  m.def("gemm_dec_f8", &gemm_dec_f8);
   m.def("gemm_dec_f8_forms", &gemm_dec_f8_forms);
-  m.def("gemm_dec_f4", &gemm_dec_f4);
   m.def("gemm_dec_f4_forms", &gemm_dec_f4_forms);
   m.def("gemm_dec_rc", &gemm_dec_rc);
   m.def("reduce_add_rms_norm", &reduce_add_rms_norm);

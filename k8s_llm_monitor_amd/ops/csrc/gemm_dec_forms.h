@@ -38,12 +38,12 @@ constexpr DecForm kDecForms[] = {
 };
 constexpr int kDecNForms = sizeof(kDecForms) / sizeof(kDecForms[0]);
 
-// The rows of kDecForms that also have the fp8-weight instantiations (k8sllm_gemm_dec_f8: e4m3
+// The rows of kDecForms that also have the fp8-weight instantiations (wf = DEC_W_F8: e4m3
 // codes [N/16][K/64][64][16] plus one fp32 power-of-two scale per packed weight row; dense
 // launches, narrow deferred norm, 1..max_mt m-tiles): the Llama-3-8B picks of ops.DEC_TABLE /
 // DEC_TABLE_M128 and the 70B TP=1 gate_up form.  k8sllm_gemm_dec_f8_forms reports the list and
 // ops.DEC_F8_FORMS mirrors it.  The SLAB and SWIGLU8 rows also serve the grouped launches over a
-// quantised expert stack (k8sllm_gemm_dec_grouped_q, <= kDecNarrowMaxM rows: the same
+// quantised expert stack (experts >= 1, <= kDecNarrowMaxM rows: the same
 // instantiations, the expert strides being run-time arguments); so do those of kDecF4Forms.
 constexpr int kDecF8Forms[] = {0, 1, 4, 6, 7, 9};
 constexpr int kDecNF8Forms = sizeof(kDecF8Forms) / sizeof(kDecF8Forms[0]);
@@ -54,7 +54,7 @@ constexpr bool dec_form_f8(int form) {
   return false;
 }
 
-// The rows of kDecForms that also have the MXFP4-weight instantiations (k8sllm_gemm_dec_f4: e2m1
+// The rows of kDecForms that also have the MXFP4-weight instantiations (wf = DEC_W_F4: e2m1
 // codes [N/16][K/128][64][16] plus the e8m0 block scales [N/16][K/128][16] dwords; dense launches,
 // narrow deferred norm, 1..max_mt m-tiles): every pick of ops.DEC_TABLE / DEC_TABLE_M128.  The F4
 // ring depth (k-steps in flight per n-tile, four per load) replaces the row's own: 8 at every row
@@ -81,10 +81,106 @@ constexpr int dec_max_mt() {
   return m;
 }
 
-// Row limits: dense launches up to the largest form; grouped launches (experts > 1 or routing
+// Row limits: dense launches up to the largest form; grouped launches (an expert stack or routing
 // weights), the wide deferred-norm form and the row-complete kernel stay at 4 m-tiles.
 constexpr int kDecNarrowMaxMT = 4;
 constexpr int kDecMaxM = 16 * dec_max_mt();        // 128
 constexpr int kDecNarrowMaxM = 16 * kDecNarrowMaxMT;  // 64
+
+// Kernel constants the plan needs (gemm_decode.hip asserts they are the kernel's own).
+constexpr int kDecAChunk = 8;     // kDecCH: k-steps (32 deep) per A chunk in the LDS ring
+constexpr int kDecRnNarrow = 16;  // 4 * kRnMax: deferred-norm partial sums per row of the narrow form
+constexpr int kDecRnWide = 256;   // 16 * kRnWide: of the wide form (a multiple of 16)
+
+// What one launch of gemm_dec_kernel does.  err: 0, or -1 arguments / limits, -3 K slicing, -4
+// splits with a non-slab epilogue, -5 no such form (nothing else is then meaningful but max_m).
+struct DecPlan {
+  int err;
+  int max_m;       // the row limit of this kind of launch (kDecMaxM or kDecNarrowMaxM)
+  int mt;          // m-tiles
+  int kchunk;      // K per split
+  int d4;          // mxfp4: the ring depth in k-steps (8 or 16), else 0
+  int rnw;         // 1: the wide deferred-norm instantiation
+  int gx, gy, gz;  // grid: column groups, splits, experts
+  int slabs;       // what the caller is told: fp32 slabs written (SLAB), else 1
+};
+
+// The row of kDecForms that is (epi, ntw, waves, depth), or -1.
+constexpr int dec_form_index(int epi, int ntw, int waves, int depth) {
+  for (int i = 0; i < kDecNForms; ++i) {
+    const DecForm& f = kDecForms[i];
+    if (f.epi == epi && f.ntw == ntw && f.waves == waves && f.depth == depth) return i;
+  }
+  return -1;
+}
+
+// THE plan of k8sllm_gemm_dec: the launcher, the binding (its row limit and slab count) and the
+// CPU tests (native().gemm_dec_plan against ops.dec_form_ok) all take their answers from here.
+// wf: DEC_W_*; experts: 0 a dense launch, E >= 1 a grouped one over an [E, ...] stack (grid.z =
+// expert); has_row_w: routing weights scale the slabs; rn_nc: deferred-norm partial sums per A row
+// (0: no deferred norm); f4_depth: mxfp4 ring depth, 0 = the rule below, 8 / 16 forced within it.
+//
+// Accepted launches (everything else is refused):
+//
+//   weights  launch   rows     K %   epilogues            deferred norm      forms (1..max_mt m-tiles)
+//   bf16     dense    <= 128   32    SLAB BF16 SWIGLU8    narrow, or wide    kDecForms; wide: its wide_norm
+//                                                         at <= 64 rows      rows at 1..4 m-tiles
+//   bf16     grouped  <= 64    32    SLAB BF16 SWIGLU8    as dense (the      as dense
+//                                                         binding gives none)
+//   fp8      dense    <= 128   64    SLAB BF16 SWIGLU8    narrow             kDecF8Forms
+//   mxfp4    dense    <= 128   128   SLAB BF16 SWIGLU8    narrow             kDecF4Forms
+//   fp8      grouped  <= 64    64    SLAB SWIGLU8         none               kDecF8Forms
+//   mxfp4    grouped  <= 64    128   SLAB SWIGLU8         none               kDecF4Forms
+//
+// Every one: N % 16 == 0, splits >= 1 dividing K, splits == 1 unless SLAB, routing weights only
+// with SLAB (and they make a launch grouped).  K slices: bf16 / fp8 a positive multiple of
+// max(depth, kDecAChunk) k-steps (one unrolled main-loop iteration); mxfp4 whole 256-deep A chunks,
+// and the ring depth d4 dividing the slice's k-steps: the kDecF4Forms row's depth at one m-tile,
+// 8 above, and 0 -> the deepest of those that divides.
+constexpr DecPlan dec_plan(int wf, int M, int N, int K, int splits, int epi, int ntw, int waves, int depth,
+                           int f4_depth, int experts, bool has_row_w, int rn_nc) {
+  DecPlan p{-1, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  const bool grouped = experts >= 1 || has_row_w, quant = wf != DEC_W_BF16;
+  p.max_m = grouped ? kDecNarrowMaxM : kDecMaxM;
+  if ((wf != DEC_W_BF16 && wf != DEC_W_F8 && wf != DEC_W_F4) || experts < 0 || M < 1 || M > p.max_m) return p;
+  if (has_row_w && epi != DEC_SLAB) return p;
+  if (quant && grouped && ((epi != DEC_SLAB && epi != DEC_SWIGLU8) || rn_nc > 0)) return p;
+  if (N % 16 || K % (wf == DEC_W_F4 ? 128 : wf == DEC_W_F8 ? 64 : 32) || splits < 1 || K % splits) return p;
+  const int form = dec_form_index(epi, ntw, waves, depth);
+  if (ntw * waves < 1 || (wf == DEC_W_F4 && (form < 0 || dec_form_f4_depth(form) == 0))) return p.err = -5, p;
+  p.mt = (M + 15) / 16;
+  p.kchunk = K / splits;
+  const int ks = p.kchunk / 32;  // k-steps per slice
+  p.err = -3;
+  if (wf == DEC_W_F4) {
+    if (p.kchunk % 128 || ks < kDecAChunk || ks % kDecAChunk) return p;
+    const int dmax = p.mt > 1 ? 8 : dec_form_f4_depth(form);
+    p.d4 = f4_depth ? f4_depth : dmax >= 16 && ks % 16 == 0 ? 16 : 8;
+    if ((p.d4 != 8 && p.d4 != 16) || p.d4 > dmax || ks % p.d4) return p;
+  } else {
+    const int iter = depth > kDecAChunk ? depth : kDecAChunk;
+    if (p.kchunk % 32 || ks < iter || ks % iter) return p;
+  }
+  if (epi != DEC_SLAB && splits != 1) return p.err = -4, p;
+  p.rnw = rn_nc > kDecRnNarrow;
+  // the wide deferred-norm form (gemm_dec_rc's sums) reads bf16 weights
+  if (p.rnw && (quant || rn_nc % 16 || rn_nc > kDecRnWide)) return p.err = -1, p;
+  // the m-tile counts the row is instantiated with for this request: dec_dispatch's conditions
+  int max_mt = 0;
+  if (form >= 0) {
+    const DecForm& f = kDecForms[form];
+    if (wf == DEC_W_F8) max_mt = dec_form_f8(form) ? f.max_mt : 0;
+    else if (wf == DEC_W_F4) max_mt = p.d4 == 16 ? 1 : f.max_mt;
+    else max_mt = p.rnw ? (f.wide_norm ? kDecNarrowMaxMT : 0) : f.max_mt;
+  }
+  if (p.mt > max_mt) return p.err = -5, p;
+  const int nwg = ntw * waves;
+  p.gx = (N / 16 + nwg - 1) / nwg;
+  p.gy = splits;
+  p.gz = experts > 1 ? experts : 1;
+  p.slabs = epi == DEC_SLAB ? p.gz * splits : 1;
+  p.err = 0;
+  return p;
+}
 
 }  // namespace k8sllm

@@ -583,63 +583,44 @@ bool dec_dispatch(int epi, int ntw, int waves, int depth, bool rnw, int mt, cons
 
 }  // namespace
 
-// Weight layout for DEC_SWIGLU8: fragment-packed over rows interleaved per 16-row n-tile as
-// [8 gate | 8 up] (ops.interleave_gate_up8).  ntw x waves n-tiles per workgroup; grid
-// (ceil((N / 16) / (ntw * waves)), splits) - the last workgroup may hold fewer n-tiles.  depth:
-// weight k-steps in flight per wave.
-// (epi, ntw, waves, depth) must be a row of kDecForms (gemm_dec_forms.h) with ceil(M / 16) <= its
-// max_mt; grouped launches (experts > 1 or rw) and the wide deferred-norm form take M <= kDecNarrowMaxM.
-// a_es / y_es: elements between experts' A / SWIGLU8 outputs; w_eb: BYTES between their weights.
-// Returns 0, or a negative code when the shape / configuration is not supported (the caller then
-// uses gemm_skinny).
-extern "C" int k8sllm_gemm_dec(const void* A, const void* Wp, float* partial, void* Y, long ldy, int M, int N, int K,
-                               int splits, int epi, int ntw, int waves, int depth, const float* rn_ss, int rn_nc,
-                               int rn_d, float rn_eps, int experts, long a_es, long w_eb,
-                               long y_es, const float* rw, int rw_ld, hipStream_t s) {
-  if (M <= 0) return 0;
-  if (experts < 1 || (rw != nullptr && epi != DEC_SLAB)) return -1;
-  if (M > kDecMaxM || (M > kDecNarrowMaxM && (experts > 1 || rw != nullptr))) return -1;
-  if (N % 16 || K % 32 || splits < 1 || K % splits) return -1;
-  const int ntiles = N / 16, nwg_tiles = ntw * waves;
-  if (nwg_tiles < 1) return -5;
-  const int kchunk = K / splits;
-  const int iter = depth > kDecCH ? depth : kDecCH;
-  if (kchunk % 32 || kchunk < 32 * iter || (kchunk / 32) % iter) return -3;
-  if (epi != DEC_SLAB && splits != 1) return -4;
-  const float inv_d = rn_d > 0 ? 1.f / (float)rn_d : 0.f;
-  const int MT = (M + 15) / 16;
-  const bool rnw = rn_ss != nullptr && rn_nc > 4 * kRnMax;  // the wide deferred-norm form (gemm_dec_rc sums)
-  if (rnw && (rn_nc % 16 || rn_nc > 16 * kRnWide)) return -1;
-  const DecLaunch l{dim3((ntiles + nwg_tiles - 1) / nwg_tiles, splits, experts), dim3(64 * waves), s,
-                    (const bf16_t*)A, (const bf16_t*)Wp, partial, (bf16_t*)Y, ldy, M, N, K, kchunk, rn_ss, rn_nc,
-                    inv_d, rn_eps, DecGroup{a_es, y_es, w_eb, 0, rw, rw_ld}, nullptr};
-  if (!dec_dispatch(epi, ntw, waves, depth, rnw, MT, l)) return -5;
-  return (int)hipGetLastError();
-}
+static_assert(kDecAChunk == kDecCH && kDecRnNarrow == 4 * kRnMax && kDecRnWide == 16 * kRnWide,
+              "dec_plan (gemm_dec_forms.h) plans with the kernel's constants");
 
-// The same over fp8 weights: Wq e4m3 codes [N/16][K/64][64][16] (ops.pack_skinny_f8), wscale [N]
-// fp32 powers of two in packed row order.  Dense launches only; (epi, ntw, waves, depth) must be a
-// row of kDecForms listed in kDecF8Forms, with ceil(M / 16) <= its max_mt and the narrow deferred
-// norm (rn_nc <= 16).  The same checks and negative codes as k8sllm_gemm_dec.
-extern "C" int k8sllm_gemm_dec_f8(const void* A, const void* Wq, const float* wscale, float* partial, void* Y,
-                                  long ldy, int M, int N, int K, int splits, int epi, int ntw, int waves, int depth,
-                                  const float* rn_ss, int rn_nc, int rn_d, float rn_eps, hipStream_t s) {
+// THE launcher of gemm_dec_kernel, for every weight format (wf) and for dense (experts 0) and
+// grouped (experts E >= 1: grid.z = expert) launches; what it accepts, the slicing and the grid are
+// dec_plan's (gemm_dec_forms.h).
+// W by wf: DEC_W_BF16 fragment-packed [N/16][K/32][64][8] (ops.pack_skinny), wscale unused;
+// DEC_W_F8 e4m3 codes [N/16][K/64][64][16] (ops.pack_skinny_f8), wscale [N] fp32 powers of two in
+// packed row order; DEC_W_F4 e2m1 codes [N/16][K/128][64][16], wscale the e8m0 block scales
+// [N/16][K/128][16] dwords (ops.pack_skinny_f4).  For DEC_SWIGLU8 the weight rows are interleaved
+// per 16-row n-tile as [8 gate | 8 up] (ops.interleave_gate_up8).  Grouped: one such weight (and
+// scale tensor) per expert, w_eb / s_eb BYTES between them; a_es / y_es: elements between experts'
+// A / SWIGLU8 outputs (a_es 0: A shared); SLAB slabs [E * splits][M][N], scaled by rw [M][rw_ld]
+// where given.  ntw x waves n-tiles per workgroup - the last workgroup may hold fewer; depth:
+// weight k-steps in flight per wave (mxfp4: f4_depth, see dec_plan).
+// Returns 0, or dec_plan's negative code when the shape / configuration is not supported (the
+// caller then uses gemm_skinny).
+extern "C" int k8sllm_gemm_dec(const void* A, const void* W, const void* wscale, int wf, float* partial, void* Y,
+                               long ldy, int M, int N, int K, int splits, int epi, int ntw, int waves, int depth,
+                               int f4_depth, const float* rn_ss, int rn_nc, int rn_d, float rn_eps, int experts,
+                               long a_es, long w_eb, long s_eb, long y_es, const float* rw, int rw_ld,
+                               hipStream_t s) {
   if (M <= 0) return 0;
-  if (M > kDecMaxM || wscale == nullptr) return -1;
-  if (N % 16 || K % 64 || splits < 1 || K % splits) return -1;
-  const int ntiles = N / 16, nwg_tiles = ntw * waves;
-  if (nwg_tiles < 1) return -5;
-  const int kchunk = K / splits;
-  const int iter = depth > kDecCH ? depth : kDecCH;
-  if (kchunk % 32 || kchunk < 32 * iter || (kchunk / 32) % iter) return -3;
-  if (epi != DEC_SLAB && splits != 1) return -4;
-  const float inv_d = rn_d > 0 ? 1.f / (float)rn_d : 0.f;
-  const int MT = (M + 15) / 16;
-  if (rn_ss != nullptr && rn_nc > 4 * kRnMax) return -1;  // the wide deferred-norm form reads bf16 weights
-  const DecLaunch l{dim3((ntiles + nwg_tiles - 1) / nwg_tiles, splits, 1), dim3(64 * waves), s,
-                    (const bf16_t*)A, (const bf16_t*)Wq, partial, (bf16_t*)Y, ldy, M, N, K, kchunk, rn_ss, rn_nc,
-                    inv_d, rn_eps, DecGroup{0, 0, 0, 0, nullptr, 0}, wscale};
-  if (!dec_dispatch<DEC_W_F8>(epi, ntw, waves, depth, false, MT, l)) return -5;
+  if (wf != DEC_W_BF16 && wscale == nullptr) return -1;
+  const DecPlan p = dec_plan(wf, M, N, K, splits, epi, ntw, waves, depth, f4_depth, experts, rw != nullptr,
+                             rn_ss != nullptr ? rn_nc : 0);
+  if (p.err < 0) return p.err;
+  const DecLaunch l{dim3(p.gx, p.gy, p.gz), dim3(64 * waves), s, (const bf16_t*)A, (const bf16_t*)W, partial,
+                    (bf16_t*)Y, ldy, M, N, K, p.kchunk, rn_ss, rn_nc, rn_d > 0 ? 1.f / (float)rn_d : 0.f, rn_eps,
+                    DecGroup{a_es, y_es, w_eb, s_eb, rw, rw_ld}, wf == DEC_W_BF16 ? nullptr : (const float*)wscale,
+                    p.d4};
+  bool ok = false;
+  switch (wf) {
+    case DEC_W_BF16: ok = dec_dispatch<DEC_W_BF16>(epi, ntw, waves, depth, p.rnw, p.mt, l); break;
+    case DEC_W_F8: ok = dec_dispatch<DEC_W_F8>(epi, ntw, waves, depth, false, p.mt, l); break;
+    case DEC_W_F4: ok = dec_dispatch<DEC_W_F4>(epi, ntw, waves, depth, false, p.mt, l); break;
+  }
+  if (!ok) return -5;
   return (int)hipGetLastError();
 }
 
@@ -648,93 +629,6 @@ extern "C" int k8sllm_gemm_dec_f8(const void* A, const void* Wq, const float* ws
 extern "C" int k8sllm_gemm_dec_f8_forms(int* out, int cap) {
   for (int i = 0; i < kDecNF8Forms && i < cap; ++i) out[i] = kDecF8Forms[i];
   return kDecNF8Forms;
-}
-
-// The same over MXFP4 weights: Wq e2m1 codes [N/16][K/128][64][16] and wscale the e8m0 block scales
-// [N/16][K/128][16] dwords (ops.pack_skinny_f4).  Dense launches only; (epi, ntw, waves, depth)
-// must be a row of kDecForms listed in kDecF4Forms, with ceil(M / 16) <= its max_mt and the narrow
-// deferred norm; every K slice holds whole 256-deep A chunks (so whole 128-deep code groups).
-// f4_depth: the ring depth in k-steps - 0: the launcher's rule (the row's one-m-tile depth at
-// <= 16 rows where it divides the slice's k-steps, else 8); 8 or 16: forced, within that rule's
-// range.  The same negative codes as k8sllm_gemm_dec.
-extern "C" int k8sllm_gemm_dec_f4(const void* A, const void* Wq, const void* wscale, float* partial, void* Y,
-                                  long ldy, int M, int N, int K, int splits, int epi, int ntw, int waves, int depth,
-                                  int f4_depth, const float* rn_ss, int rn_nc, int rn_d, float rn_eps,
-                                  hipStream_t s) {
-  if (M <= 0) return 0;
-  if (M > kDecMaxM || wscale == nullptr) return -1;
-  if (N % 16 || K % 128 || splits < 1 || K % splits) return -1;
-  const int ntiles = N / 16, nwg_tiles = ntw * waves;
-  if (nwg_tiles < 1) return -5;
-  int dmax = 0;
-  for (int i = 0; i < kDecNForms; ++i) {
-    const DecForm& f = kDecForms[i];
-    if (f.epi == epi && f.ntw == ntw && f.waves == waves && f.depth == depth) dmax = dec_form_f4_depth(i);
-  }
-  if (dmax == 0) return -5;
-  const int kchunk = K / splits;
-  if (kchunk % 128 || kchunk < 32 * kDecCH || (kchunk / 32) % kDecCH) return -3;
-  const int MT = (M + 15) / 16;
-  if (MT > 1) dmax = 8;
-  int d4 = f4_depth;
-  if (d4 == 0) d4 = dmax >= 16 && (kchunk / 32) % 16 == 0 ? 16 : 8;
-  if ((d4 != 8 && d4 != 16) || d4 > dmax || (kchunk / 32) % d4) return -3;
-  if (epi != DEC_SLAB && splits != 1) return -4;
-  const float inv_d = rn_d > 0 ? 1.f / (float)rn_d : 0.f;
-  if (rn_ss != nullptr && rn_nc > 4 * kRnMax) return -1;  // the wide deferred-norm form reads bf16 weights
-  const DecLaunch l{dim3((ntiles + nwg_tiles - 1) / nwg_tiles, splits, 1), dim3(64 * waves), s,
-                    (const bf16_t*)A, (const bf16_t*)Wq, partial, (bf16_t*)Y, ldy, M, N, K, kchunk, rn_ss, rn_nc,
-                    inv_d, rn_eps, DecGroup{0, 0, 0, 0, nullptr, 0}, (const float*)wscale, d4};
-  if (!dec_dispatch<DEC_W_F4>(epi, ntw, waves, depth, false, MT, l)) return -5;
-  return (int)hipGetLastError();
-}
-
-// Grouped launch (grid.z = expert) over a quantised expert stack: wf DEC_W_F8 - Wq e4m3 codes
-// [E][N/16][K/64][64][16], wscale [E][N] fp32 row scales in packed row order - or DEC_W_F4 - Wq e2m1
-// codes [E][N/16][K/128][64][16], wscale the e8m0 block scales [E][N/16][K/128][16] dwords.  w_eb /
-// s_eb: bytes between experts' codes / scales; a_es / y_es: elements between their A / SWIGLU8
-// outputs (a_es 0: A shared).  SLAB (slabs [E * splits][M][N], scaled by rw [M][rw_ld] where given)
-// and SWIGLU8 epilogues, M <= kDecNarrowMaxM, no deferred norm; the forms of kDecF8Forms /
-// kDecF4Forms, and for mxfp4 the ring-depth rule of k8sllm_gemm_dec_f4 (f4_depth as there).  The
-// same negative codes as k8sllm_gemm_dec.
-extern "C" int k8sllm_gemm_dec_grouped_q(const void* A, const void* Wq, const void* wscale, int wf, float* partial,
-                                         void* Y, int M, int N, int K, int splits, int epi, int ntw, int waves,
-                                         int depth, int f4_depth, int experts, long a_es, long w_eb, long s_eb,
-                                         long y_es, const float* rw, int rw_ld, hipStream_t s) {
-  if (M <= 0) return 0;
-  if ((wf != DEC_W_F8 && wf != DEC_W_F4) || wscale == nullptr) return -1;
-  if (experts < 1 || M > kDecNarrowMaxM || (epi != DEC_SLAB && epi != DEC_SWIGLU8)) return -1;
-  if (rw != nullptr && epi != DEC_SLAB) return -1;
-  if (N % 16 || K % (wf == DEC_W_F4 ? 128 : 64) || splits < 1 || K % splits) return -1;
-  const int ntiles = N / 16, nwg_tiles = ntw * waves;
-  if (nwg_tiles < 1) return -5;
-  const int kchunk = K / splits;
-  const int MT = (M + 15) / 16;
-  int d4 = 0;
-  if (wf == DEC_W_F4) {
-    int dmax = 0;
-    for (int i = 0; i < kDecNForms; ++i) {
-      const DecForm& f = kDecForms[i];
-      if (f.epi == epi && f.ntw == ntw && f.waves == waves && f.depth == depth) dmax = dec_form_f4_depth(i);
-    }
-    if (dmax == 0) return -5;
-    if (kchunk % 128 || kchunk < 32 * kDecCH || (kchunk / 32) % kDecCH) return -3;
-    if (MT > 1) dmax = 8;
-    d4 = f4_depth;
-    if (d4 == 0) d4 = dmax >= 16 && (kchunk / 32) % 16 == 0 ? 16 : 8;
-    if ((d4 != 8 && d4 != 16) || d4 > dmax || (kchunk / 32) % d4) return -3;
-  } else {
-    const int iter = depth > kDecCH ? depth : kDecCH;
-    if (kchunk % 32 || kchunk < 32 * iter || (kchunk / 32) % iter) return -3;
-  }
-  if (epi != DEC_SLAB && splits != 1) return -4;
-  const DecLaunch l{dim3((ntiles + nwg_tiles - 1) / nwg_tiles, splits, experts), dim3(64 * waves), s,
-                    (const bf16_t*)A, (const bf16_t*)Wq, partial, (bf16_t*)Y, 0, M, N, K, kchunk, nullptr, 0,
-                    0.f, 0.f, DecGroup{a_es, y_es, w_eb, s_eb, rw, rw_ld}, (const float*)wscale, d4};
-  const bool ok = wf == DEC_W_F4 ? dec_dispatch<DEC_W_F4>(epi, ntw, waves, depth, false, MT, l)
-                                 : dec_dispatch<DEC_W_F8>(epi, ntw, waves, depth, false, MT, l);
-  if (!ok) return -5;
-  return (int)hipGetLastError();
 }
 
 // The rows of kDecForms with mxfp4-weight instantiations (kDecF4Forms) as two ints each (index

@@ -229,3 +229,135 @@ def test_dec_forms_match_the_extension():
     if not ops.native_available():
         pytest.skip("the extension is not built")
     assert [tuple(r) for r in ops.native().gemm_dec_forms()] == list(ops.DEC_FORMS)
+
+
+# ---- dec_plan (csrc/gemm_dec_forms.h) through native().gemm_dec_plan against its Python mirrors
+
+_WF = {None: 0, "fp8": 1, "mxfp4": 2}  # DEC_W_BF16 / DEC_W_F8 / DEC_W_F4
+
+
+def _plan(enc, M, N, K, S, epi, ntw, waves, depth, f4_depth=0, experts=0, has_row_w=False, rn_nc=0):
+    keys = ("err", "mt", "kchunk", "d4", "rnw", "gx", "gy", "gz", "slabs", "max_m")
+    return dict(zip(keys, ops.native().gemm_dec_plan(_WF[enc], M, N, K, S, epi, ntw, waves, depth, f4_depth, experts,
+                                                      has_row_w, rn_nc)))
+
+
+def _py_launch_exists(form, enc, E, rows, rn_nc, S, K):
+    """The Python side of the same question: ops.dec_form_ok / dec_grouped_q_form_ok, with the
+    K-dependent rules dec_config applies before it proposes a configuration (the fp8 K % 64, the
+    ``depth`` iteration rule of _dec_pick; mxfp4's whole-256 slices are dec_form_ok's ``K``), the
+    launcher's "only slabs split" and "a quantised grouped launch takes no deferred norm"."""
+    epi, ntw, waves, depth = form[:4]
+    cfg = (S, ntw, waves, depth)
+    ksteps = K // 32 // S
+    if epi != ops.DEC_SLAB and S != 1:
+        return False
+    if enc == "fp8" and K % 64:
+        return False
+    if enc != "mxfp4" and ksteps % max(depth, 8):
+        return False
+    if E and enc:
+        return rn_nc == 0 and ops.dec_grouped_q_form_ok(epi, cfg, rows, K=K, **ops.enc_kw(enc))
+    return ops.dec_form_ok(epi, cfg, rows, grouped=E > 0, wide_norm=rn_nc > 16, f8=enc == "fp8", f4=enc == "mxfp4", K=K)
+
+
+def test_dec_plan_accepts_exactly_what_the_python_rules_accept():
+    """Every DEC_FORMS row x weight format x dense / grouped (E 1, 2) x rows x deferred norm (none,
+    narrow 4, wide 32 partial sums) x splits (1, 2) at N = 16 ntw waves and 256- and 512-deep K
+    slices: the plan's err is 0 exactly where the Python rules say the launch exists; its slab count
+    is E * splits for slabs and 1 otherwise; the mxfp4 ring depth follows ops.dec_f4_depth.  No launch."""
+    if not ops.native_available():
+        pytest.skip("the extension is not built")
+    n_ok = 0
+    for form in ops.DEC_FORMS:
+        epi, ntw, waves, depth = form[:4]
+        N = 16 * ntw * waves
+        for enc in (None, "fp8", "mxfp4"):
+            for E in (0, 1, 2):
+                for rows in (1, 16, 17, 64, 65, 128, 129):
+                    for rn_nc in (0, 4, 32):
+                        for S in (1, 2):
+                            for kslice in (256, 512):
+                                K = kslice * S
+                                for rw in ((False, True) if E and epi == ops.DEC_SLAB else (False,)):
+                                    p = _plan(enc, rows, N, K, S, epi, ntw, waves, depth, experts=E, has_row_w=rw,
+                                              rn_nc=rn_nc)
+                                    want = _py_launch_exists(form, enc, E, rows, rn_nc, S, K)
+                                    what = f"{form} {enc} E={E} rows={rows} rn_nc={rn_nc} S={S} K={K} rw={rw}: {p}"
+                                    assert (p["err"] == 0) == want, what
+                                    assert p["max_m"] == (ops.DEC_NARROW_MAX_M if E else ops.DEC_MAX_M), what
+                                    if p["err"]:
+                                        continue
+                                    n_ok += 1
+                                    assert p["slabs"] == (max(E, 1) * S if epi == ops.DEC_SLAB else 1), what
+                                    assert (p["mt"], p["kchunk"], p["rnw"]) == (-(-rows // 16), kslice, int(rn_nc > 16)), what
+                                    assert (p["gx"], p["gy"], p["gz"]) == (1, S, max(E, 1)), what
+                                    if enc != "mxfp4":
+                                        assert p["d4"] == 0, what
+                                        continue
+                                    deep = rows <= 16 and ops.dec_f4_depth(epi, (S, ntw, waves, depth)) == 16 and kslice % 512 == 0
+                                    assert p["d4"] == (16 if deep else 8), what
+                                    for force in (8, 16):
+                                        pf = _plan(enc, rows, N, K, S, epi, ntw, waves, depth, f4_depth=force, experts=E,
+                                                   has_row_w=rw, rn_nc=rn_nc)
+                                        assert (pf["err"] == 0) == (force == 8 or deep), what
+                                        assert pf["err"] or pf["d4"] == force, what
+                                    assert _plan(enc, rows, N, K, S, epi, ntw, waves, depth, f4_depth=4, experts=E,
+                                                 has_row_w=rw, rn_nc=rn_nc)["err"] == -3, what
+    assert n_ok > 1000
+
+
+@pytest.mark.parametrize("enc", [None, "fp8", "mxfp4"])
+def test_dec_plan_refusal_codes(enc):
+    """One refusal of each class per weight format, on a SWIGLU8 / SLAB row every format has."""
+    if not ops.native_available():
+        pytest.skip("the extension is not built")
+    assert all(ops.DEC_FORMS[i][:4] in ((0, 1, 8, 8), (2, 1, 7, 8)) for i in (0, 4))
+    assert _plan(enc, 64, 128, 512, 2, 0, 1, 8, 8)["err"] == 0
+    assert _plan(enc, 129, 128, 512, 2, 0, 1, 8, 8)["err"] == -1  # rows
+    assert _plan(enc, 64, 120, 512, 2, 0, 1, 8, 8)["err"] == -1  # N % 16
+    assert _plan(enc, 64, 128, 512 + 32, 1, 0, 1, 8, 8)["err"] == (-1 if enc else -3)  # K % 64 / 128; bf16: the slice
+    assert _plan(enc, 64, 128, 512, 2, 0, 1, 8, 8, experts=2, has_row_w=True)["err"] == 0
+    assert _plan(enc, 64, 112, 256, 1, 2, 1, 7, 8, has_row_w=True)["err"] == -1  # routing weights scale slabs only
+    assert _plan(enc, 64, 128, 256, 2, 0, 1, 8, 8)["err"] == -3  # 128-deep slices: half an A chunk
+    assert _plan(enc, 64, 112, 512, 2, 2, 1, 7, 8)["err"] == -4  # only slabs split
+    assert _plan(enc, 64, 128, 512, 2, 0, 1, 5, 8)["err"] == -5  # no such row
+    assert _plan(enc, 65, 112, 256, 1, 2, 1, 7, 16)["err"] == (-3 if enc != "mxfp4" else -5)  # depth 16: 4 m-tiles, no mxfp4
+
+
+def test_dec_refusals_need_no_launch(monkeypatch):
+    """A grouped launch at 65 rows and a wide-norm launch over fp8: the plan refuses, and the wrappers
+    raise before the extension's launch is reached (the GPU branch of the wrappers, driven here with
+    CPU tensors and a native() that fails the test if it is asked to launch)."""
+    if not ops.native_available():
+        pytest.skip("the extension is not built")
+    N, K, E = 128, 256, 2
+    for enc in (None, "fp8", "mxfp4"):
+        assert _plan(enc, 65, N, K, 1, 0, 1, 8, 8, experts=E)["err"] < 0
+        assert _plan(enc, 64, N, K, 1, 0, 1, 8, 8, experts=E)["err"] == 0
+    assert _plan("fp8", 1, 112, K, 1, 2, 1, 7, 8, rn_nc=32)["err"] < 0
+    assert _plan(None, 1, 112, K, 1, 2, 1, 7, 8, rn_nc=32)["err"] == 0
+    assert _plan("fp8", 1, 112, K, 1, 2, 1, 7, 8, rn_nc=16)["err"] == 0
+
+    class NoLaunch:
+        def gemm_dec(self, *a, **k):
+            raise AssertionError("the launch was reached")
+
+    monkeypatch.setattr(ops, "_gpu", lambda t: True)
+    monkeypatch.setattr(ops, "native", lambda: NoLaunch())
+    a65 = ops.pack_activation(torch.zeros(65, K, dtype=torch.bfloat16))
+    w = torch.zeros(N, K, dtype=torch.bfloat16)
+    ws = torch.empty(E * 65 * N)
+    with pytest.raises(RuntimeError, match="not compiled for 65 rows of a grouped launch"):
+        ops.dec_gemm_grouped(a65, torch.stack([ops.pack_skinny(w)] * E), 0, 65, workspace=ws, cfg=(1, 1, 8, 8))
+    for enc in ("fp8", "mxfp4"):
+        _, qp, sp = ops.encode_weight(w, enc)
+        with pytest.raises(ValueError, match="at most 64 rows"):
+            ops.dec_gemm_grouped_q(a65, torch.stack([qp] * E), torch.stack([sp] * E), 0, 65, workspace=ws, cfg=(1, 1, 8, 8))
+    _, qp, sp = ops.encode_weight(torch.zeros(112, K, dtype=torch.bfloat16), "fp8", gate_up8=True)
+    a1 = ops.pack_activation(torch.zeros(1, K, dtype=torch.bfloat16))
+    out = torch.empty(1, 112 // 64 + 1, 64, 8, dtype=torch.bfloat16)
+    with pytest.raises(RuntimeError, match="with the wide deferred norm over fp8 weights"):
+        ops.dec_gemm(a1, qp, 2, 1, out=out, cfg=(1, 1, 7, 8), wscale=sp, rownorm=(torch.ones(1, 32), 1e-5))
+    with pytest.raises(AssertionError, match="the launch was reached"):  # the narrow norm does launch
+        ops.dec_gemm(a1, qp, 2, 1, out=out, cfg=(1, 1, 7, 8), wscale=sp, rownorm=(torch.ones(1, 16), 1e-5))

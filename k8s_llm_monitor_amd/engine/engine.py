@@ -76,11 +76,12 @@ class EngineConfig:
     # mxfp4: the same design over OCP MXFP4 (e2m1 codes, one e8m0 scale per 32 elements along K;
     # resident weights grow by 17/64; round-to-nearest, visibly less accurate than fp8)
     decode_weights: str = "bf16"
-    # "bf16" | "fp8" (on top of decode_weights = "fp8" only): what prefill reads
+    # "bf16" | "fp8" | "mxfp4" (a quantised one on top of the same decode_weights only): what prefill reads
     # (CausalLM.PREFILL_WEIGHTS).  fp8: the prefill tile GEMM converts the decode codes on the way
     # into the MFMA (bit-identical results) and the bf16 copy of every dense projection and head
     # whose decode launches all have an fp8 form is released - dense models at TP = 1; resident
-    # weights then shrink below the bf16 model's instead of growing by half
+    # weights then shrink below the bf16 model's instead of growing by half.  mxfp4: the same over
+    # the mxfp4 codes and block scales - about 0.31x the bf16 model
     prefill_weights: str = "bf16"
     # "bf16" | "fp8": the paged KV cache's encoding.  fp8 stores e4m3 codes with one power-of-two
     # scale per (token, kv head) for K and for V (ops.quantize_kv): decode streams half the KV bytes

@@ -41,7 +41,9 @@ The four projections of every layer are resident in ONE of three layouts (``Caus
 With ``PREFILL_WEIGHTS = "fp8"`` a PACKED dense projection may be resident as its fp8 encoding
 ONLY: ``L[key]`` is then the packed e4m3 codes ([out/16, in/64, 64, 16], also under ``*_q``) with
 the row scales under ``*_qs`` and no ``*_d`` - prefill's tile GEMM and the decode GEMMs both read
-the codes (``_release_bf16``).
+the codes (``_release_bf16``).  ``PREFILL_WEIGHTS = "mxfp4"`` does the same over the mxfp4 encoding:
+``L[key]`` is the packed e2m1 codes ([out/16, in/128, 64, 16] uint8) and ``*_qs`` their packed e8m0
+block scales; ``ops.is_codes`` is true of either.
 
 ``to_resident`` / ``to_canonical`` convert one projection between CANONICAL and another layout;
 ``_init_skinny`` / ``_init_dec`` move a model forward, ``begin_load`` takes it out of service
@@ -112,7 +114,7 @@ PROJ = ("wqkv", "wo", "w13", "w2")
 # layer-dict keys with these suffixes are derived from the projections, not parameters: the
 # gemm_skinny views (dense, expert stack), the decode GEMM's packed copies (dense, expert stack)
 # and, with DEC_WEIGHTS = "fp8", the fp8 encoding of a dense projection (packed e4m3 codes, per-row scales;
-# with PREFILL_WEIGHTS = "fp8" the codes may be the projection itself: L[key] is L[key + "_q"], no "_d")
+# with PREFILL_WEIGHTS = "fp8" / "mxfp4" the codes may be the projection itself: L[key] is L[key + "_q"], no "_d")
 # or, with DEC_WEIGHTS = "mxfp4", its mxfp4 encoding under the same two keys (ops.pack_skinny_f4's
 # codes and block scales; ops.is_mxfp4 / ops.is_fp8 tell the two apart)
 # (MoE expert stacks: the same two keys hold 5-d [E, ...] stacks of per-expert codes and scales)
@@ -135,10 +137,11 @@ def to_resident(w: torch.Tensor, key: str, form: str) -> torch.Tensor:
 def to_canonical(w: torch.Tensor, key: str, form: str, scale: Optional[torch.Tensor] = None,
                  dtype=torch.bfloat16) -> torch.Tensor:
     """Projection ``key`` (or its expert stack) resident as ``form``, back to CANONICAL.  A
-    projection resident as its fp8 encoding only (packed codes, ``scale`` its row scales in packed
-    row order) is dequantised to ``dtype`` - exactly the bf16 values it was quantised from."""
-    if ops.is_fp8(w):
-        d = ops.dequantize_rows_fp8(ops.unpack_skinny_f8(w), scale, dtype)
+    projection resident as its fp8 or mxfp4 encoding only (packed codes, ``scale`` its row scales in
+    packed row order / its packed block scales) is dequantised to ``dtype`` - exactly the bf16
+    values it was quantised from."""
+    if ops.is_codes(w):
+        d = ops.dequantize_codes(w, scale, dtype)
         return ops.deinterleave_gate_up8(d) if key == "w13" else d
     if form == PACKED:
         return _each(w, lambda e: ops.deinterleave_gate_up8(ops.unpack_skinny(e)) if key == "w13"
@@ -186,6 +189,8 @@ class CausalLM:
     # bit-identical) and the bf16 copy of every dense projection (and the head) whose decode
     # launches all have an fp8 form is released: the codes are the only resident copy
     # (_f8_only_ok; dense, TP = 1, ONE_LAYOUT models - every other projection keeps both copies).
+    # "mxfp4", where DEC_WEIGHTS = "mxfp4": the same over the mxfp4 codes and block scales
+    # (gemm_tile.hip F4) - prefill and decode read one tensor, a quarter of the bf16 bytes.
     PREFILL_WEIGHTS = "bf16"
 
     def __init__(self, cfg: ModelConfig, device: torch.device | str = "cpu", dtype=torch.bfloat16, seed: int = 0,
@@ -194,7 +199,7 @@ class CausalLM:
         """``init``: "random" (seeded per tensor name) or "empty" (uninitialised storage, for
         models about to be filled by models/checkpoint.load_checkpoint).  ``dec_weights``: this
         model's DEC_WEIGHTS ("bf16" | "fp8" | "mxfp4"; None = the class constant); ``prefill_weights``: its
-        PREFILL_WEIGHTS ("bf16" | "fp8", fp8 only on top of fp8 decode weights)."""
+        PREFILL_WEIGHTS ("bf16" | "fp8" | "mxfp4", a quantised one only on top of the same decode weights)."""
         if init not in ("random", "empty"):
             raise ValueError(f"init must be 'random' or 'empty', not {init!r}")
         if dec_weights is not None:
@@ -203,10 +208,11 @@ class CausalLM:
             raise ValueError(f"decode weights must be 'bf16', 'fp8' or 'mxfp4', not {self.DEC_WEIGHTS!r}")
         if prefill_weights is not None:
             self.PREFILL_WEIGHTS = prefill_weights
-        if self.PREFILL_WEIGHTS not in ("bf16", "fp8"):
-            raise ValueError(f"prefill weights must be 'bf16' or 'fp8', not {self.PREFILL_WEIGHTS!r}")
-        if self.PREFILL_WEIGHTS == "fp8" and self.DEC_WEIGHTS != "fp8":
-            raise ValueError("prefill weights 'fp8' need decode weights 'fp8' (the codes prefill reads are decode's)")
+        if self.PREFILL_WEIGHTS not in ("bf16", "fp8", "mxfp4"):
+            raise ValueError(f"prefill weights must be 'bf16', 'fp8' or 'mxfp4', not {self.PREFILL_WEIGHTS!r}")
+        if self.PREFILL_WEIGHTS != "bf16" and self.DEC_WEIGHTS != self.PREFILL_WEIGHTS:
+            raise ValueError(f"prefill weights {self.PREFILL_WEIGHTS!r} need decode weights {self.PREFILL_WEIGHTS!r} "
+                             "(the codes prefill reads are decode's)")
         self._empty_init = init == "empty"
         self._f8_defer = self._empty_init  # uninitialised storage is not quantised: the load's closing _init_skinny does
         self.cfg = cfg
@@ -277,14 +283,14 @@ class CausalLM:
         """Drop the layer's derived tensors - but, unless ``every``, not the codes and scales of a
         projection that is resident as its fp8 encoding only: those ARE the weight (``_remat``
         turns it back)."""
-        keep = set() if every else {key + sfx for key in PROJ if ops.is_fp8(L.get(key)) for sfx in ("_q", "_qs")}
+        keep = set() if every else {key + sfx for key in PROJ if ops.is_codes(L.get(key)) for sfx in ("_q", "_qs")}
         for k in [k for k in L if k.endswith(DERIVED) and k not in keep]:
             del L[k]
 
     @staticmethod
     def _wsc(L: dict, key: str) -> Optional[torch.Tensor]:
-        """The row scales the tile GEMM needs with ``L[key]``: those of an fp8-only projection."""
-        return L[key + "_qs"] if ops.is_fp8(L[key]) else None
+        """The scales the tile GEMM needs with ``L[key]``: those of a codes-only projection."""
+        return L[key + "_qs"] if ops.is_codes(L[key]) else None
 
     def begin_load(self) -> None:
         """Before a loader replaces the weights: the derived tensors (decode copies; under
@@ -387,8 +393,8 @@ class CausalLM:
 
     def resident_weight_bytes(self) -> int:
         """Bytes of every distinct weight tensor this rank holds (parameters, decode-layout copies,
-        the LM head's packed copy and the fp8 encodings with their scales; a tensor referenced
-        under two keys counts once - the codes of an fp8-only projection are its parameter)."""
+        the LM head's packed copy and the fp8 / mxfp4 encodings with their scales; a tensor referenced
+        under two keys counts once - the codes of a codes-only projection are its parameter)."""
         seen, n = set(), 0
         ts = [self.embed, self.lm_head, self.lm_head_d, self.lm_head_q, self.lm_head_qs, self.final_norm]
         for L in self.layers:
@@ -401,7 +407,10 @@ class CausalLM:
         return n
 
     def num_local_params(self) -> int:
-        n = self.embed.numel() + (0 if self.cfg.tie_embeddings else self.lm_head.numel())
+        def count(t: torch.Tensor) -> int:  # an mxfp4 code byte holds two parameters
+            return 2 * t.numel() if ops.is_mxfp4(t) else t.numel()
+
+        n = self.embed.numel() + (0 if self.cfg.tie_embeddings else count(self.lm_head))
         for L in self.layers:
             for k, v in L.items():
                 if k.endswith(DERIVED):
@@ -409,7 +418,7 @@ class CausalLM:
                 if isinstance(v, tuple):
                     n += sum(t.numel() for t in v)
                 else:
-                    n += v.numel()
+                    n += count(v)
         return n
 
     # ------------------------------------------------------------------ forward
@@ -941,7 +950,7 @@ class CausalLM:
             self._drop_derived(L)
             if old != new:
                 for key in PROJ:
-                    if not ops.is_fp8(L[key]):
+                    if not ops.is_codes(L[key]):
                         L[key] = relayout(L[key], key, old, new).contiguous()
         self._layout = new
         if not dec:
@@ -957,7 +966,7 @@ class CausalLM:
         self.skinny_layout = "rowmajor" if rowmajor else "packed"
         for L in self.layers:
             for key in PROJ:  # MoE: stacked per local expert for the grouped (grid.z = expert) launches
-                if ops.is_fp8(L[key]):  # fp8-only so far: _init_dec's _remat makes its view
+                if ops.is_codes(L[key]):  # codes-only so far: _init_dec's _remat makes its view
                     continue
                 sfx = "_pg" if L[key].dim() == 3 else "_p"
                 L[key + sfx] = L[key] if rowmajor else _each(L[key], ops.pack_skinny)
@@ -1019,9 +1028,9 @@ class CausalLM:
         phase behind a grid seam - neutral to slower - and the down projection row-complete -
         0.2-4.5 % slower at 4-32 rows; profiles/r05/README.md.)"""
         c = self.cfg
-        if rc is True and self.layers and any(ops.is_fp8(self.layers[0][k]) for k in ("wo", "w13")):
-            raise ValueError("the row-complete o projection reads bf16 weights: wo / w13 are resident as fp8 only "
-                             "(prefill_weights=fp8)")
+        if rc is True and self.layers and any(ops.is_codes(self.layers[0][k]) for k in ("wo", "w13")):
+            raise ValueError(f"the row-complete o projection reads bf16 weights: wo / w13 are resident as "
+                             f"{self.DEC_WEIGHTS} only (prefill_weights={self.PREFILL_WEIGHTS})")
         ok = (self.tp == 1 and not c.is_moe and bool(self.layers) and "w13_d" in self.layers[0]
               and c.d_model % 512 == 0)
         # fp8 decode weights: the row-complete kernel reads bf16 and leaves the gate_up GEMM the wide
@@ -1154,11 +1163,11 @@ class CausalLM:
         return ops.dec_gemm(x, wd, epi, rows, rownorm=rownorm, **kw)
 
     def prefill_encodings(self) -> dict:
-        """What prefill reads each dense projection and the head from: "fp8" where the codes are
-        the only resident copy (the bf16 copy is released), "bf16" otherwise; layer 0 speaks for all."""
+        """What prefill reads each dense projection and the head from: "fp8" / "mxfp4" where the codes
+        are the only resident copy (the bf16 copy is released), "bf16" otherwise; layer 0 speaks for all."""
         L = self.layers[0] if self.layers else {}
-        enc = {k: "fp8" if ops.is_fp8(L[k]) else "bf16" for k in PROJ if k in L}
-        enc["head"] = "fp8" if self.lm_head_q is not None and self.lm_head_d is None else "bf16"
+        enc = {k: ops.enc_name(L[k]) for k in PROJ if k in L}
+        enc["head"] = ops.enc_name(self.lm_head_q) if self.lm_head_d is None else "bf16"
         return enc
 
     def decode_encodings(self) -> dict:
@@ -1231,8 +1240,8 @@ class CausalLM:
     def canonical_head(self) -> torch.Tensor:
         """The LM head as row-major [vocab shard, d] (ONE_LAYOUT keeps only its packed copy)."""
         h = self.lm_head
-        if ops.is_fp8(h):  # the codes are the only copy: the bf16 values they were quantised from
-            return ops.dequantize_rows_fp8(ops.unpack_skinny_f8(h), self.lm_head_qs, self.dtype)
+        if ops.is_codes(h):  # the codes are the only copy: the bf16 values they were quantised from
+            return ops.dequantize_codes(h, self.lm_head_qs, self.dtype)
         return ops.unpack_skinny(h) if h.dim() == 4 else h
 
     def canonical(self, L: dict, key: str) -> torch.Tensor:
@@ -1250,8 +1259,8 @@ class CausalLM:
         self.embed.copy_(src.embed)
         if self.lm_head is not self.embed:
             h = src.canonical_head().to(self.lm_head.device)
-            if ops.is_fp8(self.lm_head):  # fp8-only head: straight to codes and scales
-                _, q, qs = ops.encode_weight(h.to(self.dtype), "fp8")
+            if ops.is_codes(self.lm_head):  # codes-only head: straight to codes and scales
+                _, q, qs = ops.encode_weight(h.to(self.dtype), self.DEC_WEIGHTS)
                 self.lm_head.copy_(q)
                 self.lm_head_qs.copy_(qs)
             else:
@@ -1264,13 +1273,13 @@ class CausalLM:
             for k, v in Ld.items():
                 if k.endswith(DERIVED):
                     derived = True
-                elif k in PROJ and ops.is_fp8(v):
-                    # fp8-only here: the source's canonical values straight to codes and scales, one
+                elif k in PROJ and ops.is_codes(v):
+                    # codes-only here: the source's canonical values straight to codes and scales, one
                     # projection's bf16 at a time
                     q, qs = self._codes(src.canonical(Ls, k).to(device=v.device, dtype=self.dtype), k)
                     v.copy_(q)
                     Ld[k + "_qs"].copy_(qs)
-                elif k in PROJ and ops.is_fp8(Ls[k]):
+                elif k in PROJ and ops.is_codes(Ls[k]):
                     v.copy_(to_resident(src.canonical(Ls, k), k, self._layout))
                 elif k in PROJ:
                     v.copy_(relayout(Ls[k], k, src._layout, self._layout))
@@ -1312,7 +1321,7 @@ class CausalLM:
         32 along K, so the [8 gate | 8 up] row interleave carries codes and block scales along
         unchanged), the packed codes and block scales (ops.pack_skinny_f4) under the same two keys.
 
-        ``PREFILL_WEIGHTS`` = "fp8" on top: each ONE_LAYOUT layer then releases the packed bf16
+        ``PREFILL_WEIGHTS`` = "fp8" / "mxfp4" on top (of the same DEC_WEIGHTS): each ONE_LAYOUT layer then releases the packed bf16
         tensor of every projection ``_f8_only_ok`` accepts - the codes become ``L[key]`` itself
         (``_release_bf16``) - before the next layer is touched, and so does the head.  A model that
         already holds fp8-only projections (a second ``_init_skinny``, a weight copy) turns each
@@ -1322,8 +1331,8 @@ class CausalLM:
         parts, one = self._want_dec(), self._one_layout_wanted()
         f8 = self.DEC_WEIGHTS in ("fp8", "mxfp4") and not self._f8_defer
         bf16_experts = None  # why the expert stacks stay on bf16, where they do
-        f8_only = f8 and self.PREFILL_WEIGHTS == "fp8"
-        why = None  # why nothing can be fp8-only, if so
+        f8_only = f8 and self.PREFILL_WEIGHTS == self.DEC_WEIGHTS  # codes-only, in either encoding
+        why = None  # why nothing can be codes-only, if so
         if f8_only and (self.cfg.is_moe or self.tp != 1 or not one):
             why = "MoE" if self.cfg.is_moe else "TP > 1" if self.tp != 1 else "not ONE_LAYOUT-packed"
         ceil = self._dec_row_ceiling(parts) if f8_only and why is None else 0
@@ -1382,7 +1391,7 @@ class CausalLM:
             log.info("%s: decode_weights=%s leaves the MoE expert stacks on bf16 (%s)", self.cfg.name,
                      self.DEC_WEIGHTS, bf16_experts)
         if stayed:
-            log.info("%s: prefill_weights=fp8 keeps the bf16 copy of %s", self.cfg.name,
+            log.info("%s: prefill_weights=%s keeps the bf16 copy of %s", self.cfg.name, self.PREFILL_WEIGHTS,
                      ", ".join(f"{k} ({r})" for k, r in stayed.items()))
 
     def _dec_row_ceiling(self, parts: set) -> int:
@@ -1399,15 +1408,16 @@ class CausalLM:
 
     @staticmethod
     def _f8_only_why(wq: Optional[torch.Tensor], epi: int, ceil: int) -> Optional[str]:
-        """None when the weight with the codes ``wq`` may be resident as fp8 only, else why not:
-        it needs an fp8 encoding, an fp8 decode form in every row class up to the model's row
-        ceiling (nothing may ever ask for the bf16 copy) and the tile GEMM's fp8-W form."""
+        """None when the weight with the codes ``wq`` (fp8 or mxfp4) may be resident as those only,
+        else why not: it needs the encoding, a decode form over it in every row class up to the
+        model's row ceiling (nothing may ever ask for the bf16 copy) and the tile GEMM's form over it."""
         if wq is None:
-            return "no fp8 encoding"
+            return "no quantised encoding"
         N, K = ops.skinny_wdims(wq)
-        if not all(ops.dec_config(N, K, epi, rows=r, f8=True) is not None for r in ops.dec_row_classes() if r <= ceil):
-            return "no fp8 decode form in some row class"
-        return None if ops.tile_f8_ok(N, K) else "no fp8 form of the prefill GEMM for the shape"
+        enc, kw = ops.enc_name(wq), ops.enc_kw(wq)
+        if not all(ops.dec_config(N, K, epi, rows=r, **kw) is not None for r in ops.dec_row_classes() if r <= ceil):
+            return f"no {enc} decode form in some row class"
+        return None if ops.tile_codes_ok(wq) else f"no {enc} form of the prefill GEMM for the shape"
 
     @staticmethod
     def _release_bf16(L: dict, key: str) -> None:
@@ -1418,14 +1428,14 @@ class CausalLM:
 
     def _codes(self, w: torch.Tensor, key: str) -> tuple:
         """(packed codes, scales in packed row order) of the CANONICAL weight ``w`` of ``key``."""
-        return ops.encode_weight(w, "fp8", key == "w13")[1:]
+        return ops.encode_weight(w, self.DEC_WEIGHTS, key == "w13")[1:]
 
     def _remat(self, L: dict, form: str) -> None:
-        """Every fp8-only projection of the layer back to a bf16 tensor in the row-major layout
+        """Every codes-only projection of the layer back to a bf16 tensor in the row-major layout
         ``form`` (the dequantised values - what it was quantised from), its codes dropped, with the
         gemm_skinny view ``*_p`` the other projections got in _init_skinny."""
         for key in PROJ:
-            if ops.is_fp8(L.get(key)):
+            if ops.is_codes(L.get(key)):
                 w = to_resident(self.canonical(L, key), key, form).contiguous()
                 L[key] = w
                 del L[key + "_q"], L[key + "_qs"]

@@ -63,8 +63,9 @@ class LLMConfig:
     # scale per 32 elements along K, a quarter of the bf16 bytes beside the bf16 weights, less
     # accurate than fp8; docs/engine.md)
     decode_weights: str = "bf16"
-    # "bf16" | "fp8" (with decode_weights: fp8 only): prefill reads the fp8 codes too and the bf16
-    # copy of every dense projection / head that decode never needs is released (dense, TP = 1)
+    # "bf16" | "fp8" | "mxfp4" (a quantised one with the same decode_weights only): prefill reads
+    # decode's codes too and the bf16 copy of every dense projection / head that decode never needs
+    # is released (dense, TP = 1)
     prefill_weights: str = "bf16"
     # "bf16" | "fp8": the paged KV cache's encoding (fp8: e4m3 codes + one power-of-two scale per
     # token and kv head - half the KV bytes per decode step, ~1.94x the tokens per kv_cache_gb)

@@ -779,6 +779,30 @@ def enc_kw(x) -> dict:
     raise ValueError(f"not a quantised decode encoding: {x if isinstance(x, str) else x.dtype}")
 
 
+def is_codes(w: Optional[torch.Tensor]) -> bool:
+    """A weight held as a quantised decode encoding's packed codes (fp8 or mxfp4)."""
+    return is_fp8(w) or is_mxfp4(w)
+
+
+def enc_name(w: Optional[torch.Tensor]) -> str:
+    """"fp8" | "mxfp4" for a codes tensor, "bf16" for anything else (None included)."""
+    return "mxfp4" if is_mxfp4(w) else "fp8" if is_fp8(w) else "bf16"
+
+
+def dequantize_codes(w: torch.Tensor, scale: torch.Tensor, dtype=torch.bfloat16) -> torch.Tensor:
+    """Packed codes (pack_skinny_f8 with row scales, or pack_skinny_f4 with packed block scales) ->
+    the row-major [N, K] values in the codes' row order: exactly what they were quantised from."""
+    if is_mxfp4(w):
+        return dequantize_mxfp4(*unpack_skinny_f4(w, scale), dtype=dtype)
+    return dequantize_rows_fp8(unpack_skinny_f8(w), scale, dtype)
+
+
+def tile_codes_ok(w: torch.Tensor) -> bool:
+    """gemm_tile has a form that reads the codes tensor ``w`` (tile_f8_ok / tile_f4_ok of its shape)."""
+    N, K = skinny_wdims(w)
+    return tile_f4_ok(N, K) if is_mxfp4(w) else tile_f8_ok(N, K)
+
+
 def _dec_gemm(name: str, a: torch.Tensor, w: torch.Tensor, wscale: Optional[torch.Tensor], epi: int, rows: int,
               workspace: Optional[torch.Tensor], out: Optional[torch.Tensor], rownorm: Optional[tuple],
               row_w: Optional[torch.Tensor], cfg: Optional[tuple], E: int) -> int:
@@ -1407,12 +1431,17 @@ def gemm_tile(x: torch.Tensor, w: torch.Tensor, offsets: Optional[torch.Tensor] 
     its [N] fp32 row scales in packed row order: the codes are converted on the way into the MFMA,
     bit-identical to the packed bf16 form over the dequantised weight.  Compiled for dense
     launches on schedule 1 with K >= 192 (tile_f8_ok), plain / ``swiglu=8`` / ``rope`` with or
-    without ``rowscale``; any other form raises."""
+    without ``rowscale``; any other form raises.
+    ``w`` may be the mxfp4 decode encoding (pack_skinny_f4 codes [N/16, K/128, 64, 16] uint8) with
+    ``wscale`` its e8m0 block scales [N/16, K/128, 16, 4] uint8 - the tensors gemm_dec streams, converted
+    with the block scale on the way into the MFMA, bit-identical to the packed bf16 form over the
+    dequantised weight.  The same compiled forms as fp8, K % 128 == 0 and K >= 256 (tile_f4_ok)."""
     M = x.shape[0]
-    f8 = is_fp8(w)
-    if f8:
-        _tile_f8_check(w, wscale, "grouped" if offsets is not None else "swiglu=1 (per-128 pairing)"
-                       if swiglu and swiglu != 8 else None, algo)
+    f8, f4 = is_fp8(w), w.dtype == torch.uint8
+    if f8 or f4:
+        (_tile_f4_check if f4 else _tile_f8_check)(
+            w, wscale, "grouped" if offsets is not None else "swiglu=1 (per-128 pairing)"
+            if swiglu and swiglu != 8 else None, algo)
     packed = w.dim() == (5 if offsets is not None else 4)
     N = w.shape[-4] * 16 if packed else w.shape[-2]
     if out is None:
@@ -1425,6 +1454,8 @@ def gemm_tile(x: torch.Tensor, w: torch.Tensor, offsets: Optional[torch.Tensor] 
     if not _gpu(x):
         if f8:  # the dequantised values: exactly the bf16 encoding's
             w = dequantize_rows_fp8(unpack_skinny_f8(w), wscale, x.dtype)
+        elif f4:
+            w = dequantize_mxfp4(*unpack_skinny_f4(w, wscale), dtype=x.dtype)
         elif packed:
             w = (torch.stack([unpack_skinny(e) for e in w]) if offsets is not None else unpack_skinny(w))
         inv = None
@@ -1494,6 +1525,28 @@ def _tile_f8_check(w: torch.Tensor, wscale: Optional[torch.Tensor], form: Option
         raise ValueError(f"gemm_tile: no fp8-W form for N={N} K={K} (K >= 192, K % 64 == 0, N * K < 2^31)")
 
 
+def tile_f4_ok(N: int, K: int) -> bool:
+    """gemm_tile has an mxfp4-W form for a dense weight [N, K]: whole 16-row blocks and 128-deep
+    scale groups (two 64-deep k-tiles per code block), at least two of them (schedule 1 needs three
+    k-tiles and K comes in 128s), and 32-bit DMA byte offsets within the codes."""
+    return N % 16 == 0 and K % 128 == 0 and K >= 256 and N * K // 2 < (1 << 31)
+
+
+def _tile_f4_check(w: torch.Tensor, wscale: Optional[torch.Tensor], form: Optional[str], algo: int) -> None:
+    """An mxfp4 W of gemm_tile: only the compiled forms, no silent other path."""
+    if form is not None:
+        raise ValueError(f"gemm_tile: the mxfp4-W form is not compiled for {form} launches")
+    if w.dim() != 4 or w.shape[-2:] != (64, 16):
+        raise ValueError("gemm_tile: an mxfp4 w is pack_skinny_f4's [N/16, K/128, 64, 16] uint8")
+    N, K = skinny_wdims(w)
+    if wscale is None or wscale.dtype != torch.uint8 or tuple(wscale.shape) != (N // 16, K // 128, 16, 4):
+        raise ValueError(f"gemm_tile: an mxfp4 weight needs its [{N // 16}, {K // 128}, 16, 4] uint8 block scales")
+    if algo != 1:
+        raise ValueError("gemm_tile: the mxfp4-W form is compiled for schedule 1 (algo=1) only, not schedule 0")
+    if not tile_f4_ok(N, K):
+        raise ValueError(f"gemm_tile: no mxfp4-W form for N={N} K={K} (K >= 256, K % 128 == 0, N * K / 2 < 2^31)")
+
+
 def gemm_tile_resid(x: torch.Tensor, w: torch.Tensor, resid: torch.Tensor, norm_w: torch.Tensor,
                     hw: Optional[torch.Tensor] = None, ss: Optional[torch.Tensor] = None,
                     wscale: Optional[torch.Tensor] = None) -> tuple:
@@ -1502,11 +1555,13 @@ def gemm_tile_resid(x: torch.Tensor, w: torch.Tensor, resid: torch.Tensor, norm_
     bf16(x @ w^T)) in place; returns ``(hw, ss)`` - hw = bf16(resid * norm_w) [M, N] and ss [M, N / 128]
     fp32 partial sums of resid^2 over each 128 columns, the operands of the consumer's row scale
     (``gemm_tile(hw, ..., rowscale=(ss, eps))`` = the projection of rms_norm(resid) * norm_w).
-    ``w`` row-major, fragment-packed, or the fp8 encoding with ``wscale`` (see gemm_tile)."""
+    ``w`` row-major, fragment-packed, or the fp8 / mxfp4 encoding with ``wscale`` (see gemm_tile)."""
     M = x.shape[0]
-    f8 = is_fp8(w)
+    f8, f4 = is_fp8(w), w.dtype == torch.uint8
     if f8:
         _tile_f8_check(w, wscale, None, 1)
+    elif f4:
+        _tile_f4_check(w, wscale, None, 1)
     N = w.shape[0] * 16 if w.dim() == 4 else w.shape[0]  # row-major or fragment-packed W
     if N % 128 or resid.shape != (M, N):
         raise ValueError("gemm_tile_resid: N % 128 == 0 and resid [M, N]")
@@ -1515,6 +1570,8 @@ def gemm_tile_resid(x: torch.Tensor, w: torch.Tensor, resid: torch.Tensor, norm_
     if not _gpu(x):
         if f8:
             w = dequantize_rows_fp8(unpack_skinny_f8(w), wscale, x.dtype)
+        elif f4:
+            w = dequantize_mxfp4(*unpack_skinny_f4(w, wscale), dtype=x.dtype)
         elif w.dim() == 4:
             w = unpack_skinny(w)
         y = torch.nn.functional.linear(x.float(), w.float()).to(x.dtype)
@@ -1564,12 +1621,13 @@ def fused_norm_ok(M: int, d: int, n_qkv: int, n_o_in: int, n_13: int, f: int) ->
 
 def w_out(w: torch.Tensor) -> int:
     """Output features of a dense projection weight: row-major [N, K], fragment-packed
-    [N/16, K/32, 64, 8] (pack_skinny) or the fp8 encoding [N/16, K/64, 64, 16] (pack_skinny_f8)."""
+    [N/16, K/32, 64, 8] (pack_skinny), the fp8 encoding [N/16, K/64, 64, 16] (pack_skinny_f8) or the
+    mxfp4 one [N/16, K/128, 64, 16] (pack_skinny_f4)."""
     return w.shape[0] * 16 if w.dim() == 4 else w.shape[0]
 
 
 def w_in(w: torch.Tensor) -> int:
-    """Input features (K) of a row-major, fragment-packed or fp8-encoded dense projection weight."""
+    """Input features (K) of a row-major, fragment-packed, fp8- or mxfp4-encoded dense projection weight."""
     return skinny_wdims(w)[1]
 
 
@@ -1585,10 +1643,11 @@ def prefill_linear(x: torch.Tensor, w: torch.Tensor, swiglu: bool = False,
     A fragment-packed ``w`` (pack_skinny, the ONE_LAYOUT resident form; ``swiglu=8`` with the
     interleave_gate_up8 pairing) always takes the tile kernel, whatever the row count - hipBLASLt
     cannot read it; on the CPU gemm_tile unpacks it for the fp32 reference.  So does the fp8
-    encoding of a weight (pack_skinny_f8 codes with ``wscale``, where the model keeps no bf16 copy)."""
+    encoding of a weight (pack_skinny_f8 codes with ``wscale``, where the model keeps no bf16 copy)
+    and the mxfp4 one (pack_skinny_f4 codes with ``wscale`` their block scales)."""
     M, K = x.shape
     if w.dim() == 4:
-        ws = wscale if is_fp8(w) else None
+        ws = wscale if is_fp8(w) or is_mxfp4(w) else None
         if rope is not None:
             return gemm_tile(x, w, out=out, algo=TILE_ALGO, rope=rope, rowscale=rowscale, wscale=ws), True
         return gemm_tile(x, w, swiglu=swiglu, out=out, algo=TILE_ALGO, rowscale=rowscale, wscale=ws)

@@ -50,7 +50,7 @@ int k8sllm_gather_rows(void* out, const void* x, const int* idx, long n, int d, 
 int k8sllm_gemm_tile(const void* X, const void* W, void* Y, int M, int N, int K, const int* offsets, int E, long w_es,
                      int epi, int algo, const int* rope_pos, const float* rope_cs, int rope_heads,
                      const float* rs_part, int rs_np, float rs_eps, void* resid, void* hw, const void* norm_w,
-                     float* ss_out, int wpk, const float* wscale, hipStream_t s);
+                     float* ss_out, int wpk, const void* wscale, int wfmt, hipStream_t s);
 int k8sllm_moe_grouped_gemm(const void* X, const void* W, void* Y, const int* offsets, int E, long rows, int N, int K,
                             long w_es, int epi, hipStream_t s);
 int k8sllm_gemm_skinny(const void* A, long lda, const void* Wp, float* partial, void* Y, long ldy, int M, int N, int K,
@@ -449,8 +449,11 @@ void gemm_tile(torch::Tensor y, torch::Tensor x, torch::Tensor w, c10::optional<
                c10::optional<torch::Tensor> wscale) {
   dev_bf16(y, "y"); dev_bf16(x, "x");
   // fp8 W: e4m3 codes fragment-packed [N/16, K/64, 64, 16] (pack_skinny_f8) + wscale [N] fp32 in packed row order
+  // mxfp4 W: e2m1 codes [N/16, K/128, 64, 16] uint8 + wscale the e8m0 block scales [N/16, K/128, 16, 4] uint8
+  // (pack_skinny_f4) - the tensors gemm_dec streams
   const bool f8 = w.scalar_type() == torch::kFloat8_e4m3fn;
-  if (f8) {
+  const bool f4 = w.scalar_type() == torch::kUInt8;
+  if (f8 || f4) {
     TORCH_CHECK(w.is_cuda(), "w must be a GPU tensor");
   } else {
     dev_bf16(w, "w");
@@ -460,7 +463,19 @@ void gemm_tile(torch::Tensor y, torch::Tensor x, torch::Tensor w, c10::optional<
   const bool grouped = offsets.has_value();
   // w row-major [N, K] / [E, N, K], or fragment-packed [N/16, K/32, 64, 8] / [E, ...] (pack_skinny)
   const bool wpk = w.dim() == (grouped ? 5 : 4);
-  if (f8) {
+  if (f4) {
+    TORCH_CHECK(!grouped, "gemm_tile: the mxfp4-W form is not compiled for grouped launches");
+    TORCH_CHECK(w.dim() == 4 && w.size(-2) == 64 && w.size(-1) == 16,
+                "gemm_tile: mxfp4 w must be [N/16, K/128, 64, 16] uint8");
+    TORCH_CHECK(wscale.has_value() && wscale->is_cuda() && wscale->scalar_type() == torch::kUInt8 &&
+                    wscale->is_contiguous() && wscale->dim() == 4 && wscale->size(0) == w.size(0) &&
+                    wscale->size(1) == w.size(1) && wscale->size(2) == 16 && wscale->size(3) == 4,
+                "gemm_tile: an mxfp4 w needs its [N/16, K/128, 16, 4] uint8 block scales");
+    TORCH_CHECK(w.size(1) * 128 >= 256, "gemm_tile: the mxfp4-W form needs K >= 256 (schedule 1 only)");
+    TORCH_CHECK(algo == 1, "gemm_tile: the mxfp4-W form is compiled for schedule 1 (algo=1) only");
+    TORCH_CHECK(swiglu != 1, "gemm_tile: the mxfp4-W form has no per-128 SwiGLU pairing (swiglu=8 only)");
+    TORCH_CHECK((long)w.size(0) * 16 * w.size(1) * 64 < (1L << 31), "gemm_tile: mxfp4 code offsets must fit 32 bits");
+  } else if (f8) {
     TORCH_CHECK(!grouped, "gemm_tile: the fp8-W form is not compiled for grouped launches");
     TORCH_CHECK(w.dim() == 4 && w.size(-2) == 64 && w.size(-1) == 16, "gemm_tile: fp8 w must be [N/16, K/64, 64, 16]");
     TORCH_CHECK(wscale.has_value() && wscale->is_cuda() && wscale->scalar_type() == torch::kFloat32 &&
@@ -470,13 +485,13 @@ void gemm_tile(torch::Tensor y, torch::Tensor x, torch::Tensor w, c10::optional<
     TORCH_CHECK(algo == 1, "gemm_tile: the fp8-W form is compiled for schedule 1 (algo=1) only");
     TORCH_CHECK(swiglu != 1, "gemm_tile: the fp8-W form has no per-128 SwiGLU pairing (swiglu=8 only)");
   } else {
-    TORCH_CHECK(!wscale.has_value(), "gemm_tile: wscale goes with an fp8 w");
+    TORCH_CHECK(!wscale.has_value(), "gemm_tile: wscale goes with an fp8 or mxfp4 w");
   }
-  TORCH_CHECK(f8 || w.dim() == (grouped ? 3 : 2) || (wpk && w.size(-2) == 64 && w.size(-1) == 8),
+  TORCH_CHECK(f8 || f4 || w.dim() == (grouped ? 3 : 2) || (wpk && w.size(-2) == 64 && w.size(-1) == 8),
               "gemm_tile: w [N, K] (dense) or [E, N, K] (grouped), or their fragment-packed forms");
   const int E = grouped ? (int)w.size(0) : 1;
   const int N = wpk ? (int)w.size(w.dim() - 4) * 16 : (int)w.size(w.dim() - 2);
-  const int K = wpk ? (int)w.size(w.dim() - 3) * (f8 ? 64 : 32) : (int)w.size(w.dim() - 1);
+  const int K = wpk ? (int)w.size(w.dim() - 3) * (f4 ? 128 : f8 ? 64 : 32) : (int)w.size(w.dim() - 1);
   const int M = (int)x.size(0);
   TORCH_CHECK(x.size(1) == K, "gemm_tile: K mismatch");
   TORCH_CHECK(algo >= 0 && algo <= 1, "gemm_tile: algo 0 (one barrier per k-tile) or 1 (two)");
@@ -532,7 +547,7 @@ void gemm_tile(torch::Tensor y, torch::Tensor x, torch::Tensor w, c10::optional<
                          (long)N * K, epi, (int)algo, rp, rc, (int)rope_heads, rsp, rs_np, (float)rs_eps,
                          rsd ? resid->data_ptr() : nullptr, rsd ? hw->data_ptr() : nullptr,
                          rsd ? norm_w->data_ptr() : nullptr, rsd ? ss_out->data_ptr<float>() : nullptr, wpk ? 1 : 0,
-                         f8 ? wscale->data_ptr<float>() : nullptr, cur()),
+                         f8 || f4 ? wscale->data_ptr() : nullptr, f4 ? 2 : f8 ? 1 : 0, cur()),
         "gemm_tile");
 }
 

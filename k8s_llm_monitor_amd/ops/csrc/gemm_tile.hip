@@ -69,6 +69,28 @@
 //    16 j + (lane & 15), two per MFMA shadow, 32 per sub-step.  code * 2^e is exact in bf16, so
 //    the fragment registers hold exactly the bf16 weight: the MFMA sequence and every epilogue are
 //    those of the bf16 kernel, and the result is bit-identical to it over the dequantised weight.
+//
+// F4 (dense, schedule 1): W is the decode GEMMs' mxfp4 encoding - e2m1 codes fragment-packed
+// [N/16][K/128][64][16] and e8m0 block scales [N/16][K/128][16][4] (ops.pack_skinny_f4) - the one
+// tensor decode streams.  A 1-KiB code block covers two k-tiles (lane l's dword s is its 8 codes of
+// k-step 4 g + s), so the F8 form's structure is kept and only the indices change:
+//  * a B half-tile is the same 4 code pieces per wave, of block (n-tile, kt >> 1): both k-tiles of a
+//    pair fetch the same block (the second fetch is an L2 hit), plus ONE dword-wide piece per wave
+//    for the scales - the 16 n-tiles' 64-B scale blocks of the pair are 1 KiB, kept at byte 16384 of
+//    the half-slot (the half F8 leaves unused).  Every wave issues 5 pieces per B half-tile, so the
+//    counted vmcnt waits are F8's plus one per B half-tile in flight.
+//  * the codes of BOTH sub-steps of k-tile t + 1 are read once, while (t, 1) computes: one
+//    ds_read_b64 per block at lane * 16 + 8 ((t + 1) & 1) (F8's bank pattern, 4 LDS cycles; half
+//    F8's B-side reads), the second dword held for one sub-step.  Each sub-step reads the e8m0 byte
+//    2 (kt & 1) + ks of row lane & 15 of each block (ds_read_u8; a 16-lane group reads 16
+//    neighbouring dwords, the other groups the same ones) and MFMAs 16-18 shift the 8 bytes into
+//    fp32 exponents (<< 23), so the 16 conversion units stay two instructions each, in F8's MFMA
+//    shadows: four v_cvt_scalef32_pk_bf16_fp4 per fragment with the scale applied inside
+//    (gemm_decode.hip dec_f4x8).  code * 2^e is exact in bf16: bit-identical to the bf16 kernel
+//    over the dequantised weight.  (The first form - a ds_read_b32 of the code dword per sub-step,
+//    a 4-way bank conflict at the 16-B lane stride, and the scale dword with v_bfe + shift inside
+//    every other conversion unit, four dependent VALU in one MFMA shadow - was 5.5-8.5 % slower than
+//    bf16 on the Llama-3-8B projections; this one is 1.4-3.0 %: profiles/r16/README.md.)
 #include <type_traits>
 
 #include "common.h"
@@ -86,12 +108,14 @@ __device__ __forceinline__ void vm_wait_n() {
 __device__ __forceinline__ void lgkm_wait0() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 }  // namespace
 
-template <int EPI, bool GROUPED, int SCH, bool RS = false, bool F8 = false>
+template <int EPI, bool GROUPED, int SCH, bool RS = false, bool F8 = false, bool F4 = false>
 __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ W,
                                                          bf16_t* __restrict__ Y, const int* __restrict__ offsets,
                                                          int E, int M, int N, int K, long w_es, int n_mt, int n_nt,
                                                          TileEpi ep, int wpk, const float* __restrict__ wscale) {
   static_assert(!F8 || (SCH == 1 && !GROUPED), "the fp8-W form is dense, schedule 1");
+  static_assert(!F4 || (SCH == 1 && !GROUPED && !F8), "the mxfp4-W form is dense, schedule 1");
+  constexpr bool FQ = F8 || F4;  // W arrives as codes: 4 code pieces per B half-tile, fragments converted in registers
   constexpr int HS = 32768;  // one half-slot: 256 rows x 128 B
   __shared__ __attribute__((aligned(16))) char smem[5 * HS];
   const int lane = threadIdx.x & 63;
@@ -142,7 +166,8 @@ __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(const bf16_t* __restric
     const int cl = (lane & 7) ^ ((rl >> 1) & 7);
     soff[0][p] = (uint32_t)(((long)min(rl, mrows - 1) * K + cl * 8) * 2);  // rows past the end: clamped, never stored
     soff[1][p] = (uint32_t)(((long)min(rl, nrows - 1) * K + cl * 8) * 2);
-    if constexpr (F8) {  // e4m3 codes [N/16][K/64][64][16]: piece p < 4 = the 1-KiB block (n-tile 4 p + wave, k-tile):
+    if constexpr (FQ) {  // e4m3 codes [N/16][K/64][64][16]: piece p < 4 = the 1-KiB block (n-tile 4 p + wave, k-tile;
+      // F4, e2m1 codes [N/16][K/128][64][16]: k-tile pair):
       // the block's offset is wave-uniform (sB below, in the soffset); the lane part is lane * 16
       soff[1][p] = (uint32_t)(lane * 16);
     } else if (wpk) {  // W fragment-packed [N/16][K/32][64][8]: piece = one contiguous 1-KiB block (n-tile, k-step)
@@ -154,9 +179,18 @@ __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(const bf16_t* __restric
   // rows are never stored) in this tile's W range - scalar
   uint32_t sB[4];
 #pragma unroll
-  for (int p = 0; p < 4; ++p) sB[p] = F8 ? (uint32_t)(min(p * 4 + wave, (nrows >> 4) - 1) * (K >> 6)) * 1024u : 0u;
+  for (int p = 0; p < 4; ++p)
+    sB[p] = F4   ? (uint32_t)(min(p * 4 + wave, (nrows >> 4) - 1) * (K >> 7)) * 1024u
+            : F8 ? (uint32_t)(min(p * 4 + wave, (nrows >> 4) - 1) * (K >> 6)) * 1024u
+                 : 0u;
   const int kstrB = F8 ? 1024 : wpk ? 2048 : 128;  // bytes of W per k-tile step, in the piece's soffset
-  constexpr int WB = F8 ? 1 : 2;                    // bytes per W element
+  constexpr int WB = F8 ? 1 : 2;                    // bytes per W element (F4: half a byte, below)
+  // F4: the e8m0 block scales [N/16][K/128][16][4] ride as a fifth, dword-wide piece: wave w brings
+  // the 64-B scale blocks of n-tiles 4 w .. 4 w + 3 of the k-tile pair (lane l: dword l & 15 of
+  // n-tile 4 w + (l >> 4), clamped like the codes) to bytes 16384 + 256 w .. of the B half-slot -
+  // there the 16 n-tiles' blocks lie in order, 64 B each
+  [[maybe_unused]] uint32_t soffS = 0u;
+  if constexpr (F4) soffS = (uint32_t)(min(wave * 4 + (lane >> 4), (nrows >> 4) - 1) * (K >> 7) * 64 + (lane & 15) * 4);
   // buffer descriptors over this tile's X rows / W rows, built from wave-uniform values only so
   // hipcc keeps them in SGPRs (no waterfall loops, cdna_hip_programming.md T20)
   auto rsrc = [](const void* base, long bytes) {
@@ -166,7 +200,18 @@ __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(const bf16_t* __restric
     return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((uint64_t)hi << 32) | lo), 0, nb, 0x00020000);
   };
   const __amdgpu_buffer_rsrc_t xr = rsrc(reinterpret_cast<const char*>(X) + (long)row0 * K * 2, (long)mrows * K * 2);
-  const __amdgpu_buffer_rsrc_t wr = rsrc(reinterpret_cast<const char*>(Wt) + (long)n0 * K * WB, (long)nrows * K * WB);
+  // F4: half a byte per element; sr: the tile's scale blocks, (nrows / 16)(K / 128) of 64 B
+  const auto wdesc = [&] {
+    if constexpr (F4) return rsrc(reinterpret_cast<const char*>(Wt) + (long)n0 * K / 2, (long)nrows * K / 2);
+    else return rsrc(reinterpret_cast<const char*>(Wt) + (long)n0 * K * WB, (long)nrows * K * WB);
+  };
+  const __amdgpu_buffer_rsrc_t wr = wdesc();
+  const auto sdesc = [&] {
+    if constexpr (F4)
+      return rsrc(reinterpret_cast<const char*>(wscale) + (long)(n0 >> 4) * (K >> 7) * 64, (long)(nrows >> 4) * (K >> 7) * 64);
+    else return wr;
+  };
+  [[maybe_unused]] const __amdgpu_buffer_rsrc_t sr = sdesc();
   const int nk = K >> 6;
 
   // piece p of half-tile (operand o, k-tile kt) into half-slot `slot`; k-tiles past the end re-read
@@ -174,6 +219,17 @@ __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(const bf16_t* __restric
   // issues the same count and the vmcnt arithmetic never changes
   auto piece = [&](int o, int p, int kt, int slot) {
     char* dst = smem + slot * HS + (p * 4 + wave) * 1024;
+    if constexpr (F4) {
+      if (o && p == 4) {
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(sr, (lds_void_t*)(smem + slot * HS + 16384 + wave * 256), 4, soffS,
+                                                 (min(kt, nk - 1) >> 1) * 64, 0, 0);
+        return;
+      } else if (o) {
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(wr, (lds_void_t*)dst, 16, soff[1][p],
+                                                 (min(kt, nk - 1) >> 1) * 1024 + sB[p], 0, 0);
+        return;
+      }
+    }
     if (o)
       __builtin_amdgcn_raw_ptr_buffer_load_lds(wr, (lds_void_t*)dst, 16, soff[1][p], min(kt, nk - 1) * kstrB + sB[p & 3], 0, 0);
     else
@@ -181,7 +237,7 @@ __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(const bf16_t* __restric
   };
   auto issue_half = [&](int o, int kt) {
 #pragma unroll
-    for (int p = 0; p < (F8 && o ? 4 : 8); ++p) piece(o, p, kt, (2 * kt + o) % 5);
+    for (int p = 0; p < (F4 && o ? 5 : F8 && o ? 4 : 8); ++p) piece(o, p, kt, (2 * kt + o) % 5);
   };
 
   // fragment read: lane row lane & 15 of a 16-row block, 16-B chunk 4 ks + (lane >> 4)
@@ -206,13 +262,27 @@ __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(const bf16_t* __restric
 
   typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
   // F8: the B fragments are built a dword (two bf16) at a time, so they are held as dwords
-  using fragb_t = std::conditional_t<F8, u32x4, bf16x8>;
+  using fragb_t = std::conditional_t<FQ, u32x4, bf16x8>;
   bf16x8 fa0[8], fa1[8];
   fragb_t fb0[8], fb1[8];
   // F8: the next sub-step's 8 codes of each of the wave's 8 blocks as read from LDS, and the scale
   // of this lane's row of each block
-  u32x2 raw[F8 ? 8 : 1];
+  u32x2 raw[FQ ? 8 : 1];
   float wsc[F8 ? 8 : 1];
+  // F4: raw[b] holds BOTH sub-steps' code dwords of a k-tile (one 8-byte read per block and k-tile,
+  // made while the previous tile's second sub-step computes); sraw[b] is the e8m0 byte of this
+  // lane's row of block b for the next sub-step as read from LDS, then (in place) << 23, its fp32
+  uint32_t sraw[F4 ? 8 : 1];
+  auto cvt4q = [](u32x4& d, uint32_t c, float sc, int h) {  // bytes 2 h, 2 h + 1 of c -> dwords 2 h, 2 h + 1 (dec_f4x8)
+    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+    if (h == 0) {
+      d[0] = __builtin_bit_cast(uint32_t, (bf16x2)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(c, sc, 0));
+      d[1] = __builtin_bit_cast(uint32_t, (bf16x2)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(c, sc, 1));
+    } else {
+      d[2] = __builtin_bit_cast(uint32_t, (bf16x2)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(c, sc, 2));
+      d[3] = __builtin_bit_cast(uint32_t, (bf16x2)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(c, sc, 3));
+    }
+  };
   // 4 codes (one dword) x the row scale -> dwords 2 h, 2 h + 1 of a fragment; exact (common.h kv_f8_deq8)
   auto cvt4 = [](u32x4& d, uint32_t c, float sc, int h) {
     typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
@@ -236,8 +306,24 @@ __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(const bf16_t* __restric
     auto rdraw = [&](uint32_t base, int blk) -> u32x2 {
       return *reinterpret_cast<const u32x2*>(smem + base + blk * 1024);
     };
+    // F4: the scale dword of this lane's row (lane & 15) of block 0 of the wave's 8, behind the codes;
+    // block blk is 64 blk further, the sub-step's byte is added in sub
+    [[maybe_unused]] uint32_t fbS = 0u;
+    if constexpr (F4) fbS = (uint32_t)(16384 + wn * 512 + (lane & 15) * 4);
+    auto rd8 = [&](uint32_t base, int off) -> uint32_t { return *reinterpret_cast<const uint8_t*>(smem + base + off); };
     auto pc = [&](int o, int p, int kt, uint32_t slot_bytes) {
       char* dst = smem + slot_bytes + (p * 4 + wave) * 1024;
+      if constexpr (F4) {
+        if (o) {
+          if (p == 4)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(sr, (lds_void_t*)(smem + slot_bytes + 16384 + wave * 256), 4, soffS,
+                                                     (min(kt, nk - 1) >> 1) * 64, 0, 0);
+          else
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(wr, (lds_void_t*)dst, 16, soff[1][p],
+                                                     (min(kt, nk - 1) >> 1) * 1024 + sB[p], 0, 0);
+          return;
+        }
+      }
       __builtin_amdgcn_raw_ptr_buffer_load_lds(o ? wr : xr, (lds_void_t*)dst, 16, soff[o][p],
                                                min(kt, nk - 1) * (o ? kstrB : 128) + (o ? sB[p & 3] : 0u), 0, 0);
     };
@@ -251,6 +337,16 @@ __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(const bf16_t* __restric
       constexpr bool READS = !(PH == 1 && PM == 3);
       // sa / sb: half-slot bytes of the fragments read here; da / db: B_{t+2}'s / A_{t+3}'s targets
       const uint32_t ba = sa + (PH == 0 ? fbA1 : fbA0), bb = sb + (PH == 0 ? fbB1 : fbB0);
+      // F4: the sub-step read here is k-step 2 (t + PH) + (1 - PH): scale byte 2 ((t + PH) & 1) + (1 - PH)
+      // of its k-tile pair (bsq: its address in block 0); the codes of both sub-steps of k-tile t + 1 are read in
+      // (t, 1), 8 bytes at bcq: dwords 2 ((t + 1) & 1), + 1 of the pair's block
+      [[maybe_unused]] uint32_t bcq = 0u, bsq = 0u;
+      if constexpr (F4) {
+        bcq = sb + fbR + 8 * ((t + 1) & 1);
+        bsq = sb + fbS + 2 * ((t + PH) & 1) + (1 - PH);
+      }
+      // F4: B_{t+2} is 5 pieces (4 of codes, 1 of scales), MFMAs 22, 31, .., 58 of (t, 0)
+      constexpr int NPB = F4 ? 5 : 4, PST = F4 ? 9 : 12;
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int g = 0; g < 8; ++g) {
@@ -258,7 +354,7 @@ __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(const bf16_t* __restric
         for (int j = 0; j < 8; ++j) {
           const int n = g * 8 + j;
           acc[g][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, cb[j]), ca[g], acc[g][j], 0, 0, 0);
-          if constexpr (F8) {
+          if constexpr (FQ) {
             // One instruction group per MFMA shadow, as below.  B_{t+2} is 4 pieces (MFMAs 22, 34,
             // 46, 58 of (t, 0)) and A_{t+3}'s 8 ride MFMAs 19, 24, .., 54 of (t, 1).  MFMAs 0-7 read
             // the next sub-step's codes of the 8 blocks, 8-15 its A fragments; behind them the 16
@@ -268,19 +364,33 @@ __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(const bf16_t* __restric
             // 29, 34.  nb was the previous sub-step's cb: all of its MFMAs have issued (in order)
             // long before the first unit, and an MFMA reads its A / B operands when it issues.
             const int cu = n < 20 ? -1
-                           : PH == 0 ? (n <= 37 && n != 22 && n != 34 ? (n - 20) - (n > 22) - (n > 34) : -1)
+                           : PH == 0 ? (n <= 37 && n != 22 && n != 22 + PST ? (n - 20) - (n > 22) - (n > 22 + PST) : -1)
                                      : (n < 39 && (n - 19) % 5 != 0 ? (n - 20) - (n - 19) / 5 : -1);
             if (n < 8) {
-              if constexpr (READS) raw[n] = rdraw(sb + fbR + (PH == 0 ? 8 : 0), n);
+              if constexpr (READS && F4) {
+                if constexpr (PH == 1) raw[n] = rdraw(bcq, n);
+                sraw[n] = rd8(bsq, n * 64);
+              } else if constexpr (READS) {
+                raw[n] = rdraw(sb + fbR + (PH == 0 ? 8 : 0), n);
+              }
             } else if (n < 16) {
               if constexpr (READS) na[n - 8] = rd16(ba, n - 8);
+            } else if (F4 && n < 19) {  // F4: MFMAs 16-18 turn the 8 scale bytes (read 9+ MFMAs ago) into fp32s
+              if constexpr (READS && F4) {
+#pragma unroll
+                for (int i = 3 * (n - 16); i < (n == 18 ? 8 : 3 * (n - 15)); ++i) sraw[i] <<= 23;
+              }
             } else if (cu >= 0) {
-              if constexpr (READS) cvt4(nb[cu >> 1], raw[cu >> 1][cu & 1], wsc[cu >> 1], cu & 1);
+              if constexpr (READS && F4) {
+                cvt4q(nb[cu >> 1], raw[cu >> 1][PH == 0 ? 1 : 0], __uint_as_float(sraw[cu >> 1]), cu & 1);
+              } else if constexpr (READS) {
+                cvt4(nb[cu >> 1], raw[cu >> 1][cu & 1], wsc[cu >> 1], cu & 1);
+              }
             } else if (PH == 0 && PM <= 1 && n == 19) {  // frees tile t's half-slots for the refills
               lgkm_wait0();
               __builtin_amdgcn_s_barrier();
-            } else if (PH == 0 && PM <= 1 && n >= 22 && (n - 22) % 12 == 0) {
-              pc(1, (n - 22) / 12, t + 2, da);
+            } else if (PH == 0 && PM <= 1 && n >= 22 && (n - 22) % PST == 0 && (n - 22) / PST < NPB) {
+              pc(1, (n - 22) / PST, t + 2, da);
             } else if (PH == 1 && PM == 0 && n >= 19 && (n - 19) % 5 == 0 && (n - 19) / 5 < 8) {
               pc(0, (n - 19) / 5, t + 3, db);
             }
@@ -325,8 +435,8 @@ __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(const bf16_t* __restric
     issue_half(0, 1);
     issue_half(1, 1);
     issue_half(0, 2);
-    // tile 0 landed: younger are A_1 B_1 A_2 = 8 + 8 + 8 pieces; F8 (B = 4 pieces): 8 + 4 + 8
-    if constexpr (F8) vm_wait_n<20>(); else vm_wait_n<24>();
+    // tile 0 landed: younger are A_1 B_1 A_2 = 8 + 8 + 8 pieces; F8 (B = 4 pieces): 8 + 4 + 8; F4 (5): 8 + 5 + 8
+    if constexpr (F4) vm_wait_n<21>(); else if constexpr (F8) vm_wait_n<20>(); else vm_wait_n<24>();
     __builtin_amdgcn_s_barrier();
     if constexpr (RS) {
       float sum = 0.f;
@@ -336,12 +446,17 @@ __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(const bf16_t* __restric
       rs_inv = rsqrtf(sum / (float)K + ep.rs_eps);
       // F8: pin the sum here (the compiler otherwise sinks it behind the k loop and keeps the 64
       // partial-sum registers alive across it, which with the raw codes no longer fit)
-      if constexpr (F8) asm volatile("" : "+v"(rs_inv));
+      if constexpr (FQ) asm volatile("" : "+v"(rs_inv));
     }
 #pragma unroll
     for (int g = 0; g < 8; ++g) {
       fa0[g] = frag(0, 0, 0, g);
-      if constexpr (F8) {
+      if constexpr (F4) {  // k-tile 0: dwords 0, 1 of the pair's block; k-step 0: dword 0, scale byte 0
+        raw[g] = rdraw(HS + fbR, g);
+        sraw[g] = rd8(HS + fbS, g * 64) << 23;
+        cvt4q(fb0[g], raw[g][0], __uint_as_float(sraw[g]), 0);
+        cvt4q(fb0[g], raw[g][0], __uint_as_float(sraw[g]), 1);
+      } else if constexpr (F8) {
         raw[g] = rdraw(HS + fbR, g);
         cvt4(fb0[g], raw[g][0], wsc[g], 0);
         cvt4(fb0[g], raw[g][1], wsc[g], 1);
@@ -361,8 +476,8 @@ __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(const bf16_t* __restric
     };
     // vmcnt at the mid-tile wait: B_{t+1} must have landed; younger are A_{t+2} (8) + B_{t+2}'s
     // first 7 pieces (15) in the steady state and at t = nk - 3, nothing from t = nk - 2 on.
-    // F8: A_{t+2} (8) + all 4 pieces of B_{t+2}, issued in (t, 0) (12)
-    constexpr int MIDW = F8 ? 12 : 15;
+    // F8: A_{t+2} (8) + all 4 pieces of B_{t+2}, issued in (t, 0) (12); F4: all 5 (13)
+    constexpr int MIDW = F4 ? 13 : F8 ? 12 : 15;
     for (int t = 0; t < nk - 3; ++t) {
       __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): the previous sub-step's reads, explicitly
       sub(P0{}, P0{}, fa0, fb0, fa1, fb1, S0, S1, S0, S1, t);
@@ -638,12 +753,19 @@ using namespace k8sllm;
 // wscale != nullptr: W is the fp8 encoding - e4m3 codes [N/16][K/64][64][16] (ops.pack_skinny_f8) with
 // wscale [N] fp32 row scales in packed row order.  Compiled forms: dense, schedule 1 (K >= 192), the
 // BF16 / SWIGLU8 / ROPE / RESID epilogues and the row-scaled SWIGLU8 / ROPE; any other returns -4.
+// wfmt == 2: W is the mxfp4 encoding - e2m1 codes [N/16][K/128][64][16] with wscale the e8m0 block
+// scales [N/16][K/128][16][4] bytes (ops.pack_skinny_f4).  The same compiled forms as fp8, K % 128 == 0
+// and K >= 256; any other returns -4.  wfmt: 0 bf16 (wscale null), 1 fp8, 2 mxfp4.
 extern "C" int k8sllm_gemm_tile(const void* X, const void* W, void* Y, int M, int N, int K, const int* offsets, int E,
                                 long w_es, int epi, int algo, const int* rope_pos, const float* rope_cs,
                                 int rope_heads, const float* rs_part, int rs_np, float rs_eps, void* resid, void* hw,
-                                const void* norm_w, float* ss_out, int wpk, const float* wscale, hipStream_t s) {
+                                const void* norm_w, float* ss_out, int wpk, const void* wscale, int wfmt,
+                                hipStream_t s) {
+  if (wfmt < 0 || wfmt > 2 || (wfmt != 0) != (wscale != nullptr)) return -4;
   if (M <= 0) return 0;
-  const bool f8 = wscale != nullptr;
+  const bool f8 = wfmt == 1, f4 = wfmt == 2;
+  // mxfp4 W: as fp8 below, and whole 128-deep scale groups (two k-tiles per code block)
+  if (f4 && (offsets != nullptr || algo != 1 || K < 256 || K % 128 != 0 || epi == TILE_EPI_SWIGLU)) return -4;
   // fp8 W: only the forms a packed dense layer launches are compiled - no silent other schedule
   if (f8 && (offsets != nullptr || algo != 1 || K < 192 || epi == TILE_EPI_SWIGLU)) return -4;
   const bool grouped = offsets != nullptr;
@@ -667,15 +789,18 @@ extern "C" int k8sllm_gemm_tile(const void* X, const void* W, void* Y, int M, in
   const TileEpi ep{rope_pos, rope_cs, rope_heads, rs_part, rs_np, rs_eps, (bf16_t*)resid, (bf16_t*)hw,
                    (const bf16_t*)norm_w, ss_out};
   // 32-bit DMA offsets (X: relative to the tile's first row; W: within one expert / n-tile)
-  if ((long)N * K * (f8 ? 1 : 2) >= (1L << 31) || 256L * K * 2 >= (1L << 31)) return -3;
+  if ((f4 ? (long)N * K / 2 : (long)N * K * (f8 ? 1 : 2)) >= (1L << 31) || 256L * K * 2 >= (1L << 31)) return -3;
   if (epi == TILE_EPI_RESID && 256L * N * 2 >= (1L << 31)) return -3;
   const int n_mt = (M + 255) / 256 + (grouped ? E : 0), n_nt = (N + 255) / 256;
   const long nwg = (long)n_mt * n_nt;
   if (nwg > (1L << 30)) return -2;
   const dim3 grid((unsigned)nwg);
-#define K8_TILE_LAUNCH_F(EPI_, G_, SCH_, RS_, F8_)                                                                   \
-  hipLaunchKernelGGL((gemm_w4_kernel<EPI_, G_, SCH_, RS_, F8_>), grid, dim3(256), 0, s, (const bf16_t*)X,           \
-                     (const bf16_t*)W, (bf16_t*)Y, offsets, E, M, N, K, w_es, n_mt, n_nt, ep, wpk, wscale)
+#define K8_TILE_LAUNCH_Q(EPI_, G_, SCH_, RS_, F8_, F4_)                                                              \
+  hipLaunchKernelGGL((gemm_w4_kernel<EPI_, G_, SCH_, RS_, F8_, F4_>), grid, dim3(256), 0, s, (const bf16_t*)X,      \
+                     (const bf16_t*)W, (bf16_t*)Y, offsets, E, M, N, K, w_es, n_mt, n_nt, ep, wpk,                   \
+                     (const float*)wscale)
+#define K8_TILE_LAUNCH_F(EPI_, G_, SCH_, RS_, F8_) K8_TILE_LAUNCH_Q(EPI_, G_, SCH_, RS_, F8_, false)
+#define K8_TILE_LAUNCH_4(EPI_, RS_) K8_TILE_LAUNCH_Q(EPI_, false, 1, RS_, false, true)
 #define K8_TILE_LAUNCH(EPI_, G_, SCH_, RS_) K8_TILE_LAUNCH_F(EPI_, G_, SCH_, RS_, false)
 #define K8_TILE_SCH(SCH_)                                                                                            \
   if (grouped) {                                                                                                     \
@@ -688,7 +813,14 @@ extern "C" int k8sllm_gemm_tile(const void* X, const void* W, void* Y, int M, in
     else if (epi == TILE_EPI_ROPE) K8_TILE_LAUNCH(TILE_EPI_ROPE, false, SCH_, false);                                \
     else K8_TILE_LAUNCH(TILE_EPI_BF16, false, SCH_, false);                                                          \
   }
-  if (f8) {
+  if (f4) {
+    if (epi == TILE_EPI_RESID) K8_TILE_LAUNCH_4(TILE_EPI_RESID, false);
+    else if (epi == TILE_EPI_SWIGLU8 && rs) K8_TILE_LAUNCH_4(TILE_EPI_SWIGLU8, true);
+    else if (epi == TILE_EPI_SWIGLU8) K8_TILE_LAUNCH_4(TILE_EPI_SWIGLU8, false);
+    else if (epi == TILE_EPI_ROPE && rs) K8_TILE_LAUNCH_4(TILE_EPI_ROPE, true);
+    else if (epi == TILE_EPI_ROPE) K8_TILE_LAUNCH_4(TILE_EPI_ROPE, false);
+    else K8_TILE_LAUNCH_4(TILE_EPI_BF16, false);
+  } else if (f8) {
     if (epi == TILE_EPI_RESID) K8_TILE_LAUNCH_F(TILE_EPI_RESID, false, 1, false, true);
     else if (epi == TILE_EPI_SWIGLU8 && rs) K8_TILE_LAUNCH_F(TILE_EPI_SWIGLU8, false, 1, true, true);
     else if (epi == TILE_EPI_SWIGLU8) K8_TILE_LAUNCH_F(TILE_EPI_SWIGLU8, false, 1, false, true);
@@ -709,5 +841,7 @@ extern "C" int k8sllm_gemm_tile(const void* X, const void* W, void* Y, int M, in
 #undef K8_TILE_SCH
 #undef K8_TILE_LAUNCH
 #undef K8_TILE_LAUNCH_F
+#undef K8_TILE_LAUNCH_4
+#undef K8_TILE_LAUNCH_Q
   return (int)hipGetLastError();
 }

@@ -9,7 +9,9 @@ replay of back-to-back calls; the SwiGLU rows compare the fused epilogue with F.
 against the packed bf16 form of the same weights, in one process, interleaved, on the four
 Llama-3-8B projections with the epilogues the fused-norm prefill layer launches: qkv RoPE + row
 scale, o residual, gate_up SwiGLU8 + row scale, down residual.  Also checks that the two forms
-give the same bits.
+give the same bits.  ``--f4`` adds the mxfp4-W form (prefill_weights: mxfp4 - the decode GEMMs' e2m1
+codes and e8m0 block scales) of the same random weights as a third implementation in the same
+rounds, checked for the same bits against the packed bf16 form of ITS dequantised values.
 """
 from __future__ import annotations
 
@@ -28,7 +30,7 @@ from tools.bench_skinny import timeit  # noqa: E402
 F_ = torch.nn.functional
 
 
-def f8_cases(T: int, dev: str) -> list:
+def f8_cases(T: int, dev: str, f4: bool = False) -> list:
     from k8s_llm_monitor_amd.ops import reference as ref
 
     d, F = 4096, 14336
@@ -42,10 +44,20 @@ def f8_cases(T: int, dev: str) -> list:
     ssb = torch.empty(T, d // 128, device=dev, dtype=torch.float32)
     nwv = torch.ones(d, device=dev, dtype=torch.bfloat16)
 
+    w4s: list = []  # --f4: (packed codes, packed block scales) of each case's weight, in enc() order
+
     def enc(N, K, il=False):
         w = (torch.randn(N, K, device=dev) * 0.02).to(torch.bfloat16)
-        q, s = ops.quantize_rows_fp8(ops.interleave_gate_up8(w) if il else w)
+        w = ops.interleave_gate_up8(w) if il else w
+        if f4:
+            w4s.append(ops.pack_skinny_f4(*ops.quantize_mxfp4(w)))
+        q, s = ops.quantize_rows_fp8(w)
         return ops.pack_skinny(ops.dequantize_rows_fp8(q, s)), ops.pack_skinny_f8(q), s.contiguous()
+
+    def same_bits(c4, s4, run):  # the mxfp4 launch against the packed bf16 launch over its own values
+        wb4 = ops.pack_skinny(ops.dequantize_mxfp4(*ops.unpack_skinny_f4(c4, s4)))
+        a = [t.clone() for t in run(wb4, None)]
+        assert all(torch.equal(u, v) for u, v in zip(a, run(c4, s4))), "mxfp4 W differs from the bf16 packed launch"
 
     cases = []
     wb, wq, ws = enc(6144, d)
@@ -55,11 +67,26 @@ def f8_cases(T: int, dev: str) -> list:
     cases.append(("qkv+rope_rs", 2 * T * 6144 * d, {
         "bf16": (lambda i, wb=wb, kw=kw: ops.gemm_tile(x, wb, **kw)),
         "fp8": (lambda i, wq=wq, ws=ws, kw=kw: ops.gemm_tile(x, wq, wscale=ws, **kw))}))
+    if f4:
+        c4, s4 = w4s[-1]
+        same_bits(c4, s4, lambda w, sc: (ops.gemm_tile(x, w, wscale=sc, **kw),))
+        cases[-1][2]["mxfp4"] = (lambda i, c4=c4, s4=s4, kw=kw: ops.gemm_tile(x, c4, wscale=s4, **kw))
     for name, K, xin in (("o_resid", d, x), ("down_resid", F, xf)):
         wb, wq, ws = enc(d, K)
+        if f4:
+            c4, s4 = w4s[-1]
+
+            def resid_run(w, sc, xin=xin):
+                r = resid.clone()
+                h, ss_ = ops.gemm_tile_resid(xin, w, r, nwv, wscale=sc)
+                return r, h, ss_
+            same_bits(c4, s4, resid_run)
         cases.append((name, 2 * T * d * K, {
             "bf16": (lambda i, wb=wb, xin=xin: ops.gemm_tile_resid(xin, wb, resid, nwv, hw=hwb, ss=ssb)),
             "fp8": (lambda i, wq=wq, ws=ws, xin=xin: ops.gemm_tile_resid(xin, wq, resid, nwv, hw=hwb, ss=ssb, wscale=ws))}))
+        if f4:
+            cases[-1][2]["mxfp4"] = (lambda i, c4=c4, s4=s4, xin=xin: ops.gemm_tile_resid(
+                xin, c4, resid, nwv, hw=hwb, ss=ssb, wscale=s4))
     wb, wq, ws = enc(2 * F, d, il=True)
     act = torch.empty(T, F, device=dev, dtype=torch.bfloat16)
     kw2 = dict(swiglu=8, out=act, algo=1, rowscale=(ssq, 1e-5))
@@ -67,6 +94,10 @@ def f8_cases(T: int, dev: str) -> list:
     cases.append(("gate_up+swiglu8_rs", 2 * T * 2 * F * d, {
         "bf16": (lambda i, wb=wb: ops.gemm_tile(x, wb, **kw2)),
         "fp8": (lambda i, wq=wq, ws=ws: ops.gemm_tile(x, wq, wscale=ws, **kw2))}))
+    if f4:
+        c4, s4 = w4s[-1]
+        same_bits(c4, s4, lambda w, sc: (ops.gemm_tile(x, w, wscale=sc, **kw2),))
+        cases[-1][2]["mxfp4"] = (lambda i, c4=c4, s4=s4: ops.gemm_tile(x, c4, wscale=s4, **kw2))
     return cases
 
 
@@ -94,12 +125,13 @@ def main() -> None:
     ap.add_argument("--only", default="")
     ap.add_argument("--impl", default="", help="comma list of implementations to time (default all)")
     ap.add_argument("--f8", action="store_true", help="the fp8-W form against the packed bf16 form (see above)")
+    ap.add_argument("--f4", action="store_true", help="--f8 with the mxfp4-W form as a third implementation")
     a = ap.parse_args()
     dev = "cuda"
     T = a.tokens
     torch.manual_seed(0)
-    if a.f8:
-        run_cases(f8_cases(T, dev), a, T)
+    if a.f8 or a.f4:
+        run_cases(f8_cases(T, dev, a.f4), a, T)
         return
     cases = []
     d, F = 4096, 14336

@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """What ``llm.prefill_weights: fp8`` costs and saves, end to end, in ONE process on one box: for
 each weight mode - ``bf16``, ``fp8`` (decode_weights: fp8, codes beside the bf16 copy) and
-``fp8only`` (+ prefill_weights: fp8, the bf16 copy released) - build the engine, warm it up and
+``fp8only`` (+ prefill_weights: fp8, the bf16 copy released), and the same pair over MXFP4
+(``mxfp4``, ``mxfp4only``) - build the engine, warm it up and
 record
 
   * ``resident_weight_bytes`` (engine.stats()) and the GPU allocator's figures after warm-up,
@@ -26,7 +27,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import torch  # noqa: E402
 
-MODES = {"bf16": {}, "fp8": {"decode_weights": "fp8"}, "fp8only": {"decode_weights": "fp8", "prefill_weights": "fp8"}}
+MODES = {"bf16": {}, "fp8": {"decode_weights": "fp8"}, "fp8only": {"decode_weights": "fp8", "prefill_weights": "fp8"},
+         "mxfp4": {"decode_weights": "mxfp4"}, "mxfp4only": {"decode_weights": "mxfp4", "prefill_weights": "mxfp4"}}
 
 
 def main() -> None:

@@ -797,12 +797,6 @@ def dequantize_codes(w: torch.Tensor, scale: torch.Tensor, dtype=torch.bfloat16)
     return dequantize_rows_fp8(unpack_skinny_f8(w), scale, dtype)
 
 
-def tile_codes_ok(w: torch.Tensor) -> bool:
-    """gemm_tile has a form that reads the codes tensor ``w`` (tile_f8_ok / tile_f4_ok of its shape)."""
-    N, K = skinny_wdims(w)
-    return tile_f4_ok(N, K) if is_mxfp4(w) else tile_f8_ok(N, K)
-
-
 def _dec_gemm(name: str, a: torch.Tensor, w: torch.Tensor, wscale: Optional[torch.Tensor], epi: int, rows: int,
               workspace: Optional[torch.Tensor], out: Optional[torch.Tensor], rownorm: Optional[tuple],
               row_w: Optional[torch.Tensor], cfg: Optional[tuple], E: int) -> int:
@@ -1381,29 +1375,211 @@ def moe_grouped_gemm(x: torch.Tensor, w: torch.Tensor, offsets: torch.Tensor, sw
     allocated here).  GPU: no host synchronisation (gemm_tile.hip 256 x 256 tiles where N % 256 == 0,
     else moe_gemm.hip).  A fragment-packed ``w`` [E, N/16, K/32, 64, 8] (ONE_LAYOUT; ``swiglu=8``:
     the per-16 gate/up pairing) always takes the tile kernel."""
-    if w.dim() == 5:
-        if out is None:
-            alloc = torch.zeros if zero_fill else torch.empty
-            out = alloc(x.shape[0], w.shape[1] * 8 if swiglu else w.shape[1] * 16, dtype=x.dtype, device=x.device)
-        return gemm_tile(x, w, offsets, swiglu=swiglu, out=out, algo=TILE_ALGO)
-    E, N, K = w.shape
+    packed = w.dim() == 5
+    N, K = (w.shape[1] * 16, w.shape[2] * 32) if packed else w.shape[1:]
     if out is None:  # zero_fill=False when ``offsets`` covers every row (all experts are local)
         alloc = torch.zeros if zero_fill else torch.empty
         out = alloc(x.shape[0], N // 2 if swiglu else N, dtype=x.dtype, device=x.device)
-    if not _gpu(x):
+    epi = _tile_epi(swiglu)
+    # the 256 x 256 tile kernel (gemm_tile.hip) where it has whole n-tiles: 1.12-1.15 PF/s on Mixtral's
+    # expert shapes against 0.86-0.94 for the 128-tile kernel (profiles/r02/gemm_tile_vs_hipblaslt.jsonl).
+    # (The expert count is no part of the routing: past the kernel's limit the binding refuses.)
+    if packed or not _gpu(x) or (N % 256 == 0 and tile_form_why("bf16", epi, 1, 0, TILE_ALGO, N, K) is None):
+        return _gemm_tile(x, w, None, epi, TILE_ALGO, offsets=offsets, out=out)
+    native().moe_grouped_gemm(out, x.contiguous(), w, offsets.contiguous(), swiglu)
+    return out
+
+
+# ---------------------------------------------------------------- the prefill tile GEMM's forms
+# The compiled forms of gemm_tile as (weight format, epilogue, grouped, row scale, also at
+# schedule 0): the rows of kTileForms in csrc/gemm_tile_forms.h - where the table of accepted
+# launches stands, above tile_plan - which native().gemm_tile_forms() reports
+# (tests/test_tile_plan_cpu.py compares the two).  Kept here as well because the CPU path refuses
+# what the kernel has no form for, with no extension built.
+TILE_EPI_BF16, TILE_EPI_SWIGLU, TILE_EPI_ROPE, TILE_EPI_RESID, TILE_EPI_SWIGLU8 = range(5)
+TILE_ENCS = ("bf16", "fp8", "mxfp4")  # enc_name(w); the index is the weight format (TILE_W_*)
+# kTileFmts, per weight format: (least K, depth of a scale group along K or 0, bits per weight)
+TILE_FMTS = ((64, 0, 16), (192, 0, 8), (256, 128, 4))
+TILE_SCH1_MIN_K = 192  # schedule 1's peeled ring tail needs three k-tiles; below, bf16 runs schedule 0
+TILE_MAX_EXPERTS = 256
+TILE_FORMS: tuple = (
+    (0, TILE_EPI_BF16, 0, 0, 1),
+    (0, TILE_EPI_SWIGLU, 0, 0, 1),
+    (0, TILE_EPI_SWIGLU8, 0, 0, 1),
+    (0, TILE_EPI_ROPE, 0, 0, 1),
+    (0, TILE_EPI_RESID, 0, 0, 0),
+    (0, TILE_EPI_SWIGLU, 0, 1, 0),
+    (0, TILE_EPI_SWIGLU8, 0, 1, 0),
+    (0, TILE_EPI_ROPE, 0, 1, 0),
+    (0, TILE_EPI_BF16, 1, 0, 1),
+    (0, TILE_EPI_SWIGLU, 1, 0, 1),
+    (0, TILE_EPI_SWIGLU8, 1, 0, 1),
+) + tuple((fmt, epi, 0, rs, 0) for fmt in (1, 2) for epi, rs in (
+    (TILE_EPI_BF16, 0), (TILE_EPI_SWIGLU8, 0), (TILE_EPI_SWIGLU8, 1), (TILE_EPI_ROPE, 0), (TILE_EPI_ROPE, 1),
+    (TILE_EPI_RESID, 0)))
+_TILE_EPI_NAMES = ("plain", "swiglu=1 (per-128 pairing)", "RoPE", "residual", "swiglu=8")
+# the table by key (every prefill GEMM asks it): row -> has schedule 0; (format, epilogue) pairs; grouped formats
+_TILE_SCH0 = {f[:4]: f[4] for f in TILE_FORMS}
+_TILE_FMT_EPI = {f[:2] for f in TILE_FORMS}
+_TILE_FMT_GROUPED = {f[0] for f in TILE_FORMS if f[2]}
+
+
+def _tile_epi(swiglu, rope=None) -> int:
+    return TILE_EPI_ROPE if rope is not None else TILE_EPI_SWIGLU8 if swiglu == 8 else \
+        TILE_EPI_SWIGLU if swiglu else TILE_EPI_BF16
+
+
+def tile_form_why(enc: str, epi: int, experts: int = 0, rs_np: int = 0, sch: Optional[int] = 1, N: int = 0,
+                  K: int = 0, full: bool = True) -> Optional[str]:
+    """THE rule of gemm_tile's forms, tile_plan's twin (csrc/gemm_tile_forms.h; tests/test_tile_plan_cpu.py
+    sweeps the two against each other): None where TILE_FORMS has a form for a weight in encoding
+    ``enc`` [N, K] with epilogue ``epi`` over ``experts`` experts (0: dense), ``rs_np`` row-scale
+    partial sums per row (0: no row scale), requested schedule ``sch``; else the reason, as the
+    ValueError's text.  ``full=False`` asks only what defines the op - a row of the table, heads and
+    partial sums of 128 columns, and (``sch`` not None) that the row has the schedule: what is
+    asked for a bf16 weight, whose CPU reference takes any shape and whose launch the binding
+    checks against tile_plan; codes are refused here, in full, on the CPU as on the GPU."""
+    fmt = TILE_ENCS.index(enc)
+    min_k, k_group, bits = TILE_FMTS[fmt]
+    grouped, rs = experts != 0, rs_np != 0
+    if grouped and fmt not in _TILE_FMT_GROUPED:
+        return f"gemm_tile: the {enc}-W form is not compiled for grouped launches"
+    if 0 <= epi < len(_TILE_EPI_NAMES) and (fmt, epi) not in _TILE_FMT_EPI:
+        return f"gemm_tile: the {enc}-W form is not compiled for {_TILE_EPI_NAMES[epi]} launches"
+    sch0 = _TILE_SCH0.get((fmt, epi, int(grouped), int(rs)))
+    if sch0 is None:
+        return (f"gemm_tile: no {'grouped' if grouped else 'dense'} {enc} form with epilogue {epi}"
+                f"{' and a row scale' if rs else ''}: RoPE, the residual epilogue and the row scale are dense, "
+                "and the row scale is for the fused consumers (SwiGLU or RoPE)")
+    if epi in (TILE_EPI_ROPE, TILE_EPI_RESID) and N % 128:
+        return f"gemm_tile: the {_TILE_EPI_NAMES[epi]} epilogue needs N % 128 == 0, not N={N}"
+    if sch is not None:
+        if fmt and sch != 1:
+            return f"gemm_tile: the {enc}-W form is compiled for schedule 1 (algo=1) only, not schedule {sch}"
+        if full and sch not in (0, 1):
+            return f"gemm_tile: schedule (algo) 0 or 1, not {sch}"
+        if (sch != 1 or (full and K < TILE_SCH1_MIN_K)) and not sch0:
+            return (f"gemm_tile: the {_TILE_EPI_NAMES[epi]} epilogue{' with a row scale' if rs else ''} needs "
+                    f"schedule 1 (algo=1) and K >= {TILE_SCH1_MIN_K}, not schedule {sch} at K={K}")
+    if not full:
+        return None
+    why = None
+    if experts < 0 or experts > TILE_MAX_EXPERTS:
+        why = f"1..{TILE_MAX_EXPERTS} experts"
+    elif rs and (rs_np < 4 or rs_np > 64 or rs_np % 4):
+        why = "4..64 row-scale partial sums per row, a multiple of 4"
+    elif N % 16 or K % 64 or K < min_k or (k_group and K % k_group):
+        why = f"N % 16 == 0, K >= {min_k}, K % {k_group or 64} == 0"
+    elif epi in (TILE_EPI_SWIGLU, TILE_EPI_SWIGLU8) and N % 256:
+        why = "SwiGLU: N % 256 == 0"
+    elif N * K // 8 * bits >= 1 << 31 or 256 * K * 2 >= 1 << 31 or (epi == TILE_EPI_RESID and 256 * N * 2 >= 1 << 31):
+        why = "32-bit DMA offsets: the weight, 256 rows of x and of the residual below 2^31 bytes"
+    return None if why is None else f"gemm_tile: no {enc} form for N={N} K={K} ({why})"
+
+
+def tile_f8_ok(N: int, K: int) -> bool:
+    """gemm_tile has an fp8-W form for a dense weight [N, K] (schedule 1 only: at least three k-tiles)."""
+    return tile_form_why("fp8", TILE_EPI_BF16, N=N, K=K) is None
+
+
+def tile_f4_ok(N: int, K: int) -> bool:
+    """gemm_tile has an mxfp4-W form for a dense weight [N, K] (whole 128-deep scale groups, at least two)."""
+    return tile_form_why("mxfp4", TILE_EPI_BF16, N=N, K=K) is None
+
+
+def tile_codes_ok(w: torch.Tensor) -> bool:
+    """gemm_tile has a form that reads the codes tensor ``w`` (tile_f8_ok / tile_f4_ok of its shape)."""
+    N, K = skinny_wdims(w)
+    return tile_form_why(enc_name(w), TILE_EPI_BF16, N=N, K=K) is None
+
+
+def _tile_codes_check(w: torch.Tensor, wscale: Optional[torch.Tensor], enc: str) -> None:
+    """The tensors of a quantised W of gemm_tile: the codes' layout and the scales that go with them."""
+    f4 = enc == "mxfp4"
+    if w.dim() != 4 or w.shape[-2:] != (64, 16):
+        raise ValueError(f"gemm_tile: an {enc} w is pack_skinny_f{4 if f4 else 8}'s [N/16, K/{128 if f4 else 64}, 64, 16]")
+    N, K = skinny_wdims(w)
+    shape, dtype = ((N // 16, K // 128, 16, 4), torch.uint8) if f4 else ((N,), torch.float32)
+    if wscale is None or wscale.dtype != dtype or (tuple(wscale.shape) != shape if f4 else wscale.numel() != N):
+        raise ValueError(f"gemm_tile: an {enc} weight needs its {list(shape)} {dtype} scales")
+
+
+def _gemm_tile(x: torch.Tensor, w: torch.Tensor, wscale: Optional[torch.Tensor], epi: int, algo: int,
+               offsets: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+               rope: Optional[tuple] = None, rowscale: Optional[tuple] = None, resid: Optional[torch.Tensor] = None,
+               norm_w: Optional[torch.Tensor] = None, hw: Optional[torch.Tensor] = None,
+               ss: Optional[torch.Tensor] = None):
+    """The one body of gemm_tile, gemm_tile_resid and moe_grouped_gemm's tile launches: the checks
+    (tile_form_why), the CPU reference over the decoded W, and THE native().gemm_tile call.
+    Returns ``out``, or ``(hw, ss)`` for the residual epilogue."""
+    M = x.shape[0]
+    grouped, gpu = offsets is not None, _gpu(x)
+    enc = "mxfp4" if w.dtype == torch.uint8 else "fp8" if w.dtype == torch.float8_e4m3fn else "bf16"
+    quant, swg = enc != "bf16", epi in (TILE_EPI_SWIGLU, TILE_EPI_SWIGLU8)
+    packed = w.dim() == (5 if grouped else 4)
+    N = w.shape[-4] * 16 if packed else w.shape[-2]
+    rs_np = rowscale[0].shape[1] if rowscale is not None else 0
+    why = tile_form_why(enc, epi, int(grouped), rs_np, algo if quant or gpu else None, N, x.shape[1], full=quant)
+    if why is not None:
+        raise ValueError(why)
+    if quant:
+        _tile_codes_check(w, wscale, enc)
+    if epi == TILE_EPI_RESID:
+        if resid.shape != (M, N):
+            raise ValueError("gemm_tile_resid: resid [M, N]")
+        hw = hw if hw is not None else torch.empty_like(resid)
+        ss = ss if ss is not None else torch.empty(M, N // 128, dtype=torch.float32, device=resid.device)
+    elif out is None:
+        alloc = torch.zeros if grouped else torch.empty
+        out = alloc(M, N // 2 if swg else N, dtype=x.dtype, device=x.device)
+    if gpu:
+        pos, cs, heads = rope if rope is not None else (None, None, 0)
+        rs_part, rs_eps = rowscale if rowscale is not None else (None, 1e-5)
+        native().gemm_tile(y=out if resid is None else resid, x=x.contiguous(), w=w,
+                           offsets=offsets.contiguous() if grouped else None,
+                           swiglu=8 if epi == TILE_EPI_SWIGLU8 else int(swg), algo=algo, rope_pos=pos, rope_cs=cs,
+                           rope_heads=heads, rs_part=rs_part, rs_eps=rs_eps, resid=resid, hw=hw,
+                           norm_w=norm_w.contiguous() if norm_w is not None else None, ss_out=ss, wscale=wscale)
+        return out if resid is None else (hw, ss)
+    if quant:  # the dequantised values: exactly the bf16 encoding's
+        w = dequantize_codes(w, wscale, x.dtype)
+    elif packed:
+        w = torch.stack([unpack_skinny(e) for e in w]) if grouped else unpack_skinny(w)
+    inv = None
+    if rowscale is not None:
+        ssp, eps = rowscale
+        inv = torch.rsqrt(ssp[:M].float().sum(1, keepdim=True) / x.shape[1] + eps)
+
+    def one(xr, wr):
+        y = torch.nn.functional.linear(xr.float(), wr.float())
+        if inv is not None:
+            y = y * inv
+        y = y.to(x.dtype)
+        if epi == TILE_EPI_SWIGLU8:
+            g = y.view(y.shape[0], -1, 16)
+            return (torch.nn.functional.silu(g[..., :8].float()) * g[..., 8:].float()).reshape(y.shape[0], -1).to(x.dtype)
+        return silu_mul(y, interleaved=True) if swg else y
+    if epi == TILE_EPI_RESID:
+        h = (one(x, w).float() + resid.float()).to(resid.dtype)
+        resid.copy_(h)
+        hw.copy_((h.float() * norm_w.float()).to(hw.dtype))
+        ss.copy_((h.float() ** 2).view(M, N // 128, 128).sum(2))
+        return hw, ss
+    if grouped:
         off = offsets.tolist()
-        for e in range(E):
+        for e in range(w.shape[0]):
             a, b = off[e], off[e + 1]
             if b > a:
-                y = torch.nn.functional.linear(x[a:b].float(), w[e].float()).to(x.dtype)
-                out[a:b] = silu_mul(y, interleaved=True) if swiglu else y
+                out[a:b] = one(x[a:b], w[e])
         return out
-    if N % 256 == 0 and K % 64 == 0 and N * K * 2 < (1 << 31):
-        # the 256 x 256 tile kernel (gemm_tile.hip): 1.12-1.15 PF/s on Mixtral's expert shapes
-        # against 0.86-0.94 for the 128-tile kernel below (profiles/r02/gemm_tile_vs_hipblaslt.jsonl)
-        native().gemm_tile(out, x.contiguous(), w, offsets.contiguous(), swiglu, TILE_ALGO)
-    else:
-        native().moe_grouped_gemm(out, x.contiguous(), w, offsets.contiguous(), swiglu)
+    out.copy_(one(x, w))
+    if rope is not None:
+        pos, cs, heads = rope
+        h = out[:, : heads * 128].view(M, heads, 128).float()
+        c = cs[pos.long(), :64].float()[:, None]
+        s_ = cs[pos.long(), 64:].float()[:, None]
+        a, b = h[..., :64], h[..., 64:]
+        out[:, : heads * 128] = torch.cat([a * c - b * s_, b * c + a * s_], -1).reshape(M, -1).to(out.dtype)
     return out
 
 
@@ -1416,135 +1592,27 @@ def gemm_tile(x: torch.Tensor, w: torch.Tensor, offsets: Optional[torch.Tensor] 
     each expert's rows in the expert-sorted ``x`` (moe_align; a slice for this rank's experts) - no
     host synchronisation.  ``swiglu``: ``w`` is gate/up-interleaved (interleave_gate_up) and the
     result is silu(gate) * up [M, N / 2].  Grouped rows outside the offsets are left as in ``out``
-    (zeros when allocated here).  ``rope = (positions [M] int32, cos_sin [P, 128] fp32, heads)``
-    (dense, N % 128 == 0): the epilogue applies rotate-half RoPE (head_dim 128) to output heads
-    0 .. heads - 1 of each row at its position, on the bf16-rounded product.
-    ``rowscale = (ss_part [M, K / 128] fp32, eps)`` (dense, with ``swiglu`` or ``rope``, schedule 1):
-    the deferred half of an RMSNorm - every row of the product is multiplied by
-    rsqrt(sum(ss_part[row]) / K + eps) before the epilogue (``x`` holds the norm's weighted input,
-    gemm_tile_resid's ``hw``).
+    (zeros when allocated here).  ``rope = (positions [M] int32, cos_sin [P, 128] fp32, heads)``:
+    the epilogue applies rotate-half RoPE (head_dim 128) to output heads 0 .. heads - 1 of each row
+    at its position, on the bf16-rounded product.
+    ``rowscale = (ss_part [M, K / 128] fp32, eps)``: the deferred half of an RMSNorm - every row of
+    the product is multiplied by rsqrt(sum(ss_part[row]) / K + eps) before the epilogue (``x`` holds
+    the norm's weighted input, gemm_tile_resid's ``hw``).
     ``w`` may also be fragment-packed (pack_skinny: [N/16, K/32, 64, 8], grouped [E, ...]): the
     decode GEMMs' layout, consumed as is (every W DMA piece one contiguous 1-KiB block).
     ``swiglu=8``: the gate/up rows are interleaved per 16 (interleave_gate_up8, the decode GEMMs'
     SwiGLU copy) instead of per 128 - prefill and decode then share one weight.
     ``w`` may be the fp8 decode encoding (pack_skinny_f8 codes [N/16, K/64, 64, 16]) with ``wscale``
-    its [N] fp32 row scales in packed row order: the codes are converted on the way into the MFMA,
-    bit-identical to the packed bf16 form over the dequantised weight.  Compiled for dense
-    launches on schedule 1 with K >= 192 (tile_f8_ok), plain / ``swiglu=8`` / ``rope`` with or
-    without ``rowscale``; any other form raises.
-    ``w`` may be the mxfp4 decode encoding (pack_skinny_f4 codes [N/16, K/128, 64, 16] uint8) with
-    ``wscale`` its e8m0 block scales [N/16, K/128, 16, 4] uint8 - the tensors gemm_dec streams, converted
-    with the block scale on the way into the MFMA, bit-identical to the packed bf16 form over the
-    dequantised weight.  The same compiled forms as fp8, K % 128 == 0 and K >= 256 (tile_f4_ok)."""
-    M = x.shape[0]
-    f8, f4 = is_fp8(w), w.dtype == torch.uint8
-    if f8 or f4:
-        (_tile_f4_check if f4 else _tile_f8_check)(
-            w, wscale, "grouped" if offsets is not None else "swiglu=1 (per-128 pairing)"
-            if swiglu and swiglu != 8 else None, algo)
-    packed = w.dim() == (5 if offsets is not None else 4)
-    N = w.shape[-4] * 16 if packed else w.shape[-2]
-    if out is None:
-        alloc = torch.zeros if offsets is not None else torch.empty
-        out = alloc(M, N // 2 if swiglu else N, dtype=x.dtype, device=x.device)
-    if rope is not None and (offsets is not None or swiglu or N % 128):
-        raise ValueError("gemm_tile: the RoPE epilogue is dense, without SwiGLU, N % 128 == 0")
-    if rowscale is not None and (offsets is not None or not (swiglu or rope is not None)):
-        raise ValueError("gemm_tile: the row scale is for the dense fused consumers (SwiGLU or RoPE)")
-    if not _gpu(x):
-        if f8:  # the dequantised values: exactly the bf16 encoding's
-            w = dequantize_rows_fp8(unpack_skinny_f8(w), wscale, x.dtype)
-        elif f4:
-            w = dequantize_mxfp4(*unpack_skinny_f4(w, wscale), dtype=x.dtype)
-        elif packed:
-            w = (torch.stack([unpack_skinny(e) for e in w]) if offsets is not None else unpack_skinny(w))
-        inv = None
-        if rowscale is not None:
-            ssp, eps = rowscale
-            inv = torch.rsqrt(ssp[:M].float().sum(1, keepdim=True) / x.shape[1] + eps)
-
-        def one(xr, wr):
-            y = torch.nn.functional.linear(xr.float(), wr.float())
-            if inv is not None:
-                y = y * inv
-            y = y.to(x.dtype)
-            if swiglu == 8:
-                g = y.view(y.shape[0], -1, 16)
-                return (torch.nn.functional.silu(g[..., :8].float()) * g[..., 8:].float()).reshape(y.shape[0], -1).to(x.dtype)
-            return silu_mul(y, interleaved=True) if swiglu else y
-        if offsets is None:
-            out.copy_(one(x, w))
-            if rope is not None:
-                pos, cs, heads = rope
-                h = out[:, : heads * 128].view(M, heads, 128).float()
-                c = cs[pos.long(), :64].float()[:, None]
-                s_ = cs[pos.long(), 64:].float()[:, None]
-                a, b = h[..., :64], h[..., 64:]
-                out[:, : heads * 128] = torch.cat([a * c - b * s_, b * c + a * s_], -1).reshape(M, -1).to(out.dtype)
-        else:
-            off = offsets.tolist()
-            for e in range(w.shape[0]):
-                a, b = off[e], off[e + 1]
-                if b > a:
-                    out[a:b] = one(x[a:b], w[e])
-        return out
-    rs_part, rs_eps = rowscale if rowscale is not None else (None, 1e-5)
-    if rowscale is not None and algo != 1:
-        raise ValueError("gemm_tile: the row scale needs schedule 1")
-    if rope is not None:
-        pos, cs, heads = rope
-        native().gemm_tile(out, x.contiguous(), w, None, False, algo, pos, cs, heads, rs_part, rs_eps, wscale=wscale)
-    elif rowscale is not None:
-        native().gemm_tile(out, x.contiguous(), w, None, int(swiglu), algo, None, None, 0, rs_part, rs_eps,
-                           wscale=wscale)
-    else:
-        native().gemm_tile(out, x.contiguous(), w, offsets.contiguous() if offsets is not None else None,
-                           int(swiglu), algo, wscale=wscale)
-    return out
-
-
-def tile_f8_ok(N: int, K: int) -> bool:
-    """gemm_tile has an fp8-W form for a dense weight [N, K]: whole 16-row blocks and 64-deep
-    k-tiles, at least three of them (schedule 1's peeled ring tail; no schedule 0 form), and 32-bit
-    DMA byte offsets within the weight."""
-    return N % 16 == 0 and K % 64 == 0 and K >= 192 and N * K < (1 << 31)
-
-
-def _tile_f8_check(w: torch.Tensor, wscale: Optional[torch.Tensor], form: Optional[str], algo: int) -> None:
-    """An fp8 W of gemm_tile: only the compiled forms, no silent other path."""
-    if form is not None:
-        raise ValueError(f"gemm_tile: the fp8-W form is not compiled for {form} launches")
-    if w.dim() != 4 or w.shape[-2:] != (64, 16):
-        raise ValueError("gemm_tile: an fp8 w is pack_skinny_f8's [N/16, K/64, 64, 16]")
-    N, K = skinny_wdims(w)
-    if wscale is None or wscale.numel() != N or wscale.dtype != torch.float32:
-        raise ValueError(f"gemm_tile: an fp8 weight needs its [{N}] fp32 scale vector")
-    if algo != 1:
-        raise ValueError("gemm_tile: the fp8-W form is compiled for schedule 1 (algo=1) only, not schedule 0")
-    if not tile_f8_ok(N, K):
-        raise ValueError(f"gemm_tile: no fp8-W form for N={N} K={K} (K >= 192, K % 64 == 0, N * K < 2^31)")
-
-
-def tile_f4_ok(N: int, K: int) -> bool:
-    """gemm_tile has an mxfp4-W form for a dense weight [N, K]: whole 16-row blocks and 128-deep
-    scale groups (two 64-deep k-tiles per code block), at least two of them (schedule 1 needs three
-    k-tiles and K comes in 128s), and 32-bit DMA byte offsets within the codes."""
-    return N % 16 == 0 and K % 128 == 0 and K >= 256 and N * K // 2 < (1 << 31)
-
-
-def _tile_f4_check(w: torch.Tensor, wscale: Optional[torch.Tensor], form: Optional[str], algo: int) -> None:
-    """An mxfp4 W of gemm_tile: only the compiled forms, no silent other path."""
-    if form is not None:
-        raise ValueError(f"gemm_tile: the mxfp4-W form is not compiled for {form} launches")
-    if w.dim() != 4 or w.shape[-2:] != (64, 16):
-        raise ValueError("gemm_tile: an mxfp4 w is pack_skinny_f4's [N/16, K/128, 64, 16] uint8")
-    N, K = skinny_wdims(w)
-    if wscale is None or wscale.dtype != torch.uint8 or tuple(wscale.shape) != (N // 16, K // 128, 16, 4):
-        raise ValueError(f"gemm_tile: an mxfp4 weight needs its [{N // 16}, {K // 128}, 16, 4] uint8 block scales")
-    if algo != 1:
-        raise ValueError("gemm_tile: the mxfp4-W form is compiled for schedule 1 (algo=1) only, not schedule 0")
-    if not tile_f4_ok(N, K):
-        raise ValueError(f"gemm_tile: no mxfp4-W form for N={N} K={K} (K >= 256, K % 128 == 0, N * K / 2 < 2^31)")
+    its [N] fp32 row scales in packed row order, or the mxfp4 one (pack_skinny_f4 codes
+    [N/16, K/128, 64, 16] uint8) with ``wscale`` its e8m0 block scales [N/16, K/128, 16, 4] uint8 -
+    the tensors gemm_dec streams, converted on the way into the MFMA, bit-identical to the packed
+    bf16 form over the dequantised weight.
+    Which combinations of these are compiled, and for which N, K and schedule ``algo``: TILE_FORMS
+    and tile_form_why here, the table above tile_plan in csrc/gemm_tile_forms.h; any other raises."""
+    if rope is not None and swiglu:
+        raise ValueError("gemm_tile: one epilogue - SwiGLU or RoPE")
+    return _gemm_tile(x, w, wscale, _tile_epi(swiglu, rope), algo, offsets=offsets, out=out, rope=rope,
+                      rowscale=rowscale)
 
 
 def gemm_tile_resid(x: torch.Tensor, w: torch.Tensor, resid: torch.Tensor, norm_w: torch.Tensor,
@@ -1556,33 +1624,7 @@ def gemm_tile_resid(x: torch.Tensor, w: torch.Tensor, resid: torch.Tensor, norm_
     fp32 partial sums of resid^2 over each 128 columns, the operands of the consumer's row scale
     (``gemm_tile(hw, ..., rowscale=(ss, eps))`` = the projection of rms_norm(resid) * norm_w).
     ``w`` row-major, fragment-packed, or the fp8 / mxfp4 encoding with ``wscale`` (see gemm_tile)."""
-    M = x.shape[0]
-    f8, f4 = is_fp8(w), w.dtype == torch.uint8
-    if f8:
-        _tile_f8_check(w, wscale, None, 1)
-    elif f4:
-        _tile_f4_check(w, wscale, None, 1)
-    N = w.shape[0] * 16 if w.dim() == 4 else w.shape[0]  # row-major or fragment-packed W
-    if N % 128 or resid.shape != (M, N):
-        raise ValueError("gemm_tile_resid: N % 128 == 0 and resid [M, N]")
-    hw = hw if hw is not None else torch.empty_like(resid)
-    ss = ss if ss is not None else torch.empty(M, N // 128, dtype=torch.float32, device=resid.device)
-    if not _gpu(x):
-        if f8:
-            w = dequantize_rows_fp8(unpack_skinny_f8(w), wscale, x.dtype)
-        elif f4:
-            w = dequantize_mxfp4(*unpack_skinny_f4(w, wscale), dtype=x.dtype)
-        elif w.dim() == 4:
-            w = unpack_skinny(w)
-        y = torch.nn.functional.linear(x.float(), w.float()).to(x.dtype)
-        h = (y.float() + resid.float()).to(resid.dtype)
-        resid.copy_(h)
-        hw.copy_((h.float() * norm_w.float()).to(hw.dtype))
-        ss.copy_((h.float() ** 2).view(M, N // 128, 128).sum(2))
-        return hw, ss
-    native().gemm_tile(resid, x.contiguous(), w, None, False, TILE_ALGO, None, None, 0, None, 1e-5, resid, hw,
-                       norm_w.contiguous(), ss, wscale=wscale)
-    return hw, ss
+    return _gemm_tile(x, w, wscale, TILE_EPI_RESID, TILE_ALGO, resid=resid, norm_w=norm_w, hw=hw, ss=ss)
 
 
 # Prefill projections (qkv / o / gate_up + SwiGLU / down) on the hand-written 4-wave MFMA GEMM
@@ -1606,8 +1648,7 @@ TILE_ALGO = 1
 
 def tile_shape_ok(M: int, N: int, K: int, swiglu: bool = False) -> bool:
     """gemm_tile takes this prefill GEMM (rows, output columns, depth)."""
-    return (M >= TILE_MIN_M and N % 16 == 0 and K % 64 == 0 and K >= 128 and (not swiglu or N % 256 == 0)
-            and N * K * 2 < (1 << 31))
+    return M >= TILE_MIN_M and K >= 128 and tile_form_why("bf16", _tile_epi(swiglu), 0, 0, TILE_ALGO, N, K) is None
 
 
 def fused_norm_ok(M: int, d: int, n_qkv: int, n_o_in: int, n_13: int, f: int) -> bool:

@@ -7,6 +7,7 @@
 
 #include "gemm_dec_forms.h"
 #include "gemm_skinny_plan.h"
+#include "gemm_tile_forms.h"
 
 extern "C" {
 int k8sllm_rmsnorm(void* out, const void* x, void* residual, const void* w, long rows, int d, float eps,
@@ -51,6 +52,7 @@ int k8sllm_gemm_tile(const void* X, const void* W, void* Y, int M, int N, int K,
                      int epi, int algo, const int* rope_pos, const float* rope_cs, int rope_heads,
                      const float* rs_part, int rs_np, float rs_eps, void* resid, void* hw, const void* norm_w,
                      float* ss_out, int wpk, const void* wscale, int wfmt, hipStream_t s);
+int k8sllm_gemm_tile_forms(int* out, int cap);
 int k8sllm_moe_grouped_gemm(const void* X, const void* W, void* Y, const int* offsets, int E, long rows, int N, int K,
                             long w_es, int epi, hipStream_t s);
 int k8sllm_gemm_skinny(const void* A, long lda, const void* Wp, float* partial, void* Y, long ldy, int M, int N, int K,
@@ -436,24 +438,27 @@ void moe_grouped_gemm(torch::Tensor y, torch::Tensor x, torch::Tensor w, torch::
 
 // 256 x 256 MFMA GEMM (gemm_tile.hip) for prefill-sized projections: y = x . w^T, x [M, K], w [N, K]
 // (dense, offsets None) or w [E, N, K] with device offsets [E + 1] (grouped over expert-sorted rows,
-// no host sync).  swiglu: w gate/up-interleaved per 128 rows, y [M, N / 2] = silu(gate) * up.
-// rope_pos / rope_cs (dense, N % 128 == 0): the qkv projection with the rotary embedding of heads
-// 0 .. rope_heads - 1 (q and k, head_dim 128) applied in the epilogue (TILE_EPI_ROPE)
+// no host sync), row-major or fragment-packed [N/16, K/32, 64, 8] (pack_skinny); or the tensors
+// gemm_dec streams: fp8 codes [N/16, K/64, 64, 16] + wscale [N] fp32 (pack_skinny_f8), mxfp4 codes
+// [N/16, K/128, 64, 16] uint8 + wscale [N/16, K/128, 16, 4] uint8 (pack_skinny_f4).
 // swiglu: 0 none, 1 = gate/up interleaved per 128 rows (interleave_gate_up), 8 = per 16 rows
-// (interleave_gate_up8, the decode GEMMs' packed copy)
+// (interleave_gate_up8); rope_pos / rope_cs: RoPE of heads 0 .. rope_heads - 1 (head_dim 128) in the
+// epilogue; rs_part: the deferred RMSNorm row scale; resid / hw / norm_w / ss_out: the residual epilogue.
+// Which combinations are compiled and every limit on M, N, K, E and the schedule: tile_plan
+// (gemm_tile_forms.h).  Here: the tensors' layouts, dtypes, devices and sizes.
 void gemm_tile(torch::Tensor y, torch::Tensor x, torch::Tensor w, c10::optional<torch::Tensor> offsets, int64_t swiglu,
                int64_t algo, c10::optional<torch::Tensor> rope_pos, c10::optional<torch::Tensor> rope_cs,
                int64_t rope_heads, c10::optional<torch::Tensor> rs_part, double rs_eps,
                c10::optional<torch::Tensor> resid, c10::optional<torch::Tensor> hw,
                c10::optional<torch::Tensor> norm_w, c10::optional<torch::Tensor> ss_out,
                c10::optional<torch::Tensor> wscale) {
+  using namespace k8sllm;
   dev_bf16(y, "y"); dev_bf16(x, "x");
-  // fp8 W: e4m3 codes fragment-packed [N/16, K/64, 64, 16] (pack_skinny_f8) + wscale [N] fp32 in packed row order
-  // mxfp4 W: e2m1 codes [N/16, K/128, 64, 16] uint8 + wscale the e8m0 block scales [N/16, K/128, 16, 4] uint8
-  // (pack_skinny_f4) - the tensors gemm_dec streams
-  const bool f8 = w.scalar_type() == torch::kFloat8_e4m3fn;
-  const bool f4 = w.scalar_type() == torch::kUInt8;
-  if (f8 || f4) {
+  const int fmt = w.scalar_type() == torch::kFloat8_e4m3fn ? TILE_W_F8 : w.scalar_type() == torch::kUInt8 ? TILE_W_F4 : TILE_W_BF16;
+  const bool quant = fmt != TILE_W_BF16;
+  const std::string whats = std::string("gemm_tile (") + (fmt == TILE_W_F4 ? "mxfp4)" : fmt == TILE_W_F8 ? "fp8)" : "bf16)");
+  const char* what = whats.c_str();
+  if (quant) {
     TORCH_CHECK(w.is_cuda(), "w must be a GPU tensor");
   } else {
     dev_bf16(w, "w");
@@ -461,42 +466,47 @@ void gemm_tile(torch::Tensor y, torch::Tensor x, torch::Tensor w, c10::optional<
   TORCH_CHECK(x.dim() == 2 && x.is_contiguous() && w.is_contiguous() && y.is_contiguous(),
               "gemm_tile: x [M, K], w contiguous, y contiguous");
   const bool grouped = offsets.has_value();
-  // w row-major [N, K] / [E, N, K], or fragment-packed [N/16, K/32, 64, 8] / [E, ...] (pack_skinny)
-  const bool wpk = w.dim() == (grouped ? 5 : 4);
-  if (f4) {
-    TORCH_CHECK(!grouped, "gemm_tile: the mxfp4-W form is not compiled for grouped launches");
-    TORCH_CHECK(w.dim() == 4 && w.size(-2) == 64 && w.size(-1) == 16,
-                "gemm_tile: mxfp4 w must be [N/16, K/128, 64, 16] uint8");
+  const int g = grouped ? 1 : 0;
+  const bool wpk = w.dim() == 4 + g;  // fragment-packed blocks (codes always are), else row-major
+  TORCH_CHECK(wpk ? w.size(-2) == 64 && w.size(-1) == (quant ? 16 : 8) : !quant && w.dim() == 2 + g, what,
+              ": w must be bf16 [N, K] or fragment-packed [N/16, K/32, 64, 8], float8_e4m3fn [N/16, K/64, 64, 16] "
+              "or uint8 [N/16, K/128, 64, 16], or an [E, ...] stack of such with offsets");
+  const int E = grouped ? (int)w.size(0) : 1;
+  const int N = wpk ? (int)w.size(g) * 16 : (int)w.size(g);
+  const int K = wpk ? (int)w.size(g + 1) * (fmt == TILE_W_F4 ? 128 : fmt == TILE_W_F8 ? 64 : 32) : (int)w.size(g + 1);
+  const int M = (int)x.size(0);
+  TORCH_CHECK(x.size(1) == K, "gemm_tile: K mismatch");
+  TORCH_CHECK(swiglu == 0 || swiglu == 1 || swiglu == 8, "gemm_tile: swiglu 0, 1 or 8");
+  const bool rsd = resid.has_value(), rp = rope_pos.has_value(), rs = rs_part.has_value();
+  TORCH_CHECK(!(rp && swiglu) && !(rsd && (swiglu || rp)), "gemm_tile: one epilogue - swiglu, rope or the residual one");
+  TORCH_CHECK(!rs || K % 128 == 0, "gemm_tile: row scale needs K % 128 == 0");
+  const int epi = rsd ? TILE_EPI_RESID : rp ? TILE_EPI_ROPE : swiglu == 8 ? TILE_EPI_SWIGLU8 : swiglu ? TILE_EPI_SWIGLU : TILE_EPI_BF16;
+  const int rs_np = rs ? K / 128 : 0;
+  const TilePlan p = tile_plan(fmt, M, N, K, epi, (int)algo, tile_count_arg(grouped, E), tile_count_arg(rs, rs_np));
+  // what tile_plan refused, by its code (the limits themselves: the table above tile_plan)
+  static const char* const why[] = {
+      "", "N % 16 == 0 (swiglu: % 256; rope, residual: % 128), K % 64 == 0, K >= 64, schedule (algo) 0 or 1, 1..256 "
+      "experts; rope, the residual epilogue and the row scale are dense; the row scale goes with swiglu or rope and "
+      "4..64 partial sums, a multiple of 4; it and the residual epilogue need schedule 1 and K >= 192",
+      "more than 2^30 tiles", "w (one expert's), 256 rows of x and of resid must stay below 2^31 bytes (32-bit offsets)",
+      "a quantised w is compiled for dense (not grouped) launches on schedule 1 (algo=1), swiglu 0 or 8 (no per-128 "
+      "pairing), fp8 K >= 192, mxfp4 K >= 256 and K % 128 == 0"};
+  TORCH_CHECK(p.err == 0, what, ": no form for N=", N, " K=", K, " (rc=", p.err, "): ", why[-p.err]);
+  const void* sp = nullptr;
+  if (fmt == TILE_W_F8) {
+    TORCH_CHECK(wscale.has_value() && wscale->is_cuda() && wscale->scalar_type() == torch::kFloat32 &&
+                    wscale->is_contiguous() && wscale->numel() == N,
+                what, ": w needs its [N] fp32 scale vector");
+    sp = wscale->data_ptr();
+  } else if (fmt == TILE_W_F4) {
     TORCH_CHECK(wscale.has_value() && wscale->is_cuda() && wscale->scalar_type() == torch::kUInt8 &&
                     wscale->is_contiguous() && wscale->dim() == 4 && wscale->size(0) == w.size(0) &&
                     wscale->size(1) == w.size(1) && wscale->size(2) == 16 && wscale->size(3) == 4,
-                "gemm_tile: an mxfp4 w needs its [N/16, K/128, 16, 4] uint8 block scales");
-    TORCH_CHECK(w.size(1) * 128 >= 256, "gemm_tile: the mxfp4-W form needs K >= 256 (schedule 1 only)");
-    TORCH_CHECK(algo == 1, "gemm_tile: the mxfp4-W form is compiled for schedule 1 (algo=1) only");
-    TORCH_CHECK(swiglu != 1, "gemm_tile: the mxfp4-W form has no per-128 SwiGLU pairing (swiglu=8 only)");
-    TORCH_CHECK((long)w.size(0) * 16 * w.size(1) * 64 < (1L << 31), "gemm_tile: mxfp4 code offsets must fit 32 bits");
-  } else if (f8) {
-    TORCH_CHECK(!grouped, "gemm_tile: the fp8-W form is not compiled for grouped launches");
-    TORCH_CHECK(w.dim() == 4 && w.size(-2) == 64 && w.size(-1) == 16, "gemm_tile: fp8 w must be [N/16, K/64, 64, 16]");
-    TORCH_CHECK(wscale.has_value() && wscale->is_cuda() && wscale->scalar_type() == torch::kFloat32 &&
-                    wscale->is_contiguous() && wscale->numel() == w.size(0) * 16,
-                "gemm_tile: an fp8 w needs its [N] fp32 scale vector");
-    TORCH_CHECK(w.size(1) * 64 >= 192, "gemm_tile: the fp8-W form needs K >= 192 (schedule 1 only)");
-    TORCH_CHECK(algo == 1, "gemm_tile: the fp8-W form is compiled for schedule 1 (algo=1) only");
-    TORCH_CHECK(swiglu != 1, "gemm_tile: the fp8-W form has no per-128 SwiGLU pairing (swiglu=8 only)");
+                what, ": w needs its [N/16, K/128, 16, 4] uint8 block scales");
+    sp = wscale->data_ptr();
   } else {
     TORCH_CHECK(!wscale.has_value(), "gemm_tile: wscale goes with an fp8 or mxfp4 w");
   }
-  TORCH_CHECK(f8 || f4 || w.dim() == (grouped ? 3 : 2) || (wpk && w.size(-2) == 64 && w.size(-1) == 8),
-              "gemm_tile: w [N, K] (dense) or [E, N, K] (grouped), or their fragment-packed forms");
-  const int E = grouped ? (int)w.size(0) : 1;
-  const int N = wpk ? (int)w.size(w.dim() - 4) * 16 : (int)w.size(w.dim() - 2);
-  const int K = wpk ? (int)w.size(w.dim() - 3) * (f4 ? 128 : f8 ? 64 : 32) : (int)w.size(w.dim() - 1);
-  const int M = (int)x.size(0);
-  TORCH_CHECK(x.size(1) == K, "gemm_tile: K mismatch");
-  TORCH_CHECK(algo >= 0 && algo <= 1, "gemm_tile: algo 0 (one barrier per k-tile) or 1 (two)");
-  TORCH_CHECK(N % 16 == 0 && K % 64 == 0 && K >= 64 && (!swiglu || N % 256 == 0),
-              "gemm_tile: N % 16 == 0 (SwiGLU: % 256), K % 64 == 0");
   TORCH_CHECK(y.dim() == 2 && y.size(0) == M && y.size(1) == (swiglu ? N / 2 : N), "gemm_tile: y shape");
   const int* op = nullptr;
   if (grouped) {
@@ -504,35 +514,24 @@ void gemm_tile(torch::Tensor y, torch::Tensor x, torch::Tensor w, c10::optional<
     TORCH_CHECK(offsets->numel() == E + 1, "gemm_tile: offsets must hold E + 1 entries");
     op = offsets->data_ptr<int>();
   }
-  const int* rp = nullptr;
-  const float* rc = nullptr;
-  if (rope_pos.has_value()) {
-    TORCH_CHECK(!grouped && !swiglu && rope_cs.has_value() && N % 128 == 0, "gemm_tile: rope epilogue is dense qkv");
+  if (rp) {
+    TORCH_CHECK(rope_cs.has_value(), "gemm_tile: rope_pos goes with rope_cs");
     dev_i32(*rope_pos, "rope_pos");
     TORCH_CHECK(rope_pos->numel() >= M, "gemm_tile: rope_pos needs a position per row");
     TORCH_CHECK(rope_heads >= 0 && rope_heads * 128 <= N, "gemm_tile: rope_heads * 128 must fit in N");
     TORCH_CHECK(rope_cs->is_cuda() && rope_cs->scalar_type() == torch::kFloat32 && rope_cs->is_contiguous() &&
                     rope_cs->dim() == 2 && rope_cs->size(1) == 128,
                 "gemm_tile: rope_cs must be [max_pos, 128] fp32 (head_dim 128)");
-    rp = rope_pos->data_ptr<int>();
-    rc = rope_cs->data_ptr<float>();
   }
   // row scale (deferred RMSNorm of the A rows): rs_part [M][K / 128] fp32 partial sums of squares
-  const float* rsp = nullptr;
-  int rs_np = 0;
-  if (rs_part.has_value()) {
-    TORCH_CHECK(!grouped && K % 128 == 0, "gemm_tile: row scale needs dense, K % 128 == 0");
+  if (rs)
     TORCH_CHECK(rs_part->is_cuda() && rs_part->scalar_type() == torch::kFloat32 && rs_part->is_contiguous() &&
-                    rs_part->dim() == 2 && rs_part->size(0) >= M && rs_part->size(1) == K / 128,
+                    rs_part->dim() == 2 && rs_part->size(0) >= M && rs_part->size(1) == rs_np,
                 "gemm_tile: rs_part must be [M, K / 128] fp32");
-    rsp = rs_part->data_ptr<float>();
-    rs_np = K / 128;
-  }
   // residual epilogue: resid [M][N] += y (in place), hw = resid * norm_w, ss_out [M][N / 128]
-  const bool rsd = resid.has_value();
   if (rsd) {
-    TORCH_CHECK(!grouped && !swiglu && !rp && !rsp && N % 128 == 0 && hw.has_value() && norm_w.has_value() &&
-                    ss_out.has_value(), "gemm_tile: residual epilogue is dense, N % 128 == 0, with hw / norm_w / ss_out");
+    TORCH_CHECK(hw.has_value() && norm_w.has_value() && ss_out.has_value(),
+                "gemm_tile: the residual epilogue goes with hw / norm_w / ss_out");
     dev_bf16(*resid, "resid"); dev_bf16(*hw, "hw"); dev_bf16(*norm_w, "norm_w");
     TORCH_CHECK(resid->is_contiguous() && resid->dim() == 2 && resid->size(0) == M && resid->size(1) == N,
                 "gemm_tile: resid [M, N]");
@@ -541,14 +540,35 @@ void gemm_tile(torch::Tensor y, torch::Tensor x, torch::Tensor w, c10::optional<
     TORCH_CHECK(ss_out->is_cuda() && ss_out->scalar_type() == torch::kFloat32 && ss_out->is_contiguous() &&
                     ss_out->numel() >= (long)M * (N / 128), "gemm_tile: ss_out [M, N / 128] fp32");
   }
-  TORCH_CHECK(swiglu == 0 || swiglu == 1 || swiglu == 8, "gemm_tile: swiglu 0, 1 or 8");
-  const int epi = rsd ? 3 : rp ? 2 : (swiglu == 8 ? 4 : swiglu ? 1 : 0);
   check(k8sllm_gemm_tile(x.data_ptr(), w.data_ptr(), rsd ? resid->data_ptr() : y.data_ptr(), M, N, K, op, E,
-                         (long)N * K, epi, (int)algo, rp, rc, (int)rope_heads, rsp, rs_np, (float)rs_eps,
+                         (long)N * K, epi, (int)algo, rp ? rope_pos->data_ptr<int>() : nullptr,
+                         rp ? rope_cs->data_ptr<float>() : nullptr, (int)rope_heads,
+                         rs ? rs_part->data_ptr<float>() : nullptr, rs_np, (float)rs_eps,
                          rsd ? resid->data_ptr() : nullptr, rsd ? hw->data_ptr() : nullptr,
-                         rsd ? norm_w->data_ptr() : nullptr, rsd ? ss_out->data_ptr<float>() : nullptr, wpk ? 1 : 0,
-                         f8 || f4 ? wscale->data_ptr() : nullptr, f4 ? 2 : f8 ? 1 : 0, cur()),
-        "gemm_tile");
+                         rsd ? norm_w->data_ptr() : nullptr, rsd ? ss_out->data_ptr<float>() : nullptr, wpk ? 1 : 0, sp,
+                         fmt, cur()),
+        what);
+}
+
+// tile_plan (gemm_tile_forms.h), what a launch with these arguments does: (err, schedule, row of
+// gemm_tile_forms(), m-tiles, n-tiles, workgroups).  experts 0: a dense launch; rs_np 0: no row
+// scale.  No launch.
+std::vector<int64_t> gemm_tile_plan(int64_t fmt, int64_t M, int64_t N, int64_t K, int64_t epi, int64_t sch, int64_t experts,
+                                    int64_t rs_np) {
+  const k8sllm::TilePlan p =
+      k8sllm::tile_plan((int)fmt, (int)M, (int)N, (int)K, (int)epi, (int)sch, (int)experts, (int)rs_np);
+  return {p.err, p.sch, p.form, p.n_mt, p.n_nt, p.nwg};
+}
+
+// The compiled forms of gemm_tile (kTileForms): (weight format, epi, grouped, row scale, also at
+// schedule 0) per row.
+std::vector<std::vector<int64_t>> gemm_tile_forms() {
+  std::vector<int> v(5 * k8sllm::kTileNForms);
+  const int n = k8sllm_gemm_tile_forms(v.data(), k8sllm::kTileNForms);
+  TORCH_CHECK(n == k8sllm::kTileNForms, "gemm_tile_forms: ", n, " rows compiled, ", k8sllm::kTileNForms, " in the header");
+  std::vector<std::vector<int64_t>> rows;
+  for (int i = 0; i < n; ++i) rows.emplace_back(v.begin() + 5 * i, v.begin() + 5 * i + 5);
+  return rows;
 }
 
 void gather_rows(torch::Tensor out, torch::Tensor x, torch::Tensor idx, int64_t div) {
@@ -1082,6 +1102,8 @@ PYBIND11_MODULE(_k8sllm_ops, m) {
         py::arg("rope_heads") = 0, py::arg("rs_part") = py::none(), py::arg("rs_eps") = 1e-5,
         py::arg("resid") = py::none(), py::arg("hw") = py::none(), py::arg("norm_w") = py::none(),
         py::arg("ss_out") = py::none(), py::arg("wscale") = py::none());
+  m.def("gemm_tile_plan", &gemm_tile_plan);
+  m.def("gemm_tile_forms", &gemm_tile_forms);
   m.def("gelu_tanh", &gelu_tanh);
   m.def("embedding", &embedding);
   m.def("resolve_ids", &resolve_ids);

@@ -744,104 +744,84 @@ __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(const bf16_t* __restric
 
 using namespace k8sllm;
 
+namespace {
+
+struct TileLaunch {  // what every instantiation is launched with
+  dim3 grid;
+  hipStream_t s;
+  const bf16_t *X, *W;
+  bf16_t* Y;
+  const int* offsets;
+  int E, M, N, K;
+  long w_es;
+  int n_mt, n_nt;
+  TileEpi ep;
+  int wpk;
+  const float* wscale;
+};
+
+// The walk over kTileForms from row F on: launches row `form` at schedule `sch` - each row is
+// instantiated at schedule 1 and, where it says so, at schedule 0, and nothing else is.
+template <int F = 0>
+bool tile_dispatch(int form, int sch, const TileLaunch& l) {
+  if constexpr (F == kTileNForms) {
+    return false;
+  } else {
+    if (form != F) return tile_dispatch<F + 1>(form, sch, l);
+    constexpr TileForm f = kTileForms[F];
+    auto launch = [&](auto sc) {
+      hipLaunchKernelGGL((gemm_w4_kernel<f.epi, f.grouped != 0, decltype(sc)::value, f.rs != 0, f.fmt == TILE_W_F8,
+                                         f.fmt == TILE_W_F4>),
+                         l.grid, dim3(256), 0, l.s, l.X, l.W, l.Y, l.offsets, l.E, l.M, l.N, l.K, l.w_es, l.n_mt,
+                         l.n_nt, l.ep, l.wpk, l.wscale);
+      return true;
+    };
+    if constexpr (f.sch0 != 0)
+      if (sch == 0) return launch(std::integral_constant<int, 0>{});
+    return sch == 1 && launch(std::integral_constant<int, 1>{});
+  }
+}
+
+}  // namespace
+
+// THE launcher of gemm_w4_kernel; what it accepts, the schedule that runs and the grid are
+// tile_plan's (gemm_tile_forms.h, with the table of accepted launches).
 // Dense (offsets == nullptr): Y [M][N] (SwiGLU: [M][N / 2]) = X [M][K] . W[N][K]^T.
 // Grouped: W [E][N][K] with expert stride w_es elements; M = total expert-sorted rows (the grid
 // bound: ceil(M / 256) + E m-tiles); expert e's rows are offsets[e] .. offsets[e + 1] - 1.
-// Shapes: N % 16 == 0 (SwiGLU: N % 256 == 0), K % 64 == 0.  algo: the refill schedule (0 or 1).
-// wpk: W is fragment-packed ([E][N/16][K/32][64][8], ops.pack_skinny - the decode GEMMs' layout)
-// instead of row-major: every W DMA piece is one contiguous 1-KiB block, read lane-linear from LDS.
-// wscale != nullptr: W is the fp8 encoding - e4m3 codes [N/16][K/64][64][16] (ops.pack_skinny_f8) with
-// wscale [N] fp32 row scales in packed row order.  Compiled forms: dense, schedule 1 (K >= 192), the
-// BF16 / SWIGLU8 / ROPE / RESID epilogues and the row-scaled SWIGLU8 / ROPE; any other returns -4.
-// wfmt == 2: W is the mxfp4 encoding - e2m1 codes [N/16][K/128][64][16] with wscale the e8m0 block
-// scales [N/16][K/128][16][4] bytes (ops.pack_skinny_f4).  The same compiled forms as fp8, K % 128 == 0
-// and K >= 256; any other returns -4.  wfmt: 0 bf16 (wscale null), 1 fp8, 2 mxfp4.
+// W by wfmt: 0 bf16, row-major or (wpk) fragment-packed [E][N/16][K/32][64][8] (ops.pack_skinny - the
+// decode GEMMs' layout: every W DMA piece is one contiguous 1-KiB block, read lane-linear from LDS),
+// wscale null; 1 fp8, e4m3 codes [N/16][K/64][64][16] (ops.pack_skinny_f8) with wscale [N] fp32 row
+// scales in packed row order; 2 mxfp4, e2m1 codes [N/16][K/128][64][16] with wscale the e8m0 block
+// scales [N/16][K/128][16][4] bytes (ops.pack_skinny_f4).
+// Returns 0 or tile_plan's negative code; a wfmt / wscale mismatch is -4, a missing epilogue operand -1.
 extern "C" int k8sllm_gemm_tile(const void* X, const void* W, void* Y, int M, int N, int K, const int* offsets, int E,
                                 long w_es, int epi, int algo, const int* rope_pos, const float* rope_cs,
                                 int rope_heads, const float* rs_part, int rs_np, float rs_eps, void* resid, void* hw,
                                 const void* norm_w, float* ss_out, int wpk, const void* wscale, int wfmt,
                                 hipStream_t s) {
-  if (wfmt < 0 || wfmt > 2 || (wfmt != 0) != (wscale != nullptr)) return -4;
-  if (M <= 0) return 0;
-  const bool f8 = wfmt == 1, f4 = wfmt == 2;
-  // mxfp4 W: as fp8 below, and whole 128-deep scale groups (two k-tiles per code block)
-  if (f4 && (offsets != nullptr || algo != 1 || K < 256 || K % 128 != 0 || epi == TILE_EPI_SWIGLU)) return -4;
-  // fp8 W: only the forms a packed dense layer launches are compiled - no silent other schedule
-  if (f8 && (offsets != nullptr || algo != 1 || K < 192 || epi == TILE_EPI_SWIGLU)) return -4;
-  const bool grouped = offsets != nullptr;
-  const bool rs = rs_part != nullptr;
-  if (grouped && (E < 1 || E > 256)) return -1;
-  if (algo < 0 || algo > 1) return -1;
-  if (algo == 1 && K < 192) {  // schedule 1's peeled ring tail needs three k-tiles
-    if (epi == TILE_EPI_RESID || rs_part != nullptr) return -1;
-    algo = 0;
-  }
-  const bool swg = epi == TILE_EPI_SWIGLU || epi == TILE_EPI_SWIGLU8;
-  if (N % 16 != 0 || K % 64 != 0 || K < 64 || (swg && N % 256 != 0) || epi < 0 || epi > 4) return -1;
-  if (epi == TILE_EPI_ROPE && (grouped || N % 128 != 0 || rope_pos == nullptr || rope_cs == nullptr)) return -1;
-  if (epi == TILE_EPI_RESID && (grouped || rs || N % 128 != 0 || resid == nullptr || hw == nullptr ||
-                                norm_w == nullptr || ss_out == nullptr || algo != 1))
-    return -1;
-  // row scale: the fused consumers only (qkv + RoPE, gate_up + SwiGLU), schedule 1
-  if (rs && (grouped || algo != 1 || rs_np < 4 || rs_np > 64 || rs_np % 4 != 0 ||
-             (epi != TILE_EPI_ROPE && !swg)))
-    return -1;
-  const TileEpi ep{rope_pos, rope_cs, rope_heads, rs_part, rs_np, rs_eps, (bf16_t*)resid, (bf16_t*)hw,
-                   (const bf16_t*)norm_w, ss_out};
-  // 32-bit DMA offsets (X: relative to the tile's first row; W: within one expert / n-tile)
-  if ((f4 ? (long)N * K / 2 : (long)N * K * (f8 ? 1 : 2)) >= (1L << 31) || 256L * K * 2 >= (1L << 31)) return -3;
-  if (epi == TILE_EPI_RESID && 256L * N * 2 >= (1L << 31)) return -3;
-  const int n_mt = (M + 255) / 256 + (grouped ? E : 0), n_nt = (N + 255) / 256;
-  const long nwg = (long)n_mt * n_nt;
-  if (nwg > (1L << 30)) return -2;
-  const dim3 grid((unsigned)nwg);
-#define K8_TILE_LAUNCH_Q(EPI_, G_, SCH_, RS_, F8_, F4_)                                                              \
-  hipLaunchKernelGGL((gemm_w4_kernel<EPI_, G_, SCH_, RS_, F8_, F4_>), grid, dim3(256), 0, s, (const bf16_t*)X,      \
-                     (const bf16_t*)W, (bf16_t*)Y, offsets, E, M, N, K, w_es, n_mt, n_nt, ep, wpk,                   \
-                     (const float*)wscale)
-#define K8_TILE_LAUNCH_F(EPI_, G_, SCH_, RS_, F8_) K8_TILE_LAUNCH_Q(EPI_, G_, SCH_, RS_, F8_, false)
-#define K8_TILE_LAUNCH_4(EPI_, RS_) K8_TILE_LAUNCH_Q(EPI_, false, 1, RS_, false, true)
-#define K8_TILE_LAUNCH(EPI_, G_, SCH_, RS_) K8_TILE_LAUNCH_F(EPI_, G_, SCH_, RS_, false)
-#define K8_TILE_SCH(SCH_)                                                                                            \
-  if (grouped) {                                                                                                     \
-    if (epi == TILE_EPI_SWIGLU) K8_TILE_LAUNCH(TILE_EPI_SWIGLU, true, SCH_, false);                                  \
-    else if (epi == TILE_EPI_SWIGLU8) K8_TILE_LAUNCH(TILE_EPI_SWIGLU8, true, SCH_, false);                           \
-    else K8_TILE_LAUNCH(TILE_EPI_BF16, true, SCH_, false);                                                           \
-  } else {                                                                                                           \
-    if (epi == TILE_EPI_SWIGLU) K8_TILE_LAUNCH(TILE_EPI_SWIGLU, false, SCH_, false);                                 \
-    else if (epi == TILE_EPI_SWIGLU8) K8_TILE_LAUNCH(TILE_EPI_SWIGLU8, false, SCH_, false);                          \
-    else if (epi == TILE_EPI_ROPE) K8_TILE_LAUNCH(TILE_EPI_ROPE, false, SCH_, false);                                \
-    else K8_TILE_LAUNCH(TILE_EPI_BF16, false, SCH_, false);                                                          \
-  }
-  if (f4) {
-    if (epi == TILE_EPI_RESID) K8_TILE_LAUNCH_4(TILE_EPI_RESID, false);
-    else if (epi == TILE_EPI_SWIGLU8 && rs) K8_TILE_LAUNCH_4(TILE_EPI_SWIGLU8, true);
-    else if (epi == TILE_EPI_SWIGLU8) K8_TILE_LAUNCH_4(TILE_EPI_SWIGLU8, false);
-    else if (epi == TILE_EPI_ROPE && rs) K8_TILE_LAUNCH_4(TILE_EPI_ROPE, true);
-    else if (epi == TILE_EPI_ROPE) K8_TILE_LAUNCH_4(TILE_EPI_ROPE, false);
-    else K8_TILE_LAUNCH_4(TILE_EPI_BF16, false);
-  } else if (f8) {
-    if (epi == TILE_EPI_RESID) K8_TILE_LAUNCH_F(TILE_EPI_RESID, false, 1, false, true);
-    else if (epi == TILE_EPI_SWIGLU8 && rs) K8_TILE_LAUNCH_F(TILE_EPI_SWIGLU8, false, 1, true, true);
-    else if (epi == TILE_EPI_SWIGLU8) K8_TILE_LAUNCH_F(TILE_EPI_SWIGLU8, false, 1, false, true);
-    else if (epi == TILE_EPI_ROPE && rs) K8_TILE_LAUNCH_F(TILE_EPI_ROPE, false, 1, true, true);
-    else if (epi == TILE_EPI_ROPE) K8_TILE_LAUNCH_F(TILE_EPI_ROPE, false, 1, false, true);
-    else K8_TILE_LAUNCH_F(TILE_EPI_BF16, false, 1, false, true);
-  } else if (epi == TILE_EPI_RESID) {
-    K8_TILE_LAUNCH(TILE_EPI_RESID, false, 1, false);
-  } else if (rs) {
-    if (epi == TILE_EPI_SWIGLU) K8_TILE_LAUNCH(TILE_EPI_SWIGLU, false, 1, true);
-    else if (epi == TILE_EPI_SWIGLU8) K8_TILE_LAUNCH(TILE_EPI_SWIGLU8, false, 1, true);
-    else K8_TILE_LAUNCH(TILE_EPI_ROPE, false, 1, true);
-  } else if (algo == 1) {
-    K8_TILE_SCH(1)
-  } else {
-    K8_TILE_SCH(0)
-  }
-#undef K8_TILE_SCH
-#undef K8_TILE_LAUNCH
-#undef K8_TILE_LAUNCH_F
-#undef K8_TILE_LAUNCH_4
-#undef K8_TILE_LAUNCH_Q
+  const TilePlan p = tile_plan((wfmt != 0) == (wscale != nullptr) ? wfmt : -1, M, N, K, epi, algo,
+                               tile_count_arg(offsets != nullptr, E), tile_count_arg(rs_part != nullptr, rs_np));
+  if (M <= 0 || p.err == -4) return p.err;
+  if (epi == TILE_EPI_ROPE && (rope_pos == nullptr || rope_cs == nullptr)) return -1;
+  if (epi == TILE_EPI_RESID && (resid == nullptr || hw == nullptr || norm_w == nullptr || ss_out == nullptr)) return -1;
+  if (p.err < 0) return p.err;
+  const TileLaunch l{dim3((unsigned)p.nwg), s, (const bf16_t*)X, (const bf16_t*)W, (bf16_t*)Y, offsets, E, M, N, K,
+                     w_es, p.n_mt, p.n_nt,
+                     TileEpi{rope_pos, rope_cs, rope_heads, rs_part, rs_np, rs_eps, (bf16_t*)resid, (bf16_t*)hw,
+                             (const bf16_t*)norm_w, ss_out},
+                     wpk, (const float*)wscale};
+  if (!tile_dispatch(p.form, p.sch, l)) return -1;
   return (int)hipGetLastError();
+}
+
+// The rows of kTileForms as five ints each (weight format, epi, grouped, rs, sch0), at most cap
+// rows into out; returns the row count.
+extern "C" int k8sllm_gemm_tile_forms(int* out, int cap) {
+  for (int i = 0; i < kTileNForms && i < cap; ++i) {
+    const TileForm& f = kTileForms[i];
+    const int row[5] = {f.fmt, f.epi, f.grouped, f.rs, f.sch0};
+    for (int j = 0; j < 5; ++j) out[5 * i + j] = row[j];
+  }
+  return kTileNForms;
 }

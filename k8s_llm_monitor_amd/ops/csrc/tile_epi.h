@@ -2,10 +2,9 @@
 // 16-lane row reduction.
 #pragma once
 #include "common.h"
+#include "gemm_tile_forms.h"  // the TILE_EPI_* kinds
 
 namespace k8sllm {
-
-enum { TILE_EPI_BF16 = 0, TILE_EPI_SWIGLU = 1, TILE_EPI_ROPE = 2, TILE_EPI_RESID = 3, TILE_EPI_SWIGLU8 = 4 };
 
 // Fused epilogues of the dense prefill projections.
 //

@@ -135,6 +135,7 @@ class LLMEngine:
                                                chunked_prefill=cfg.chunked_prefill,
                                                mixed_prefill_tokens=cfg.mixed_prefill_tokens,
                                                max_decode_stall_steps=cfg.max_decode_stall_steps), self.blocks)
+        self.sched.on_free = self.runner.penalty_release
         self.tokenizer = tokenizer_from_dir(cfg.weights, mc) if cfg.weights else tokenizer_for(mc)
         self.eos = set(mc.eos_ids)
         self.init_s = time.perf_counter() - t0
@@ -181,6 +182,12 @@ class LLMEngine:
         """``deadline`` (time.perf_counter clock): the sequence stops with finish_reason "deadline"
         at the first step resolved after it - an answer truncated to what fits the caller's time
         budget instead of work the caller has stopped waiting for."""
+        if params is not None and params.has_penalties():
+            if not params.repetition_penalty > 0:
+                raise ValueError(f"repetition_penalty must be > 0, not {params.repetition_penalty!r}")
+            if self.ps.tp_size > 1:  # the workers replay raw staging words and would sample without the state
+                raise ValueError("sampling penalties are not supported with tensor parallelism (tp_size > 1)")
+            self.runner.penalty_enable()
         ids = self.tokenizer.encode(prompt) if isinstance(prompt, str) else list(prompt)
         limit = self.runner.max_len - 1
         if len(ids) > limit - 1:  # keep room for at least one generated token; trim the middle
@@ -477,7 +484,7 @@ class LLMEngine:
         d.update({"model": self.model_cfg.name, "tp_size": self.ps.tp_size, "device": str(self.device),
                   "graph_buckets": sorted(self.runner.graphs), "max_num_seqs": self.cfg.max_num_seqs,
                   "decode_weights": self.cfg.decode_weights, "prefill_weights": self.cfg.prefill_weights,
-                  **self.runner.kv_stats(),
+                  **self.runner.kv_stats(), **self.runner.penalty_stats(),
                   "resident_weight_bytes": self.model.resident_weight_bytes(),
                   "decode_encodings": self.model.decode_encodings(),
                   "prefill_encodings": self.model.prefill_encodings()})
@@ -528,7 +535,8 @@ class LLMEngine:
 
 
 def _params_t(p: SamplingParams) -> tuple:
-    return (p.max_tokens, p.temperature, p.top_k, p.top_p, p.ignore_eos, tuple(p.stop_token_ids))
+    return (p.max_tokens, p.temperature, p.top_k, p.top_p, p.ignore_eos, tuple(p.stop_token_ids),
+            p.repetition_penalty, p.presence_penalty, p.frequency_penalty)
 
 
 class _Skip(Exception):

@@ -82,6 +82,15 @@ class ModelRunner:
         self.d_topp.fill_(1.0)
         self.rng = torch.tensor([cfg.seed, 0], dtype=torch.int64, device=dev)
         self.d_out = torch.zeros(B, dtype=torch.int32, device=dev)
+        # sampling penalties: the device-resident state (ops.PenaltyState, allocated by the first
+        # request that asks for a penalty), the sequences' slots in it, and the decode rows' slots -
+        # a graph input of its own (not part of the staging buffer: it changes only when the batch
+        # does), all -1 until the feature is used
+        self.pen: Optional[ops.PenaltyState] = None
+        self._pen_slot: dict[int, int] = {}  # seq_id -> slot
+        self._pen_free: list[int] = []
+        self.d_pslot = torch.full((B,), -1, dtype=torch.int32, device=dev)
+        self._pslot_sent = np.full(B, -1, dtype=np.int32)  # what d_pslot holds (as of the last upload)
         self.decode_ws = ops.decode_workspace(B, model.hq, D, self.max_blocks_per_seq * BLOCK_SIZE, dev, model.hkv) \
             if self.is_gpu else None
         # pinned host staging, double-buffered: with pipelined decode the host fills step N+1's
@@ -129,9 +138,64 @@ class ModelRunner:
                 return b
         raise ValueError(f"batch {n} exceeds max_num_seqs {self.B}")
 
-    def _sample(self, logits: torch.Tensor, temp, topk, topp, out=None) -> torch.Tensor:
+    def _sample(self, logits: torch.Tensor, temp, topk, topp, out=None, pslot=None) -> torch.Tensor:
         # fresh numbers next step: the counter advances inside the sampling kernel (also in a graph)
-        return ops.sample(logits, temp, topk, topp, self.rng, out=out, advance=True)
+        if self.pen is None:
+            return ops.sample(logits, temp, topk, topp, self.rng, out=out, advance=True)
+        return ops.sample(logits, temp, topk, topp, self.rng, out=out, advance=True, penalties=self.pen, slots=pslot)
+
+    # --------------------------------------------------------------------- sampling penalties
+    def penalty_enable(self) -> None:
+        """Allocate the penalty state (``max_num_seqs`` slots) on first use.  Decode graphs
+        captured without it sample without it: they are captured again, once, with the state and
+        ``d_pslot`` as inputs (the in-flight step's tokens in ``d_out`` survive the capture)."""
+        if self.pen is not None:
+            return
+        self.pen = ops.PenaltyState(self.B, self.model.cfg.vocab_size, self.device)
+        self._pen_free = list(range(self.B - 1, -1, -1))
+        if self.graphs:
+            buckets = sorted(self.graphs)
+            self.graphs = {}
+            self.capture_graphs(buckets)
+
+    def penalty_release(self, seq) -> None:
+        """The sequence left the batch (finished, aborted, preempted): its slot is free.  A step
+        still in flight may count one more token there; the next owner's reset runs after it."""
+        slot = self._pen_slot.pop(getattr(seq, "seq_id", None), None)
+        if slot is not None:
+            self._pen_free.append(slot)
+
+    def _penalty_slot(self, seq, take: bool = False) -> int:
+        """The sequence's slot (-1: none).  ``take`` (a prefill chunk of a newly admitted or
+        re-admitted sequence): a penalised sequence without a slot gets one, reset from its prompt
+        and the tokens it generated before a preemption."""
+        sid = getattr(seq, "seq_id", None)
+        slot = self._pen_slot.get(sid, -1)
+        p = seq.params
+        if slot < 0 and take and sid is not None and p.has_penalties():
+            if not self._pen_free:
+                raise RuntimeError("no free penalty slot (more penalised sequences than max_num_seqs)")
+            slot = self._pen_free.pop()
+            self._pen_slot[sid] = slot
+            self.pen.reset(slot, seq.prompt_ids, [t for t in seq.output_ids if t >= 0], p.repetition_penalty,
+                           p.presence_penalty, p.frequency_penalty)
+        return slot
+
+    def _upload_pslot(self, seqs: list) -> None:
+        """Decode rows -> slots, copied to ``d_pslot`` in front of the step only when it differs
+        from what the device holds."""
+        m = np.full(self.B, -1, dtype=np.int32)
+        if self._pen_slot:
+            m[: len(seqs)] = [self._pen_slot.get(s.seq_id, -1) for s in seqs]
+        if np.array_equal(m, self._pslot_sent):
+            return
+        self._pslot_sent = m
+        h = torch.from_numpy(m)
+        self.d_pslot.copy_(h.pin_memory() if self.is_gpu else h, non_blocking=True)
+
+    def penalty_stats(self) -> dict:
+        return {"penalty_slots_in_use": len(self._pen_slot),
+                "penalty_state_bytes": self.pen.nbytes if self.pen is not None else 0}
 
     # --------------------------------------------------------------------- prefill
     def prefill(self, seqs: list[Sequence], decode: Optional[list] = None) -> list[int]:
@@ -187,7 +251,7 @@ class ModelRunner:
         sizes = dict(ids=T, pos=T, slots=T, cu=len(seqs) + 1, qs=nq, st=nq, lidx=R, temp=R, topk=R, topp=R,
                      cst=len(seqs) if paged else 0, bt=len(seqs) * W, dbt=nd * Wd, dlen=nd,
                      mcu=len(seqs) + 2 if kA else 0, mqs=nq if kA else 0, mst=nq if kA else 0,
-                     mlidx=len(seqs) if kA else 0)
+                     mlidx=len(seqs) if kA else 0, pslot=R if self.pen is not None else 0)
         off, o = {}, 0
         for k, n in sizes.items():
             off[k] = o
@@ -218,6 +282,12 @@ class ModelRunner:
         v["temp"].view(np.float32)[:] = [s.params.temperature for s in rows]
         v["topk"][:] = [s.params.top_k for s in rows]
         v["topp"].view(np.float32)[:] = [s.params.top_p for s in rows]
+        if self.pen is not None:
+            # a chunk short of its prompt's end samples a token nobody keeps: it must not be counted
+            v["pslot"][:nd] = [self._penalty_slot(q) for q in decode]
+            for i, (s, c, n) in enumerate(zip(seqs, starts, lens)):
+                slot = self._penalty_slot(s, take=True)
+                v["pslot"][nd + i] = slot if c + n >= s.num_tokens else -1
         if paged:
             v["cst"][:] = starts
             bt2 = v["bt"].reshape(len(seqs), W)
@@ -269,7 +339,8 @@ class ModelRunner:
         self.n_steps["prefill_context_tokens"] = self.n_steps.get("prefill_context_tokens", 0) + sum(starts)
         self.n_steps["prefill_tokens"] = self.n_steps.get("prefill_tokens", 0) + T
         logits = self.model.forward(dv["ids"], meta, self.kv)
-        tok = self._sample(logits, dv["temp"].view(torch.float32), dv["topk"], dv["topp"].view(torch.float32))
+        tok = self._sample(logits, dv["temp"].view(torch.float32), dv["topk"], dv["topp"].view(torch.float32),
+                           pslot=dv["pslot"])
         self.n_steps["prefill"] += 1
         if self.on_launched is not None:  # TP: the custom-AR error flag, read back with the tokens
             self.on_launched()
@@ -293,7 +364,8 @@ class ModelRunner:
                         block_tables=self.d_bt[:b], seq_lens=self.d_lens[:b], decode_ws=self.decode_ws,
                         dec_src=self.d_src[:b], dec_prev=self.d_out)
         logits = self.model.forward(self.d_ids[:b], meta, self.kv)
-        self._sample(logits, self.d_temp[:b], self.d_topk[:b], self.d_topp[:b], out=self.d_out[:b])
+        self._sample(logits, self.d_temp[:b], self.d_topk[:b], self.d_topp[:b], out=self.d_out[:b],
+                     pslot=self.d_pslot[:b])
 
     def capture_graphs(self, buckets: Optional[list[int]] = None) -> None:
         if not (self.is_gpu and self.cfg.use_graphs):
@@ -302,7 +374,9 @@ class ModelRunner:
         # replays must not disturb real sequences: capture with empty rows (len 0, no cache write)
         self.d_lens.zero_()
         self.d_slots.fill_(-1)
-        rng_state = self.rng.clone()
+        self.d_pslot.fill_(-1)  # ... and count nothing; the next decode step uploads its rows' slots again
+        self._pslot_sent[:] = -1
+        rng_state, out_state = self.rng.clone(), self.d_out.clone()
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
@@ -324,6 +398,7 @@ class ModelRunner:
             self.graphs[b] = gs
         torch.cuda.synchronize()
         self.rng.copy_(rng_state)
+        self.d_out.copy_(out_state)
 
     def decode(self, seqs: list, src_rows: Optional[list] = None, publish=None) -> list[int]:
         """One decode step, synchronous: the sampled token per sequence."""
@@ -367,6 +442,8 @@ class ModelRunner:
             topk[n:b] = 0
             topp[n:b] = 1
         n_el = _Staging.prefix(self.B, self.max_blocks_per_seq, b)  # the per-row fields + b block-table rows
+        if self.pen is not None:
+            self._upload_pslot(seqs)
         if publish is not None:
             publish(st.message(n, b, n_el))
         return self._launch_staged(st, n, b, n_el)
@@ -425,7 +502,8 @@ class ModelRunner:
                 "kv_blocks": self.num_blocks, "block_size": BLOCK_SIZE}
 
     def memory_report(self) -> dict:
-        return {**self.kv_stats(), "max_model_len": self.max_len, "graph_buckets": sorted(self.graphs)}
+        return {**self.kv_stats(), "max_model_len": self.max_len, "graph_buckets": sorted(self.graphs),
+                "penalty_state_bytes": self.penalty_stats()["penalty_state_bytes"]}
 
 
 class _Staging:

@@ -79,6 +79,9 @@ class Scheduler:
         # optional admission gate ``(seq, running_after) -> bool`` (EngineService: deadline-feasible
         # admission); False keeps the head of the queue waiting (FIFO: nothing behind it starts)
         self.admit_gate = None
+        # optional ``(seq) -> None`` called whenever a sequence gives up its blocks (preempted,
+        # finished, aborted): the engine frees what else it held for the sequence
+        self.on_free = None
 
     def add(self, seq: Sequence) -> None:
         if len(seq.prompt_ids) == 0:
@@ -97,7 +100,7 @@ class Scheduler:
             self.waiting.remove(seq)
         except ValueError:
             pass
-        self.blocks.free(seq)
+        self._free(seq)
         seq.status = SeqStatus.ABORTED
 
     def has_work(self) -> bool:
@@ -197,8 +200,13 @@ class Scheduler:
         seq.prefilled = seq.num_computed >= seq.num_tokens
         return seq.prefilled
 
-    def _preempt(self, seq: Sequence) -> None:
+    def _free(self, seq: Sequence) -> None:
         self.blocks.free(seq)
+        if self.on_free is not None:
+            self.on_free(seq)
+
+    def _preempt(self, seq: Sequence) -> None:
+        self._free(seq)
         seq.status = SeqStatus.WAITING
         seq.n_preemptions += 1
         self.waiting.appendleft(seq)
@@ -208,7 +216,7 @@ class Scheduler:
         seq.finish_reason = reason
         if seq in self.running:
             self.running.remove(seq)
-        self.blocks.free(seq)
+        self._free(seq)
 
     def stats(self) -> dict:
         d = {

@@ -19,6 +19,15 @@ class SamplingParams:
     top_p: float = 1.0
     ignore_eos: bool = False
     stop_token_ids: tuple = ()
+    # sampling penalties (ops/reference.py apply_penalties), neutral by default: the repetition
+    # penalty (> 0) scales the logits of tokens in the prompt or the answer so far; presence and
+    # frequency are subtracted for tokens of the answer so far (once / per occurrence)
+    repetition_penalty: float = 1.0
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
+
+    def has_penalties(self) -> bool:
+        return self.repetition_penalty != 1.0 or self.presence_penalty != 0.0 or self.frequency_penalty != 0.0
 
 
 class SeqStatus(enum.Enum):

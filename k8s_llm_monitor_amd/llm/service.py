@@ -52,7 +52,8 @@ class LocalEngineBackend:
     enforces_deadline = True
 
     def __init__(self, service, max_tokens: int = 2000, temperature: float = 0.1, top_p: float = 1.0,
-                 top_k: int = 0, timeout_s: float = 30.0, answer_budget_s: Optional[float] = None):
+                 top_k: int = 0, timeout_s: float = 30.0, answer_budget_s: Optional[float] = None,
+                 repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0):
         """``timeout_s`` is ``llm.timeout``.  ``answer_budget_s`` (default: timeout_s): the time a
         synchronous answer may take - the server sets it below its write timeout
         (``answer_budget``) so the engine ends the generation at the deadline with
@@ -62,7 +63,9 @@ class LocalEngineBackend:
 
         self.svc = service
         self.model = service.engine.model_cfg.name
-        self.default = SamplingParams(max_tokens=max_tokens, temperature=temperature, top_p=top_p, top_k=top_k)
+        self.default = SamplingParams(max_tokens=max_tokens, temperature=temperature, top_p=top_p, top_k=top_k,
+                                      repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
+                                      frequency_penalty=frequency_penalty)
         self.timeout_s = timeout_s
         self.answer_budget_s = answer_budget_s if answer_budget_s is not None else (timeout_s if timeout_s > 0 else None)
         self.tokenizer = service.engine.tokenizer
@@ -81,13 +84,17 @@ class LocalEngineBackend:
 
     def generate(self, prompt: str, max_tokens: Optional[int] = None, temperature: Optional[float] = None,
                  request_id: Optional[str] = None, ignore_eos: bool = False,
-                 top_p: Optional[float] = None) -> GenResult:
+                 top_p: Optional[float] = None, presence_penalty: Optional[float] = None,
+                 frequency_penalty: Optional[float] = None, repetition_penalty: Optional[float] = None) -> GenResult:
         from ..engine import SamplingParams
 
         d = self.default
         p = SamplingParams(max_tokens=max_tokens or d.max_tokens,
                            temperature=d.temperature if temperature is None else temperature,
-                           top_k=d.top_k, top_p=d.top_p if top_p is None else top_p, ignore_eos=ignore_eos)
+                           top_k=d.top_k, top_p=d.top_p if top_p is None else top_p, ignore_eos=ignore_eos,
+                           repetition_penalty=d.repetition_penalty if repetition_penalty is None else repetition_penalty,
+                           presence_penalty=d.presence_penalty if presence_penalty is None else presence_penalty,
+                           frequency_penalty=d.frequency_penalty if frequency_penalty is None else frequency_penalty)
         budget = self.answer_budget_s
         fut = self.svc.submit(P.SYSTEM_PREAMBLE + prompt, p, request_id,
                               deadline=time.perf_counter() + budget if budget else None)
@@ -115,7 +122,9 @@ class LocalEngineBackend:
         d = self.default
         p = SamplingParams(max_tokens=max_tokens or d.max_tokens,
                            temperature=d.temperature if temperature is None else temperature,
-                           top_k=d.top_k, top_p=d.top_p, ignore_eos=ignore_eos)
+                           top_k=d.top_k, top_p=d.top_p, ignore_eos=ignore_eos,
+                           repetition_penalty=d.repetition_penalty, presence_penalty=d.presence_penalty,
+                           frequency_penalty=d.frequency_penalty)
         q: queue.SimpleQueue = queue.SimpleQueue()
         fut = self.svc.submit(P.SYSTEM_PREAMBLE + prompt, p, request_id, on_tokens=q.put,
                               deadline=time.perf_counter() + self.timeout_s if self.timeout_s > 0 else None)
@@ -178,8 +187,10 @@ class IncrementalDetokenizer:
 class OpenAIBackend:
     provider = "openai"
 
-    def __init__(self, api_key: str, base_url: str, model: str, max_tokens: int, temperature: float, timeout_s: float):
+    def __init__(self, api_key: str, base_url: str, model: str, max_tokens: int, temperature: float, timeout_s: float,
+                 presence_penalty: float = 0.0, frequency_penalty: float = 0.0):
         self.api_key, self.model = api_key, model
+        self.presence_penalty, self.frequency_penalty = presence_penalty, frequency_penalty
         self.base_url = (base_url or "https://api.openai.com/v1").rstrip("/")
         self.max_tokens, self.temperature, self.timeout_s = max_tokens, temperature, timeout_s
 
@@ -188,7 +199,9 @@ class OpenAIBackend:
 
     def generate(self, prompt: str, max_tokens: Optional[int] = None, temperature: Optional[float] = None,
                  request_id: Optional[str] = None, ignore_eos: bool = False,
-                 top_p: Optional[float] = None) -> GenResult:
+                 top_p: Optional[float] = None, presence_penalty: Optional[float] = None,
+                 frequency_penalty: Optional[float] = None, repetition_penalty: Optional[float] = None) -> GenResult:
+        """``repetition_penalty`` is not an OpenAI field: it is not forwarded."""
         if not self.api_key:
             raise RuntimeError("llm.api_key / OPENAI_API_KEY not configured")
         req_d = {"model": self.model, "max_tokens": max_tokens or self.max_tokens,
@@ -197,6 +210,12 @@ class OpenAIBackend:
                               {"role": "user", "content": prompt}]}
         if top_p is not None:
             req_d["top_p"] = top_p
+        pp = self.presence_penalty if presence_penalty is None else presence_penalty
+        fp = self.frequency_penalty if frequency_penalty is None else frequency_penalty
+        if pp:
+            req_d["presence_penalty"] = pp
+        if fp:
+            req_d["frequency_penalty"] = fp
         body = json.dumps(req_d).encode()
         req = urllib.request.Request(self.base_url + "/chat/completions", data=body, method="POST",
                                      headers={"Content-Type": "application/json",
@@ -221,7 +240,8 @@ class RuleBackend:
 
     def generate(self, prompt: str, max_tokens: Optional[int] = None, temperature: Optional[float] = None,
                  request_id: Optional[str] = None, ignore_eos: bool = False,
-                 top_p: Optional[float] = None) -> GenResult:
+                 top_p: Optional[float] = None, presence_penalty: Optional[float] = None,
+                 frequency_penalty: Optional[float] = None, repetition_penalty: Optional[float] = None) -> GenResult:
         flagged = [ln.strip() for ln in prompt.splitlines()
                    if any(k in ln for k in ("[资源压力]", "[不健康]", "状态=", "接近限制", "不通", "告警", "UAV "))]
         text = ("未发现明显异常。" if not flagged else

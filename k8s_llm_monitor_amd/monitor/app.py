@@ -95,10 +95,13 @@ def make_llm_backend(cfg: Config, pstate=None, device: Optional[str] = None):
             eng.warmup()
             svc = EngineService(eng)
         return (LocalEngineBackend(svc, cfg.llm.max_tokens, cfg.llm.temperature, cfg.llm.top_p, cfg.llm.top_k,
-                                   timeout_s=float(cfg.llm.timeout)), eng, svc)
+                                   timeout_s=float(cfg.llm.timeout), repetition_penalty=cfg.llm.repetition_penalty,
+                                   presence_penalty=cfg.llm.presence_penalty,
+                                   frequency_penalty=cfg.llm.frequency_penalty), eng, svc)
     if prov == "openai":
         return OpenAIBackend(cfg.llm.api_key, cfg.llm.base_url, cfg.llm.model, cfg.llm.max_tokens,
-                             cfg.llm.temperature, float(cfg.llm.timeout)), None, None
+                             cfg.llm.temperature, float(cfg.llm.timeout), presence_penalty=cfg.llm.presence_penalty,
+                             frequency_penalty=cfg.llm.frequency_penalty), None, None
     return RuleBackend(), None, None
 
 
@@ -108,7 +111,9 @@ def make_routes(cfg: Config) -> dict:
     from ..llm.service import OpenAIBackend
 
     return {kind: OpenAIBackend(cfg.llm.api_key or "none", url, cfg.llm.model, cfg.llm.max_tokens,
-                                cfg.llm.temperature, float(cfg.llm.timeout))
+                                cfg.llm.temperature, float(cfg.llm.timeout),
+                                presence_penalty=cfg.llm.presence_penalty,
+                                frequency_penalty=cfg.llm.frequency_penalty)
             for kind, url in (cfg.llm.routes or {}).items() if url}
 
 

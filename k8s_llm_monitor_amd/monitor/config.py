@@ -9,7 +9,8 @@ keys are ignored.  A missing file is an error, like ``viper.ReadInConfig``.
 New engine knobs live under ``llm`` next to the reference's keys: ``provider: local-rocm`` selects
 the in-process MI355X engine (``openai`` keeps the reference's remote semantics: no local model),
 plus ``tp_size``, ``dp_replicas``, ``max_batch``, ``kv_cache_gb``, ``max_model_len``, ``dtype``,
-``seed``, ``use_graphs``, ``decode_weights``, ``prefill_weights``, ``kv_cache_dtype``.
+``seed``, ``use_graphs``, ``decode_weights``, ``prefill_weights``, ``kv_cache_dtype``, and the
+sampling penalties ``repetition_penalty``, ``presence_penalty``, ``frequency_penalty``.
 """
 from __future__ import annotations
 
@@ -72,6 +73,11 @@ class LLMConfig:
     kv_cache_dtype: str = "bf16"
     top_p: float = 1.0
     top_k: int = 0
+    # sampling penalties, neutral by default (docs/engine.md): repetition (> 0, 1 = off) over the
+    # prompt and the answer so far; presence / frequency (0 = off) over the answer so far
+    repetition_penalty: float = 1.0
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
     max_prefill_tokens: int = 16384  # token budget of one prefill step
     chunked_prefill: bool = True  # longer prompts prefill in chunks of that budget
     prefix_caching: bool = True  # reuse the KV blocks of shared prompt prefixes

@@ -420,7 +420,9 @@ class MonitorApp:
         prompt is the caller's: system message(s) then the user / assistant turns, fitted to the
         local model's window (oldest turns dropped first).  Non-streaming: ``stream: true`` and
         ``stop`` sequences are refused with 400 rather than silently ignored; ``top_p`` is
-        honoured."""
+        honoured, and so are ``presence_penalty`` / ``frequency_penalty`` (numbers in [-2, 2]) and
+        the extension ``repetition_penalty`` (a number in (0, 10]) - an invalid value is a 400, and
+        so is a penalty the engine cannot apply (tensor parallelism)."""
         _only(method, "POST")
         if self.analysis is None:
             raise http_error(503, "Analysis engine not available")
@@ -444,12 +446,25 @@ class MonitorApp:
         temp = float(temp) if isinstance(temp, (int, float)) else None
         top_p = d.get("top_p")
         top_p = float(top_p) if isinstance(top_p, (int, float)) and 0 < top_p <= 1 else None
+        pen = {}
+        for key, lo, hi in (("presence_penalty", -2.0, 2.0), ("frequency_penalty", -2.0, 2.0),
+                            ("repetition_penalty", 0.0, 10.0)):
+            val = d.get(key)
+            if val is None:
+                continue
+            ok = isinstance(val, (int, float)) and not isinstance(val, bool) and lo <= val <= hi
+            if not ok or (key == "repetition_penalty" and val == 0):
+                rng = "(0, 10]" if key == "repetition_penalty" else "[-2, 2]"
+                raise http_error(400, f"{key} must be a number in {rng}")
+            pen[key] = float(val)
         backend = self.analysis.backend
         try:
             prompt = self.analysis.fit_chat(parts, mt)
-            g = self._bounded(lambda: backend.generate(prompt, max_tokens=mt, temperature=temp, top_p=top_p))
+            g = self._bounded(lambda: backend.generate(prompt, max_tokens=mt, temperature=temp, top_p=top_p, **pen))
         except _BUSY as e:
             return self._busy_reply(e)
+        except ValueError as e:  # the engine refused the sampling parameters
+            raise http_error(400, str(e))
         except FutTimeout:
             raise http_error(504, "answer not ready within the server write timeout")
         except Exception as e:  # noqa: BLE001

@@ -1284,37 +1284,119 @@ def flash_prefill(qkv: torch.Tensor, cu_seqlens: torch.Tensor, Hq: int, Hkv: int
 
 # ---------------------------------------------------------------- sampling
 
+class PenaltyState:
+    """Per-sequence token counts for the sampling penalties (``ref.apply_penalties``), resident
+    on the sampler's device so a captured decode step reads and updates them itself.
+
+    ``table`` int16 ``[slots, stride]`` (stride = V rounded up to 8, so every row is 16-byte
+    aligned): bit 15 = the token is in the prompt, bits 0..14 = how often it was generated,
+    saturating at ``MAX_COUNT``.  ``params`` fp32 ``[slots, 4]``: (rep, fp32(1 / rep), presence,
+    frequency) per slot.  A sampler row names its slot through ``ops.sample(..., slots=)``."""
+
+    MAX_COUNT = 0x7FFF
+    SEEN = -0x8000  # bit 15 of an int16
+
+    def __init__(self, slots: int, V: int, device):
+        self.slots, self.V = int(slots), int(V)
+        self.device = torch.device(device)
+        stride = (self.V + 7) // 8 * 8
+        self.table = torch.zeros(self.slots, stride, dtype=torch.int16, device=self.device)
+        self.params = torch.tensor([[1.0, 1.0, 0.0, 0.0]] * self.slots, dtype=torch.float32, device=self.device)
+        self.device = self.table.device  # with its index ("cuda" -> "cuda:0")
+
+    @property
+    def nbytes(self) -> int:
+        return self.table.numel() * 2 + self.params.numel() * 4
+
+    def reset(self, slot: int, prompt_ids, output_ids, rep: float = 1.0, presence: float = 0.0,
+              frequency: float = 0.0) -> None:
+        """Make ``slot`` describe one sequence: clear its row, mark ``prompt_ids`` as seen, count
+        ``output_ids`` and set its parameters.  Enqueued on the current stream; no host sync."""
+        if not 0 <= slot < self.slots:
+            raise ValueError(f"slot {slot} outside [0, {self.slots})")
+        if not rep > 0:
+            raise ValueError("repetition penalty must be > 0")
+        inv = ref.penalty_inv_rep(rep)
+        n_p, n_o = len(prompt_ids), len(output_ids)
+        ids = torch.tensor(list(prompt_ids) + list(output_ids), dtype=torch.int32)
+        if self.device.type == "cuda":
+            ids = ids.pin_memory().to(self.device, non_blocking=True)
+            native().penalty_reset(self.table, self.params, self.V, slot, ids, n_p, n_o, rep, inv, presence,
+                                   frequency)
+            return
+        row = self.table[slot]
+        row.zero_()
+        ids = ids.long()
+        ok = (ids >= 0) & (ids < self.V)
+        row[ids[:n_p][ok[:n_p]]] = self.SEEN
+        cnt = torch.bincount(ids[n_p:][ok[n_p:]], minlength=self.V).clamp_(max=self.MAX_COUNT)
+        row[: self.V] |= cnt.to(torch.int16)
+        self.params[slot] = torch.tensor([rep, inv, presence, frequency], dtype=torch.float32)
+
+    def counts(self) -> torch.Tensor:
+        """int32 ``[slots, V]``: how often each token was generated."""
+        return (self.table[:, : self.V].to(torch.int32) & self.MAX_COUNT)
+
+    def seen(self) -> torch.Tensor:
+        """bool ``[slots, V]``: the token is in the slot's prompt."""
+        return self.table[:, : self.V] < 0
+
+
 def sample(logits: torch.Tensor, temperature: Optional[torch.Tensor] = None, top_k: Optional[torch.Tensor] = None,
            top_p: Optional[torch.Tensor] = None, rng: Optional[torch.Tensor] = None,
-           out: Optional[torch.Tensor] = None, advance: bool = False) -> torch.Tensor:
+           out: Optional[torch.Tensor] = None, advance: bool = False, penalties: Optional[PenaltyState] = None,
+           slots: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Next tokens [B] int32.  temperature <= 0 (or None) is greedy.  ``advance``: bump the RNG
     counter ``rng[1]`` after drawing (on the GPU inside the final sampling kernel - no extra
-    launch inside a captured decode step)."""
+    launch inside a captured decode step).  ``penalties`` with ``slots`` (int32 [B], -1 = none):
+    row b's logits are penalised by the state's slot ``slots[b]`` first (``ref.apply_penalties``),
+    and the token drawn is counted there (distinct rows must name distinct slots)."""
+    if penalties is not None:
+        if slots is None or slots.dtype != torch.int32 or slots.numel() < logits.shape[0]:
+            raise ValueError("penalties need slots: int32 [B]")
+        if penalties.V != logits.shape[1] or penalties.device != logits.device:
+            raise ValueError("the penalty state belongs to another vocabulary or device")
     if not _gpu(logits):
-        r = _sample_cpu(logits, temperature, top_k, top_p, rng)
+        r = _sample_cpu(logits, temperature, top_k, top_p, rng, penalties, slots)
         if advance and rng is not None:
             rng[1] += 1
         return out.copy_(r) if out is not None else r
     if out is None:
         out = torch.empty(logits.shape[0], dtype=torch.int32, device=logits.device)
-    native().sample(out, logits, temperature, top_k, top_p, rng, advance and rng is not None)
+    if penalties is None:
+        native().sample(out, logits, temperature, top_k, top_p, rng, advance and rng is not None)
+    else:
+        native().sample(out, logits, temperature, top_k, top_p, rng, advance and rng is not None,
+                        penalties.table, penalties.params, slots, penalties.V)
     return out
 
 
-def _sample_cpu(logits, temperature, top_k, top_p, rng):
+def _sample_cpu(logits, temperature, top_k, top_p, rng, penalties=None, slots=None):
     B = logits.shape[0]
     res = torch.empty(B, dtype=torch.int32)
     gen = torch.Generator().manual_seed(int(rng[0]) * 1000003 + int(rng[1])) if rng is not None else None
     for b in range(B):
         t = float(temperature[b]) if temperature is not None else 0.0
-        x = logits[b].float()
+        row = logits[b]
+        slot = int(slots[b]) if penalties is not None else -1
+        if penalties is not None and slot >= penalties.slots:
+            slot = -1  # like the kernel: a slot the state does not have is no slot
+        if slot >= 0:
+            rep, _, pres, freq = penalties.params[slot].tolist()
+            e = penalties.table[slot, : penalties.V]
+            row = ref.apply_penalties(row, e < 0, e.to(torch.int32) & PenaltyState.MAX_COUNT, rep, pres, freq)
+        x = row.float()
         if t <= 0:
             res[b] = int(x.argmax())
-            continue
-        keep = ref.sample_keep(logits[b], t, int(top_k[b]) if top_k is not None else 0,
-                               float(top_p[b]) if top_p is not None else 1.0)
-        x = (x / t).masked_fill(~keep, float("-inf"))
-        res[b] = int(torch.multinomial(torch.softmax(x, -1), 1, generator=gen))
+        else:
+            keep = ref.sample_keep(row, t, int(top_k[b]) if top_k is not None else 0,
+                                   float(top_p[b]) if top_p is not None else 1.0)
+            x = (x / t).masked_fill(~keep, float("-inf"))
+            res[b] = int(torch.multinomial(torch.softmax(x, -1), 1, generator=gen))
+        if slot >= 0:  # count the drawn token, saturating
+            e = penalties.table[slot, int(res[b])]
+            if int(e) & PenaltyState.MAX_COUNT != PenaltyState.MAX_COUNT:
+                penalties.table[slot, int(res[b])] = e + 1
     return res
 
 

@@ -38,6 +38,12 @@ int k8sllm_flash_prefill(void* out, long out_stride, const void* qkv, long qkv_s
                          int bt_stride, const float* kv_scale, hipStream_t s);
 int k8sllm_sample(int* out, const void* logits, int is_fp32, long B, long stride, int V, const float* temps,
                   const int* top_k, const float* top_p, const int64_t* rng, float* pv, int* pi, int advance, hipStream_t s);
+int k8sllm_sample_pen(int* out, const void* logits, int is_fp32, long B, long stride, int V, const float* temps,
+                      const int* top_k, const float* top_p, const int64_t* rng, float* pv, int* pi, int advance,
+                      const int* pslot, void* table, long tstride, const float* pparams, int nslots, hipStream_t s);
+int k8sllm_penalty_reset(void* table, long tstride, int V, int nslots, int slot, const int* ids, int n_prompt,
+                         int n_out, float* pparams, float rep, float inv_rep, float presence, float frequency,
+                         hipStream_t s);
 int k8sllm_sample_parts(long B, int V);
 int k8sllm_moe_route(const void* logits, long T, int E, int K, int renorm, int* topk_ids, float* topk_w,
                      hipStream_t s);
@@ -351,9 +357,19 @@ void flash_prefill(torch::Tensor out, torch::Tensor qkv, torch::Tensor cu_seqlen
         "flash_prefill");
 }
 
+static void check_penalty_state(const torch::Tensor& table, const torch::Tensor& params, int64_t vocab) {
+  TORCH_CHECK(table.is_cuda() && table.scalar_type() == torch::kInt16 && table.dim() == 2 && table.is_contiguous() &&
+                  table.size(1) % 8 == 0 && vocab > 0 && vocab <= table.size(1),
+              "penalty table: contiguous int16 [slots, stride], stride a multiple of 8 and >= the vocabulary");
+  TORCH_CHECK(params.is_cuda() && params.scalar_type() == torch::kFloat32 && params.is_contiguous() &&
+                  params.dim() == 2 && params.size(0) == table.size(0) && params.size(1) == 4,
+              "penalty params: contiguous fp32 [slots, 4]");
+}
+
 void sample(torch::Tensor out, torch::Tensor logits, c10::optional<torch::Tensor> temps,
             c10::optional<torch::Tensor> top_k, c10::optional<torch::Tensor> top_p, c10::optional<torch::Tensor> rng,
-            bool advance) {
+            bool advance, c10::optional<torch::Tensor> pen_table, c10::optional<torch::Tensor> pen_params,
+            c10::optional<torch::Tensor> pen_slots, int64_t pen_vocab) {
   dev_i32(out, "out");
   TORCH_CHECK(logits.is_cuda() && logits.dim() == 2 && logits.stride(1) == 1, "logits [B, V]");
   const bool f32 = logits.scalar_type() == torch::kFloat32;
@@ -368,9 +384,41 @@ void sample(torch::Tensor out, torch::Tensor logits, c10::optional<torch::Tensor
   // partial (value, index) workspace: stream-ordered caching allocator (graph-pool safe)
   auto pv = torch::empty({np}, logits.options().dtype(torch::kFloat32));
   auto pi = torch::empty({np}, logits.options().dtype(torch::kInt32));
-  check(k8sllm_sample(out.data_ptr<int>(), logits.data_ptr(), f32 ? 1 : 0, B, logits.stride(0), V, t, k, p, r,
-                      pv.data_ptr<float>(), pi.data_ptr<int>(), advance ? 1 : 0, cur()),
+  // penalty state (ops.PenaltyState): table [slots, stride] int16, params [slots, 4] fp32, slots [B] int32
+  const int* ps = nullptr;
+  void* tb = nullptr;
+  const float* pp = nullptr;
+  long tstride = 0;
+  int nslots = 0;
+  if (pen_table) {
+    TORCH_CHECK(pen_params && pen_slots, "sample: penalties need params and slots");
+    check_penalty_state(*pen_table, *pen_params, pen_vocab);
+    TORCH_CHECK(pen_vocab == V, "sample: the penalty state is for a vocabulary of ", pen_vocab, ", logits have ", V);
+    dev_i32(*pen_slots, "slots");
+    TORCH_CHECK(pen_slots->is_contiguous() && pen_slots->numel() >= B, "sample: slots [B]");
+    ps = pen_slots->data_ptr<int>();
+    tb = pen_table->data_ptr();
+    pp = pen_params->data_ptr<float>();
+    tstride = pen_table->size(1);
+    nslots = (int)pen_table->size(0);
+  }
+  check(k8sllm_sample_pen(out.data_ptr<int>(), logits.data_ptr(), f32 ? 1 : 0, B, logits.stride(0), V, t, k, p, r,
+                          pv.data_ptr<float>(), pi.data_ptr<int>(), advance ? 1 : 0, ps, tb, tstride, pp, nslots,
+                          cur()),
         "sample");
+}
+
+void penalty_reset(torch::Tensor table, torch::Tensor params, int64_t vocab, int64_t slot, torch::Tensor ids,
+                   int64_t n_prompt, int64_t n_out, double rep, double inv_rep, double presence, double frequency) {
+  check_penalty_state(table, params, vocab);
+  dev_i32(ids, "ids");
+  TORCH_CHECK(slot >= 0 && slot < table.size(0), "penalty_reset: slot ", slot, " of ", table.size(0));
+  TORCH_CHECK(ids.is_contiguous() && n_prompt >= 0 && n_out >= 0 && n_prompt + n_out <= ids.numel(),
+              "penalty_reset: ids holds n_prompt + n_out entries");
+  check(k8sllm_penalty_reset(table.data_ptr(), table.size(1), (int)vocab, (int)table.size(0), (int)slot,
+                             ids.data_ptr<int>(), (int)n_prompt, (int)n_out, params.data_ptr<float>(), (float)rep,
+                             (float)inv_rep, (float)presence, (float)frequency, cur()),
+        "penalty_reset");
 }
 
 void moe_router(torch::Tensor x, torch::Tensor wr, torch::Tensor ids, torch::Tensor w, torch::Tensor wd, bool renorm) {
@@ -1114,7 +1162,9 @@ PYBIND11_MODULE(_k8sllm_ops, m) {
   m.def("flash_prefill", &flash_prefill);
   m.def("embed_norm_partial", &embed_norm_partial);
   m.def("sample", &sample, py::arg("out"), py::arg("logits"), py::arg("temps"), py::arg("top_k"), py::arg("top_p"),
-        py::arg("rng"), py::arg("advance") = false);
+        py::arg("rng"), py::arg("advance") = false, py::arg("pen_table") = py::none(),
+        py::arg("pen_params") = py::none(), py::arg("pen_slots") = py::none(), py::arg("pen_vocab") = 0);
+  m.def("penalty_reset", &penalty_reset);
   m.def("moe_route", &moe_route);
   m.def("moe_router", &moe_router);
   m.def("moe_align", &moe_align);

@@ -19,6 +19,14 @@
 // with top-k / top-p need a row-wide threshold; part 0 of such a row runs the whole-row bisection
 // path and its answer is taken as is.  The per-element hash is 32-bit (two murmur3 finalisers of
 // a per-row 64-bit key) - 64-bit multiplies are multi-instruction sequences on CDNA.
+//
+// Penalties (ops/reference.py apply_penalties): an optional device-resident state - a table
+// [slots][tstride] of 16-bit entries (bit 15: the token is in the prompt, bits 0..14: how often it
+// was generated, saturating) and (rep, 1/rep, presence, frequency) per slot.  A row with
+// pslot[row] >= 0 reads every logit through `ldp<T, true>`, which penalises it before the
+// pipeline above; the final kernel counts the drawn token in the row's slot, so a captured decode
+// step keeps its own state the way it advances the RNG counter.  Without a table the kernels
+// are the <T, false> instantiations: the plain loads.
 #include <type_traits>
 
 #include "common.h"
@@ -34,6 +42,50 @@ template <>
 __device__ __forceinline__ float ld<bf16_t>(const bf16_t* p, long i) { return bf2f(p[i]); }
 template <>
 __device__ __forceinline__ float ld<float>(const float* p, long i) { return p[i]; }
+
+// one slot's penalty parameters (the slot's table row travels beside them as a plain pointer)
+struct PenRow {
+  float rep, inv_rep, presence, frequency;
+};
+
+constexpr uint32_t kPenSeen = 0x8000u, kPenCount = 0x7fffu;
+
+// repetition penalty over prompt + output tokens, then frequency / presence over output tokens;
+// each step rounded on its own (no contraction), like the fp32 reference
+__device__ __forceinline__ float penalise(float x, uint32_t e, const PenRow& q) {
+#pragma clang fp contract(off)
+  if (e != 0u) x = x > 0.f ? x * q.inv_rep : x * q.rep;
+  const uint32_t c = e & kPenCount;
+  if (c == 0u) return x;
+  const float fc = q.frequency * (float)c;
+  return (x - fc) - q.presence;
+}
+
+// Logit i of a row as the sampler reads it: plain (PEN = false), or penalised by the row's table
+// entries `cnt` (16-byte aligned) and parameters.
+template <typename T, bool PEN>
+__device__ __forceinline__ float ldp(const T* __restrict__ x, const uint16_t* __restrict__ cnt, const PenRow& q,
+                                     int i) {
+  const float v = ld<T>(x, i);
+  if constexpr (PEN) return penalise(v, cnt[i], q);
+  return v;
+}
+
+// 8 logits from a 16-byte aligned bf16 address (and their 8 table entries, one 16-byte load)
+template <bool PEN>
+__device__ __forceinline__ void ldp8(const bf16_t* __restrict__ x, const uint16_t* __restrict__ cnt,
+                                     const PenRow& q, int i, float* v) {
+  unpack8(*reinterpret_cast<const uint4*>(x + i), v);
+  if constexpr (PEN) {
+    const uint4 e = *reinterpret_cast<const uint4*>(cnt + i);
+    const uint32_t w[4] = {e.x, e.y, e.z, e.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      v[2 * j] = penalise(v[2 * j], w[j] & 0xffffu, q);
+      v[2 * j + 1] = penalise(v[2 * j + 1], w[j] >> 16, q);
+    }
+  }
+}
 
 __device__ __forceinline__ uint64_t mix64(uint64_t z) {
   z += 0x9e3779b97f4a7c15ull;
@@ -111,14 +163,14 @@ __device__ __forceinline__ float order_key_inv(uint32_t u) {
 }
 
 // Whole-row path for rows with top-k / top-p (one workgroup); returns the token on every thread.
-template <typename T>
-__device__ int sample_row_filtered(const T* __restrict__ x, int V, float temp, int k, float p, uint64_t key,
-                                   float* sv, int* si) {
+template <typename T, bool PEN>
+__device__ int sample_row_filtered(const T* __restrict__ x, const uint16_t* __restrict__ cnt, const PenRow& q, int V,
+                                   float temp, int k, float p, uint64_t key, float* sv, int* si) {
   const int tid = threadIdx.x;
   const float itemp = 1.f / temp;
   float mx = -INFINITY, mn = INFINITY;
   for (int i = tid; i < V; i += kST) {
-    const float v = ld<T>(x, i) * itemp;
+    const float v = ldp<T, PEN>(x, cnt, q, i) * itemp;
     mx = fmaxf(mx, v);
     mn = fminf(mn, v);
   }
@@ -132,7 +184,7 @@ __device__ int sample_row_filtered(const T* __restrict__ x, int V, float temp, i
     for (int bit = 31; bit >= 0; --bit) {
       const uint32_t cand = t | (1u << bit);
       float c = 0.f;  // V < 2^24: an exact count
-      for (int i = tid; i < V; i += kST) c += (order_key(ld<T>(x, i) * itemp) >= cand) ? 1.f : 0.f;
+      for (int i = tid; i < V; i += kST) c += (order_key(ldp<T, PEN>(x, cnt, q, i) * itemp) >= cand) ? 1.f : 0.f;
       c = block_sum<kST>(c, sv);
       if (c >= (float)k) t = cand;
     }
@@ -142,7 +194,7 @@ __device__ int sample_row_filtered(const T* __restrict__ x, int V, float temp, i
     // mass over the top-k survivors only (thr = -inf without top-k: the whole row)
     float z = 0.f;
     for (int i = tid; i < V; i += kST) {
-      const float v = ld<T>(x, i) * itemp;
+      const float v = ldp<T, PEN>(x, cnt, q, i) * itemp;
       z += (v >= thr) ? __expf(v - mx) : 0.f;
     }
     z = block_sum<kST>(z, sv);
@@ -152,7 +204,7 @@ __device__ int sample_row_filtered(const T* __restrict__ x, int V, float temp, i
       const float mid = 0.5f * (lo + hi);
       float s = 0.f;
       for (int i = tid; i < V; i += kST) {
-        const float v = ld<T>(x, i) * itemp;
+        const float v = ldp<T, PEN>(x, cnt, q, i) * itemp;
         s += (v >= mid) ? __expf(v - mx) : 0.f;
       }
       s = block_sum<kST>(s, sv);
@@ -162,7 +214,7 @@ __device__ int sample_row_filtered(const T* __restrict__ x, int V, float temp, i
   }
   ArgMax a{-INFINITY, 0x7fffffff};
   for (int i = tid; i < V; i += kST) {
-    const float v = ld<T>(x, i) * itemp;
+    const float v = ldp<T, PEN>(x, cnt, q, i) * itemp;
     if (v >= thr) a = better(a, ArgMax{v + gumbel(key, i), i});
   }
   return block_argmax(a, sv, si).i;
@@ -172,25 +224,18 @@ __device__ __forceinline__ bool row_filtered(int V, float temp, int k, float p) 
   return temp > 0.f && ((k > 0 && k < V) || p < 1.f);
 }
 
-// grid (B, P): partial argmax of part `blockIdx.y` of row `blockIdx.x` -> pv/pi[row * P + part]
-template <typename T>
-__global__ __launch_bounds__(kST) void sample_partial_kernel(float* __restrict__ pv, int* __restrict__ pi,
-                                                             const T* __restrict__ logits, long stride, int V, int P,
-                                                             const float* __restrict__ temps,
-                                                             const int* __restrict__ top_k,
-                                                             const float* __restrict__ top_p,
-                                                             const int64_t* __restrict__ rng) {
-  __shared__ float sv[kST / 64];
-  __shared__ int si[kST / 64];
-  const int row = blockIdx.x, part = blockIdx.y, tid = threadIdx.x;
-  const T* x = logits + (long)row * stride;
-  const float temp = temps ? temps[row] : 0.f;
-  const int k = top_k ? top_k[row] : 0;
-  const float p = top_p ? top_p[row] : 1.f;
+// part `part` of one row -> pv/pi[part] (pv, pi: the row's P partials)
+template <typename T, bool PEN>
+__device__ __forceinline__ void sample_partial_row(float* __restrict__ pv, int* __restrict__ pi,
+                                                   const T* __restrict__ x, const uint16_t* __restrict__ cnt,
+                                                   const PenRow& q, long stride, int V, int P, int part, int row,
+                                                   float temp, int k, float p, const int64_t* __restrict__ rng,
+                                                   float* sv, int* si) {
+  const int tid = threadIdx.x;
   if (row_filtered(V, temp, k, p)) {
     if (part != 0) return;
-    const int tok = sample_row_filtered<T>(x, V, temp, k, p, row_key(rng, row), sv, si);
-    if (tid == 0) pi[row * P] = tok;
+    const int tok = sample_row_filtered<T, PEN>(x, cnt, q, V, temp, k, p, row_key(rng, row), sv, si);
+    if (tid == 0) pi[0] = tok;
     return;
   }
   // parts start on 8-element boundaries so that bf16 rows with an 8-aligned stride and a 16-byte
@@ -208,19 +253,53 @@ __global__ __launch_bounds__(kST) void sample_partial_kernel(float* __restrict__
   if constexpr (std::is_same<T, bf16_t>::value) {
     for (int i = lo + tid * 8; i < hv; i += kST * 8) {
       float v[8];
-      unpack8(*reinterpret_cast<const uint4*>(x + i), v);
+      ldp8<PEN>(x, cnt, q, i, v);
 #pragma unroll
       for (int j = 0; j < 8; ++j)
         a = better(a, ArgMax{greedy ? v[j] : v[j] * itemp + gumbel(key, i + j), i + j});
     }
   }
   for (int i = hv + tid; i < hi; i += kST)
-    a = better(a, ArgMax{greedy ? ld<T>(x, i) : ld<T>(x, i) * itemp + gumbel(key, i), i});
+    a = better(a, ArgMax{greedy ? ldp<T, PEN>(x, cnt, q, i) : ldp<T, PEN>(x, cnt, q, i) * itemp + gumbel(key, i), i});
   a = block_argmax(a, sv, si);
   if (tid == 0) {
-    pv[row * P + part] = a.v;
-    pi[row * P + part] = a.i;
+    pv[part] = a.v;
+    pi[part] = a.i;
   }
+}
+
+// grid (B, P): partial argmax of part `blockIdx.y` of row `blockIdx.x` -> pv/pi[row * P + part].
+// PEN: rows with a slot (pslot[row] in [0, nslots)) are penalised - a row-uniform branch.
+template <typename T, bool PEN>
+__global__ __launch_bounds__(kST) void sample_partial_kernel(float* __restrict__ pv, int* __restrict__ pi,
+                                                             const T* __restrict__ logits, long stride, int V, int P,
+                                                             const float* __restrict__ temps,
+                                                             const int* __restrict__ top_k,
+                                                             const float* __restrict__ top_p,
+                                                             const int64_t* __restrict__ rng,
+                                                             const int* __restrict__ pslot,
+                                                             const uint16_t* __restrict__ table, long tstride,
+                                                             const float4* __restrict__ pparams, int nslots) {
+  __shared__ float sv[kST / 64];
+  __shared__ int si[kST / 64];
+  const int row = blockIdx.x, part = blockIdx.y;
+  int slot = -1;
+  if constexpr (PEN) slot = pslot[row];  // first, so the load is in flight with the row's parameters
+  const T* x = logits + (long)row * stride;
+  const float temp = temps ? temps[row] : 0.f;
+  const int k = top_k ? top_k[row] : 0;
+  const float p = top_p ? top_p[row] : 1.f;
+  pv += row * P;
+  pi += row * P;
+  if constexpr (PEN) {
+    if (slot >= 0 && slot < nslots) {
+      const float4 q = pparams[slot];
+      sample_partial_row<T, true>(pv, pi, x, table + (long)slot * tstride, PenRow{q.x, q.y, q.z, q.w}, stride, V, P,
+                                  part, row, temp, k, p, rng, sv, si);
+      return;
+    }
+  }
+  sample_partial_row<T, false>(pv, pi, x, nullptr, PenRow{}, stride, V, P, part, row, temp, k, p, rng, sv, si);
 }
 
 // one thread per row: the best of the P partials (or part 0's answer for a filtered row)
@@ -229,22 +308,65 @@ __global__ __launch_bounds__(64) void sample_final_kernel(int* __restrict__ out,
                                                           const float* __restrict__ temps,
                                                           const int* __restrict__ top_k,
                                                           const float* __restrict__ top_p,
-                                                          int64_t* __restrict__ rng_advance) {
+                                                          int64_t* __restrict__ rng_advance,
+                                                          const int* __restrict__ pslot,
+                                                          uint16_t* __restrict__ table, long tstride, int nslots) {
   const int row = blockIdx.x * 64 + threadIdx.x;
   // the partial kernel has drawn this step's numbers: advance the counter for the next step here
   // (one lane, a vector store) instead of a separate `rng[1] += 1` launch after every sample
   if (rng_advance != nullptr && row == 0) rng_advance[1] = rng_advance[1] + 1;
   if (row >= B) return;
+  const int slot = table != nullptr ? pslot[row] : -1;  // issued first: in flight while the partials are read
   const float temp = temps ? temps[row] : 0.f;
   const int k = top_k ? top_k[row] : 0;
   const float p = top_p ? top_p[row] : 1.f;
+  int tok;
   if (row_filtered(V, temp, k, p)) {
-    out[row] = pi[row * P];
-    return;
+    tok = pi[row * P];
+  } else {
+    ArgMax a{pv[row * P], pi[row * P]};
+    for (int j = 1; j < P; ++j) a = better(a, ArgMax{pv[row * P + j], pi[row * P + j]});
+    tok = a.i;
   }
-  ArgMax a{pv[row * P], pi[row * P]};
-  for (int j = 1; j < P; ++j) a = better(a, ArgMax{pv[row * P + j], pi[row * P + j]});
-  out[row] = a.i;
+  out[row] = tok;
+  // count the drawn token in the row's slot (live rows hold distinct slots: a plain
+  // read-modify-write); a row of NaNs draws no token in [0, V) and counts nothing
+  if (slot >= 0 && slot < nslots && (unsigned)tok < (unsigned)V) {
+    uint16_t* e = table + (long)slot * tstride + tok;
+    const uint32_t c = *e;
+    if ((c & kPenCount) != kPenCount) *e = (uint16_t)(c + 1u);
+  }
+}
+
+// One workgroup: clear a slot's table row, set its parameters, then mark ids[0, n_prompt) as seen
+// and count ids[n_prompt, n_prompt + n_out) (repeated ids add up; ids outside [0, V) are skipped).
+__global__ __launch_bounds__(kST) void penalty_reset_kernel(uint16_t* __restrict__ trow, int V, int tstride,
+                                                            const int* __restrict__ ids, int n_prompt, int n_out,
+                                                            float4* __restrict__ params, float4 q) {
+  const int tid = threadIdx.x;
+  uint4* r4 = reinterpret_cast<uint4*>(trow);
+  for (int i = tid; i < tstride / 8; i += kST) r4[i] = make_uint4(0u, 0u, 0u, 0u);
+  if (tid == 0) *params = q;
+  __syncthreads();
+  for (int j = tid; j < n_prompt; j += kST) {
+    const int id = ids[j];
+    if ((unsigned)id < (unsigned)V) trow[id] = (uint16_t)kPenSeen;  // the same value from every writer
+  }
+  __syncthreads();
+  // 16-bit entries, 32-bit atomics: a saturating increment of one half of the aligned word
+  uint32_t* w32 = reinterpret_cast<uint32_t*>(trow);
+  for (int j = tid; j < n_out; j += kST) {
+    const int id = ids[n_prompt + j];
+    if ((unsigned)id >= (unsigned)V) continue;
+    uint32_t* w = w32 + (id >> 1);
+    const int sh = (id & 1) * 16;
+    uint32_t old = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    while (((old >> sh) & kPenCount) != kPenCount) {
+      const uint32_t seen = atomicCAS(w, old, old + (1u << sh));
+      if (seen == old) break;
+      old = seen;
+    }
+  }
 }
 
 }  // namespace k8sllm
@@ -259,20 +381,53 @@ extern "C" int k8sllm_sample_parts(long B, int V) {
   return (int)(p < pmax ? p : pmax);
 }
 
-// pv/pi: workspace of at least B * k8sllm_sample_parts(B, V) entries
+// pv/pi: workspace of at least B * k8sllm_sample_parts(B, V) entries.  Penalties: `table` (null =
+// none) [nslots][tstride] with tstride a multiple of 8 and a 16-byte aligned base, `pparams`
+// [nslots] x (rep, 1/rep, presence, frequency), `pslot` [B] (-1 = the row has no penalties).
+extern "C" int k8sllm_sample_pen(int* out, const void* logits, int is_fp32, long B, long stride, int V,
+                                 const float* temps, const int* top_k, const float* top_p, const int64_t* rng,
+                                 float* pv, int* pi, int advance, const int* pslot, void* table, long tstride,
+                                 const float* pparams, int nslots, hipStream_t s) {
+  if (B <= 0) return 0;
+  if (table != nullptr && (pslot == nullptr || pparams == nullptr || tstride < V || (tstride & 7) != 0 ||
+                           (reinterpret_cast<uintptr_t>(table) & 15) != 0 ||
+                           (reinterpret_cast<uintptr_t>(pparams) & 15) != 0))
+    return (int)hipErrorInvalidValue;
+  const int P = k8sllm_sample_parts(B, V);
+  dim3 grid((unsigned)B, P);
+  uint16_t* tb = (uint16_t*)table;
+  const float4* pp = (const float4*)pparams;
+#define K8SLLM_SAMPLE_PARTIAL(T, PEN)                                                                              \
+  hipLaunchKernelGGL((sample_partial_kernel<T, PEN>), grid, dim3(kST), 0, s, pv, pi, (const T*)logits, stride, V, P, \
+                     temps, top_k, top_p, rng, pslot, tb, tstride, pp, nslots)
+  if (is_fp32) {
+    if (tb) K8SLLM_SAMPLE_PARTIAL(float, true); else K8SLLM_SAMPLE_PARTIAL(float, false);
+  } else {
+    if (tb) K8SLLM_SAMPLE_PARTIAL(bf16_t, true); else K8SLLM_SAMPLE_PARTIAL(bf16_t, false);
+  }
+#undef K8SLLM_SAMPLE_PARTIAL
+  hipLaunchKernelGGL(sample_final_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, out, pv, pi, (int)B, V, P,
+                     temps, top_k, top_p, advance && rng ? const_cast<int64_t*>(rng) : nullptr, pslot, tb, tstride,
+                     nslots);
+  return (int)hipGetLastError();
+}
+
 extern "C" int k8sllm_sample(int* out, const void* logits, int is_fp32, long B, long stride, int V,
                              const float* temps, const int* top_k, const float* top_p, const int64_t* rng,
                              float* pv, int* pi, int advance, hipStream_t s) {
-  if (B <= 0) return 0;
-  const int P = k8sllm_sample_parts(B, V);
-  dim3 grid((unsigned)B, P);
-  if (is_fp32)
-    hipLaunchKernelGGL((sample_partial_kernel<float>), grid, dim3(kST), 0, s, pv, pi, (const float*)logits, stride,
-                       V, P, temps, top_k, top_p, rng);
-  else
-    hipLaunchKernelGGL((sample_partial_kernel<bf16_t>), grid, dim3(kST), 0, s, pv, pi, (const bf16_t*)logits,
-                       stride, V, P, temps, top_k, top_p, rng);
-  hipLaunchKernelGGL(sample_final_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, out, pv, pi, (int)B, V, P,
-                     temps, top_k, top_p, advance && rng ? const_cast<int64_t*>(rng) : nullptr);
+  return k8sllm_sample_pen(out, logits, is_fp32, B, stride, V, temps, top_k, top_p, rng, pv, pi, advance, nullptr,
+                           nullptr, 0, nullptr, 0, s);
+}
+
+// ids: n_prompt prompt ids followed by n_out output ids (device memory); no host sync
+extern "C" int k8sllm_penalty_reset(void* table, long tstride, int V, int nslots, int slot, const int* ids,
+                                    int n_prompt, int n_out, float* pparams, float rep, float inv_rep, float presence,
+                                    float frequency, hipStream_t s) {
+  if (slot < 0 || slot >= nslots || tstride < V || (tstride & 7) != 0 || n_prompt < 0 || n_out < 0 ||
+      (reinterpret_cast<uintptr_t>(table) & 15) != 0 || (reinterpret_cast<uintptr_t>(pparams) & 15) != 0)
+    return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(penalty_reset_kernel, dim3(1), dim3(kST), 0, s, (uint16_t*)table + (long)slot * tstride, V,
+                     (int)tstride, ids, n_prompt, n_out, (float4*)pparams + slot,
+                     make_float4(rep, inv_rep, presence, frequency));
   return (int)hipGetLastError();
 }

@@ -241,6 +241,34 @@ def sample_keep(logits_row: torch.Tensor, temperature: float, top_k: int, top_p:
     return keep
 
 
+def penalty_inv_rep(rep: float) -> float:
+    """fp32(1 / rep): computed once on the host, so the kernels and the reference multiply positive
+    logits by the same number."""
+    return float(torch.tensor(1.0 / float(rep), dtype=torch.float32))
+
+
+def apply_penalties(logits_row: torch.Tensor, prompt_seen: torch.Tensor, out_count: torch.Tensor, rep: float,
+                    presence: float, frequency: float) -> torch.Tensor:
+    """fp32[V]: one row of logits after the sampling penalties, every step rounded to fp32.
+
+    1. repetition (HF / vLLM rule, over prompt and output tokens): a token with ``prompt_seen`` or
+       ``out_count > 0`` has its logit multiplied by ``fp32(1 / rep)`` when positive, by ``rep``
+       otherwise (``rep > 0``, 1 is neutral);
+    2. frequency and presence (OpenAI rule, over output tokens only):
+       ``x - frequency * out_count - presence * (out_count > 0)``.
+
+    The sampler's pipeline (greedy argmax, or / T, top-k, top-p, the draw) runs on the result."""
+    f32 = torch.float32
+    x = logits_row.detach().to(f32)
+    cnt = out_count.to(torch.int64)
+    rep_t = torch.tensor(float(rep), dtype=f32)
+    inv_rep = torch.tensor(penalty_inv_rep(rep), dtype=f32)
+    hit = prompt_seen.to(torch.bool) | (cnt > 0)
+    x = torch.where(hit, torch.where(x > 0, x * inv_rep, x * rep_t), x)
+    x = x - torch.tensor(float(frequency), dtype=f32) * cnt.to(f32)
+    return x - torch.tensor(float(presence), dtype=f32) * (cnt > 0).to(f32)
+
+
 def moe_route(logits: torch.Tensor, k: int, renorm: bool):
     p = torch.softmax(logits.float(), dim=-1)
     w, ids = torch.topk(p, k, dim=-1)

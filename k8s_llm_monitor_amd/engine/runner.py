@@ -53,8 +53,9 @@ class ModelRunner:
             raise ValueError(f"kv_cache_dtype must be one of {KV_CACHE_DTYPES}, not {cfg.kv_cache_dtype!r}")
         self.kv_cache_dtype = cfg.kv_cache_dtype
         fp8 = cfg.kv_cache_dtype == "fp8"
-        if fp8 and self.device.type == "cuda" and D != 128:
-            raise ValueError(f"kv_cache_dtype 'fp8' needs head_dim 128 on the GPU (model has {D})")
+        why = ops.paged_decode_why(D, None, f8=True) if fp8 and self.device.type == "cuda" else None
+        if why is not None:  # no fp8 form for this head dim, whatever the group
+            raise ValueError(f"kv_cache_dtype 'fp8': {why}")
         kv_dtype = torch.float8_e4m3fn if fp8 else model.dtype
         per_block = ops.kv_bytes_per_block(L, hkv, D, kv_dtype)  # K + V over all layers (+ scales for fp8)
         if cfg.num_blocks:

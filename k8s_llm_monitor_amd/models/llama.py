@@ -960,8 +960,10 @@ class CausalLM:
         # 5-6 us per layer-op SLOWER than the slab GEMM + separate reduce kernel on the row-major
         # kernel too (profiles/r03/fused_epilogues_rowmajor.jsonl) and were removed.)
         # decode RoPE + KV write inside the attention kernel (paged_decode_fused), reading the qkv
-        # GEMM's split-K slabs directly: one launch per layer fewer
-        self._attn_rope = self.D == 128
+        # GEMM's split-K slabs directly: one launch per layer fewer - where ops.PD_FORMS has a fused
+        # row for this head dim and group (the same rows for a bf16 and an fp8 cache); else
+        # rope_and_cache + the unfused kernel
+        self._attn_rope = ops.paged_decode_why(self.D, self.hq // self.hkv, fused=True) is None
         rowmajor = (self.hq * self.D) % 64 == 0
         self.skinny_layout = "rowmajor" if rowmajor else "packed"
         for L in self.layers:

@@ -1148,7 +1148,37 @@ def _empty_i32(device) -> torch.Tensor:
     return t
 
 
-MAX_SPLITS = 64
+MAX_SPLITS = 64  # kPdMaxSplits
+
+# The compiled forms of paged decode attention as (head dim, query heads per KV head, fused, fp8
+# cache): the rows of kPdForms in csrc/paged_decode_forms.h, which native().paged_decode_forms()
+# reports (tests/test_attn_decode_plan_cpu.py compares the two).  Each row is compiled for both
+# chunk widths, a fused row also with and without the in-launch merge.  Kept here as well because
+# the model and the engine choose their decode path by it with no extension built.
+PD_FORMS: tuple = (
+    tuple((128, g, 0, 0) for g in (1, 2, 4, 8, 16)) + tuple((64, g, 0, 0) for g in (1, 2, 4, 8))
+    + tuple((128, g, 0, 1) for g in (1, 2, 4, 8, 16))
+    + tuple((128, g, 1, f8) for f8 in (0, 1) for g in (1, 2, 4, 8)))  # fused: no G = 16
+_PD_GS: dict = {}  # the table by key (every decode layer's setup asks it): (D, fused, f8) -> the row's Gs
+for _f in PD_FORMS:
+    _PD_GS.setdefault((_f[0], _f[2], _f[3]), set()).add(_f[1])
+
+
+def paged_decode_why(D: int, G: Optional[int], fused: bool = False, f8: bool = False) -> Optional[str]:
+    """THE rule of paged decode's forms, pd_plan's twin (csrc/paged_decode_forms.h;
+    tests/test_attn_decode_plan_cpu.py sweeps the two against each other): None where PD_FORMS has
+    a form for head dim ``D`` with ``G`` query heads per KV head (None: with any), ``fused``
+    (paged_decode_fused) or not, over an e4m3 cache (``f8``) or a bf16 one; else the reason.  Asked
+    for the GPU only: the CPU reference takes any shape."""
+    gs = _PD_GS.get((D, int(fused), int(f8)))
+    if gs is not None and (G is None or G in gs):
+        return None
+    what = f"{'fused ' if fused else ''}paged decode{' over an fp8 KV cache' if f8 else ''}"
+    if (f8 or fused) and D != 128:
+        return f"{what} needs head_dim 128 on the GPU, not {D}"
+    if gs is None:
+        return f"{what}: no form for head_dim {D}"
+    return f"{what}: head_dim {D} has forms for {sorted(gs)} query heads per KV head, not {G}"
 
 
 def decode_splits(batch: int, Hkv: int, n_cu: int = 256) -> int:

@@ -8,6 +8,7 @@
 #include "gemm_dec_forms.h"
 #include "gemm_skinny_plan.h"
 #include "gemm_tile_forms.h"
+#include "paged_decode_forms.h"
 
 extern "C" {
 int k8sllm_rmsnorm(void* out, const void* x, void* residual, const void* w, long rows, int d, float eps,
@@ -23,15 +24,12 @@ int k8sllm_rope_cache(void* qkv, long qkv_stride, const int* positions, const fl
                       void* v_cache, const int* slot_mapping, long T, int Hq, int Hkv, int D, int block_size,
                       int apply_rope, const float* partial, int S, float* kv_scale, hipStream_t s);
 int k8sllm_paged_decode(void* out, long out_stride, float* part_out, float* part_ml, const void* q, long q_stride,
-                        const void* k_cache, const void* v_cache, const int* block_tables, int bt_stride,
-                        const int* seq_lens, int B, int Hq, int Hkv, int D, int S, float scale, const float* kv_scale,
-                        hipStream_t s);
+                        void* k_cache, void* v_cache, const int* block_tables, int bt_stride, const int* seq_lens,
+                        int B, int Hq, int Hkv, int D, int S, float scale, float* kv_scale, const float* slabs,
+                        int nslabs, const int* positions, const float* cos_sin, const int* slot_mapping,
+                        int* merge_ctr, hipStream_t s);
+int k8sllm_paged_decode_forms(int* out, int cap);
 void k8sllm_decode_tw_force(int tw);
-int k8sllm_paged_decode_fused(void* out, long out_stride, float* part_out, float* part_ml, const float* slabs,
-                              int nslabs, const int* positions, const float* cos_sin, const int* slot_mapping,
-                              void* k_cache, void* v_cache, const int* block_tables, int bt_stride,
-                              const int* seq_lens, int B, int Hq, int Hkv, int D, int S, float scale, int* merge_ctr,
-                              float* kv_scale, hipStream_t s);
 int k8sllm_flash_prefill(void* out, long out_stride, const void* qkv, long qkv_stride, const int* cu_seqlens,
                          const int* qb_seq, const int* qb_start, int n_qblocks, int Hq, int Hkv, int D, float scale,
                          const int* ctx_start, const void* k_cache, const void* v_cache, const int* block_tables,
@@ -236,33 +234,59 @@ void rope_and_cache(torch::Tensor qkv, torch::Tensor positions, torch::Tensor co
         "rope_and_cache");
 }
 
+// What paged_decode and paged_decode_fused check alike.  Every rule about numbers - the head dim,
+// the query heads per KV head, the split range, the fp8 head dim - is pd_plan's
+// (paged_decode_forms.h); here: the tensors' layouts, dtypes and sizes.  Returns (the scales'
+// pointer or null, the launcher's out_stride, B).
+struct PdArgs {
+  float* kv_scale;
+  long out_stride;
+  int B;
+};
+
+PdArgs pd_check(const char* what, bool fused, const torch::Tensor& out, const torch::Tensor& k_cache,
+                const torch::Tensor& v_cache, const c10::optional<torch::Tensor>& kv_scale,
+                const torch::Tensor& block_tables, const torch::Tensor& seq_lens, const torch::Tensor& part_out,
+                const torch::Tensor& part_ml, int64_t Hq, int64_t Hkv, int64_t D, int64_t splits) {
+  dev_bf16(out, "out");
+  dev_i32(block_tables, "block_tables"); dev_i32(seq_lens, "seq_lens");
+  const int B = (int)seq_lens.size(0);
+  const bool f8 = k_cache.scalar_type() == torch::kFloat8_e4m3fn;
+  const k8sllm::PdPlan p = k8sllm::pd_plan((int)D, (int)Hq, (int)Hkv, B, (int)splits, fused, f8, false, 0);
+  TORCH_CHECK(p.err != -2, what, ": splits must be in [1, ", k8sllm::kPdMaxSplits, "]");
+  TORCH_CHECK(p.err != -3, what, ": ", fused ? "the fused form" : "an fp8 KV cache", " needs head_dim 128, not ", D);
+  TORCH_CHECK(p.err == 0, what, ": no ", fused ? "fused " : "", f8 ? "fp8" : "bf16", " form for head_dim ", D, " with ",
+              Hq, " query heads over ", Hkv, " KV heads");
+  float* ksp = kv_cache_pair(k_cache, v_cache, kv_scale, Hkv, D);
+  const bool packed = out.dim() == 4;  // fragment-packed [ceil(B/16), Hq*D/32, 64, 8] for gemm_skinny
+  if (packed) {
+    TORCH_CHECK(out.is_contiguous() && out.size(1) * 32 == Hq * D && out.size(2) == 64 && out.size(3) == 8 &&
+                    out.size(0) * 16 >= B, "packed out must be [ceil(B/16), Hq*D/32, 64, 8]");
+  } else {
+    TORCH_CHECK(out.dim() == 2 && out.stride(1) == 1 && out.size(1) == Hq * D, "out must be [B, Hq*D]");
+  }
+  TORCH_CHECK(k_cache.dim() == 5 && v_cache.dim() == 4 && k_cache.size(1) == Hkv && k_cache.size(3) == k8sllm::kBS &&
+                  v_cache.size(3) == k8sllm::kBS,
+              what, " expects block_size 16: caches [NB, Hkv, D/8, 16, 8] / [NB, Hkv, D, 16]");
+  TORCH_CHECK(part_out.scalar_type() == torch::kFloat32 && part_ml.scalar_type() == torch::kFloat32, "partials fp32");
+  TORCH_CHECK(part_out.numel() >= (int64_t)B * Hq * splits * D && part_ml.numel() >= (int64_t)B * Hq * splits * 2,
+              "decode workspace too small for batch x splits");
+  return {ksp, packed ? -(long)(Hq * D / 32) : (long)out.stride(0), B};
+}
+
 void paged_decode(torch::Tensor out, torch::Tensor q, torch::Tensor k_cache, torch::Tensor v_cache,
                   torch::Tensor block_tables, torch::Tensor seq_lens, torch::Tensor part_out, torch::Tensor part_ml,
                   int64_t Hq, int64_t Hkv, int64_t D, double scale, int64_t splits,
                   c10::optional<torch::Tensor> kv_scale) {
-  dev_bf16(out, "out"); dev_bf16(q, "q");
-  const float* ksp = kv_cache_pair(k_cache, v_cache, kv_scale, Hkv, D);
-  dev_i32(block_tables, "block_tables"); dev_i32(seq_lens, "seq_lens");
+  const PdArgs a = pd_check("paged_decode", false, out, k_cache, v_cache, kv_scale, block_tables, seq_lens, part_out,
+                            part_ml, Hq, Hkv, D, splits);
+  dev_bf16(q, "q");
   TORCH_CHECK(q.dim() == 2 && q.stride(1) == 1, "q must be [B, >=Hq*D] rows");
-  const bool packed = out.dim() == 4;  // fragment-packed [ceil(B/16), Hq*D/32, 64, 8] for gemm_skinny
-  if (packed) {
-    TORCH_CHECK(out.is_contiguous() && out.size(1) * 32 == Hq * D && out.size(2) == 64 && out.size(3) == 8 &&
-                    out.size(0) * 16 >= seq_lens.size(0),
-                "packed out must be [ceil(B/16), Hq*D/32, 64, 8]");
-  } else {
-    TORCH_CHECK(out.dim() == 2 && out.stride(1) == 1 && out.size(1) == Hq * D, "out must be [B, Hq*D]");
-  }
-  TORCH_CHECK(k_cache.size(3) == 16 && v_cache.size(3) == 16, "paged_decode expects block_size 16");
-  TORCH_CHECK(part_out.scalar_type() == torch::kFloat32 && part_ml.scalar_type() == torch::kFloat32, "partials fp32");
-  const int B = (int)seq_lens.size(0);
-  TORCH_CHECK(splits >= 1 && splits <= 64, "splits must be in [1, 64]");
-  TORCH_CHECK(part_out.numel() >= (int64_t)B * Hq * splits * D && part_ml.numel() >= (int64_t)B * Hq * splits * 2,
-              "decode workspace too small for batch x splits");
-  check(k8sllm_paged_decode(out.data_ptr(), packed ? -(long)(Hq * D / 32) : (long)out.stride(0),
-                            part_out.data_ptr<float>(), part_ml.data_ptr<float>(),
+  check(k8sllm_paged_decode(out.data_ptr(), a.out_stride, part_out.data_ptr<float>(), part_ml.data_ptr<float>(),
                             q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(),
-                            block_tables.data_ptr<int>(), (int)block_tables.stride(0), seq_lens.data_ptr<int>(), B,
-                            (int)Hq, (int)Hkv, (int)D, (int)splits, (float)scale, ksp, cur()),
+                            block_tables.data_ptr<int>(), (int)block_tables.stride(0), seq_lens.data_ptr<int>(), a.B,
+                            (int)Hq, (int)Hkv, (int)D, (int)splits, (float)scale, a.kv_scale, nullptr, 0, nullptr,
+                            nullptr, nullptr, nullptr, cur()),
         "paged_decode");
 }
 
@@ -275,11 +299,10 @@ void paged_decode_fused(torch::Tensor out, torch::Tensor slabs, int64_t nslabs, 
                         torch::Tensor part_out, torch::Tensor part_ml, int64_t Hq, int64_t Hkv, int64_t D,
                         double scale, int64_t splits, torch::Tensor merge_ctr,
                         c10::optional<torch::Tensor> kv_scale) {
-  dev_bf16(out, "out");
-  float* ksp = kv_cache_pair(k_cache, v_cache, kv_scale, Hkv, D);
-  dev_i32(block_tables, "block_tables"); dev_i32(seq_lens, "seq_lens"); dev_i32(positions, "positions");
-  TORCH_CHECK(D == 128, "paged_decode_fused: head_dim 128");
-  const int B = (int)seq_lens.size(0);
+  const PdArgs a = pd_check("paged_decode_fused", true, out, k_cache, v_cache, kv_scale, block_tables, seq_lens,
+                            part_out, part_ml, Hq, Hkv, D, splits);
+  const int B = a.B;
+  dev_i32(positions, "positions");
   TORCH_CHECK(slabs.is_cuda() && slabs.scalar_type() == torch::kFloat32 && slabs.is_contiguous() &&
                   slabs.numel() >= nslabs * B * (Hq + 2 * Hkv) * D && nslabs >= 1,
               "paged_decode_fused: slabs must hold nslabs x [B, (Hq + 2 Hkv) * D] fp32");
@@ -291,32 +314,40 @@ void paged_decode_fused(torch::Tensor out, torch::Tensor slabs, int64_t nslabs, 
     dev_i32(slot_mapping, "slot_mapping");
     TORCH_CHECK(slot_mapping.numel() >= B, "paged_decode_fused: slot_mapping [B]");
   }
-  const bool packed = out.dim() == 4;
-  if (packed) {
-    TORCH_CHECK(out.is_contiguous() && out.size(1) * 32 == Hq * D && out.size(2) == 64 && out.size(3) == 8 &&
-                    out.size(0) * 16 >= B, "packed out must be [ceil(B/16), Hq*D/32, 64, 8]");
-  } else {
-    TORCH_CHECK(out.dim() == 2 && out.stride(1) == 1 && out.size(1) == Hq * D, "out must be [B, Hq*D]");
-  }
-  TORCH_CHECK(k_cache.dim() == 5 && k_cache.size(1) == Hkv && k_cache.size(3) == 16 && v_cache.size(3) == 16,
-              "paged_decode_fused: caches [NB, Hkv, D/8, 16, 8] / [NB, Hkv, D, 16]");
-  TORCH_CHECK(splits >= 1 && splits <= 64, "splits must be in [1, 64]");
-  TORCH_CHECK(part_out.numel() >= (int64_t)B * Hq * splits * D && part_ml.numel() >= (int64_t)B * Hq * splits * 2,
-              "decode workspace too small for batch x splits");
   // merge_ctr (numel > 0): B x Hkv int32 counters, zero between launches (the kernel resets them)
   const bool merge = merge_ctr.numel() > 0;
   if (merge) {
     dev_i32(merge_ctr, "merge_ctr");
     TORCH_CHECK(merge_ctr.numel() >= (int64_t)B * Hkv, "paged_decode_fused: merge_ctr must hold B x Hkv counters");
   }
-  check(k8sllm_paged_decode_fused(out.data_ptr(), packed ? -(long)(Hq * D / 32) : (long)out.stride(0),
-                                  part_out.data_ptr<float>(), part_ml.data_ptr<float>(), slabs.data_ptr<float>(),
-                                  (int)nslabs, positions.data_ptr<int>(), cos_sin.data_ptr<float>(),
-                                  has_slots ? slot_mapping.data_ptr<int>() : nullptr, k_cache.data_ptr(),
-                                  v_cache.data_ptr(), block_tables.data_ptr<int>(), (int)block_tables.stride(0),
-                                  seq_lens.data_ptr<int>(), B, (int)Hq, (int)Hkv, (int)D, (int)splits, (float)scale,
-                                  merge ? merge_ctr.data_ptr<int>() : nullptr, ksp, cur()),
+  check(k8sllm_paged_decode(out.data_ptr(), a.out_stride, part_out.data_ptr<float>(), part_ml.data_ptr<float>(),
+                            nullptr, 0, k_cache.data_ptr(), v_cache.data_ptr(), block_tables.data_ptr<int>(),
+                            (int)block_tables.stride(0), seq_lens.data_ptr<int>(), B, (int)Hq, (int)Hkv, (int)D,
+                            (int)splits, (float)scale, a.kv_scale, slabs.data_ptr<float>(), (int)nslabs,
+                            positions.data_ptr<int>(), cos_sin.data_ptr<float>(),
+                            has_slots ? slot_mapping.data_ptr<int>() : nullptr,
+                            merge ? merge_ctr.data_ptr<int>() : nullptr, cur()),
         "paged_decode_fused");
+}
+
+// pd_plan (paged_decode_forms.h), what a launch with these arguments does: (err, row of
+// paged_decode_forms(), TW, merge, reduce, grid x, y, z).  tw_force: what decode_tw_force was given.
+// No launch.
+std::vector<int64_t> paged_decode_plan(int64_t D, int64_t Hq, int64_t Hkv, int64_t B, int64_t S, bool fused, bool f8,
+                                       bool merge_wanted, int64_t tw_force) {
+  const k8sllm::PdPlan p =
+      k8sllm::pd_plan((int)D, (int)Hq, (int)Hkv, (int)B, (int)S, fused, f8, merge_wanted, (int)tw_force);
+  return {p.err, p.form, p.tw, p.merge, p.reduce, p.gx, p.gy, p.gz};
+}
+
+// The compiled forms of paged decode (kPdForms): (D, G, fused, fp8 cache) per row.
+std::vector<std::vector<int64_t>> paged_decode_forms() {
+  std::vector<int> v(4 * k8sllm::kPdNForms);
+  const int n = k8sllm_paged_decode_forms(v.data(), k8sllm::kPdNForms);
+  TORCH_CHECK(n == k8sllm::kPdNForms, "paged_decode_forms: ", n, " rows compiled, ", k8sllm::kPdNForms, " in the header");
+  std::vector<std::vector<int64_t>> rows;
+  for (int i = 0; i < n; ++i) rows.emplace_back(v.begin() + 4 * i, v.begin() + 4 * i + 4);
+  return rows;
 }
 
 // paged (optional, all or none): ctx_start [S] (cached tokens before each sequence's new rows),
@@ -1158,6 +1189,8 @@ PYBIND11_MODULE(_k8sllm_ops, m) {
   m.def("rope_and_cache", &rope_and_cache);
   m.def("paged_decode", &paged_decode);
   m.def("paged_decode_fused", &paged_decode_fused);
+  m.def("paged_decode_plan", &paged_decode_plan);
+  m.def("paged_decode_forms", &paged_decode_forms);
   m.def("decode_tw_force", [](int64_t tw) { k8sllm_decode_tw_force((int)tw); });
   m.def("flash_prefill", &flash_prefill);
   m.def("embed_norm_partial", &embed_norm_partial);

@@ -28,12 +28,18 @@
 //    launch.  (An earlier in-kernel merge with agent release/acquire FENCES measured 2.3x slower at
 //    batch 64 x 1.8k context: every workgroup paid an L2 write-back.)
 // Everything is static-shaped so the decode step can be captured in a hipGraph.
+//
+// Which instantiations exist - (D, G, fused, fp8 cache), each at both chunk widths TW, a fused one
+// with and without MERGE - is the table kPdForms of paged_decode_forms.h, and what one launch does
+// (the refusal codes, the form, TW by grid size, merge or reduce launch, the grid) is pd_plan there:
+// the one launcher at the end of this file walks the table with the plan and decides nothing itself.
 #include "common.h"
+#include "paged_decode_forms.h"
 #include <stdlib.h>
+#include <type_traits>
 
 namespace k8sllm {
 
-constexpr int kBS = 16;   // tokens per KV-cache block
 constexpr int kPdSC1 = 16;  // buffer-op aux bits: sc1 (write-through stores / L2-coherent loads)
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t pd_rsrc(const void* base, long bytes) {
@@ -82,10 +88,9 @@ __device__ __forceinline__ bf16x8 pd_frag(u32x2 f, float scale) { return kv_f8_d
 template <bool F8> struct PdFrag { typedef bf16x8 type; typedef bf16_t elem; };
 template <> struct PdFrag<true> { typedef u32x2 type; typedef uint8_t elem; };
 
-// TW: tokens per wave per chunk.  TW = 32: two chunk buffers per wave (double-buffered loads,
-// ~240 VGPRs: 2 waves per SIMD) for grids that fill the chip (batch 64: 512 workgroups);
-// TW = 64: one buffer of 64 tokens (~120 VGPRs: up to 4 workgroups per CU) for small, split
-// grids, where residency, not the per-wave pipeline, hides the memory latency.
+// TW: tokens per wave per chunk.  TW = 32: two chunk buffers per wave (double-buffered loads);
+// TW = 64: one buffer of 64 tokens.  Which one a launch takes, and the measurements behind that, are
+// at kPdTw32MinWg (paged_decode_forms.h).
 template <int D, int G, bool FQ, int TW, bool MERGE = false, bool F8 = false>
 __global__ __launch_bounds__(256, TW == 32 ? 2 : 1) void paged_decode_kernel(bf16_t* __restrict__ out, long out_stride,
                                                            float* __restrict__ part_out,  // [B][Hq][S][D]
@@ -532,134 +537,105 @@ __global__ __launch_bounds__(256) void paged_decode_reduce_kernel(bf16_t* __rest
 
 using namespace k8sllm;
 
+namespace {
+
+struct PdLaunch {  // what every instantiation is launched with
+  hipStream_t s;
+  bf16_t* out;
+  long out_stride;
+  float *part_out, *part_ml;
+  const bf16_t* q;
+  long q_stride;
+  const bf16_t *k_cache, *v_cache;
+  const int* block_tables;
+  int bt_stride;
+  const int* seq_lens;
+  int Hq, Hkv, S;
+  float scale_log2;
+  DecodeFuse fz;
+  int* merge_ctr;
+  float* kv_scale;
+};
+
+// The walk over kPdForms from row F on: launches row p.form at the plan's TW and, a fused row, with
+// or without the in-launch merge - each row is instantiated at TW = 32 and 64 (a fused one times
+// MERGE false / true) and nothing else is - then the reduce kernel of the row's (D, G) where the
+// plan says so.
+template <int F = 0>
+bool pd_dispatch(const PdPlan& p, const PdLaunch& l) {
+  if constexpr (F == kPdNForms) {
+    return false;
+  } else {
+    if (p.form != F) return pd_dispatch<F + 1>(p, l);
+    constexpr PdForm f = kPdForms[F];
+    const dim3 grid(p.gx, p.gy, p.gz), blk(256);
+    auto launch = [&](auto tw, auto mg) {
+      constexpr int TW = decltype(tw)::value;
+      constexpr bool MERGE = decltype(mg)::value;
+      hipLaunchKernelGGL((paged_decode_kernel<f.D, f.G, f.fused != 0, TW, MERGE, f.f8 != 0>), grid, blk, 0, l.s, l.out,
+                         l.out_stride, l.part_out, l.part_ml, l.q, l.q_stride, l.k_cache, l.v_cache, l.block_tables,
+                         l.bt_stride, l.seq_lens, l.Hq, l.Hkv, l.S, l.scale_log2, l.fz, l.merge_ctr, l.kv_scale);
+    };
+    auto by_tw = [&](auto mg) {
+      if (p.tw == 32) launch(std::integral_constant<int, 32>{}, mg); else launch(std::integral_constant<int, 64>{}, mg);
+    };
+    if constexpr (f.fused != 0) {
+      if (p.merge) by_tw(std::true_type{}); else by_tw(std::false_type{});
+    } else {
+      by_tw(std::false_type{});
+    }
+    if (p.reduce)
+      hipLaunchKernelGGL((paged_decode_reduce_kernel<f.D, f.G>), dim3(p.gy, p.gz), blk, 0, l.s, l.out, l.out_stride,
+                         l.part_out, l.part_ml, l.seq_lens, l.Hq, l.S, 4 * p.tw);
+    return true;
+  }
+}
+
+int g_tw_force = 0;  // tools/bench_decode_step.py: 32 / 64 forces one TW (0: pd_plan's rule, by grid size)
+
+}  // namespace
+
+extern "C" void k8sllm_decode_tw_force(int tw) { g_tw_force = tw; }
+
+// THE launcher of paged_decode_kernel; what it accepts, the form, TW, the merge and the grid are
+// pd_plan's (paged_decode_forms.h).
 // S = number of splits per (sequence, kv head); part buffers hold [B][Hq][S][D].
 // out_stride < 0: write the output fragment-packed for gemm_skinny (common.h act_index).
 // slabs != nullptr: the fused q/k/v form (D = 128; see DecodeFuse) - q is ignored, the new token's
 // q / k / v come from the qkv projection's nslabs fp32 slabs [nslabs][B][(Hq + 2 Hkv) * D], are
-// rotated at `positions` and k / v written to the cache at `slot_mapping` (nullptr: no write).
+// rotated at `positions` and k / v written to the cache at `slot_mapping` (nullptr: no write);
+// merge_ctr (B x Hkv ints, zero; nullptr: a reduce launch): the split partials are merged in-launch
+// by the last arriving split.  slabs == nullptr: q [B][q_stride] holds the rotated query rows and
+// the cache the new token; the other fused arguments are ignored.
 // kv_scale != nullptr: the caches hold e4m3 codes and kv_scale their per-token scales (D = 128).
-extern "C" int k8sllm_paged_decode_fused(void* out, long out_stride, float* part_out, float* part_ml,
-                                         const float* slabs, int nslabs, const int* positions, const float* cos_sin,
-                                         const int* slot_mapping, void* k_cache, void* v_cache,
-                                         const int* block_tables, int bt_stride, const int* seq_lens, int B, int Hq,
-                                         int Hkv, int D, int S, float scale, int* merge_ctr, float* kv_scale,
-                                         hipStream_t s);
-
-// Tokens per wave per chunk: the double-buffered 32-token form once the grid fills the chip
-// (>= 384 workgroups, e.g. batch 64 x 8 kv heads), else the single-buffered 64-token form (small
-// batches, split grids: higher residency).
-static int g_tw_force = 0;  // tools/bench_decode_step.py: 32 / 64 forces one form (0: by grid size)
-extern "C" void k8sllm_decode_tw_force(int tw) { g_tw_force = tw; }
-
-static int decode_tw(int S, int Hkv, int B) {
-  if (g_tw_force == 32 || g_tw_force == 64) return g_tw_force;
-  return (long)S * Hkv * B >= 384 ? 32 : 64;
-}
-
+// Returns 0 or pd_plan's negative code; a fused launch without positions, cos_sin or a slab is -3.
 extern "C" int k8sllm_paged_decode(void* out, long out_stride, float* part_out, float* part_ml, const void* q,
-                                   long q_stride, const void* k_cache, const void* v_cache, const int* block_tables,
+                                   long q_stride, void* k_cache, void* v_cache, const int* block_tables,
                                    int bt_stride, const int* seq_lens, int B, int Hq, int Hkv, int D, int S,
-                                   float scale, const float* kv_scale, hipStream_t s) {
-  if (B <= 0) return 0;
-  if (S < 1 || S > 64) return -2;
-  if (kv_scale != nullptr && D != 128) return -3;
-  const int G = Hq / Hkv;
-  const float sl2 = scale * 1.4426950408889634f;
-  const DecodeFuse fz{};
-  const int tw = decode_tw(S, Hkv, B);
-  dim3 grid(S, Hkv, B), blk(256);
-#define K8S_DEC_T(DD, GG, TWV, F8V)                                                                                \
-  hipLaunchKernelGGL((paged_decode_kernel<DD, GG, false, TWV, false, F8V>), grid, blk, 0, s, (bf16_t*)out,           \
-                     out_stride, part_out, part_ml, (const bf16_t*)q, q_stride, (const bf16_t*)k_cache,              \
-                     (const bf16_t*)v_cache, block_tables, bt_stride, seq_lens, Hq, Hkv, S, sl2, fz, nullptr,        \
-                     const_cast<float*>(kv_scale))
-#define K8S_DEC_F(DD, GG, F8V)                                                                                       \
-  if (tw == 32) K8S_DEC_T(DD, GG, 32, F8V); else K8S_DEC_T(DD, GG, 64, F8V);                                        \
-  if (S > 1)                                                                                                         \
-    hipLaunchKernelGGL((paged_decode_reduce_kernel<DD, GG>), dim3(Hkv, B), blk, 0, s, (bf16_t*)out, out_stride,      \
-                       part_out, part_ml, seq_lens, Hq, S, 4 * tw);
-#define K8S_DEC(DD, GG) K8S_DEC_F(DD, GG, false)
-#define K8S_DEC8(GG) K8S_DEC_F(128, GG, true)
-  if (kv_scale != nullptr) {
-    switch (G) {
-      case 1: K8S_DEC8(1); break;
-      case 2: K8S_DEC8(2); break;
-      case 4: K8S_DEC8(4); break;
-      case 8: K8S_DEC8(8); break;
-      case 16: K8S_DEC8(16); break;
-      default: return -1;
-    }
-  } else if (D == 128) {
-    switch (G) {
-      case 1: K8S_DEC(128, 1); break;
-      case 2: K8S_DEC(128, 2); break;
-      case 4: K8S_DEC(128, 4); break;
-      case 8: K8S_DEC(128, 8); break;
-      case 16: K8S_DEC(128, 16); break;
-      default: return -1;
-    }
-  } else if (D == 64) {
-    switch (G) {
-      case 1: K8S_DEC(64, 1); break;
-      case 2: K8S_DEC(64, 2); break;
-      case 4: K8S_DEC(64, 4); break;
-      case 8: K8S_DEC(64, 8); break;
-      default: return -1;
-    }
-  } else {
-    return -1;
-  }
-#undef K8S_DEC8
-#undef K8S_DEC
-#undef K8S_DEC_F
-#undef K8S_DEC_T
+                                   float scale, float* kv_scale, const float* slabs, int nslabs,
+                                   const int* positions, const float* cos_sin, const int* slot_mapping,
+                                   int* merge_ctr, hipStream_t s) {
+  const bool fused = slabs != nullptr;
+  const PdPlan p = pd_plan(D, Hq, Hkv, B, S, fused, kv_scale != nullptr, merge_ctr != nullptr, g_tw_force);
+  if (B <= 0 || p.err == -2) return p.err;
+  if (fused && (nslabs < 1 || positions == nullptr || cos_sin == nullptr)) return -3;
+  if (p.err < 0) return p.err;
+  const DecodeFuse fz =
+      fused ? DecodeFuse{slabs, nslabs, positions, cos_sin, slot_mapping, (bf16_t*)k_cache, (bf16_t*)v_cache} : DecodeFuse{};
+  const PdLaunch l{s, (bf16_t*)out, out_stride, part_out, part_ml, fused ? nullptr : (const bf16_t*)q,
+                   fused ? 0 : q_stride, (const bf16_t*)k_cache, (const bf16_t*)v_cache, block_tables, bt_stride,
+                   seq_lens, Hq, Hkv, S, scale * 1.4426950408889634f, fz, fused ? merge_ctr : nullptr, kv_scale};
+  if (!pd_dispatch(p, l)) return -1;
   return (int)hipGetLastError();
 }
 
-extern "C" int k8sllm_paged_decode_fused(void* out, long out_stride, float* part_out, float* part_ml,
-                                         const float* slabs, int nslabs, const int* positions, const float* cos_sin,
-                                         const int* slot_mapping, void* k_cache, void* v_cache,
-                                         const int* block_tables, int bt_stride, const int* seq_lens, int B, int Hq,
-                                         int Hkv, int D, int S, float scale, int* merge_ctr, float* kv_scale,
-                                         hipStream_t s) {
-  if (B <= 0) return 0;
-  if (S < 1 || S > 64) return -2;
-  if (D != 128 || slabs == nullptr || nslabs < 1 || positions == nullptr || cos_sin == nullptr) return -3;
-  const int G = Hq / Hkv;
-  const float sl2 = scale * 1.4426950408889634f;
-  const DecodeFuse fz{slabs, nslabs, positions, cos_sin, slot_mapping, (bf16_t*)k_cache, (bf16_t*)v_cache};
-  const int tw = decode_tw(S, Hkv, B);
-  // merge_ctr (B x Hkv ints, zero): split partials merged in-launch by the last arriving split
-  const bool merge = merge_ctr != nullptr && S > 1;
-  dim3 grid(S, Hkv, B), blk(256);
-#define K8S_DECF_T(GG, TWV, MG, F8V)                                                                                 \
-  hipLaunchKernelGGL((paged_decode_kernel<128, GG, true, TWV, MG, F8V>), grid, blk, 0, s, (bf16_t*)out, out_stride,  \
-                     part_out, part_ml, nullptr, 0, (const bf16_t*)k_cache, (const bf16_t*)v_cache, block_tables,    \
-                     bt_stride, seq_lens, Hq, Hkv, S, sl2, fz, merge_ctr, kv_scale)
-#define K8S_DECF_M(GG, MG)                                                                                           \
-  if (kv_scale != nullptr) {                                                                                         \
-    if (tw == 32) K8S_DECF_T(GG, 32, MG, true); else K8S_DECF_T(GG, 64, MG, true);                                  \
-  } else {                                                                                                           \
-    if (tw == 32) K8S_DECF_T(GG, 32, MG, false); else K8S_DECF_T(GG, 64, MG, false);                                \
+// The rows of kPdForms as four ints each (D, G, fused, f8), at most cap rows into out; returns the
+// row count.
+extern "C" int k8sllm_paged_decode_forms(int* out, int cap) {
+  for (int i = 0; i < kPdNForms && i < cap; ++i) {
+    const PdForm& f = kPdForms[i];
+    const int row[4] = {f.D, f.G, f.fused, f.f8};
+    for (int j = 0; j < 4; ++j) out[4 * i + j] = row[j];
   }
-#define K8S_DECF(GG)                                                                                                 \
-  if (merge) {                                                                                                       \
-    K8S_DECF_M(GG, true)                                                                                             \
-  } else {                                                                                                           \
-    K8S_DECF_M(GG, false)                                                                                            \
-    if (S > 1)                                                                                                       \
-      hipLaunchKernelGGL((paged_decode_reduce_kernel<128, GG>), dim3(Hkv, B), blk, 0, s, (bf16_t*)out, out_stride,   \
-                         part_out, part_ml, seq_lens, Hq, S, 4 * tw);                                                \
-  }
-  switch (G) {
-    case 1: K8S_DECF(1); break;
-    case 2: K8S_DECF(2); break;
-    case 4: K8S_DECF(4); break;
-    case 8: K8S_DECF(8); break;
-    default: return -1;
-  }
-#undef K8S_DECF
-#undef K8S_DECF_M
-#undef K8S_DECF_T
-  return (int)hipGetLastError();
+  return kPdNForms;
 }

@@ -37,6 +37,7 @@ class RemoteSeq:
         self.finish_reason = d.get("finish_reason")
         self.output_ids = d.get("output_ids", [])
         self.prompt_ids = d.get("prompt_ids", [])
+        self.output_logprobs = d.get("output_logprobs")  # None unless the request asked (SamplingParams.logprobs)
         self.replica = d.get("replica")
 
     def timings(self) -> dict:
@@ -94,7 +95,7 @@ def _replica_main(conn, idx: int, cfg: dict, device: str) -> None:
             text, seq = fut.result()
             send(("done", key, {"text": text, "timings": seq.timings(), "finish_reason": seq.finish_reason,
                                 "output_ids": list(seq.output_ids), "prompt_ids": list(seq.prompt_ids),
-                                "replica": idx}))
+                                "output_logprobs": seq.output_logprobs, "replica": idx}))
         except (EngineOverloaded, EngineUnavailable) as e:
             send(("busy", key, str(e)))
         except BaseException as e:  # noqa: BLE001

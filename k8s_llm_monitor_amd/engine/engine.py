@@ -26,6 +26,7 @@ from typing import Optional, Union
 
 import torch
 
+from .. import ops
 from ..models.checkpoint import config_from_hf, load_checkpoint
 from ..models.config import ModelConfig, get_config
 from ..models.llama import CausalLM
@@ -188,6 +189,16 @@ class LLMEngine:
             if self.ps.tp_size > 1:  # the workers replay raw staging words and would sample without the state
                 raise ValueError("sampling penalties are not supported with tensor parallelism (tp_size > 1)")
             self.runner.penalty_enable()
+        want_lp = params is not None and params.logprobs
+        if params is not None and (params.logprobs or params.top_logprobs):
+            n_top = params.top_logprobs
+            if isinstance(n_top, bool) or not isinstance(n_top, int) or not 0 <= n_top <= ops.LP_MAX_TOP:
+                raise ValueError(f"top_logprobs must be an integer in [0, {ops.LP_MAX_TOP}], not {n_top!r}")
+            if n_top > 0 and not params.logprobs:
+                raise ValueError("top_logprobs needs logprobs")
+            if self.ps.tp_size > 1:  # the workers replay raw staging words and capture their own graphs
+                raise ValueError("logprobs are not supported with tensor parallelism (tp_size > 1)")
+            self.runner.logprob_enable()
         ids = self.tokenizer.encode(prompt) if isinstance(prompt, str) else list(prompt)
         limit = self.runner.max_len - 1
         if len(ids) > limit - 1:  # keep room for at least one generated token; trim the middle
@@ -195,6 +206,8 @@ class LLMEngine:
             ids = ids[: keep // 2] + ids[len(ids) - (keep - keep // 2):]
         seq = Sequence(prompt_ids=ids, params=params or SamplingParams(),
                        request_id=request_id or uuid.uuid4().hex[:16], user=user, deadline=deadline)
+        if want_lp:
+            seq.output_logprobs = []
         self.sched.add(seq)
         if self.trace is not None:
             self.trace.append((time.perf_counter(), "add", 1, len(ids)))
@@ -315,18 +328,21 @@ class LLMEngine:
         plan, h, sid = self._pf_inflight
         self._pf_inflight = None
         toks = self.runner.decode_collect(h)
+        lps = self.runner.collect_logprobs(h)
         self._check_collectives()
         self.counters["prefill_steps"] += 1
         if self.trace is not None:
             self.trace.append((time.perf_counter(), "prefill", len(plan.seqs), sum(plan.chunks)))
         now = time.perf_counter()
         done = []
-        for seq, tok in zip(plan.seqs, toks):
+        for row, (seq, tok) in enumerate(zip(plan.seqs, toks)):
             if seq.pending_first != sid:
                 continue  # a chunk short of the prompt's end, or freed (preempted / aborted) since
             seq.pending_first = 0
             seq.prefilled = True
             seq.output_ids.append(int(tok))
+            if seq.output_logprobs is not None:
+                seq.output_logprobs.append(lps[row] if lps is not None else None)
             self.counters["generated_tokens"] += 1
             if seq.t_first_token is None:
                 seq.t_first_token = now
@@ -353,6 +369,7 @@ class LLMEngine:
     def _resolve_step(self, seqs: list, handle) -> list[Sequence]:
         t_w = time.perf_counter() if self.trace is not None else 0.0
         toks = self.runner.decode_collect(handle)
+        lps = self.runner.collect_logprobs(handle) if hasattr(handle, "lp") else None
         if self.trace is not None:  # host ms blocked on the step's tokens (0: the host is the bottleneck)
             self.trace.append((time.perf_counter(), "dwait", len(seqs), (time.perf_counter() - t_w) * 1e3))
         self._check_collectives()
@@ -361,7 +378,7 @@ class LLMEngine:
             self.step_samples.append((len(seqs), ms, sum(q.num_tokens for q in seqs)))
         now = time.perf_counter()
         done = []
-        for q, tok in zip(seqs, toks):
+        for row, (q, tok) in enumerate(zip(seqs, toks)):
             if q.status in (SeqStatus.FINISHED, SeqStatus.ABORTED):
                 continue  # stopped on the previous step; this step's token is discarded
             tok = int(tok)
@@ -370,12 +387,16 @@ class LLMEngine:
             while i > 0 and out[i - 1] == self.PENDING:
                 i -= 1
             out[i] = tok
+            if q.output_logprobs is not None:  # at the placeholder's index, like the token
+                q.output_logprobs[i:] = [lps[row] if lps is not None else None]
             self.counters["generated_tokens"] += 1
             if q.t_first_token is None:
                 q.t_first_token = now
             reason = self._stop_reason(q, tok, n_out=i + 1, now=now)
             if reason:
                 del q.output_ids[i + 1:]  # drop the token of a step launched past the stop
+                if q.output_logprobs is not None:
+                    del q.output_logprobs[i + 1:]
                 q.t_finish = now
                 self._finish(q, reason)
                 done.append(q)
@@ -401,7 +422,8 @@ class LLMEngine:
         if self.bus is not None and plan.is_prefill:
             self.bus.send_obj(self._pack(plan))
         if plan.is_prefill:
-            toks = self.runner.prefill(plan.seqs, plan.decode)
+            h = self.runner.prefill_launch(plan.seqs, plan.decode)
+            toks = self.runner.decode_collect(h)
             self._check_collectives()  # prefill / mixed steps route small all-reduces through custom AR too
             self.counters["prefill_steps"] += 1
             if plan.decode:
@@ -412,16 +434,20 @@ class LLMEngine:
             rows = list(plan.decode) + list(plan.seqs)
             nd = len(plan.decode)
         else:
-            toks = self.runner.decode(plan.seqs, publish=self._publish)
+            h = self.runner.decode_launch(plan.seqs, publish=self._publish)
+            toks = self.runner.decode_collect(h)
             self._check_collectives()
             self.counters["decode_steps"] += 1
             rows, nd = plan.seqs, len(plan.seqs)
+        lps = self.runner.collect_logprobs(h)
         now = time.perf_counter()
         done = []
         for i, (seq, tok) in enumerate(zip(rows, toks)):
             if i >= nd and not self.sched.chunk_done(seq):
                 continue  # a chunk short of the prompt's end: no token yet
             seq.output_ids.append(int(tok))
+            if seq.output_logprobs is not None:
+                seq.output_logprobs.append(lps[i] if lps is not None else None)
             self.counters["generated_tokens"] += 1
             if seq.t_first_token is None:
                 seq.t_first_token = now
@@ -485,6 +511,7 @@ class LLMEngine:
                   "graph_buckets": sorted(self.runner.graphs), "max_num_seqs": self.cfg.max_num_seqs,
                   "decode_weights": self.cfg.decode_weights, "prefill_weights": self.cfg.prefill_weights,
                   **self.runner.kv_stats(), **self.runner.penalty_stats(),
+                  "logprobs_enabled": self.runner.lp_on,
                   "resident_weight_bytes": self.model.resident_weight_bytes(),
                   "decode_encodings": self.model.decode_encodings(),
                   "prefill_encodings": self.model.prefill_encodings()})

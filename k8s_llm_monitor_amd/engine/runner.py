@@ -92,6 +92,16 @@ class ModelRunner:
         self._pen_free: list[int] = []
         self.d_pslot = torch.full((B,), -1, dtype=torch.int32, device=dev)
         self._pslot_sent = np.full(B, -1, dtype=np.int32)  # what d_pslot holds (as of the last upload)
+        # token log-probabilities (ops.token_logprobs), off until the first request asks
+        # (logprob_enable): the rows' packed records, what each decode row wants (-1: nothing; a
+        # graph input of its own like d_pslot) and the pinned buffers a step's records are read
+        # back into, beside the tokens
+        self.lp_on = False
+        self.d_lp: Optional[torch.Tensor] = None
+        self.d_want: Optional[torch.Tensor] = None
+        self._want_sent = np.full(B, -1, dtype=np.int32)  # what d_want holds (as of the last upload)
+        self.h_lp: list = [None, None]
+        self._pf_lp: list = [None, None]  # pinned records of in-flight prefill steps
         self.decode_ws = ops.decode_workspace(B, model.hq, D, self.max_blocks_per_seq * BLOCK_SIZE, dev, model.hkv) \
             if self.is_gpu else None
         # pinned host staging, double-buffered: with pipelined decode the host fills step N+1's
@@ -198,6 +208,54 @@ class ModelRunner:
         return {"penalty_slots_in_use": len(self._pen_slot),
                 "penalty_state_bytes": self.pen.nbytes if self.pen is not None else 0}
 
+    # --------------------------------------------------------------------- token log-probabilities
+    def logprob_enable(self) -> None:
+        """Allocate the logprob buffers on first use.  Decode graphs captured without the extra
+        pass are captured again, once, with it and ``d_want`` as an input (the in-flight step's
+        tokens in ``d_out`` survive the capture)."""
+        if self.lp_on:
+            return
+        B, dev = self.B, self.device
+        self.d_lp = torch.zeros(B, ops.LP_WIDTH, dtype=torch.int32, device=dev)
+        self.d_want = torch.full((B,), -1, dtype=torch.int32, device=dev)
+        self._want_sent[:] = -1
+        self.h_lp = [torch.zeros(B, ops.LP_WIDTH, dtype=torch.int32, pin_memory=self.is_gpu) for _ in range(2)]
+        self.lp_on = True
+        if self.graphs:
+            buckets = sorted(self.graphs)
+            self.graphs = {}
+            self.capture_graphs(buckets)
+
+    @staticmethod
+    def _lp_want(seq) -> int:
+        """What a sequence asks of ``ops.token_logprobs``: -1 nothing, else its ``top_logprobs``."""
+        p = seq.params
+        return int(p.top_logprobs) if getattr(p, "logprobs", False) else -1
+
+    def _upload_want(self, seqs: list) -> Optional[list]:
+        """Decode rows -> want, copied to ``d_want`` in front of the step only when it differs
+        from what the device holds.  Returns the rows' wants, or None when no row asks."""
+        want = [self._lp_want(s) for s in seqs]
+        m = np.full(self.B, -1, dtype=np.int32)
+        m[: len(seqs)] = want
+        if not np.array_equal(m, self._want_sent):
+            self._want_sent = m
+            h = torch.from_numpy(m)
+            self.d_want.copy_(h.pin_memory() if self.is_gpu else h, non_blocking=True)
+        return want if max(want, default=-1) >= 0 else None
+
+    @staticmethod
+    def collect_logprobs(handle: "DecodeHandle") -> Optional[list]:
+        """After :meth:`decode_collect`: per row of the step ``(lp, [(id, lp), ...])``
+        (``ops.unpack_logprobs``) or None for a row that did not ask; None when no row did."""
+        if handle.lp is None:
+            return None
+        rec = handle.lp[: handle.n].numpy()  # one conversion per step, not one per row
+        lps = rec[:, : 1 + ops.LP_MAX_TOP].view(np.float32).tolist()
+        ids = rec[:, 1 + ops.LP_MAX_TOP:].tolist()
+        return [(f[0], [(i, v) for i, v in zip(t[:w], f[1:1 + w]) if i >= 0]) if w >= 0 else None
+                for w, f, t in zip(handle.lp_want, lps, ids)]
+
     # --------------------------------------------------------------------- prefill
     def prefill(self, seqs: list[Sequence], decode: Optional[list] = None) -> list[int]:
         """One prefill (or mixed) step, synchronous: see :meth:`prefill_launch`."""
@@ -252,7 +310,8 @@ class ModelRunner:
         sizes = dict(ids=T, pos=T, slots=T, cu=len(seqs) + 1, qs=nq, st=nq, lidx=R, temp=R, topk=R, topp=R,
                      cst=len(seqs) if paged else 0, bt=len(seqs) * W, dbt=nd * Wd, dlen=nd,
                      mcu=len(seqs) + 2 if kA else 0, mqs=nq if kA else 0, mst=nq if kA else 0,
-                     mlidx=len(seqs) if kA else 0, pslot=R if self.pen is not None else 0)
+                     mlidx=len(seqs) if kA else 0, pslot=R if self.pen is not None else 0,
+                     want=R if self.lp_on else 0)
         off, o = {}, 0
         for k, n in sizes.items():
             off[k] = o
@@ -289,6 +348,14 @@ class ModelRunner:
             for i, (s, c, n) in enumerate(zip(seqs, starts, lens)):
                 slot = self._penalty_slot(s, take=True)
                 v["pslot"][nd + i] = slot if c + n >= s.num_tokens else -1
+        lp_want = None
+        if self.lp_on:
+            # a chunk short of its prompt's end samples a token nobody keeps: no logprobs for it
+            v["want"][:nd] = [self._lp_want(q) for q in decode]
+            v["want"][nd:] = [self._lp_want(s) if c + n >= s.num_tokens else -1
+                              for s, c, n in zip(seqs, starts, lens)]
+            if int(v["want"].max()) >= 0:
+                lp_want = v["want"].tolist()
         if paged:
             v["cst"][:] = starts
             bt2 = v["bt"].reshape(len(seqs), W)
@@ -342,19 +409,26 @@ class ModelRunner:
         logits = self.model.forward(dv["ids"], meta, self.kv)
         tok = self._sample(logits, dv["temp"].view(torch.float32), dv["topk"], dv["topp"].view(torch.float32),
                            pslot=dv["pslot"])
+        lp = ops.token_logprobs(logits[:R], tok, dv["want"]) if lp_want is not None else None
         self.n_steps["prefill"] += 1
         if self.on_launched is not None:  # TP: the custom-AR error flag, read back with the tokens
             self.on_launched()
         if not self.is_gpu:
-            return DecodeHandle(R, None, tok[:R].tolist())
+            return DecodeHandle(R, None, tok[:R].tolist(), lp=lp, lp_want=lp_want)
         j = self._pf_oi
         self._pf_oi ^= 1  # two in flight at most: step N+1 is launched before step N is read back
         if self._pf_out[j] is None or self._pf_out[j].numel() < R:
             self._pf_out[j] = torch.empty(max(R, 2 * self.B), dtype=torch.int32, pin_memory=True)
         out = self._pf_out[j]
         out[:R].copy_(tok[:R], non_blocking=True)
+        h_lp = None
+        if lp is not None:
+            if self._pf_lp[j] is None or self._pf_lp[j].shape[0] < R:
+                self._pf_lp[j] = torch.empty(max(R, 2 * self.B), ops.LP_WIDTH, dtype=torch.int32, pin_memory=True)
+            h_lp = self._pf_lp[j]
+            h_lp[:R].copy_(lp, non_blocking=True)
         ev, _ = self._chain_event()
-        return DecodeHandle(R, ev, out)
+        return DecodeHandle(R, ev, out, lp=h_lp, lp_want=lp_want)
 
     # --------------------------------------------------------------------- decode
     def _decode_body(self, b: int) -> None:
@@ -367,6 +441,8 @@ class ModelRunner:
         logits = self.model.forward(self.d_ids[:b], meta, self.kv)
         self._sample(logits, self.d_temp[:b], self.d_topk[:b], self.d_topp[:b], out=self.d_out[:b],
                      pslot=self.d_pslot[:b])
+        if self.lp_on:  # after the sampler on the stream: it reads the tokens just drawn
+            ops.token_logprobs(logits, self.d_out[:b], self.d_want[:b], out=self.d_lp[:b])
 
     def capture_graphs(self, buckets: Optional[list[int]] = None) -> None:
         if not (self.is_gpu and self.cfg.use_graphs):
@@ -377,6 +453,9 @@ class ModelRunner:
         self.d_slots.fill_(-1)
         self.d_pslot.fill_(-1)  # ... and count nothing; the next decode step uploads its rows' slots again
         self._pslot_sent[:] = -1
+        if self.lp_on:  # ... and compute no logprobs
+            self.d_want.fill_(-1)
+            self._want_sent[:] = -1
         rng_state, out_state = self.rng.clone(), self.d_out.clone()
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
@@ -445,9 +524,10 @@ class ModelRunner:
         n_el = _Staging.prefix(self.B, self.max_blocks_per_seq, b)  # the per-row fields + b block-table rows
         if self.pen is not None:
             self._upload_pslot(seqs)
+        lp_want = self._upload_want(seqs) if self.lp_on else None
         if publish is not None:
             publish(st.message(n, b, n_el))
-        return self._launch_staged(st, n, b, n_el)
+        return self._launch_staged(st, n, b, n_el, lp_want)
 
     def decode_launch_raw(self, n: int, b: int, n_el: int, words: np.ndarray) -> "DecodeHandle":
         """TP worker: launch the decode step the leader staged (its raw staging words)."""
@@ -456,7 +536,10 @@ class ModelRunner:
         st.raw[:n_el] = words
         return self._launch_staged(st, n, b, n_el)
 
-    def _launch_staged(self, st: "_Staging", n: int, b: int, n_el: int) -> "DecodeHandle":
+    def _launch_staged(self, st: "_Staging", n: int, b: int, n_el: int,
+                       lp_want: Optional[list] = None) -> "DecodeHandle":
+        """``lp_want`` (logprobs enabled and some row of the step asks): the rows' wants - their
+        records are read back beside the tokens."""
         gs = self.graphs.get(b)
         if gs is not None and self.graph_h2d:
             gs[st.idx].replay()  # its first node copies this staging buffer (n_el = the bucket's prefix)
@@ -470,12 +553,16 @@ class ModelRunner:
         if self.on_launched is not None:
             self.on_launched()
         if not self.is_gpu:
-            return DecodeHandle(n, None, self.d_out[:n].tolist())
+            return DecodeHandle(n, None, self.d_out[:n].tolist(),
+                                lp=self.d_lp[:n].clone() if lp_want is not None else None, lp_want=lp_want)
         h = self.h_out[self._out_i]
+        h_lp = self.h_lp[self._out_i] if lp_want is not None else None
         self._out_i ^= 1
         h[:n].copy_(self.d_out[:n], non_blocking=True)
+        if h_lp is not None:
+            h_lp[:n].copy_(self.d_lp[:n], non_blocking=True)
         ev, prev = self._chain_event()
-        return DecodeHandle(n, ev, h, prev)
+        return DecodeHandle(n, ev, h, prev, lp=h_lp, lp_want=lp_want)
 
     def _chain_event(self) -> tuple:
         """Record the end-of-step event (timing-enabled) and return it with the previous launched
@@ -563,6 +650,8 @@ class DecodeHandle:
     event: object  # torch.cuda.Event, None on the CPU
     out: object  # pinned host tensor (GPU) or the token list (CPU)
     prev_event: object = None  # the back-to-back predecessor's end event (ModelRunner._chain_event)
+    lp: object = None  # the step's packed logprob records (pinned on the GPU), None when no row asked
+    lp_want: Optional[list] = None  # with lp: per row what it asked (-1: nothing, its record is stale)
 
     def gpu_ms(self) -> Optional[float]:
         """This step's GPU time (after the event completed), or None when not measurable."""

@@ -25,6 +25,11 @@ class SamplingParams:
     repetition_penalty: float = 1.0
     presence_penalty: float = 0.0
     frequency_penalty: float = 0.0
+    # token log-probabilities (ops/reference.py token_logprobs): of each answer token under the
+    # model's distribution - before penalties, temperature and top-k / top-p - and of the
+    # ``top_logprobs`` (0..20, needs ``logprobs``) most likely alternatives; Sequence.output_logprobs
+    logprobs: bool = False
+    top_logprobs: int = 0
 
     def has_penalties(self) -> bool:
         return self.repetition_penalty != 1.0 or self.presence_penalty != 0.0 or self.frequency_penalty != 0.0
@@ -47,6 +52,9 @@ class Sequence:
     request_id: str = ""
     seq_id: int = field(default_factory=lambda: next(_ids))
     output_ids: list[int] = field(default_factory=list)
+    # for a sequence that asked (SamplingParams.logprobs), aligned with output_ids: per token
+    # (lp, [(id, lp), ...]) - its log-probability and the top_logprobs alternatives; else None
+    output_logprobs: Optional[list] = None
     status: SeqStatus = SeqStatus.WAITING
     block_table: list[int] = field(default_factory=list)
     finish_reason: Optional[str] = None

@@ -88,6 +88,10 @@ class ByteBPETokenizer:
             return self._bytes[256 + (t - nb) % (nb - 256)]
         return self._bytes[t % 256]
 
+    def token_bytes(self, t: int) -> bytes:
+        """The bytes token ``t`` stands for (special tokens: none)."""
+        return self._token_bytes(int(t), False)
+
     def decode(self, ids: Iterable[int], skip_special: bool = True) -> str:
         # one bytes object per vocabulary id, built on first use: a whole answer is then one
         # list lookup per token and one join (an engine step's finished answers are decoded on the
@@ -193,6 +197,10 @@ class HFTokenizer:
 
     def decode(self, ids: Iterable[int], skip_special: bool = True) -> str:
         return self.tok.decode([int(t) for t in ids if t >= 0], skip_special_tokens=skip_special)
+
+    def token_bytes(self, t: int) -> bytes:
+        """The UTF-8 bytes of token ``t`` decoded on its own."""
+        return self.decode([int(t)], skip_special=False).encode("utf-8")
 
 
 def tokenizer_from_dir(path, model_cfg):

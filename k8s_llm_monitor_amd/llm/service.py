@@ -36,7 +36,18 @@ log = logging.getLogger("llm")
 
 
 class GenResult(dict):
-    """{text, prompt_tokens, completion_tokens, latency_ms, ttft_ms, model, provider}"""
+    """{text, prompt_tokens, completion_tokens, latency_ms, ttft_ms, model, provider}; with
+    ``logprobs`` requested also {logprobs}: per answer token {token, logprob, bytes, top_logprobs:
+    [{token, logprob, bytes}, ...]} (OpenAI's ``choices[0].logprobs.content``)."""
+
+
+def logprob_summary(entries) -> dict:
+    """{mean_logprob, min_logprob} of an answer's per-token entries (None for an empty or missing
+    list): the confidence signal of a generated analysis."""
+    vals = [e["logprob"] for e in entries or [] if e.get("logprob") is not None]
+    if not vals:
+        return {"mean_logprob": None, "min_logprob": None}
+    return {"mean_logprob": sum(vals) / len(vals), "min_logprob": min(vals)}
 
 
 class AnswerBudgetExceeded(FutTimeout):
@@ -85,7 +96,11 @@ class LocalEngineBackend:
     def generate(self, prompt: str, max_tokens: Optional[int] = None, temperature: Optional[float] = None,
                  request_id: Optional[str] = None, ignore_eos: bool = False,
                  top_p: Optional[float] = None, presence_penalty: Optional[float] = None,
-                 frequency_penalty: Optional[float] = None, repetition_penalty: Optional[float] = None) -> GenResult:
+                 frequency_penalty: Optional[float] = None, repetition_penalty: Optional[float] = None,
+                 logprobs: bool = False, top_logprobs: int = 0) -> GenResult:
+        """``logprobs`` / ``top_logprobs`` (0..20): the result carries ``logprobs``, one entry per
+        answer token - its log-probability under the model's distribution (before penalties,
+        temperature and top-k / top-p) and that many most likely alternatives."""
         from ..engine import SamplingParams
 
         d = self.default
@@ -94,7 +109,8 @@ class LocalEngineBackend:
                            top_k=d.top_k, top_p=d.top_p if top_p is None else top_p, ignore_eos=ignore_eos,
                            repetition_penalty=d.repetition_penalty if repetition_penalty is None else repetition_penalty,
                            presence_penalty=d.presence_penalty if presence_penalty is None else presence_penalty,
-                           frequency_penalty=d.frequency_penalty if frequency_penalty is None else frequency_penalty)
+                           frequency_penalty=d.frequency_penalty if frequency_penalty is None else frequency_penalty,
+                           logprobs=logprobs, top_logprobs=top_logprobs)
         budget = self.answer_budget_s
         fut = self.svc.submit(P.SYSTEM_PREAMBLE + prompt, p, request_id,
                               deadline=time.perf_counter() + budget if budget else None)
@@ -107,8 +123,23 @@ class LocalEngineBackend:
             # a futures TimeoutError: the HTTP layer answers it 504, as its own write-timeout backstop
             raise AnswerBudgetExceeded("answer not ready within the answer budget") from None
         t = seq.timings()
-        return GenResult(text=text, model=self.model, provider=self.provider, finish_reason=seq.finish_reason, **t)
+        g = GenResult(text=text, model=self.model, provider=self.provider, finish_reason=seq.finish_reason, **t)
+        if logprobs:
+            g["logprobs"] = self._logprob_entries(seq)
+        return g
 
+    def _logprob_token(self, tid: int, lp: float) -> dict:
+        tok = self.tokenizer
+        return {"token": tok.decode([tid], skip_special=False), "logprob": lp, "bytes": list(tok.token_bytes(tid))}
+
+    def _logprob_entries(self, seq) -> list:
+        out = []
+        for tid, e in zip(seq.output_ids, seq.output_logprobs or []):
+            lp, top = e if e is not None else (None, [])
+            d = self._logprob_token(tid, lp)
+            d["top_logprobs"] = [self._logprob_token(i, v) for i, v in top]
+            out.append(d)
+        return out
 
     def stream(self, prompt: str, max_tokens: Optional[int] = None, temperature: Optional[float] = None,
                request_id: Optional[str] = None, ignore_eos: bool = False):
@@ -200,8 +231,10 @@ class OpenAIBackend:
     def generate(self, prompt: str, max_tokens: Optional[int] = None, temperature: Optional[float] = None,
                  request_id: Optional[str] = None, ignore_eos: bool = False,
                  top_p: Optional[float] = None, presence_penalty: Optional[float] = None,
-                 frequency_penalty: Optional[float] = None, repetition_penalty: Optional[float] = None) -> GenResult:
-        """``repetition_penalty`` is not an OpenAI field: it is not forwarded."""
+                 frequency_penalty: Optional[float] = None, repetition_penalty: Optional[float] = None,
+                 logprobs: bool = False, top_logprobs: int = 0) -> GenResult:
+        """``repetition_penalty`` is not an OpenAI field: it is not forwarded.  ``logprobs`` /
+        ``top_logprobs`` are, and ``choices[0].logprobs.content`` comes back as ``logprobs``."""
         if not self.api_key:
             raise RuntimeError("llm.api_key / OPENAI_API_KEY not configured")
         req_d = {"model": self.model, "max_tokens": max_tokens or self.max_tokens,
@@ -216,6 +249,10 @@ class OpenAIBackend:
             req_d["presence_penalty"] = pp
         if fp:
             req_d["frequency_penalty"] = fp
+        if logprobs:
+            req_d["logprobs"] = True
+            if top_logprobs:
+                req_d["top_logprobs"] = int(top_logprobs)
         body = json.dumps(req_d).encode()
         req = urllib.request.Request(self.base_url + "/chat/completions", data=body, method="POST",
                                      headers={"Content-Type": "application/json",
@@ -224,11 +261,14 @@ class OpenAIBackend:
         with urllib.request.urlopen(req, timeout=self.timeout_s) as r:
             d = json.loads(r.read())
         usage = d.get("usage") or {}
-        return GenResult(text=d["choices"][0]["message"]["content"], model=d.get("model") or self.model,
-                         provider=self.provider,
-                         prompt_tokens=usage.get("prompt_tokens"), completion_tokens=usage.get("completion_tokens"),
-                         latency_ms=round((time.perf_counter() - t0) * 1e3, 3), ttft_ms=None,
-                         finish_reason=d["choices"][0].get("finish_reason"))
+        g = GenResult(text=d["choices"][0]["message"]["content"], model=d.get("model") or self.model,
+                      provider=self.provider,
+                      prompt_tokens=usage.get("prompt_tokens"), completion_tokens=usage.get("completion_tokens"),
+                      latency_ms=round((time.perf_counter() - t0) * 1e3, 3), ttft_ms=None,
+                      finish_reason=d["choices"][0].get("finish_reason"))
+        if logprobs:
+            g["logprobs"] = (d["choices"][0].get("logprobs") or {}).get("content") or []
+        return g
 
 
 class RuleBackend:
@@ -241,7 +281,9 @@ class RuleBackend:
     def generate(self, prompt: str, max_tokens: Optional[int] = None, temperature: Optional[float] = None,
                  request_id: Optional[str] = None, ignore_eos: bool = False,
                  top_p: Optional[float] = None, presence_penalty: Optional[float] = None,
-                 frequency_penalty: Optional[float] = None, repetition_penalty: Optional[float] = None) -> GenResult:
+                 frequency_penalty: Optional[float] = None, repetition_penalty: Optional[float] = None,
+                 logprobs: bool = False, top_logprobs: int = 0) -> GenResult:
+        """No model, so no log-probabilities: ``logprobs`` / ``top_logprobs`` are ignored."""
         flagged = [ln.strip() for ln in prompt.splitlines()
                    if any(k in ln for k in ("[资源压力]", "[不健康]", "状态=", "接近限制", "不通", "告警", "UAV "))]
         text = ("未发现明显异常。" if not flagged else
@@ -404,13 +446,19 @@ class AnalysisService:
 
     # ------------------------------------------------------------------ entry points
     def _respond(self, rid: str, kind: str, prompt: str, extra: dict, max_tokens: Optional[int] = None,
-                 ignore_eos: bool = False) -> AnalysisResponse:
+                 ignore_eos: bool = False, logprobs: bool = False) -> AnalysisResponse:
+        """``logprobs``: the record's result gains ``mean_logprob`` and ``min_logprob`` over the
+        answer's tokens (None for an empty answer or a backend without a model) - how sure the
+        model was of what it wrote."""
         from ..engine import EngineOverloaded, EngineUnavailable
 
         backend = self.backend_for(kind)
         try:
+            lp_kw = {"logprobs": True} if logprobs else {}
             g = backend.generate(prompt, max_tokens=max_tokens or self.max_tokens, request_id=rid,
-                                 ignore_eos=ignore_eos)
+                                 ignore_eos=ignore_eos, **lp_kw)
+            if logprobs:
+                extra = {**extra, **logprob_summary(g.pop("logprobs", None))}
             result = {"type": kind, "answer": g.pop("text"), **g, **extra}
             resp = AnalysisResponse(request_id=rid, status="success", result=result, timestamp=utcnow())
         except (EngineOverloaded, EngineUnavailable):
@@ -455,14 +503,15 @@ class AnalysisService:
         yield resp
 
     def query(self, question: str, max_tokens: Optional[int] = None, ignore_eos: bool = False,
-              context_text: Optional[str] = None) -> AnalysisResponse:
+              context_text: Optional[str] = None, logprobs: bool = False) -> AnalysisResponse:
         """POST /api/v1/query (README.md:91-96; not implemented by the reference).  ``context_text``
-        lets a caller supply the cluster state itself (e.g. another collector's snapshot)."""
+        lets a caller supply the cluster state itself (e.g. another collector's snapshot).
+        ``logprobs``: the result carries ``mean_logprob`` / ``min_logprob`` of the answer."""
         rid = uuid.uuid4().hex
         ctx = context_text if context_text else self.cluster_context()
         ctx = self._fit(ctx, P.build_query_prompt("", question), max_tokens, "query")
         prompt = P.build_query_prompt(ctx, question)
-        return self._respond(rid, "query", prompt, {"question": question}, max_tokens, ignore_eos)
+        return self._respond(rid, "query", prompt, {"question": question}, max_tokens, ignore_eos, logprobs)
 
     def analyze(self, req: AnalysisRequest) -> AnalysisResponse:
         kind = req.type or "anomaly_detection"
@@ -478,7 +527,8 @@ class AnalysisService:
         mt = int(params.get("max_tokens") or 0) or None
         ctx = self._fit(self.cluster_context(), P.build_analysis_prompt(kind, "", params), mt, kind)
         prompt = P.build_analysis_prompt(kind, ctx, params)
-        return self._respond(uuid.uuid4().hex, kind, prompt, {"parameters": params}, mt)
+        return self._respond(uuid.uuid4().hex, kind, prompt, {"parameters": params}, mt,
+                             logprobs=params.get("logprobs") is True)
 
     def explain_pod_communication(self, analysis, max_tokens: Optional[int] = None,
                                   ignore_eos: bool = False) -> AnalysisResponse:

@@ -380,6 +380,12 @@ class MonitorApp:
         ctx_text = ctx.get("cluster_state") if isinstance(ctx, dict) else None
         if ctx_text is not None and not isinstance(ctx_text, str):
             raise http_error(400, "context.cluster_state must be a string")
+        want_lp = d.get("logprobs", False)
+        if not isinstance(want_lp, bool):
+            raise http_error(400, "logprobs must be a boolean")
+        if want_lp and d.get("stream") is True:
+            raise http_error(400, "logprobs are not supported with stream: true")
+        lp_kw = {"logprobs": True} if want_lp else {}
         if d.get("stream") is True:  # Server-Sent Events: {"delta"} events, then event "done" = the record
             gen = self.analysis.query_stream(question, max_tokens=mt, ignore_eos=bool(d.get("ignore_eos", False)),
                                              context_text=ctx_text)
@@ -403,7 +409,7 @@ class MonitorApp:
         try:
             resp = self._bounded(lambda: self.analysis.query(question, max_tokens=mt,
                                                              ignore_eos=bool(d.get("ignore_eos", False)),
-                                                             context_text=ctx_text),
+                                                             context_text=ctx_text, **lp_kw),
                                  kind="query" if inline else None)
         except _BUSY as e:
             return self._busy_reply(e)
@@ -422,7 +428,11 @@ class MonitorApp:
         ``stop`` sequences are refused with 400 rather than silently ignored; ``top_p`` is
         honoured, and so are ``presence_penalty`` / ``frequency_penalty`` (numbers in [-2, 2]) and
         the extension ``repetition_penalty`` (a number in (0, 10]) - an invalid value is a 400, and
-        so is a penalty the engine cannot apply (tensor parallelism)."""
+        so is a penalty the engine cannot apply (tensor parallelism).  ``logprobs`` (a boolean) and
+        ``top_logprobs`` (an integer in [0, 20], needs ``logprobs: true``) add
+        ``choices[0].logprobs.content``: per answer token its log-probability under the model's
+        distribution - before penalties, temperature and top-k / top-p - and the most likely
+        alternatives; invalid values are a 400, and without the fields the reply has no such key."""
         _only(method, "POST")
         if self.analysis is None:
             raise http_error(503, "Analysis engine not available")
@@ -457,6 +467,17 @@ class MonitorApp:
                 rng = "(0, 10]" if key == "repetition_penalty" else "[-2, 2]"
                 raise http_error(400, f"{key} must be a number in {rng}")
             pen[key] = float(val)
+        want_lp, n_top = d.get("logprobs"), d.get("top_logprobs")
+        if want_lp is not None and not isinstance(want_lp, bool):
+            raise http_error(400, "logprobs must be a boolean")
+        if n_top is not None:
+            if isinstance(n_top, bool) or not isinstance(n_top, int) or not 0 <= n_top <= 20:
+                raise http_error(400, "top_logprobs must be an integer in [0, 20]")
+            if not want_lp:
+                raise http_error(400, "top_logprobs needs logprobs: true")
+        if want_lp:
+            pen["logprobs"] = True
+            pen["top_logprobs"] = n_top or 0
         backend = self.analysis.backend
         try:
             prompt = self.analysis.fit_chat(parts, mt)
@@ -472,11 +493,13 @@ class MonitorApp:
         pt, ct = g.get("prompt_tokens"), g.get("completion_tokens")
         usage = {"prompt_tokens": pt, "completion_tokens": ct,
                  "total_tokens": (pt or 0) + (ct or 0) if pt is not None or ct is not None else None}
+        choice = {"index": 0, "message": {"role": "assistant", "content": g.get("text", "")},
+                  "finish_reason": g.get("finish_reason") or "stop"}
+        if want_lp:
+            choice["logprobs"] = {"content": g.get("logprobs") or []}
         return json_reply({"id": "chatcmpl-" + uuid.uuid4().hex, "object": "chat.completion",
                            "created": int(time.time()), "model": g.get("model") or d.get("model", ""),
-                           "choices": [{"index": 0, "message": {"role": "assistant", "content": g.get("text", "")},
-                                        "finish_reason": g.get("finish_reason") or "stop"}],
-                           "usage": usage})
+                           "choices": [choice], "usage": usage})
 
     def analyze(self, method, body, q) -> Reply:
         _only(method, "POST")

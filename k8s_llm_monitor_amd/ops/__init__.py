@@ -1430,6 +1430,60 @@ def _sample_cpu(logits, temperature, top_k, top_p, rng, penalties=None, slots=No
     return res
 
 
+# ---------------------------------------------------------------- token log-probabilities
+
+LP_MAX_TOP = 20  # kLpMaxTop: OpenAI's top_logprobs limit
+LP_WIDTH = 1 + 2 * LP_MAX_TOP  # int32 words of one row's packed record
+
+
+def token_logprobs(logits: torch.Tensor, tokens: torch.Tensor, want: torch.Tensor,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Log-probabilities of the drawn tokens and of the most likely alternatives
+    (``ref.token_logprobs``): the model's distribution over the logits as given, before penalties,
+    temperature and top-k / top-p.  ``tokens`` int32 [B] (what ``sample`` wrote), ``want`` int32
+    [B]: < 0 the row did not ask (its record is left as it is), 0 the token's logprob only,
+    1..``LP_MAX_TOP`` plus that many alternatives.  Returns ``out``: int32 ``[B, LP_WIDTH]``, per
+    row word 0 = the bits of lp(token), words 1..20 = the bits of the alternatives' logprobs,
+    words 21..40 = their ids (``unpack_logprobs``) - one buffer, so a step's logprobs reach the
+    host in one copy."""
+    B = logits.shape[0]
+    if tokens.dtype != torch.int32 or want.dtype != torch.int32 or tokens.numel() < B or want.numel() < B:
+        raise ValueError("token_logprobs: tokens and want are int32 [B]")
+    if out is None:
+        out = torch.zeros(B, LP_WIDTH, dtype=torch.int32, device=logits.device)
+    elif out.dtype != torch.int32 or out.dim() != 2 or out.shape[0] < B or out.shape[1] != LP_WIDTH:
+        raise ValueError(f"token_logprobs: out is int32 [>= B, {LP_WIDTH}]")
+    if _gpu(logits):
+        native().token_logprobs(out, logits, tokens, want)
+        return out
+    for b in range(B):
+        n = min(int(want[b]), LP_MAX_TOP)
+        if n < 0:
+            continue
+        lp, ids, lps = ref.token_logprobs(logits[b], int(tokens[b]), n)
+        rec = out[b]
+        rec[0] = torch.tensor(lp, dtype=torch.float32).view(torch.int32)
+        rec[1:1 + LP_MAX_TOP] = torch.tensor(float("-inf"), dtype=torch.float32).view(torch.int32)
+        rec[1 + LP_MAX_TOP:] = -1
+        rec[1:1 + n] = lps.view(torch.int32)
+        rec[1 + LP_MAX_TOP:1 + LP_MAX_TOP + n] = ids
+    return out
+
+
+def unpack_logprobs(rec_row) -> tuple:
+    """``(lp, [(id, lp), ...])`` of one packed record (a host int32 row of ``token_logprobs``):
+    the alternatives up to the first empty entry."""
+    rec = torch.as_tensor(rec_row, dtype=torch.int32).contiguous()
+    f = rec.view(torch.float32).tolist()
+    ids = rec[1 + LP_MAX_TOP:].tolist()
+    top = []
+    for j, i in enumerate(ids):
+        if i < 0:
+            break
+        top.append((i, f[1 + j]))
+    return f[0], top
+
+
 # ---------------------------------------------------------------- mixture of experts
 
 def moe_route(router_logits: torch.Tensor, k: int, renorm: bool = True):

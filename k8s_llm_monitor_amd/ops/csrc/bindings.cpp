@@ -43,6 +43,9 @@ int k8sllm_penalty_reset(void* table, long tstride, int V, int nslots, int slot,
                          int n_out, float* pparams, float rep, float inv_rep, float presence, float frequency,
                          hipStream_t s);
 int k8sllm_sample_parts(long B, int V);
+long k8sllm_token_logprobs_ws(long B, int V);
+int k8sllm_token_logprobs(int* out, const void* logits, int is_fp32, long B, long stride, int V, const int* tok,
+                          const int* want, void* ws, hipStream_t s);
 int k8sllm_moe_route(const void* logits, long T, int E, int K, int renorm, int* topk_ids, float* topk_w,
                      hipStream_t s);
 int k8sllm_moe_router(const void* x, const void* wr, long T, int d, int E, int K, int renorm, int* ids, float* w,
@@ -450,6 +453,25 @@ void penalty_reset(torch::Tensor table, torch::Tensor params, int64_t vocab, int
                              ids.data_ptr<int>(), (int)n_prompt, (int)n_out, params.data_ptr<float>(), (float)rep,
                              (float)inv_rep, (float)presence, (float)frequency, cur()),
         "penalty_reset");
+}
+
+// Token log-probabilities (ops.token_logprobs): out int32 [>= B, 41] packed records, tok / want int32 [>= B]
+void token_logprobs(torch::Tensor out, torch::Tensor logits, torch::Tensor tok, torch::Tensor want) {
+  dev_i32(out, "out"); dev_i32(tok, "tok"); dev_i32(want, "want");
+  TORCH_CHECK(logits.is_cuda() && logits.dim() == 2 && logits.stride(1) == 1, "logits [B, V]");
+  const bool f32 = logits.scalar_type() == torch::kFloat32;
+  TORCH_CHECK(f32 || logits.scalar_type() == torch::kBFloat16, "logits must be fp32 or bf16");
+  const long B = logits.size(0);
+  const int V = (int)logits.size(1);
+  TORCH_CHECK(V > 0, "token_logprobs: empty vocabulary");
+  TORCH_CHECK(tok.numel() >= B && want.numel() >= B, "token_logprobs: tok [B], want [B]");
+  TORCH_CHECK(out.dim() == 2 && out.size(0) >= B && out.size(1) == 41, "token_logprobs: out int32 [>= B, 41]");
+  if (B == 0) return;
+  // partials and candidates: stream-ordered caching allocator (graph-pool safe), like sample
+  auto ws = torch::empty({(int64_t)k8sllm_token_logprobs_ws(B, V)}, logits.options().dtype(torch::kInt32));
+  check(k8sllm_token_logprobs(out.data_ptr<int>(), logits.data_ptr(), f32 ? 1 : 0, B, logits.stride(0), V,
+                              tok.data_ptr<int>(), want.data_ptr<int>(), ws.data_ptr(), cur()),
+        "token_logprobs");
 }
 
 void moe_router(torch::Tensor x, torch::Tensor wr, torch::Tensor ids, torch::Tensor w, torch::Tensor wd, bool renorm) {
@@ -1198,6 +1220,7 @@ PYBIND11_MODULE(_k8sllm_ops, m) {
         py::arg("rng"), py::arg("advance") = false, py::arg("pen_table") = py::none(),
         py::arg("pen_params") = py::none(), py::arg("pen_slots") = py::none(), py::arg("pen_vocab") = 0);
   m.def("penalty_reset", &penalty_reset);
+  m.def("token_logprobs", &token_logprobs);
   m.def("moe_route", &moe_route);
   m.def("moe_router", &moe_router);
   m.def("moe_align", &moe_align);

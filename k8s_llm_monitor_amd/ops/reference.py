@@ -269,6 +269,29 @@ def apply_penalties(logits_row: torch.Tensor, prompt_seen: torch.Tensor, out_cou
     return x - torch.tensor(float(presence), dtype=f32) * (cnt > 0).to(f32)
 
 
+def token_logprobs(logits_row: torch.Tensor, token: int, n: int):
+    """``(lp, ids[n], lps[n])`` of one row of logits, in fp32.
+
+    ``lp = x[token] - lse`` over the logits as given (``float()``): the model's distribution,
+    before penalties, temperature and top-k / top-p; NaN for a token outside ``[0, V)``.  ``ids``
+    (int32) are the ``n`` largest logits in the order (value descending, index ascending) - a
+    stable descending sort - and ``lps`` (fp32) their log-probabilities; entries past
+    ``min(n, V)`` are id -1, logprob -inf."""
+    x = logits_row.detach().float()
+    V = x.numel()
+    lps_all = torch.log_softmax(x, -1)
+    t = int(token)
+    lp = float(lps_all[t]) if 0 <= t < V else float("nan")
+    ids = torch.full((n,), -1, dtype=torch.int32)
+    lps = torch.full((n,), float("-inf"), dtype=torch.float32)
+    k = min(n, V)
+    if k > 0:
+        order = torch.sort(x, descending=True, stable=True).indices[:k]
+        ids[:k] = order.to(torch.int32)
+        lps[:k] = lps_all[order]
+    return lp, ids, lps
+
+
 def moe_route(logits: torch.Tensor, k: int, renorm: bool):
     p = torch.softmax(logits.float(), dim=-1)
     w, ids = torch.topk(p, k, dim=-1)

@@ -27,6 +27,11 @@ __global__ __launch_bounds__(256) void moe_route_kernel(const float* __restrict_
         bv = x[e];
         best = e;
       }
+    if (best < 0) {  // NaN logits, or only -inf left: no comparison holds - take the first untaken expert
+      for (best = 0; (taken >> best) & 1ull; ++best) {
+      }
+      bv = x[best];
+    }
     taken |= 1ull << best;
     const float p = __expf(bv - mx) / z;
     ids[t * K + k] = best;

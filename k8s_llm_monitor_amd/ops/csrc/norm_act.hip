@@ -133,6 +133,19 @@ __global__ __launch_bounds__(256) void silu_mul_kernel(bf16_t* __restrict__ out,
     unpack8(make_uint4(ua.x, ua.y, ua.z, ua.w), u);
 #pragma unroll
     for (int j = 0; j < 8; ++j) o[j] = g[j] / (1.f + __expf(-g[j])) * u[j];
+    // below -87 exp(-gate) nears fp32's largest value (inf past -88.7) and silu(gate) turns subnormal, then
+    // 0, while silu(gate) * up can still be a normal number (gate -100, up 1e4: -3.7e-38).  There
+    // sigmoid(gate) = exp(gate) = exp(gate / 2)^2 to fp32 precision: give each factor one half.
+    // One test per 8 values keeps the rare path out of the common one.
+    const float gmin = fminf(fminf(fminf(g[0], g[1]), fminf(g[2], g[3])), fminf(fminf(g[4], g[5]), fminf(g[6], g[7])));
+    if (__builtin_expect(gmin < -87.f, 0)) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        if (g[j] < -87.f) {
+          const float e = __expf(0.5f * g[j]);
+          o[j] = (g[j] * e) * (u[j] * e);
+        }
+    }
     *reinterpret_cast<uint4*>(out + r * F + c) = pack8(o);
   }
 }

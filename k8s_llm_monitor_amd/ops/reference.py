@@ -1,4 +1,5 @@
-"""Plain-PyTorch fp32 references of every fused op.
+"""Plain-PyTorch fp32 references of every fused op (fp64 inside rms_norm, silu_mul and moe_combine,
+where a chain of fp32 roundings or fp32's range would show in the bf16 result).
 
 They define the semantics the HIP kernels must reproduce (tests compare the two), and they
 are the execution path for CPU tensors (unit tests, the GPT-2 CPU plumbing config).
@@ -16,8 +17,12 @@ import torch.nn.functional as F
 
 
 def rms_norm(x: torch.Tensor, w: torch.Tensor, eps: float) -> torch.Tensor:
-    xf = x.float()
-    y = xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps) * w.float()
+    # fp64: the fp32 sum of squares loses the small terms of a row that holds an outlier, and the
+    # chain of fp32 roundings after it is visible at a bf16 rounding boundary
+    # (tests/test_small_ops_models_cpu.py holds every reference to one fp32 rounding)
+    xf = x.double()
+    eps32 = float(torch.tensor(eps, dtype=torch.float32))  # the kernel's eps is an fp32 argument
+    y = xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps32) * w.double()
     return y.to(x.dtype)
 
 
@@ -33,7 +38,7 @@ def layer_norm(x, w, b, eps):
 def silu_mul(x: torch.Tensor, interleaved: bool = False) -> torch.Tensor:
     """silu(gate) * up; ``interleaved``: columns are [64 gate | 64 up] per 128."""
     f = x.shape[-1] // 2
-    xf = x.float()
+    xf = x.double()  # fp32 loses silu(gate) below -88 (exp overflows) while silu(gate) * up is still normal
     if interleaved:
         t = xf.reshape(*xf.shape[:-1], f // 64, 2, 64)
         return (F.silu(t[..., 0, :]) * t[..., 1, :]).reshape(*xf.shape[:-1], f).to(x.dtype)
@@ -313,5 +318,5 @@ def moe_align(ids: torch.Tensor, E: int):
 
 def moe_combine(y: torch.Tensor, inv_idx: torch.Tensor, w: torch.Tensor, T: int) -> torch.Tensor:
     K = w.shape[1]
-    g = y.float()[inv_idx.long()].view(T, K, -1)
-    return (g * w.float().unsqueeze(-1)).sum(1).to(y.dtype)
+    g = y.double()[inv_idx.long()].view(T, K, -1)  # K products and their sum, rounded once
+    return (g * w.double().unsqueeze(-1)).sum(1).to(y.dtype)

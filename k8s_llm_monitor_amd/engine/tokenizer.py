@@ -25,8 +25,9 @@ DEFAULT_MERGES = Path(__file__).resolve().parent / "data" / "bpe_merges.json"
 
 class ByteBPETokenizer:
     def __init__(self, merges: Optional[list[tuple[int, int]]] = None, bos_id: int = 1, eos_id: int = 2,
-                 vocab_size: int = 0):
+                 vocab_size: int = 0, add_bos: bool = True):
         self.merges = list(merges or [])
+        self.add_bos = add_bos  # False (Qwen3): encode(bos=True) prepends nothing either
         self.ranks = {tuple(p): i for i, p in enumerate(self.merges)}
         self.bos_id = bos_id
         self.eos_id = eos_id
@@ -63,6 +64,7 @@ class ByteBPETokenizer:
         return ids
 
     def encode(self, text: str, bos: bool = True) -> list[int]:
+        bos = bos and self.add_bos
         if self._native is not None:
             out = self._native.encode(text.encode("utf-8"))
             return ([self.bos_id] if bos else []) + list(out)
@@ -177,23 +179,24 @@ def tokenizer_for(model_cfg, merges_path: Path = DEFAULT_MERGES) -> ByteBPEToken
         room = min(room, specials_hi - 256)  # keep merges below the special ids (Llama-3: 128000)
     merges = merges[:max(0, room)]
     return ByteBPETokenizer(merges, bos_id=model_cfg.bos_id, eos_id=model_cfg.eos_ids[0],
-                            vocab_size=model_cfg.vocab_size)
+                            vocab_size=model_cfg.vocab_size, add_bos=model_cfg.add_bos)
 
 
 class HFTokenizer:
     """A Hugging Face ``tokenizer.json`` (the ``tokenizers`` library, Rust BPE) behind the same
     encode / decode interface, for engines loading real checkpoints (EngineConfig.weights)."""
 
-    def __init__(self, path: Path, bos_id: Optional[int], eos_id: Optional[int]):
+    def __init__(self, path: Path, bos_id: Optional[int], eos_id: Optional[int], add_bos: bool = True):
         from tokenizers import Tokenizer
 
         self.tok = Tokenizer.from_file(str(path))
         self.bos_id, self.eos_id = bos_id, eos_id
+        self.add_bos = add_bos
         self.vocab_size = self.tok.get_vocab_size()
 
     def encode(self, text: str, bos: bool = True) -> list[int]:
         ids = self.tok.encode(text, add_special_tokens=False).ids
-        return ([self.bos_id] if bos and self.bos_id is not None else []) + ids
+        return ([self.bos_id] if bos and self.add_bos and self.bos_id is not None else []) + ids
 
     def decode(self, ids: Iterable[int], skip_special: bool = True) -> str:
         return self.tok.decode([int(t) for t in ids if t >= 0], skip_special_tokens=skip_special)
@@ -207,5 +210,5 @@ def tokenizer_from_dir(path, model_cfg):
     """``path/tokenizer.json`` as an :class:`HFTokenizer` when present, else the built-in BPE."""
     f = Path(path) / "tokenizer.json"
     if f.exists():
-        return HFTokenizer(f, model_cfg.bos_id, model_cfg.eos_ids[0])
+        return HFTokenizer(f, model_cfg.bos_id, model_cfg.eos_ids[0], add_bos=model_cfg.add_bos)
     return tokenizer_for(model_cfg)

@@ -5,7 +5,7 @@ resume": "Optional safetensors loading when weights exist"); benchmarks here run
 weights because the GPU box has no network.  A deployment with real weights on disk points
 ``llm.weights`` (EngineConfig.weights) at a Hugging Face model directory:
 
-* :func:`config_from_hf` maps ``config.json`` (``llama`` / ``mixtral`` / ``gpt2``) onto a
+* :func:`config_from_hf` maps ``config.json`` (``llama`` / ``mistral`` / ``mixtral`` / ``qwen3`` / ``gpt2``) onto a
   :class:`ModelConfig`;
 * :func:`load_checkpoint` streams the tensors (safetensors, memory-mapped, nothing executed from
   the file) into a :class:`CausalLM`, fusing q/k/v -> ``wqkv`` and gate/up -> ``w13``, cutting this
@@ -21,6 +21,7 @@ Name maps (HF -> this framework):
     post_attention_layernorm -> mlp_norm, mlp.{gate,up}_proj -> w13, mlp.down_proj -> w2,
     block_sparse_moe.gate -> router, block_sparse_moe.experts.e.{w1,w3} -> w13[e], .w2 -> w2[e]
     (or the fused-expert form mlp.gate / mlp.experts.gate_up_proj / mlp.experts.down_proj)
+  qwen3: llama's names, plus layers.i.self_attn.{q,k}_norm -> q_norm, k_norm
   gpt2: transformer.wte / wpe / ln_f, h.i.ln_1 / ln_2, attn.c_attn / c_proj, mlp.c_fc / c_proj
     (Conv1D weights are stored [in, out]: transposed on load and on save)
 """
@@ -65,8 +66,14 @@ def config_from_hf(hf: Union[dict, PathLike], name: Optional[str] = None) -> Mod
                            head_dim=d // hf["n_head"], ffn_dim=_first(hf, "n_inner", default=4 * d) or 4 * d,
                            max_position=hf.get("n_positions", 1024), norm_eps=hf.get("layer_norm_epsilon", 1e-5),
                            tie_embeddings=True, bos_id=bos if bos is not None else 50256, eos_ids=eos_ids)
-    if mt not in ("llama", "mistral", "mixtral"):
-        raise ValueError(f"unsupported model_type {mt!r} (llama, mistral, mixtral, gpt2)")
+    if mt not in ("llama", "mistral", "mixtral", "qwen3"):
+        raise ValueError(f"unsupported model_type {mt!r} (llama, mistral, mixtral, qwen3, gpt2)")
+    qwen = mt == "qwen3"
+    if qwen:  # what a Qwen3 config may ask for that nothing here computes
+        if hf.get("attention_bias"):
+            raise ValueError("qwen3: attention_bias is not supported (the qkv / o projections take no bias)")
+        if hf.get("use_sliding_window"):
+            raise ValueError("qwen3: use_sliding_window is not supported (attention is over the whole context)")
     d, nh = hf["hidden_size"], hf["num_attention_heads"]
     rope = hf.get("rope_parameters") or {}  # transformers >= 5 keeps theta / scaling here
     theta = _first(hf, "rope_theta", default=rope.get("rope_theta", 10000.0))
@@ -82,7 +89,7 @@ def config_from_hf(hf: Union[dict, PathLike], name: Optional[str] = None) -> Mod
         max_position=hf.get("max_position_embeddings", 8192), rope_theta=float(theta), rope_scaling=scaling,
         norm_eps=hf.get("rms_norm_eps", 1e-5), n_experts=hf.get("num_local_experts", 0) if mt == "mixtral" else 0,
         top_k_experts=hf.get("num_experts_per_tok", 2), tie_embeddings=bool(hf.get("tie_word_embeddings", False)),
-        bos_id=bos if bos is not None else 1, eos_ids=eos_ids)
+        bos_id=bos if bos is not None else 1, eos_ids=eos_ids, qk_norm=qwen, add_bos=not qwen)
 
 
 def config_to_hf(c: ModelConfig) -> dict:
@@ -92,8 +99,8 @@ def config_to_hf(c: ModelConfig) -> dict:
                 "n_embd": c.d_model, "n_layer": c.n_layers, "n_head": c.n_heads, "n_inner": c.ffn_dim,
                 "n_positions": c.max_position, "layer_norm_epsilon": c.norm_eps, "bos_token_id": c.bos_id,
                 "eos_token_id": c.eos_ids[0], "activation_function": "gelu_new", "tie_word_embeddings": True}
-    hf = {"model_type": "mixtral" if c.is_moe else "llama",
-          "architectures": ["MixtralForCausalLM" if c.is_moe else "LlamaForCausalLM"],
+    mt, cls = ("mixtral", "Mixtral") if c.is_moe else (("qwen3", "Qwen3") if c.qk_norm else ("llama", "Llama"))
+    hf = {"model_type": mt, "architectures": [cls + "ForCausalLM"],
           "vocab_size": c.vocab_size, "hidden_size": c.d_model, "num_hidden_layers": c.n_layers,
           "num_attention_heads": c.n_heads, "num_key_value_heads": c.n_kv_heads, "head_dim": c.head_dim,
           "intermediate_size": c.ffn_dim, "max_position_embeddings": c.max_position, "rope_theta": c.rope_theta,
@@ -101,6 +108,8 @@ def config_to_hf(c: ModelConfig) -> dict:
           "eos_token_id": list(c.eos_ids) if len(c.eos_ids) > 1 else c.eos_ids[0], "hidden_act": "silu"}
     if c.rope_scaling:
         hf["rope_scaling"] = dict(c.rope_scaling)
+    if c.qk_norm:
+        hf.update(attention_bias=False, use_sliding_window=False)
     if c.is_moe:
         hf["num_local_experts"] = c.n_experts
         hf["num_experts_per_tok"] = c.top_k_experts
@@ -211,6 +220,9 @@ def load_checkpoint(model, path: PathLike, strict: bool = True) -> list[str]:
             L["wo"] = put(get(a + "o_proj.weight")[:, q_lo:q_hi])
             L["attn_norm"] = put(get(p + "input_layernorm.weight"))
             L["mlp_norm"] = put(get(p + "post_attention_layernorm.weight"))
+            if c.qk_norm:
+                L["q_norm"] = put(get(a + "q_norm.weight"))
+                L["k_norm"] = put(get(a + "k_norm.weight"))
             if c.is_moe:
                 _load_experts(model, L, p, src, get, put, used)
             else:
@@ -295,6 +307,9 @@ def hf_state_dict(model) -> Iterator[tuple[str, torch.Tensor]]:
         yield p + "self_attn.o_proj.weight", model.canonical(L, "wo")
         yield p + "input_layernorm.weight", L["attn_norm"]
         yield p + "post_attention_layernorm.weight", L["mlp_norm"]
+        if c.qk_norm:
+            yield p + "self_attn.q_norm.weight", L["q_norm"]
+            yield p + "self_attn.k_norm.weight", L["k_norm"]
         F = c.ffn_dim
 
         if c.is_moe:

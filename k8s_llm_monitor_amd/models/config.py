@@ -16,7 +16,7 @@ from typing import Optional
 @dataclass(frozen=True)
 class ModelConfig:
     name: str
-    arch: str  # "llama" (Llama-3 / Mixtral) or "gpt2"
+    arch: str  # "llama" (Llama-3 / Mixtral / Qwen3) or "gpt2"
     vocab_size: int
     d_model: int
     n_layers: int
@@ -33,6 +33,8 @@ class ModelConfig:
     tie_embeddings: bool = False
     bos_id: int = 128000
     eos_ids: tuple = (128001, 128009)
+    qk_norm: bool = False  # Qwen3: a learned RMSNorm over head_dim on every q and k head, before RoPE
+    add_bos: bool = True  # the tokenizer starts a prompt with bos_id (Qwen3 does not)
     extra: dict = field(default_factory=dict)
 
     @property
@@ -54,6 +56,8 @@ class ModelConfig:
         if self.arch == "gpt2":
             mlp = 2 * d * f
         emb = self.vocab_size * d * (1 if self.tie_embeddings else 2)
+        if self.qk_norm:
+            attn += 2 * self.head_dim
         return L * (attn + mlp) + emb
 
     def vocab_size_padded(self, tp: int = 1) -> int:
@@ -98,6 +102,18 @@ MIXTRAL_8X7B = _reg(ModelConfig(
     head_dim=128, ffn_dim=14336, max_position=32768, rope_theta=1e6, n_experts=8, top_k_experts=2,
     bos_id=1, eos_ids=(2,)))
 
+# Qwen3 dense (QK-norm, head_dim 128 whatever d_model / n_heads is, no BOS; ids of the Qwen
+# tokenizer: <|endoftext|> 151643, <|im_end|> 151645).
+QWEN3_8B = _reg(ModelConfig(
+    name="qwen3-8b", arch="llama", vocab_size=151936, d_model=4096, n_layers=36, n_heads=32, n_kv_heads=8,
+    head_dim=128, ffn_dim=12288, max_position=40960, rope_theta=1e6, norm_eps=1e-6, bos_id=151643,
+    eos_ids=(151645, 151643), qk_norm=True, add_bos=False))
+
+QWEN3_0_6B = _reg(ModelConfig(
+    name="qwen3-0.6b", arch="llama", vocab_size=151936, d_model=1024, n_layers=28, n_heads=16, n_kv_heads=8,
+    head_dim=128, ffn_dim=3072, max_position=40960, rope_theta=1e6, norm_eps=1e-6, tie_embeddings=True,
+    bos_id=151643, eos_ids=(151645, 151643), qk_norm=True, add_bos=False))
+
 # Small shapes with the same structure, for CPU tests and GPU smoke runs.
 LLAMA_TINY = _reg(ModelConfig(
     name="llama-tiny", arch="llama", vocab_size=512, d_model=256, n_layers=2, n_heads=4, n_kv_heads=2,
@@ -122,6 +138,16 @@ MIXTRAL_TINY_E8 = _reg(ModelConfig(  # 8 query heads, 8 experts: TP / EP 8 parit
     head_dim=32, ffn_dim=256, max_position=1024, rope_theta=10000.0, n_experts=8, top_k_experts=2,
     bos_id=1, eos_ids=(2,)))
 
+QWEN3_TINY = _reg(ModelConfig(  # head_dim 64 != d_model / n_heads, as in every Qwen3 size but 8B
+    name="qwen3-tiny", arch="llama", vocab_size=512, d_model=128, n_layers=2, n_heads=4, n_kv_heads=2,
+    head_dim=64, ffn_dim=256, max_position=1024, rope_theta=1e6, norm_eps=1e-6, bos_id=1, eos_ids=(2,),
+    qk_norm=True, add_bos=False))
+
+QWEN3_TINY128 = _reg(ModelConfig(  # head_dim 128: the HIP attention kernels' shape, for GPU tests
+    name="qwen3-tiny-d128", arch="llama", vocab_size=1024, d_model=512, n_layers=2, n_heads=8, n_kv_heads=2,
+    head_dim=128, ffn_dim=1024, max_position=2048, rope_theta=1e6, norm_eps=1e-6, bos_id=1, eos_ids=(2,),
+    qk_norm=True, add_bos=False))
+
 GPT2_TINY = _reg(ModelConfig(
     name="gpt2-tiny", arch="gpt2", vocab_size=512, d_model=128, n_layers=2, n_heads=2, n_kv_heads=2,
     head_dim=64, ffn_dim=512, max_position=512, tie_embeddings=True, bos_id=0, eos_ids=(0,)))
@@ -129,7 +155,7 @@ GPT2_TINY = _reg(ModelConfig(
 _ALIASES = {
     "gpt2": "gpt2-small", "gpt-2": "gpt2-small", "llama3-8b": "llama-3-8b", "meta-llama-3-8b": "llama-3-8b",
     "llama-3.1-8b": "llama-3-8b", "llama3-70b": "llama-3-70b", "mixtral": "mixtral-8x7b",
-    "mixtral-8x7b-v0.1": "mixtral-8x7b",
+    "mixtral-8x7b-v0.1": "mixtral-8x7b", "qwen3": "qwen3-8b",
 }
 
 

@@ -1,5 +1,5 @@
-"""Decoder-only causal LMs served by the diagnostic engine: Llama-3 (dense), Mixtral (MoE) and
-GPT-2 (the CPU plumbing config), with Megatron tensor parallelism.
+"""Decoder-only causal LMs served by the diagnostic engine: Llama-3 and Qwen3 (dense), Mixtral (MoE)
+and GPT-2 (the CPU plumbing config), with Megatron tensor parallelism.
 
 Nothing here exists in the reference ("no LLM, no GPU code"); the model replaces
 the remote ``callLLMAPI`` step of the doc sketch ``docs/metrics-usage-example.md:244-306``.
@@ -22,6 +22,13 @@ paged_decode_fused (slab reduce + RoPE + KV write + attention) -> o (slabs) -> a
 projections and the LM head run on the shared-A decode GEMM over fragment-packed weights
 (ops/csrc/gemm_decode.hip), or on the row-major skinny kernel (gemm_skinny.hip) where no packed
 form exists.
+
+Qwen3 (``cfg.qk_norm``: a learned RMSNorm over head_dim on every q and k head, before RoPE) takes
+the norm inside rope_and_cache's kernel, so neither the qkv GEMM's RoPE epilogue nor the fused
+decode attention applies.  Prefill: qkv (plain) -> rope_and_cache (QK-norm + RoPE + KV write) ->
+flash_prefill, the RMSNorms between projections as fused_add_rms_norm launches.  Decode (8
+launches): qkv (slabs) -> rope_and_cache (slab reduce + QK-norm + RoPE + KV write) -> paged_decode
+-> o ... as above.  ``q_norm`` / ``k_norm`` ([D]) are whole on every TP rank.
 
 Weights are stored fused and pre-sharded: ``wqkv`` [(Hq+2Hkv)/tp * D, d] (column-parallel),
 ``wo`` [d, Hq/tp * D] (row-parallel), ``w13`` [2F/tp, d] (this rank's gate and up rows), ``w2``
@@ -369,6 +376,9 @@ class CausalLM:
             else:
                 L["attn_norm"] = self._ones(d)
                 L["mlp_norm"] = self._ones(d)
+                if c.qk_norm:  # one [D] weight for all q heads, one for all k heads: whole on every rank
+                    L["q_norm"] = (1.0 + self._rand(p + "q_norm", (D,), 0.1).float()).to(self.dtype)
+                    L["k_norm"] = (1.0 + self._rand(p + "k_norm", (D,), 0.1).float()).to(self.dtype)
                 if c.is_moe:
                     L["router"] = self._rand(p + "router", (c.n_experts, d))
                     w13, w2s = [], []
@@ -463,15 +473,17 @@ class CausalLM:
             qkv = torch.empty(T, ops.w_out(L["wqkv"]), dtype=self.dtype, device=self.device)
         elif "bqkv" in L:
             qkv = F.linear(x, L["wqkv"], L["bqkv"])
-        elif c.arch == "llama" and self.D == 128 and self.cos_sin is not None:
-            # prefill-sized qkv on the tile kernel: RoPE of q / k fused into its epilogue
+        elif c.arch == "llama" and self.D == 128 and self.cos_sin is not None and not c.qk_norm:
+            # prefill-sized qkv on the tile kernel: RoPE of q / k fused into its epilogue (not for a
+            # QK-norm model: its heads are normalised between the projection and the rotation)
             qkv, roped = ops.prefill_linear(x, L["wqkv"], rope=(meta.positions, cs, self.hq + self.hkv),
                                             rowscale=rowscale, wscale=self._wsc(L, "wqkv"))
         else:
             qkv = ops.prefill_linear(x, L["wqkv"], wscale=self._wsc(L, "wqkv"))
         ops.rope_and_cache(qkv, meta.positions, cs, k_cache, v_cache,
                            meta.slot_mapping if k_cache is not None else None, self.hq, self.hkv, self.D,
-                           apply_rope=c.arch == "llama" and not roped, partial=partial, nslabs=ns, kv_scale=kv_scale)
+                           apply_rope=c.arch == "llama" and not roped, partial=partial, nslabs=ns, kv_scale=kv_scale,
+                           qk_norm=(L["q_norm"], L["k_norm"], c.norm_eps) if c.qk_norm else None)
         if meta.is_prefill:
             qb = (meta.qb_seq, meta.qb_start) if meta.qb_seq is not None else None
             paged = None
@@ -812,6 +824,8 @@ class CausalLM:
         c = self.cfg
         if not h.is_cuda or c.arch != "llama" or c.is_moe or self.tp != 1 or not self._w13_il:
             return False
+        if c.qk_norm:  # the qkv GEMM's row scale exists only with its RoPE epilogue, which QK-norm rules out
+            return False
         if self.D != 128 or self.cos_sin is None or any(k in self.layers[0] for k in ("bqkv", "bo")):
             return False
         L = self.layers[0]
@@ -963,7 +977,8 @@ class CausalLM:
         # GEMM's split-K slabs directly: one launch per layer fewer - where ops.PD_FORMS has a fused
         # row for this head dim and group (the same rows for a bf16 and an fp8 cache); else
         # rope_and_cache + the unfused kernel
-        self._attn_rope = ops.paged_decode_why(self.D, self.hq // self.hkv, fused=True) is None
+        # (a QK-norm model normalises its heads in rope_and_cache: no fused row does that)
+        self._attn_rope = not c.qk_norm and ops.paged_decode_why(self.D, self.hq // self.hkv, fused=True) is None
         rowmajor = (self.hq * self.D) % 64 == 0
         self.skinny_layout = "rowmajor" if rowmajor else "packed"
         for L in self.layers:
@@ -1250,6 +1265,8 @@ class CausalLM:
         """A dense projection as the row-major [out, in] weight of the reference / the checkpoint
         format (w13 as [gate; up]), whatever its resident layout (row-major, gate/up interleaved
         per 128 rows, or the one fragment-packed copy)."""
+        if key not in PROJ:  # norm weights (attn_norm, mlp_norm, q_norm, k_norm): stored as they are
+            return L[key]
         return to_canonical(L[key], key, self._layout, L.get(key + "_qs"), self.dtype)
 
     @torch.no_grad()

@@ -38,7 +38,11 @@ def fp32_logits(model, ids: torch.Tensor, rows: Optional[list] = None, device: O
     for L in model.layers:
         h = F.rms_norm(x, (c.d_model,), w(L["attn_norm"]), c.norm_eps)
         q, k, v = (h @ w(model.canonical(L, "wqkv")).t()).split([Hq * D, Hk * D, Hk * D], 1)
-        q, k = rope(q.view(T, Hq, D)), rope(k.view(T, Hk, D))
+        q, k = q.view(T, Hq, D), k.view(T, Hk, D)
+        if c.qk_norm:  # Qwen3: per-head RMSNorm over D before the rotation
+            q = F.rms_norm(q, (D,), w(L["q_norm"]), c.norm_eps)
+            k = F.rms_norm(k, (D,), w(L["k_norm"]), c.norm_eps)
+        q, k = rope(q), rope(k)
         att = F.scaled_dot_product_attention(q.transpose(0, 1)[None], k.transpose(0, 1)[None],
                                              v.view(T, Hk, D).transpose(0, 1)[None], is_causal=True,
                                              enable_gqa=Hq != Hk)[0]

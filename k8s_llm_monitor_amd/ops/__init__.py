@@ -633,6 +633,11 @@ DEC_TABLE: dict = {
     (28672, 4096, 2): (1, 1, 7, 8),     # gate_up  39.9 / 38.1   (47.9 / 40.0)
     (4096, 14336, 0): (8, 1, 8, 8),     # down     22.3 / 19.0   (24.3 / 19.9)
     (128256, 4096, 1): (1, 4, 8, 4),    # LM head 173.8 / 166.0  (hipBLASLt 202.2 / 176.2)
+    # Qwen3-8B (profiles/r21/dec_gemm_qwen3.jsonl, M = 64 / M = 1 us): its LM head's 9496 n-tiles
+    # leave the rule's (1, 4, 8, 4) at 264.8 / 261.0 (4.70 / 4.77 TB/s, Llama's head: 6.16 / 6.40).
+    # (1, 3, 8, 8) measured 228.8 / 204.9 but has no fp8 / mxfp4 instantiation; gate_up and down
+    # stay on the rule's picks, Llama's (5.63 / 6.36 and 4.65 / 5.91 TB/s against 5.77 / 6.36 and 4.48 / 6.27)
+    (151936, 4096, 1): (1, 2, 8, 8),    # LM head 234.3 / 205.3
 }
 
 # The same at 65..128 rows (the 5..8 m-tile instantiations of gemm_dec_kernel), from the sweep
@@ -1116,18 +1121,31 @@ def rope_and_cache(qkv: torch.Tensor, positions: torch.Tensor, cos_sin: torch.Te
                    k_cache: Optional[torch.Tensor], v_cache: Optional[torch.Tensor],
                    slot_mapping: Optional[torch.Tensor], Hq: int, Hkv: int, D: int,
                    apply_rope: bool = True, partial: Optional[torch.Tensor] = None, nslabs: int = 0,
-                   kv_scale: Optional[torch.Tensor] = None) -> None:
+                   kv_scale: Optional[torch.Tensor] = None, qk_norm: Optional[tuple] = None) -> None:
     """In place: rotate q and k inside the fused QKV rows; write k, v into the paged cache.
     With ``partial`` (GPU), the QKV values are first reduced from ``nslabs`` fp32 split-K slabs
     [nslabs, T, (Hq+2Hkv)*D] (skinny_slabs) and the reduced rows are written to ``qkv``.
     An e4m3 cache (``kv_scale`` its scales, :func:`kv_cache_alloc`) takes every token quantised
-    from the rotated rows (:func:`quantize_kv`)."""
+    from the rotated rows (:func:`quantize_kv`).
+    ``qk_norm = (q_w, k_w, eps)`` (Qwen3): every q head and every k head is RMS-normalised over
+    its D values and scaled by ``q_w`` / ``k_w`` ([D], fp32 or bf16) before the rotation, in fp32
+    inside the same kernel - the rows and the K cache still see one rounding to bf16."""
+    qw = kw = None
+    eps = 0.0
+    if qk_norm is not None:
+        qw, kw, eps = qk_norm
+        for w in (qw, kw):
+            if not isinstance(w, torch.Tensor) or w.shape != (D,):
+                raise ValueError(f"qk_norm weights must be [D = {D}] tensors")
+            if w.device != qkv.device or w.dtype != qw.dtype or w.dtype not in (torch.float32, torch.bfloat16):
+                raise ValueError("qk_norm weights must be on qkv's device, both fp32 or both bf16")
+        eps = float(eps)
     if not _gpu(qkv):
         if partial is not None:
             T, n = qkv.shape[0], qkv.shape[1]
             qkv.copy_(partial[: nslabs * T * n].view(nslabs, T, n).sum(0).to(qkv.dtype))
         ref.rope_and_cache(qkv, positions, cos_sin, k_cache, v_cache, slot_mapping, Hq, Hkv, D, apply_rope,
-                           kv_scale=kv_scale)
+                           kv_scale=kv_scale, qk_norm=qk_norm)
         return
     empty = _empty_i32(qkv.device)
     native().rope_and_cache(qkv, positions, cos_sin,
@@ -1135,7 +1153,8 @@ def rope_and_cache(qkv: torch.Tensor, positions: torch.Tensor, cos_sin: torch.Te
                             v_cache if v_cache is not None else empty,
                             slot_mapping if slot_mapping is not None else empty,
                             Hq, Hkv, D, apply_rope, partial, nslabs,
-                            kv_scale if k_cache is not None and slot_mapping is not None else None)
+                            kv_scale if k_cache is not None and slot_mapping is not None else None,
+                            qw, kw, eps)
 
 
 _EMPTY = {}

@@ -5,6 +5,8 @@
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime.h>
 
+#include <cmath>
+
 #include "gemm_dec_forms.h"
 #include "gemm_skinny_plan.h"
 #include "gemm_tile_forms.h"
@@ -22,7 +24,8 @@ int k8sllm_embedding(void* out, const int* ids, const void* weight, long T, int 
 int k8sllm_resolve_ids(int* out, const int* ids, const int* src, const int* prev, int n, hipStream_t s);
 int k8sllm_rope_cache(void* qkv, long qkv_stride, const int* positions, const float* cos_sin, void* k_cache,
                       void* v_cache, const int* slot_mapping, long T, int Hq, int Hkv, int D, int block_size,
-                      int apply_rope, const float* partial, int S, float* kv_scale, hipStream_t s);
+                      int apply_rope, const float* partial, int S, float* kv_scale, const void* q_norm_w,
+                      const void* k_norm_w, float eps, int norm_bf16, hipStream_t s);
 int k8sllm_paged_decode(void* out, long out_stride, float* part_out, float* part_ml, const void* q, long q_stride,
                         void* k_cache, void* v_cache, const int* block_tables, int bt_stride, const int* seq_lens,
                         int B, int Hq, int Hkv, int D, int S, float scale, float* kv_scale, const float* slabs,
@@ -208,8 +211,28 @@ void resolve_ids(torch::Tensor out, torch::Tensor ids, torch::Tensor src, torch:
 void rope_and_cache(torch::Tensor qkv, torch::Tensor positions, torch::Tensor cos_sin, torch::Tensor k_cache,
                     torch::Tensor v_cache, torch::Tensor slot_mapping, int64_t Hq, int64_t Hkv, int64_t D,
                     bool apply_rope, c10::optional<torch::Tensor> partial, int64_t S,
-                    c10::optional<torch::Tensor> kv_scale) {
+                    c10::optional<torch::Tensor> kv_scale, c10::optional<torch::Tensor> q_norm_w,
+                    c10::optional<torch::Tensor> k_norm_w, double eps) {
   dev_bf16(qkv, "qkv"); dev_i32(positions, "positions");
+  // QK-norm: one [D] weight for every q head and one for every k head, both fp32 or both bf16
+  TORCH_CHECK(q_norm_w.has_value() == k_norm_w.has_value(), "qk_norm: q and k weights come together");
+  const void *qnw = nullptr, *knw = nullptr;
+  int norm_bf16 = 0;
+  if (q_norm_w.has_value()) {
+    const torch::Tensor &qw = *q_norm_w, &kw = *k_norm_w;
+    TORCH_CHECK(qw.is_cuda() && kw.is_cuda() && qw.device() == qkv.device() && kw.device() == qkv.device(),
+                "qk_norm: weights must be on qkv's device");
+    TORCH_CHECK(qw.scalar_type() == kw.scalar_type() &&
+                    (qw.scalar_type() == torch::kFloat32 || qw.scalar_type() == torch::kBFloat16),
+                "qk_norm: weights must both be fp32 or both bf16");
+    TORCH_CHECK(qw.dim() == 1 && kw.dim() == 1 && qw.size(0) == D && kw.size(0) == D && qw.is_contiguous() &&
+                    kw.is_contiguous(),
+                "qk_norm: weights must be contiguous [D]");
+    TORCH_CHECK(std::isfinite(eps) && eps >= 0.0, "qk_norm: eps must be finite and >= 0");
+    qnw = qw.data_ptr();
+    knw = kw.data_ptr();
+    norm_bf16 = qw.scalar_type() == torch::kBFloat16 ? 1 : 0;
+  }
   TORCH_CHECK(qkv.stride(-1) == 1 && qkv.dim() == 2, "qkv must be [T, (Hq+2Hkv)*D] with unit inner stride");
   TORCH_CHECK(qkv.size(1) >= (Hq + 2 * Hkv) * D, "qkv width");
   TORCH_CHECK(cos_sin.scalar_type() == torch::kFloat32 && cos_sin.is_contiguous() && cos_sin.size(1) == D, "cos_sin");
@@ -233,7 +256,7 @@ void rope_and_cache(torch::Tensor qkv, torch::Tensor positions, torch::Tensor co
   check(k8sllm_rope_cache(qkv.data_ptr(), qkv.stride(0), positions.data_ptr<int>(), cos_sin.data_ptr<float>(),
                           has_cache ? k_cache.data_ptr() : nullptr, has_cache ? v_cache.data_ptr() : nullptr,
                           has_cache ? slot_mapping.data_ptr<int>() : nullptr, qkv.size(0), (int)Hq, (int)Hkv, (int)D,
-                          block_size, apply_rope ? 1 : 0, pp, (int)S, ksp, cur()),
+                          block_size, apply_rope ? 1 : 0, pp, (int)S, ksp, qnw, knw, (float)eps, norm_bf16, cur()),
         "rope_and_cache");
 }
 

@@ -26,6 +26,28 @@ __device__ __forceinline__ void slab_sum(const float* __restrict__ p, long slab_
   }
 }
 
+// One 16-lane DPP row step of a butterfly sum: v + the value CTRL brings from another lane of the row.
+template <int CTRL>
+__device__ __forceinline__ float dpp_add(float v) {
+  return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
+}
+
+// Sum of v over the N (8 or 16) adjacent lanes of one head, the same bits in every one of them.  The
+// lanes are aligned to N inside a 16-lane DPP row, so the steps are register-to-register VALU moves
+// (no LDS crossbar as __shfl_xor's ds_bpermute takes): xor 1, xor 2 by quad_perm; the other quad
+// of the half row by row_half_mirror and the other half row by row_mirror - after the quad steps
+// every lane of a quad holds the same sum, so a mirrored partner serves as well as the xor one, and
+// a + b = b + a keeps the two sides bit-equal.
+template <int N>
+__device__ __forceinline__ float head_sum(float v) {
+  static_assert(N == 8 || N == 16, "a head is 8 or 16 lanes");
+  v = dpp_add<0xB1>(v);   // quad_perm [1, 0, 3, 2]
+  v = dpp_add<0x4E>(v);   // quad_perm [2, 3, 0, 1]
+  v = dpp_add<0x141>(v);  // row_half_mirror
+  if constexpr (N == 16) v = dpp_add<0x140>(v);  // row_mirror
+  return v;
+}
+
 // grid = (T, ceil(items / 128)), 128 threads, one work item per thread.  Items: (Hq + Hkv) heads
 // x D/8 "quads" of rotary pairs (each rotates 4 pairs = 8 B of the lower half and 8 B of the upper
 // half), then Hkv heads x D/8 value chunks of 8 dims (16 B) that are only copied into the cache.
@@ -34,14 +56,23 @@ __device__ __forceinline__ void slab_sum(const float* __restrict__ p, long slab_
 // row (the attention reads q from there).
 // VROW (SLAB only, the fp8 cache's form: launched without slots): the reduced v is written to the
 // bf16 qkv row as well, where kv_cache_write_f8_kernel reads the whole token.
-template <int D, bool SLAB, bool VROW = false>
+// NORM (QK-norm, Qwen3): between the load (the SLAB form's bf16 rounding included - the norm sees
+// what an unfused GEMM would have written) and the rotation, each q / k head is RMS-normalised
+// over its D values in fp32: x * rsqrt(mean(x^2) + eps) * w[dim], w = q_norm_w for a q head and
+// k_norm_w for a k head ([D], bf16 when norm_bf16 else fp32).  A head's D/8 items are adjacent
+// lanes, aligned to D/8, and n_rope / n_total are multiples of D/8: the lanes of a head are all
+// rope items and all alive, whatever else shares the wave.  Still one rounding to bf16, on the
+// store.  V items are untouched.
+template <int D, bool SLAB, bool VROW = false, bool NORM = false>
 __global__ __launch_bounds__(128) void rope_cache_kernel(bf16_t* __restrict__ qkv, long qkv_stride,
                                                          const int* __restrict__ positions,
                                                          const float* __restrict__ cos_sin,  // [max_pos][D]: cos | sin
                                                          bf16_t* __restrict__ k_cache, bf16_t* __restrict__ v_cache,
                                                          const int* __restrict__ slot_mapping, int Hq, int Hkv,
                                                          int block_size, int apply_rope, const float* __restrict__ partial,
-                                                         int S, int T) {
+                                                         int S, int T, const void* __restrict__ q_norm_w,
+                                                         const void* __restrict__ k_norm_w, float eps,
+                                                         int norm_bf16) {
   constexpr int HALF = D / 2;
   constexpr int QPH = D / 8;  // items per head
   const int t = blockIdx.x;
@@ -75,6 +106,33 @@ __global__ __launch_bounds__(128) void rope_cache_kernel(bf16_t* __restrict__ qk
       for (int j = 0; j < 4; ++j) {
         x1[j] = bf2f(f2bf(x1[j]));
         x2[j] = bf2f(f2bf(x2[j]));
+      }
+    }
+    if constexpr (NORM) {
+      float ss = 0.f;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) ss += x1[j] * x1[j];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) ss += x2[j] * x2[j];
+      ss = head_sum<QPH>(ss);
+      const float r = rsqrtf(ss * (1.f / D) + eps);
+      const void* wp = head < Hq ? q_norm_w : k_norm_w;
+      float w1[4], w2[4];
+      if (norm_bf16) {
+        const uint2 a = *reinterpret_cast<const uint2*>((const bf16_t*)wp + p);
+        const uint2 b = *reinterpret_cast<const uint2*>((const bf16_t*)wp + HALF + p);
+        w1[0] = lo_bf(a.x); w1[1] = hi_bf(a.x); w1[2] = lo_bf(a.y); w1[3] = hi_bf(a.y);
+        w2[0] = lo_bf(b.x); w2[1] = hi_bf(b.x); w2[2] = lo_bf(b.y); w2[3] = hi_bf(b.y);
+      } else {
+        const float4 a = *reinterpret_cast<const float4*>((const float*)wp + p);
+        const float4 b = *reinterpret_cast<const float4*>((const float*)wp + HALF + p);
+        w1[0] = a.x; w1[1] = a.y; w1[2] = a.z; w1[3] = a.w;
+        w2[0] = b.x; w2[1] = b.y; w2[2] = b.z; w2[3] = b.w;
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        x1[j] = x1[j] * r * w1[j];
+        x2[j] = x2[j] * r * w2[j];
       }
     }
     if (apply_rope) {
@@ -308,6 +366,7 @@ using namespace k8sllm;
 extern "C" int k8sllm_rope_cache(void* qkv, long qkv_stride, const int* positions, const float* cos_sin, void* k_cache,
                                  void* v_cache, const int* slot_mapping, long T, int Hq, int Hkv, int D,
                                  int block_size, int apply_rope, const float* partial, int S, float* kv_scale,
+                                 const void* q_norm_w, const void* k_norm_w, float eps, int norm_bf16,
                                  hipStream_t s) {
   if (T <= 0) return 0;
   if (D != 128 && D != 64) return -1;
@@ -322,24 +381,29 @@ extern "C" int k8sllm_rope_cache(void* qkv, long qkv_stride, const int* position
   dim3 grid((unsigned)T, (items + 127) / 128);
   // nothing to rotate (q / k rotated by the qkv GEMM epilogue, or a model without RoPE) and the
   // cache written run-wise below: the in-place pass would only copy q / k onto themselves
-  const bool skip_rope = runs && !apply_rope && partial == nullptr;
-#define K8S_ROPE(DV, SL)                                                                                       \
-  hipLaunchKernelGGL((rope_cache_kernel<DV, SL>), grid, dim3(128), 0, s, (bf16_t*)qkv, qkv_stride, positions,  \
-                     cos_sin, (bf16_t*)k_cache, (bf16_t*)v_cache, rope_slots, Hq, Hkv, block_size, apply_rope,   \
-                     partial, S, (int)T)
+  // (QK-norm always has work to do: the norm itself)
+  const bool norm = q_norm_w != nullptr && k_norm_w != nullptr;
+  const bool skip_rope = runs && !apply_rope && partial == nullptr && !norm;
+#define K8S_ROPE_(DV, SL, VR, NM, KC, VC)                                                                       \
+  hipLaunchKernelGGL((rope_cache_kernel<DV, SL, VR, NM>), grid, dim3(128), 0, s, (bf16_t*)qkv, qkv_stride,      \
+                     positions, cos_sin, (bf16_t*)(KC), (bf16_t*)(VC), rope_slots, Hq, Hkv, block_size,         \
+                     apply_rope, partial, S, (int)T, q_norm_w, k_norm_w, eps, norm_bf16)
+#define K8S_ROPE(DV, SL, VR, KC, VC)                                                     \
+  do {                                                                                   \
+    if (norm) K8S_ROPE_(DV, SL, VR, true, KC, VC); else K8S_ROPE_(DV, SL, VR, false, KC, VC); \
+  } while (0)
   if (skip_rope) {
   } else if (f8 && partial) {
-    hipLaunchKernelGGL((rope_cache_kernel<128, true, true>), grid, dim3(128), 0, s, (bf16_t*)qkv, qkv_stride,
-                       positions, cos_sin, (bf16_t*)nullptr, (bf16_t*)nullptr, rope_slots, Hq, Hkv, block_size,
-                       apply_rope, partial, S, (int)T);
+    K8S_ROPE(128, true, true, nullptr, nullptr);
   } else if (D == 128) {
-    if (partial) K8S_ROPE(128, true); else K8S_ROPE(128, false);
+    if (partial) K8S_ROPE(128, true, false, k_cache, v_cache); else K8S_ROPE(128, false, false, k_cache, v_cache);
   } else if (D == 64) {
-    if (partial) K8S_ROPE(64, true); else K8S_ROPE(64, false);
+    if (partial) K8S_ROPE(64, true, false, k_cache, v_cache); else K8S_ROPE(64, false, false, k_cache, v_cache);
   } else {
     return -1;
   }
 #undef K8S_ROPE
+#undef K8S_ROPE_
   if (f8) {
     dim3 g2((unsigned)((T + 15) / 16), Hkv);
     hipLaunchKernelGGL((kv_cache_write_f8_kernel<128>), g2, dim3(256), 0, s, (const bf16_t*)qkv, qkv_stride,

@@ -81,23 +81,40 @@ def rope_cos_sin(max_pos: int, head_dim: int, theta: float, scaling: dict | None
 
 
 def apply_rope(x: torch.Tensor, positions: torch.Tensor, cos_sin: torch.Tensor) -> torch.Tensor:
-    """x: [T, H, D]; returns rotated fp32."""
+    """x: [T, H, D]; returns rotated fp32 (fp64 for an fp64 ``x``)."""
     d = x.shape[-1]
     half = d // 2
     cs = cos_sin[positions.long()]
     c, s = cs[:, None, :half], cs[:, None, half:]
-    xf = x.float()
+    xf = x if x.dtype == torch.float64 else x.float()
     x1, x2 = xf[..., :half], xf[..., half:]
     return torch.cat([x1 * c - x2 * s, x2 * c + x1 * s], dim=-1)
 
 
+def head_rms_norm(x: torch.Tensor, w: torch.Tensor, eps: float) -> torch.Tensor:
+    """QK-norm: x [T, H, D] RMS-normalised over D and scaled by w [D]; fp32."""
+    xf = x.float()
+    r = torch.rsqrt(xf.square().sum(-1, keepdim=True) * (1.0 / x.shape[-1]) + eps)
+    return xf * r * w.float()
+
+
 def rope_and_cache(qkv, positions, cos_sin, k_cache, v_cache, slot_mapping, Hq, Hkv, D, apply_rope_=True,
-                   kv_scale=None):
+                   kv_scale=None, qk_norm=None):
+    """``qk_norm = (q_w, k_w, eps)``: each q / k head RMS-normalised over D and scaled by its
+    weight in fp32, in the kernel's order (x * rsqrt(mean(x^2) + eps) * w), before the rotation;
+    one rounding to ``qkv.dtype`` at the end."""
     T = qkv.shape[0]
     q = qkv[:, : Hq * D].view(T, Hq, D)
     k = qkv[:, Hq * D:(Hq + Hkv) * D].view(T, Hkv, D)
     v = qkv[:, (Hq + Hkv) * D:(Hq + 2 * Hkv) * D].view(T, Hkv, D)
-    if apply_rope_:
+    if qk_norm is not None:
+        q_w, k_w, eps = qk_norm
+        qn, kn = head_rms_norm(q, q_w, eps), head_rms_norm(k, k_w, eps)
+        if apply_rope_:
+            qn, kn = apply_rope(qn, positions, cos_sin), apply_rope(kn, positions, cos_sin)
+        q.copy_(qn.to(qkv.dtype))
+        k.copy_(kn.to(qkv.dtype))
+    elif apply_rope_:
         q.copy_(apply_rope(q, positions, cos_sin).to(qkv.dtype))
         k.copy_(apply_rope(k, positions, cos_sin).to(qkv.dtype))
     if slot_mapping is not None and slot_mapping.numel() > 0:

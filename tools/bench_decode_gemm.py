@@ -16,7 +16,7 @@ the MXFP4 encoding (``f4_`` cases, ops.DEC_F4_FORMS: 17/64 of the bytes), ``--wd
 both in one session (each checked against the bf16 launch over its own dequantised weights;
 the timed bf16 cases stream the last encoding's).  ``--f4-depths 8,16`` times the mxfp4 cases
 once per forced F4 ring depth (ops.DEC_F4_DEPTH_FORCE; 0 = the launcher's choice) where the
-launcher takes it.  ``--shape 70b_gate_up`` etc.: SHAPES.
+launcher takes it.  ``--ops 70b_gate_up``, ``--ops q3_gate_up,q3_down,q3_lm_head`` (Qwen3-8B) etc.: SHAPES.
 ``--experts E``: the grouped (grid.z = expert) launches of a Mixtral-8x7B MoE layer over E local
 experts instead - gate_up and down (``--ops``), bf16 stacks on ops.dec_config's pick against the
 ``--wdtype`` code stacks on ops.dec_grouped_q_config's (and the bf16 stacks on that pick where it
@@ -41,7 +41,9 @@ from tools.bench_skinny import timeit  # noqa: E402
 
 D, FF, V = 4096, 14336, 128256
 SHAPES = {"qkv": (6144, D, 0), "o": (D, D, 0), "gate_up": (2 * FF, D, 2), "down": (D, FF, 0), "lm_head": (V, D, 1),
-          "70b_gate_up": (2 * 28672, 8192, 2)}  # Llama-3-70B at TP=1
+          "70b_gate_up": (2 * 28672, 8192, 2),  # Llama-3-70B at TP=1
+          # Qwen3-8B (qkv and o are Llama-3-8B's shapes)
+          "q3_gate_up": (2 * 12288, D, 2), "q3_down": (D, 12288, 0), "q3_lm_head": (151936, D, 1)}
 CFGS = {  # the sweep list: forms of ops.DEC_FORMS (another form: add its row to the table first)
     "qkv": [(4, 1, 6, 8), (8, 1, 8, 8), (4, 1, 4, 16), (4, 1, 4, 8)],
     "o": [(4, 1, 4, 16), (4, 1, 4, 8), (8, 1, 8, 8), (16, 1, 8, 8)],
@@ -49,6 +51,9 @@ CFGS = {  # the sweep list: forms of ops.DEC_FORMS (another form: add its row to
     "down": [(4, 1, 4, 16), (4, 1, 4, 8), (8, 1, 8, 8), (4, 1, 8, 8)],
     "lm_head": [(1, 4, 8, 4), (1, 3, 8, 8), (1, 2, 8, 8)],
     "70b_gate_up": [(1, 1, 8, 16)],
+    "q3_gate_up": [(1, 1, 7, 8), (1, 1, 7, 16), (1, 1, 8, 16)],
+    "q3_down": [(8, 1, 8, 8), (4, 1, 4, 16), (4, 1, 8, 8)],
+    "q3_lm_head": [(1, 4, 8, 4), (1, 3, 8, 8), (1, 2, 8, 8)],
 }
 
 

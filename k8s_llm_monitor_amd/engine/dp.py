@@ -26,6 +26,7 @@ from concurrent.futures import Future
 from dataclasses import asdict
 from typing import Optional, Sequence as Seq, Union
 
+from .guide import compile_guide
 from .sequence import SamplingParams
 
 
@@ -149,6 +150,7 @@ class ReplicaRouter:
         if not devices:
             raise ValueError("ReplicaRouter needs at least one device")
         self.engine = _EngineInfo(engine_cfg.model, engine_cfg.model_overrides, engine_cfg.weights, engine_cfg)
+        self.guide_max_states = engine_cfg.guide_max_states
         self._keys = itertools.count()
         self._pending: dict = {}
         self._streams: dict = {}  # key -> on_tokens of streaming requests
@@ -192,6 +194,14 @@ class ReplicaRouter:
         if self._error is not None:
             fut.set_exception(RuntimeError(f"replica failed: {self._error}"))
             return fut
+        if params is not None and params.guide is not None:
+            # validated where the request enters (a bad spec is this request's ValueError); the
+            # replica compiles the plain spec again, into its own cache
+            try:
+                compile_guide(params.guide, self.guide_max_states)
+            except ValueError as e:
+                fut.set_exception(e)
+                return fut
         p = asdict(params or SamplingParams())
         p["stop_token_ids"] = tuple(p["stop_token_ids"])
         key = next(self._keys)

@@ -34,10 +34,11 @@ from ..parallel.state import ParallelState, get_state, serving_timeouts
 from ..parallel.step_bus import KIND_DECODE, KIND_PICKLE, KIND_STOP, bus_slot_bytes, decode_message, make_step_bus
 from ..parallel.health import PeerMonitor, gather_identities
 from .block_manager import BlockManager
+from .guide import compile_guide
 from .runner import ModelRunner, RunnerConfig
 from .scheduler import Scheduler, SchedulerConfig
 from .sequence import SamplingParams, Sequence, SeqStatus
-from .tokenizer import tokenizer_for, tokenizer_from_dir
+from .tokenizer import tokenizer_for, tokenizer_from_dir, vocab_bytes
 
 
 @dataclass
@@ -88,6 +89,9 @@ class EngineConfig:
     # scale per (token, kv head) for K and for V (ops.quantize_kv): decode streams half the KV bytes
     # and a kv_cache_gb budget holds ~1.94x the blocks.  GPU: head_dim 128 only
     kv_cache_dtype: str = "bf16"
+    # constrained decoding (engine/guide.py): the most DFA states one guide may have; the guide
+    # state (allocated by the first guided request) holds max_num_seqs * guide_max_states rows
+    guide_max_states: int = 512
 
 
 class _View:
@@ -136,7 +140,8 @@ class LLMEngine:
                                                chunked_prefill=cfg.chunked_prefill,
                                                mixed_prefill_tokens=cfg.mixed_prefill_tokens,
                                                max_decode_stall_steps=cfg.max_decode_stall_steps), self.blocks)
-        self.sched.on_free = self.runner.penalty_release
+        self.sched.on_free = self._on_free
+        self._vocab_bytes = None  # engine.tokenizer.vocab_bytes, built by the first guided request
         self.tokenizer = tokenizer_from_dir(cfg.weights, mc) if cfg.weights else tokenizer_for(mc)
         self.eos = set(mc.eos_ids)
         self.init_s = time.perf_counter() - t0
@@ -199,13 +204,24 @@ class LLMEngine:
             if self.ps.tp_size > 1:  # the workers replay raw staging words and capture their own graphs
                 raise ValueError("logprobs are not supported with tensor parallelism (tp_size > 1)")
             self.runner.logprob_enable()
+        guide = None
+        if params is not None and params.guide is not None:
+            if params.ignore_eos:
+                raise ValueError("a guide cannot be combined with ignore_eos (the answer ends where the guide does)")
+            if self.ps.tp_size > 1:  # the workers replay raw staging words and would sample without the state
+                raise ValueError("guided decoding is not supported with tensor parallelism (tp_size > 1)")
+            guide = compile_guide(params.guide, self.cfg.guide_max_states)
+            if self._vocab_bytes is None:
+                self._vocab_bytes = vocab_bytes(self.tokenizer, self.model_cfg.vocab_size)
+            self.runner.guide_enable(self._vocab_bytes, self.model_cfg.eos_ids, self.cfg.guide_max_states)
+            self.runner.gd.load(guide)  # a guide this vocabulary cannot follow is refused here
         ids = self.tokenizer.encode(prompt) if isinstance(prompt, str) else list(prompt)
         limit = self.runner.max_len - 1
         if len(ids) > limit - 1:  # keep room for at least one generated token; trim the middle
             keep = limit - 1
             ids = ids[: keep // 2] + ids[len(ids) - (keep - keep // 2):]
         seq = Sequence(prompt_ids=ids, params=params or SamplingParams(),
-                       request_id=request_id or uuid.uuid4().hex[:16], user=user, deadline=deadline)
+                       request_id=request_id or uuid.uuid4().hex[:16], user=user, deadline=deadline, guide=guide)
         if want_lp:
             seq.output_logprobs = []
         self.sched.add(seq)
@@ -214,6 +230,12 @@ class LLMEngine:
         self.counters["requests"] += 1
         self.counters["prompt_tokens"] += len(ids)
         return seq
+
+    def _on_free(self, seq) -> None:
+        """A sequence gave up its blocks (finished, aborted, preempted): its penalty and guide
+        slots go with them."""
+        self.runner.penalty_release(seq)
+        self.runner.guide_release(seq)
 
     def has_work(self) -> bool:
         return self.sched.has_work() or self._inflight is not None or self._pf_inflight is not None
@@ -231,7 +253,12 @@ class LLMEngine:
         work (scheduling, block bookkeeping, staging, stop checks, HTTP completions) then overlaps
         the GPU's step instead of sitting between steps.  A sequence that stops on EOS therefore
         runs one extra (discarded) step; length stops are predicted and never overrun.  Prefill
-        steps resolve the in-flight decode first (they change the batch)."""
+        steps resolve the in-flight decode first (they change the batch) - which is also why a
+        prefill step never sees a token still in flight: a guide's state is reset over a re-admitted
+        sequence's outputs (``ModelRunner._guide_slot``) and cannot lose one.  A prefill plan comes
+        only out of a ``schedule()`` whose ``prefill_pending()`` was true on entry, and the in-flight
+        decode is read back in front of exactly those calls; the second ``schedule()`` below runs
+        only with a prefill step in flight, which excludes a decode step in flight."""
         if not self.cfg.pipeline:
             return self._step_sync()
         done: list[Sequence] = []
@@ -510,7 +537,7 @@ class LLMEngine:
         d.update({"model": self.model_cfg.name, "tp_size": self.ps.tp_size, "device": str(self.device),
                   "graph_buckets": sorted(self.runner.graphs), "max_num_seqs": self.cfg.max_num_seqs,
                   "decode_weights": self.cfg.decode_weights, "prefill_weights": self.cfg.prefill_weights,
-                  **self.runner.kv_stats(), **self.runner.penalty_stats(),
+                  **self.runner.kv_stats(), **self.runner.penalty_stats(), **self.runner.guide_stats(),
                   "logprobs_enabled": self.runner.lp_on,
                   "resident_weight_bytes": self.model.resident_weight_bytes(),
                   "decode_encodings": self.model.decode_encodings(),
@@ -840,6 +867,16 @@ class EngineService:
         if not self.healthy:
             fut.set_exception(EngineUnavailable(f"engine unhealthy: {self._error!r}"))
             return fut
+        if params is not None and params.guide is not None:
+            # compile on the caller's thread (a bad spec is this request's ValueError); the engine
+            # thread then finds the guide in the compiler's cache
+            try:
+                if self.engine.ps.tp_size > 1:
+                    raise ValueError("guided decoding is not supported with tensor parallelism (tp_size > 1)")
+                compile_guide(params.guide, self.engine.cfg.guide_max_states)
+            except ValueError as e:
+                fut.set_exception(e)
+                return fut
         if isinstance(prompt, str):
             # tokenize on the caller's thread: the native BPE releases the GIL, so a burst's HTTP
             # handler threads encode in parallel instead of the engine thread encoding the whole

@@ -92,6 +92,14 @@ class ModelRunner:
         self._pen_free: list[int] = []
         self.d_pslot = torch.full((B,), -1, dtype=torch.int32, device=dev)
         self._pslot_sent = np.full(B, -1, dtype=np.int32)  # what d_pslot holds (as of the last upload)
+        # constrained decoding: the device-resident guide state (ops.GuideState, allocated by the
+        # first guided request), the sequences' slots in it and the decode rows' slots - a graph
+        # input of its own like d_pslot, all -1 until the feature is used
+        self.gd: Optional[ops.GuideState] = None
+        self._gd_slot: dict[int, int] = {}  # seq_id -> slot
+        self._gd_free: list[int] = []
+        self.d_gslot = torch.full((B,), -1, dtype=torch.int32, device=dev)
+        self._gslot_sent = np.full(B, -1, dtype=np.int32)  # what d_gslot holds (as of the last upload)
         # token log-probabilities (ops.token_logprobs), off until the first request asks
         # (logprob_enable): the rows' packed records, what each decode row wants (-1: nothing; a
         # graph input of its own like d_pslot) and the pinned buffers a step's records are read
@@ -149,11 +157,14 @@ class ModelRunner:
                 return b
         raise ValueError(f"batch {n} exceeds max_num_seqs {self.B}")
 
-    def _sample(self, logits: torch.Tensor, temp, topk, topp, out=None, pslot=None) -> torch.Tensor:
+    def _sample(self, logits: torch.Tensor, temp, topk, topp, out=None, pslot=None, gslot=None) -> torch.Tensor:
         # fresh numbers next step: the counter advances inside the sampling kernel (also in a graph)
-        if self.pen is None:
-            return ops.sample(logits, temp, topk, topp, self.rng, out=out, advance=True)
-        return ops.sample(logits, temp, topk, topp, self.rng, out=out, advance=True, penalties=self.pen, slots=pslot)
+        kw = {}
+        if self.pen is not None:
+            kw.update(penalties=self.pen, slots=pslot)
+        if self.gd is not None:
+            kw.update(guide=self.gd, gslots=gslot)
+        return ops.sample(logits, temp, topk, topp, self.rng, out=out, advance=True, **kw)
 
     # --------------------------------------------------------------------- sampling penalties
     def penalty_enable(self) -> None:
@@ -207,6 +218,67 @@ class ModelRunner:
     def penalty_stats(self) -> dict:
         return {"penalty_slots_in_use": len(self._pen_slot),
                 "penalty_state_bytes": self.pen.nbytes if self.pen is not None else 0}
+
+    # --------------------------------------------------------------------- constrained decoding
+    def guide_enable(self, vocab_bytes, eos_ids, max_states: int) -> None:
+        """Allocate the guide state on first use: ``max_num_seqs`` slots and ``max_num_seqs *
+        max_states`` rows, so a guide always loads once unreferenced ones are evicted.  Decode
+        graphs captured without it sample without it: they are captured again, once, with the state
+        and ``d_gslot`` as inputs (the in-flight step's tokens in ``d_out`` survive the capture)."""
+        if self.gd is not None:
+            return
+        self.gd = ops.GuideState(self.B, self.model.cfg.vocab_size, vocab_bytes, eos_ids, self.device,
+                                 rows=self.B * int(max_states))
+        self._gd_free = list(range(self.B - 1, -1, -1))
+        if self.graphs:
+            buckets = sorted(self.graphs)
+            self.graphs = {}
+            self.capture_graphs(buckets)
+
+    def guide_release(self, seq) -> None:
+        """The sequence left the batch (finished, aborted, preempted): its slot is free.  A step
+        still in flight may advance the slot once more; the next owner's reset runs after it."""
+        slot = self._gd_slot.pop(getattr(seq, "seq_id", None), None)
+        if slot is not None:
+            self.gd.release(slot)
+            self._gd_free.append(slot)
+
+    def _guide_slot(self, seq, take: bool = False) -> int:
+        """The sequence's guide slot (-1: none).  ``take`` (a prefill chunk of a newly admitted or
+        re-admitted sequence): a guided sequence without a slot gets one, reset to its guide's start
+        state advanced over the tokens it generated before a preemption.  Unlike the penalty counts
+        a guide cannot lose a token, so every one of those must be known: the engine reads the
+        in-flight decode step back before it plans any prefill step (LLMEngine.step)."""
+        sid = getattr(seq, "seq_id", None)
+        slot = self._gd_slot.get(sid, -1)
+        guide = getattr(seq, "guide", None)
+        if slot < 0 and take and sid is not None and guide is not None:
+            if any(t < 0 for t in seq.output_ids):
+                raise RuntimeError("guide reset over a token still in flight")
+            if not self._gd_free:
+                raise RuntimeError("no free guide slot (more guided sequences than max_num_seqs)")
+            slot = self._gd_free.pop()
+            self._gd_slot[sid] = slot
+            self.gd.reset(slot, guide, seq.output_ids)
+        return slot
+
+    def _upload_gslot(self, seqs: list) -> None:
+        """Decode rows -> guide slots, copied to ``d_gslot`` in front of the step only when it
+        differs from what the device holds."""
+        m = np.full(self.B, -1, dtype=np.int32)
+        if self._gd_slot:
+            m[: len(seqs)] = [self._gd_slot.get(s.seq_id, -1) for s in seqs]
+        if np.array_equal(m, self._gslot_sent):
+            return
+        self._gslot_sent = m
+        h = torch.from_numpy(m)
+        self.d_gslot.copy_(h.pin_memory() if self.is_gpu else h, non_blocking=True)
+
+    def guide_stats(self) -> dict:
+        g = self.gd
+        return {"guide_enabled": g is not None, "guide_state_bytes": g.nbytes if g is not None else 0,
+                "guides_resident": g.guides_resident if g is not None else 0,
+                "guide_slots_in_use": len(self._gd_slot)}
 
     # --------------------------------------------------------------------- token log-probabilities
     def logprob_enable(self) -> None:
@@ -311,7 +383,7 @@ class ModelRunner:
                      cst=len(seqs) if paged else 0, bt=len(seqs) * W, dbt=nd * Wd, dlen=nd,
                      mcu=len(seqs) + 2 if kA else 0, mqs=nq if kA else 0, mst=nq if kA else 0,
                      mlidx=len(seqs) if kA else 0, pslot=R if self.pen is not None else 0,
-                     want=R if self.lp_on else 0)
+                     want=R if self.lp_on else 0, gslot=R if self.gd is not None else 0)
         off, o = {}, 0
         for k, n in sizes.items():
             off[k] = o
@@ -348,6 +420,12 @@ class ModelRunner:
             for i, (s, c, n) in enumerate(zip(seqs, starts, lens)):
                 slot = self._penalty_slot(s, take=True)
                 v["pslot"][nd + i] = slot if c + n >= s.num_tokens else -1
+        if self.gd is not None:
+            # a chunk short of its prompt's end samples a token nobody keeps: it must not advance the state
+            v["gslot"][:nd] = [self._guide_slot(q) for q in decode]
+            for i, (s, c, n) in enumerate(zip(seqs, starts, lens)):
+                slot = self._guide_slot(s, take=True)
+                v["gslot"][nd + i] = slot if c + n >= s.num_tokens else -1
         lp_want = None
         if self.lp_on:
             # a chunk short of its prompt's end samples a token nobody keeps: no logprobs for it
@@ -408,7 +486,7 @@ class ModelRunner:
         self.n_steps["prefill_tokens"] = self.n_steps.get("prefill_tokens", 0) + T
         logits = self.model.forward(dv["ids"], meta, self.kv)
         tok = self._sample(logits, dv["temp"].view(torch.float32), dv["topk"], dv["topp"].view(torch.float32),
-                           pslot=dv["pslot"])
+                           pslot=dv["pslot"], gslot=dv["gslot"])
         lp = ops.token_logprobs(logits[:R], tok, dv["want"]) if lp_want is not None else None
         self.n_steps["prefill"] += 1
         if self.on_launched is not None:  # TP: the custom-AR error flag, read back with the tokens
@@ -440,7 +518,7 @@ class ModelRunner:
                         dec_src=self.d_src[:b], dec_prev=self.d_out)
         logits = self.model.forward(self.d_ids[:b], meta, self.kv)
         self._sample(logits, self.d_temp[:b], self.d_topk[:b], self.d_topp[:b], out=self.d_out[:b],
-                     pslot=self.d_pslot[:b])
+                     pslot=self.d_pslot[:b], gslot=self.d_gslot[:b])
         if self.lp_on:  # after the sampler on the stream: it reads the tokens just drawn
             ops.token_logprobs(logits, self.d_out[:b], self.d_want[:b], out=self.d_lp[:b])
 
@@ -453,6 +531,8 @@ class ModelRunner:
         self.d_slots.fill_(-1)
         self.d_pslot.fill_(-1)  # ... and count nothing; the next decode step uploads its rows' slots again
         self._pslot_sent[:] = -1
+        self.d_gslot.fill_(-1)  # ... and advance no guide
+        self._gslot_sent[:] = -1
         if self.lp_on:  # ... and compute no logprobs
             self.d_want.fill_(-1)
             self._want_sent[:] = -1
@@ -524,6 +604,8 @@ class ModelRunner:
         n_el = _Staging.prefix(self.B, self.max_blocks_per_seq, b)  # the per-row fields + b block-table rows
         if self.pen is not None:
             self._upload_pslot(seqs)
+        if self.gd is not None:
+            self._upload_gslot(seqs)
         lp_want = self._upload_want(seqs) if self.lp_on else None
         if publish is not None:
             publish(st.message(n, b, n_el))
@@ -591,7 +673,8 @@ class ModelRunner:
 
     def memory_report(self) -> dict:
         return {**self.kv_stats(), "max_model_len": self.max_len, "graph_buckets": sorted(self.graphs),
-                "penalty_state_bytes": self.penalty_stats()["penalty_state_bytes"]}
+                "penalty_state_bytes": self.penalty_stats()["penalty_state_bytes"],
+                "guide_state_bytes": self.guide_stats()["guide_state_bytes"]}
 
 
 class _Staging:

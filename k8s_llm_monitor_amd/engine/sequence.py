@@ -30,6 +30,10 @@ class SamplingParams:
     # ``top_logprobs`` (0..20, needs ``logprobs``) most likely alternatives; Sequence.output_logprobs
     logprobs: bool = False
     top_logprobs: int = 0
+    # constrained decoding (engine/guide.py): plain data, one of {"choice": [str, ...]},
+    # {"regex": str}, {"json_schema": dict}; the answer then matches it in full when it finishes
+    # with "stop" (cut by max_tokens or the deadline it may be an incomplete match)
+    guide: Optional[dict] = None
 
     def has_penalties(self) -> bool:
         return self.repetition_penalty != 1.0 or self.presence_penalty != 0.0 or self.frequency_penalty != 0.0
@@ -75,6 +79,7 @@ class Sequence:
     pending_first: int = 0
     user: object = None  # opaque payload for the caller (future, callback, ...)
     deadline: Optional[float] = None  # time.perf_counter() by which the answer is due (engine.add_request)
+    guide: object = None  # the compiled engine.guide.Guide of params.guide (engine.add_request)
 
     @property
     def num_tokens(self) -> int:

@@ -206,6 +206,48 @@ class HFTokenizer:
         return self.decode([int(t)], skip_special=False).encode("utf-8")
 
 
+def _gpt2_unicode_to_byte() -> dict:
+    """Inverse of the GPT-2 byte-to-unicode table that byte-level BPE vocabularies are written in."""
+    keep = list(range(0x21, 0x7F)) + list(range(0xA1, 0xAD)) + list(range(0xAE, 0x100))
+    table, n = {}, 0
+    for b in range(256):
+        if b in keep:
+            table[chr(b)] = b
+        else:
+            table[chr(256 + n)] = b
+            n += 1
+    return table
+
+
+def vocab_bytes(tokenizer, vocab_size: int) -> list:
+    """The bytes every id in ``[0, vocab_size)`` adds to an answer - what guided decoding walks
+    its DFA over.  Special tokens (bos / eos, added tokens) give ``b""``.
+
+    :class:`ByteBPETokenizer`: exactly what ``decode`` appends per id (the fold of ids a random-init
+    model draws beyond the covered range included).  :class:`HFTokenizer`: the raw bytes of a
+    byte-level vocabulary - not ``token_bytes``, which decodes a lone token and turns a partial
+    UTF-8 sequence into U+FFFD; any other kind of vocabulary is refused."""
+    if isinstance(tokenizer, ByteBPETokenizer):
+        return [tokenizer._token_bytes(t, True) for t in range(vocab_size)]
+    tok = tokenizer.tok
+    conf = json.loads(tok.to_str())
+    if '"ByteLevel"' not in json.dumps([conf.get("decoder"), conf.get("pre_tokenizer")]):
+        raise ValueError("guided decoding needs a byte-level vocabulary")
+    u2b = _gpt2_unicode_to_byte()
+    special = set(tok.get_added_tokens_decoder())
+    out = []
+    for t in range(vocab_size):
+        s = None if t in special else tok.id_to_token(t)
+        if s is None:
+            out.append(b"")
+            continue
+        try:
+            out.append(bytes([u2b[c] for c in s]))
+        except KeyError:
+            raise ValueError("guided decoding needs a byte-level vocabulary") from None
+    return out
+
+
 def tokenizer_from_dir(path, model_cfg):
     """``path/tokenizer.json`` as an :class:`HFTokenizer` when present, else the built-in BPE."""
     f = Path(path) / "tokenizer.json"

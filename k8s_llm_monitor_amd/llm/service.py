@@ -97,10 +97,13 @@ class LocalEngineBackend:
                  request_id: Optional[str] = None, ignore_eos: bool = False,
                  top_p: Optional[float] = None, presence_penalty: Optional[float] = None,
                  frequency_penalty: Optional[float] = None, repetition_penalty: Optional[float] = None,
-                 logprobs: bool = False, top_logprobs: int = 0) -> GenResult:
+                 logprobs: bool = False, top_logprobs: int = 0, guide: Optional[dict] = None) -> GenResult:
         """``logprobs`` / ``top_logprobs`` (0..20): the result carries ``logprobs``, one entry per
         answer token - its log-probability under the model's distribution (before penalties,
-        temperature and top-k / top-p) and that many most likely alternatives."""
+        temperature and top-k / top-p) and that many most likely alternatives.  ``guide``
+        (engine/guide.py: ``{"choice": [...]}``, ``{"regex": "..."}`` or ``{"json_schema": {...}}``):
+        the answer matches it in full when it finishes with "stop"; an unsupported spec is a
+        ``ValueError``."""
         from ..engine import SamplingParams
 
         d = self.default
@@ -110,7 +113,7 @@ class LocalEngineBackend:
                            repetition_penalty=d.repetition_penalty if repetition_penalty is None else repetition_penalty,
                            presence_penalty=d.presence_penalty if presence_penalty is None else presence_penalty,
                            frequency_penalty=d.frequency_penalty if frequency_penalty is None else frequency_penalty,
-                           logprobs=logprobs, top_logprobs=top_logprobs)
+                           logprobs=logprobs, top_logprobs=top_logprobs, guide=guide)
         budget = self.answer_budget_s
         fut = self.svc.submit(P.SYSTEM_PREAMBLE + prompt, p, request_id,
                               deadline=time.perf_counter() + budget if budget else None)
@@ -232,9 +235,11 @@ class OpenAIBackend:
                  request_id: Optional[str] = None, ignore_eos: bool = False,
                  top_p: Optional[float] = None, presence_penalty: Optional[float] = None,
                  frequency_penalty: Optional[float] = None, repetition_penalty: Optional[float] = None,
-                 logprobs: bool = False, top_logprobs: int = 0) -> GenResult:
+                 logprobs: bool = False, top_logprobs: int = 0, guide: Optional[dict] = None) -> GenResult:
         """``repetition_penalty`` is not an OpenAI field: it is not forwarded.  ``logprobs`` /
-        ``top_logprobs`` are, and ``choices[0].logprobs.content`` comes back as ``logprobs``."""
+        ``top_logprobs`` are, and ``choices[0].logprobs.content`` comes back as ``logprobs``.
+        ``guide`` goes out in the form /v1/chat/completions takes it: ``response_format`` for a
+        JSON schema, ``guided_choice`` / ``guided_regex`` otherwise."""
         if not self.api_key:
             raise RuntimeError("llm.api_key / OPENAI_API_KEY not configured")
         req_d = {"model": self.model, "max_tokens": max_tokens or self.max_tokens,
@@ -249,6 +254,12 @@ class OpenAIBackend:
             req_d["presence_penalty"] = pp
         if fp:
             req_d["frequency_penalty"] = fp
+        if guide is not None:
+            (kind, val), = guide.items()
+            if kind == "json_schema":
+                req_d["response_format"] = {"type": "json_schema", "json_schema": {"name": "answer", "schema": val}}
+            else:
+                req_d["guided_" + kind] = val
         if logprobs:
             req_d["logprobs"] = True
             if top_logprobs:
@@ -282,8 +293,9 @@ class RuleBackend:
                  request_id: Optional[str] = None, ignore_eos: bool = False,
                  top_p: Optional[float] = None, presence_penalty: Optional[float] = None,
                  frequency_penalty: Optional[float] = None, repetition_penalty: Optional[float] = None,
-                 logprobs: bool = False, top_logprobs: int = 0) -> GenResult:
-        """No model, so no log-probabilities: ``logprobs`` / ``top_logprobs`` are ignored."""
+                 logprobs: bool = False, top_logprobs: int = 0, guide: Optional[dict] = None) -> GenResult:
+        """No model, so no log-probabilities and no guide: ``logprobs`` / ``top_logprobs`` /
+        ``guide`` are ignored."""
         flagged = [ln.strip() for ln in prompt.splitlines()
                    if any(k in ln for k in ("[资源压力]", "[不健康]", "状态=", "接近限制", "不通", "告警", "UAV "))]
         text = ("未发现明显异常。" if not flagged else
@@ -356,6 +368,7 @@ class AnalysisService:
         prompt is built here, from this server's cluster context, and only generation is remote."""
         self.backend = backend
         self.routes = dict(routes or {})
+        self.guide_max_states = 512  # llm.guide_max_states (set by the application)
         self.manager = manager
         self.client = client
         self.analyzer = analyzer
@@ -446,8 +459,9 @@ class AnalysisService:
 
     # ------------------------------------------------------------------ entry points
     def _respond(self, rid: str, kind: str, prompt: str, extra: dict, max_tokens: Optional[int] = None,
-                 ignore_eos: bool = False, logprobs: bool = False) -> AnalysisResponse:
-        """``logprobs``: the record's result gains ``mean_logprob`` and ``min_logprob`` over the
+                 ignore_eos: bool = False, logprobs: bool = False, guide: Optional[dict] = None) -> AnalysisResponse:
+        """``guide``: passed on to the backend (``generate(guide=)``).
+        ``logprobs``: the record's result gains ``mean_logprob`` and ``min_logprob`` over the
         answer's tokens (None for an empty answer or a backend without a model) - how sure the
         model was of what it wrote."""
         from ..engine import EngineOverloaded, EngineUnavailable
@@ -455,6 +469,8 @@ class AnalysisService:
         backend = self.backend_for(kind)
         try:
             lp_kw = {"logprobs": True} if logprobs else {}
+            if guide is not None:
+                lp_kw["guide"] = guide
             g = backend.generate(prompt, max_tokens=max_tokens or self.max_tokens, request_id=rid,
                                  ignore_eos=ignore_eos, **lp_kw)
             if logprobs:
@@ -525,10 +541,18 @@ class AnalysisService:
         if kind not in ("anomaly_detection", "root_cause"):
             raise ValueError(f"unknown analysis type: {kind}")
         mt = int(params.get("max_tokens") or 0) or None
+        guide = None
+        if params.get("response_schema") is not None:  # the answer is compact JSON of this schema
+            from ..engine.guide import compile_guide
+
+            if not isinstance(params["response_schema"], dict):
+                raise ValueError("parameters.response_schema must be a JSON schema object")
+            guide = {"json_schema": params["response_schema"]}
+            compile_guide(guide, self.guide_max_states)  # an unsupported schema is the caller's error (400)
         ctx = self._fit(self.cluster_context(), P.build_analysis_prompt(kind, "", params), mt, kind)
         prompt = P.build_analysis_prompt(kind, ctx, params)
         return self._respond(uuid.uuid4().hex, kind, prompt, {"parameters": params}, mt,
-                             logprobs=params.get("logprobs") is True)
+                             logprobs=params.get("logprobs") is True, guide=guide)
 
     def explain_pod_communication(self, analysis, max_tokens: Optional[int] = None,
                                   ignore_eos: bool = False) -> AnalysisResponse:

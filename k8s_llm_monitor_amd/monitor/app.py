@@ -72,7 +72,7 @@ def engine_config(cfg: Config):
                         max_prefill_tokens=cfg.llm.max_prefill_tokens, chunked_prefill=cfg.llm.chunked_prefill,
                         prefix_caching=cfg.llm.prefix_caching, weights=cfg.llm.weights or None,
                         decode_weights=cfg.llm.decode_weights, prefill_weights=cfg.llm.prefill_weights,
-                        kv_cache_dtype=cfg.llm.kv_cache_dtype)
+                        kv_cache_dtype=cfg.llm.kv_cache_dtype, guide_max_states=cfg.llm.guide_max_states)
 
 
 def make_llm_backend(cfg: Config, pstate=None, device: Optional[str] = None):
@@ -162,7 +162,9 @@ def build_monitor(cfg: Config, backend=None, start_manager: bool = True, llm: bo
                                  max_context_events=cfg.analysis.max_context_events,
                                  token_budget=cfg.analysis.prompt_token_budget, max_tokens=cfg.llm.max_tokens,
                                  routes=make_routes(cfg))
+    m.analysis.guide_max_states = cfg.llm.guide_max_states
     m.app = MonitorApp(m.client, m.manager, m.analysis, m.engine_service, llm_timeout_s=float(cfg.llm.timeout))
+    m.app.guide_max_states = cfg.llm.guide_max_states
     if hasattr(backend_llm, "answer_budget_s"):  # the engine stops generations before the write timeout
         backend_llm.answer_budget_s = m.app.answer_budget_s()
     m.analysis.analyzer = m.app.analyzer if analyzer is None else analyzer

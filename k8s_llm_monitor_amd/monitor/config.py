@@ -10,7 +10,8 @@ New engine knobs live under ``llm`` next to the reference's keys: ``provider: lo
 the in-process MI355X engine (``openai`` keeps the reference's remote semantics: no local model),
 plus ``tp_size``, ``dp_replicas``, ``max_batch``, ``kv_cache_gb``, ``max_model_len``, ``dtype``,
 ``seed``, ``use_graphs``, ``decode_weights``, ``prefill_weights``, ``kv_cache_dtype``, and the
-sampling penalties ``repetition_penalty``, ``presence_penalty``, ``frequency_penalty``.
+sampling penalties ``repetition_penalty``, ``presence_penalty``, ``frequency_penalty`` and
+``guide_max_states`` (constrained decoding).
 """
 from __future__ import annotations
 
@@ -78,6 +79,9 @@ class LLMConfig:
     repetition_penalty: float = 1.0
     presence_penalty: float = 0.0
     frequency_penalty: float = 0.0
+    # constrained decoding (docs/engine.md): the most DFA states one guide (guided_choice,
+    # guided_regex, a response_format JSON schema) may compile to; larger ones are a 400
+    guide_max_states: int = 512
     max_prefill_tokens: int = 16384  # token budget of one prefill step
     chunked_prefill: bool = True  # longer prompts prefill in chunks of that budget
     prefix_caching: bool = True  # reuse the KV blocks of shared prompt prefixes

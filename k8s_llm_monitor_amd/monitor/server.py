@@ -112,6 +112,7 @@ class MonitorApp:
         self.web_dir = web_dir
         self.write_timeout_s = write_timeout_s
         self.llm_timeout_s = llm_timeout_s
+        self.guide_max_states = 512  # llm.guide_max_states (set by the application)
         self.analyzer = None
         if client is not None:
             from .analysis.network import NetworkAnalyzer
@@ -432,7 +433,15 @@ class MonitorApp:
         ``top_logprobs`` (an integer in [0, 20], needs ``logprobs: true``) add
         ``choices[0].logprobs.content``: per answer token its log-probability under the model's
         distribution - before penalties, temperature and top-k / top-p - and the most likely
-        alternatives; invalid values are a 400, and without the fields the reply has no such key."""
+        alternatives; invalid values are a 400, and without the fields the reply has no such key.
+
+        Constrained decoding (docs/api.md): at most one of ``response_format: {"type":
+        "json_schema", "json_schema": {"schema": {...}}}`` (compact JSON of the schema subset) and
+        the extensions ``guided_choice: [...]`` / ``guided_regex: "..."``.  The answer then matches
+        in full when ``finish_reason`` is ``stop``; cut by ``max_tokens`` or the deadline it may be
+        an incomplete match.  ``{"type": "text"}`` is a no-op; an invalid or unsupported spec, and
+        a guide the engine cannot apply (tensor parallelism), are a 400 with the compiler's message.
+        ``logprobs`` stay those of the unconstrained distribution."""
         _only(method, "POST")
         if self.analysis is None:
             raise http_error(503, "Analysis engine not available")
@@ -478,6 +487,9 @@ class MonitorApp:
         if want_lp:
             pen["logprobs"] = True
             pen["top_logprobs"] = n_top or 0
+        guide = self._guide_spec(d)
+        if guide is not None:
+            pen["guide"] = guide
         backend = self.analysis.backend
         try:
             prompt = self.analysis.fit_chat(parts, mt)
@@ -500,6 +512,41 @@ class MonitorApp:
         return json_reply({"id": "chatcmpl-" + uuid.uuid4().hex, "object": "chat.completion",
                            "created": int(time.time()), "model": g.get("model") or d.get("model", ""),
                            "choices": [choice], "usage": usage})
+
+    def _guide_spec(self, d: dict) -> Optional[dict]:
+        """The guide a chat-completions body asks for (None: none), compiled once here so that a
+        bad spec is a 400 whatever backend answers."""
+        from ..engine.guide import compile_guide
+
+        specs = []
+        rf = d.get("response_format")
+        if rf is not None:
+            if not isinstance(rf, dict) or not isinstance(rf.get("type"), str):
+                raise http_error(400, "response_format must be an object with a type")
+            if rf["type"] == "json_schema":
+                js = rf.get("json_schema")
+                schema = js.get("schema") if isinstance(js, dict) else None
+                if not isinstance(schema, dict):
+                    raise http_error(400, "response_format.json_schema.schema must be a JSON schema object")
+                specs.append({"json_schema": schema})
+            elif rf["type"] == "json_object":
+                raise http_error(400, "response_format json_object: a JSON schema is needed (type json_schema) - "
+                                      "free-form JSON is not a regular language")
+            elif rf["type"] != "text":
+                raise http_error(400, f"response_format type {rf['type']!r} is not supported")
+        if d.get("guided_choice") is not None:
+            specs.append({"choice": d["guided_choice"]})
+        if d.get("guided_regex") is not None:
+            specs.append({"regex": d["guided_regex"]})
+        if len(specs) > 1:
+            raise http_error(400, "at most one of response_format, guided_choice and guided_regex")
+        if not specs:
+            return None
+        try:
+            compile_guide(specs[0], self.guide_max_states)
+        except ValueError as e:
+            raise http_error(400, str(e))
+        return specs[0]
 
     def analyze(self, method, body, q) -> Reply:
         _only(method, "POST")

@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import importlib
 import math
+from collections import OrderedDict
 from typing import Optional
 
 import torch
@@ -1391,36 +1392,204 @@ class PenaltyState:
         return self.table[:, : self.V] < 0
 
 
+class GuideState:
+    """Constrained decoding on the sampler's device (engine/guide.py compiles the guides): an
+    arena of DFA states, one row each, and the guide state of every sequence slot, so a captured
+    decode step masks its logits and advances its guides by itself.
+
+    * the vocabulary as CSR: ``tok_off`` int32 ``[V + 1]`` and ``blob`` uint8;
+    * ``mask`` ``[rows, W]`` 32-bit words (stored as int32), ``W = ceil(V / 32)`` rounded up to 4
+      words so every row is 16-byte aligned: token ``t`` is bit ``t & 31`` of word ``t >> 5``
+      (``ref.guide_mask``); ``popc`` int32 ``[rows]`` counts a row's allowed tokens;
+    * ``trans`` int32 ``[rows, 256]`` holding **absolute** row numbers (-1 dead), ``accept`` uint8
+      ``[rows]``;
+    * ``state`` int32 ``[slots]``: the slot's current absolute row, -1 = unguided.
+
+    Rows are handed out one by one from ``free_rows``; transitions are absolute, so a guide's rows
+    need not be contiguous and the arena cannot fragment.  Resident guides are keyed by their
+    canonical spec text, ref-counted by the slots using them and evicted least recently used, when
+    unreferenced, once rows run out.  A sampler row names its slot through
+    ``ops.sample(..., guide=, gslots=)``."""
+
+    def __init__(self, slots: int, V: int, vocab_bytes, eos_ids, device, rows: int):
+        import numpy as np
+
+        self.slots, self.V, self.rows = int(slots), int(V), int(rows)
+        if len(vocab_bytes) != self.V:
+            raise ValueError(f"vocab_bytes has {len(vocab_bytes)} entries, the vocabulary {self.V}")
+        if self.slots <= 0 or self.rows <= 0:
+            raise ValueError("a guide state needs slots and rows")
+        self.vocab_bytes = [bytes(b) for b in vocab_bytes]
+        self.eos_ids = tuple(sorted({int(t) for t in eos_ids}))
+        self.W = ((self.V + 31) // 32 + 3) // 4 * 4
+        dev = torch.device(device)
+        off = np.zeros(self.V + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(b) for b in self.vocab_bytes])
+        if off[-1] >= 1 << 31:
+            raise ValueError("vocabulary bytes exceed 2 GiB")
+        blob = np.frombuffer(b"".join(self.vocab_bytes) + b"\0", dtype=np.uint8).copy()  # never empty
+        self.tok_off = torch.from_numpy(off.astype(np.int32)).to(dev)
+        self.blob = torch.from_numpy(blob).to(dev)
+        self.eos = torch.tensor(self.eos_ids, dtype=torch.int32, device=dev)
+        self.mask = torch.zeros(self.rows, self.W, dtype=torch.int32, device=dev)
+        self.popc = torch.zeros(self.rows, dtype=torch.int32, device=dev)
+        self.trans = torch.full((self.rows, 256), -1, dtype=torch.int32, device=dev)
+        self.accept = torch.zeros(self.rows, dtype=torch.uint8, device=dev)
+        self.state = torch.full((self.slots,), -1, dtype=torch.int32, device=dev)
+        self.device = self.mask.device  # with its index ("cuda" -> "cuda:0")
+        self.free_rows: list = list(range(self.rows - 1, -1, -1))
+        self._resident: "OrderedDict[str, list]" = OrderedDict()  # key -> [guide, rows (np), refs]
+        self._slot_key: dict = {}
+        # with every single-byte token in the vocabulary no reachable state can have an empty row
+        self._all_bytes = len({b for b in self.vocab_bytes if len(b) == 1}) == 256
+
+    @property
+    def nbytes(self) -> int:
+        return sum(t.numel() * t.element_size() for t in (self.tok_off, self.blob, self.eos, self.mask, self.popc,
+                                                          self.trans, self.accept, self.state))
+
+    @property
+    def guides_resident(self) -> int:
+        return len(self._resident)
+
+    @property
+    def slots_in_use(self) -> int:
+        return len(self._slot_key)
+
+    def resident_rows(self, guide):
+        """The absolute rows of a resident guide (state i in ``rows[i]``), or None."""
+        r = self._resident.get(guide.key)
+        return None if r is None else r[1]
+
+    def load(self, guide):
+        """Make ``guide`` resident (upload ``trans`` / ``accept``, build its mask rows on the
+        current stream) and return its absolute rows.  ``ValueError`` for a guide with a
+        non-accepting state whose row is empty (a vocabulary lacking some single-byte token);
+        ``RuntimeError`` when its rows cannot be found even after evicting every unreferenced guide."""
+        import numpy as np
+
+        r = self._resident.get(guide.key)
+        if r is not None:
+            self._resident.move_to_end(guide.key)
+            return r[1]
+        n = guide.n
+        while len(self.free_rows) < n:
+            victim = next((k for k, v in self._resident.items() if v[2] == 0), None)
+            if victim is None:
+                raise RuntimeError(f"guide arena full: {n} rows needed, {len(self.free_rows)} free of {self.rows}")
+            self.free_rows.extend(int(x) for x in self._resident.pop(victim)[1][::-1])
+        rows = np.array([self.free_rows.pop() for _ in range(n)], dtype=np.int64)
+        t = np.asarray(guide.trans)
+        t_abs = np.where(t >= 0, rows[np.maximum(t, 0)], -1).astype(np.int32)
+        acc = np.asarray(guide.accept).astype(np.uint8)
+        rows_t = torch.from_numpy(rows)
+        if self.device.type == "cuda":
+            rows_d = rows_t.to(torch.int32).pin_memory().to(self.device, non_blocking=True)
+            idx = rows_d.long()
+            self.trans[idx] = torch.from_numpy(t_abs).pin_memory().to(self.device, non_blocking=True)
+            self.accept[idx] = torch.from_numpy(acc).pin_memory().to(self.device, non_blocking=True)
+            native().guide_mask_build(self.mask, self.trans, self.accept, self.popc, rows_d, self.tok_off, self.blob,
+                                      self.eos)
+        else:
+            ok = ref.guide_mask(t, guide.accept, self.vocab_bytes, self.eos_ids).numpy()
+            bits = np.zeros((n, self.W * 32), dtype=bool)
+            bits[:, : self.V] = ok
+            words = np.packbits(bits, axis=1, bitorder="little").view("<u4").astype(np.uint32).view(np.int32)
+            self.trans[rows_t] = torch.from_numpy(t_abs)
+            self.accept[rows_t] = torch.from_numpy(acc)
+            self.mask[rows_t] = torch.from_numpy(words.copy())
+            self.popc[rows_t] = torch.from_numpy(ok.sum(1).astype(np.int32))
+        if not self._all_bytes:  # the only case with a possibly empty row: worth one readback
+            empty = (self.popc[rows_t.to(self.device)].cpu().numpy() == 0) & (acc == 0)
+            if empty.any():
+                self.free_rows.extend(int(x) for x in rows[::-1])
+                raise ValueError(f"guide state {int(np.flatnonzero(empty)[0])} allows no token of this vocabulary "
+                                 "(it lacks some single-byte token)")
+        self._resident[guide.key] = [guide, rows, 0]
+        return rows
+
+    def walk(self, guide, output_token_ids) -> int:
+        """The guide's own state after the given tokens, by the sampler's rules: an eos token, a
+        token outside ``[0, V)``, a token without bytes and a walk that would die leave it."""
+        s = 0
+        for t in output_token_ids:
+            t = int(t)
+            if not 0 <= t < self.V or t in self.eos_ids or not self.vocab_bytes[t]:
+                continue
+            nxt = ref.guide_advance(guide.trans, s, self.vocab_bytes[t])
+            if nxt >= 0:
+                s = nxt
+        return s
+
+    def reset(self, slot: int, guide, output_token_ids=()) -> None:
+        """Make ``slot`` follow ``guide`` from its start state advanced over ``output_token_ids``
+        (walked on the host); the slot's state is written on the current stream, no host sync."""
+        if not 0 <= slot < self.slots:
+            raise ValueError(f"slot {slot} outside [0, {self.slots})")
+        rows = self.load(guide)
+        self._drop(slot)
+        self._resident[guide.key][2] += 1
+        self._slot_key[slot] = guide.key
+        self.state[slot:slot + 1].fill_(int(rows[self.walk(guide, output_token_ids)]))
+
+    def _drop(self, slot: int) -> None:
+        key = self._slot_key.pop(slot, None)
+        if key is not None:
+            self._resident[key][2] -= 1
+
+    def release(self, slot: int) -> None:
+        """The slot follows no guide any more (stream-ordered like :meth:`reset`)."""
+        self._drop(slot)
+        self.state[slot:slot + 1].fill_(-1)
+
+    def mask_bits(self, rows) -> torch.Tensor:
+        """bool ``[len(rows), V]`` (host): the mask rows unpacked."""
+        import numpy as np
+
+        idx = torch.as_tensor(np.asarray(rows, dtype=np.int64)).to(self.device)
+        w = self.mask[idx].cpu().numpy().view(np.uint32).astype("<u4")
+        return torch.from_numpy(np.unpackbits(w.view(np.uint8), axis=1, bitorder="little")[:, : self.V].astype(bool))
+
+
 def sample(logits: torch.Tensor, temperature: Optional[torch.Tensor] = None, top_k: Optional[torch.Tensor] = None,
            top_p: Optional[torch.Tensor] = None, rng: Optional[torch.Tensor] = None,
            out: Optional[torch.Tensor] = None, advance: bool = False, penalties: Optional[PenaltyState] = None,
-           slots: Optional[torch.Tensor] = None) -> torch.Tensor:
+           slots: Optional[torch.Tensor] = None, guide: Optional[GuideState] = None,
+           gslots: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Next tokens [B] int32.  temperature <= 0 (or None) is greedy.  ``advance``: bump the RNG
     counter ``rng[1]`` after drawing (on the GPU inside the final sampling kernel - no extra
     launch inside a captured decode step).  ``penalties`` with ``slots`` (int32 [B], -1 = none):
     row b's logits are penalised by the state's slot ``slots[b]`` first (``ref.apply_penalties``),
-    and the token drawn is counted there (distinct rows must name distinct slots)."""
+    and the token drawn is counted there (distinct rows must name distinct slots).  ``guide`` with
+    ``gslots`` (int32 [B], -1 = none): a row whose slot holds a state reads its (penalised) logits
+    through that state's token mask - disallowed tokens are -inf - and the token drawn advances the
+    slot's state (distinct rows must name distinct slots)."""
+    if guide is not None:
+        if gslots is None or gslots.dtype != torch.int32 or gslots.numel() < logits.shape[0]:
+            raise ValueError("a guide needs gslots: int32 [B]")
+        if guide.V != logits.shape[1] or guide.device != logits.device:
+            raise ValueError("the guide state belongs to another vocabulary or device")
     if penalties is not None:
         if slots is None or slots.dtype != torch.int32 or slots.numel() < logits.shape[0]:
             raise ValueError("penalties need slots: int32 [B]")
         if penalties.V != logits.shape[1] or penalties.device != logits.device:
             raise ValueError("the penalty state belongs to another vocabulary or device")
     if not _gpu(logits):
-        r = _sample_cpu(logits, temperature, top_k, top_p, rng, penalties, slots)
+        r = _sample_cpu(logits, temperature, top_k, top_p, rng, penalties, slots, guide, gslots)
         if advance and rng is not None:
             rng[1] += 1
         return out.copy_(r) if out is not None else r
     if out is None:
         out = torch.empty(logits.shape[0], dtype=torch.int32, device=logits.device)
-    if penalties is None:
-        native().sample(out, logits, temperature, top_k, top_p, rng, advance and rng is not None)
-    else:
-        native().sample(out, logits, temperature, top_k, top_p, rng, advance and rng is not None,
-                        penalties.table, penalties.params, slots, penalties.V)
+    pen = () if penalties is None else (penalties.table, penalties.params, slots, penalties.V)
+    if guide is not None:
+        pen = pen or (None, None, None, 0)
+        pen += (guide.mask, guide.trans, guide.state, gslots, guide.tok_off, guide.blob, guide.eos)
+    native().sample(out, logits, temperature, top_k, top_p, rng, advance and rng is not None, *pen)
     return out
 
 
-def _sample_cpu(logits, temperature, top_k, top_p, rng, penalties=None, slots=None):
+def _sample_cpu(logits, temperature, top_k, top_p, rng, penalties=None, slots=None, guide=None, gslots=None):
     B = logits.shape[0]
     res = torch.empty(B, dtype=torch.int32)
     gen = torch.Generator().manual_seed(int(rng[0]) * 1000003 + int(rng[1])) if rng is not None else None
@@ -1434,6 +1603,12 @@ def _sample_cpu(logits, temperature, top_k, top_p, rng, penalties=None, slots=No
             rep, _, pres, freq = penalties.params[slot].tolist()
             e = penalties.table[slot, : penalties.V]
             row = ref.apply_penalties(row, e < 0, e.to(torch.int32) & PenaltyState.MAX_COUNT, rep, pres, freq)
+        gs = int(gslots[b]) if guide is not None else -1
+        st = int(guide.state[gs]) if 0 <= gs < (guide.slots if guide is not None else 0) else -1
+        if not 0 <= st < (guide.rows if guide is not None else 0):
+            st = -1  # like the kernel: no slot, or a slot without a state, is no guide
+        if st >= 0:
+            row = row.float().masked_fill(~guide.mask_bits([st])[0], float("-inf"))
         x = row.float()
         if t <= 0:
             res[b] = int(x.argmax())
@@ -1446,6 +1621,11 @@ def _sample_cpu(logits, temperature, top_k, top_p, rng, penalties=None, slots=No
             e = penalties.table[slot, int(res[b])]
             if int(e) & PenaltyState.MAX_COUNT != PenaltyState.MAX_COUNT:
                 penalties.table[slot, int(res[b])] = e + 1
+        tok = int(res[b])
+        if st >= 0 and 0 <= tok < guide.V and tok not in guide.eos_ids and guide.vocab_bytes[tok]:
+            nxt = ref.guide_advance(guide.trans, st, guide.vocab_bytes[tok])  # absolute rows
+            if 0 <= nxt < guide.rows:
+                guide.state[gs] = nxt
     return res
 
 

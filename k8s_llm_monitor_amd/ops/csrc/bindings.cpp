@@ -42,6 +42,14 @@ int k8sllm_sample(int* out, const void* logits, int is_fp32, long B, long stride
 int k8sllm_sample_pen(int* out, const void* logits, int is_fp32, long B, long stride, int V, const float* temps,
                       const int* top_k, const float* top_p, const int64_t* rng, float* pv, int* pi, int advance,
                       const int* pslot, void* table, long tstride, const float* pparams, int nslots, hipStream_t s);
+int k8sllm_sample_guided(int* out, const void* logits, int is_fp32, long B, long stride, int V, const float* temps,
+                         const int* top_k, const float* top_p, const int64_t* rng, float* pv, int* pi, int advance,
+                         const int* pslot, void* table, long tstride, const float* pparams, int nslots,
+                         const int* gslot, int* gstate, int gnslots, const void* gmask, int gW, const int* gtrans,
+                         int grows, const int* tok_off, const void* blob, const int* eos_ids, int n_eos, hipStream_t s);
+int k8sllm_guide_mask_build(void* mask, int W, const int* trans, const void* accept, int* popc, const int* rows, int n,
+                            int nrows, const int* tok_off, const void* blob, int V, const int* eos_ids, int n_eos,
+                            hipStream_t s);
 int k8sllm_penalty_reset(void* table, long tstride, int V, int nslots, int slot, const int* ids, int n_prompt,
                          int n_out, float* pparams, float rep, float inv_rep, float presence, float frequency,
                          hipStream_t s);
@@ -423,10 +431,28 @@ static void check_penalty_state(const torch::Tensor& table, const torch::Tensor&
               "penalty params: contiguous fp32 [slots, 4]");
 }
 
+static void check_guide_state(const torch::Tensor& mask, const torch::Tensor& trans, const torch::Tensor& tok_off,
+                              const torch::Tensor& blob, const torch::Tensor& eos, int64_t vocab) {
+  TORCH_CHECK(mask.is_cuda() && mask.scalar_type() == torch::kInt32 && mask.dim() == 2 && mask.is_contiguous() &&
+                  mask.size(1) % 4 == 0 && vocab > 0 && vocab <= mask.size(1) * 32,
+              "guide mask: contiguous int32 [rows, W], W a multiple of 4 words covering the vocabulary");
+  TORCH_CHECK(trans.is_cuda() && trans.scalar_type() == torch::kInt32 && trans.is_contiguous() && trans.dim() == 2 &&
+                  trans.size(0) == mask.size(0) && trans.size(1) == 256,
+              "guide trans: contiguous int32 [rows, 256]");
+  TORCH_CHECK(tok_off.is_cuda() && tok_off.scalar_type() == torch::kInt32 && tok_off.is_contiguous() &&
+                  tok_off.numel() == vocab + 1,
+              "guide tok_off: contiguous int32 [V + 1]");
+  TORCH_CHECK(blob.is_cuda() && blob.scalar_type() == torch::kUInt8 && blob.is_contiguous(), "guide blob: uint8");
+  TORCH_CHECK(eos.is_cuda() && eos.scalar_type() == torch::kInt32 && eos.is_contiguous(), "guide eos: int32");
+}
+
 void sample(torch::Tensor out, torch::Tensor logits, c10::optional<torch::Tensor> temps,
             c10::optional<torch::Tensor> top_k, c10::optional<torch::Tensor> top_p, c10::optional<torch::Tensor> rng,
             bool advance, c10::optional<torch::Tensor> pen_table, c10::optional<torch::Tensor> pen_params,
-            c10::optional<torch::Tensor> pen_slots, int64_t pen_vocab) {
+            c10::optional<torch::Tensor> pen_slots, int64_t pen_vocab, c10::optional<torch::Tensor> g_mask,
+            c10::optional<torch::Tensor> g_trans, c10::optional<torch::Tensor> g_state,
+            c10::optional<torch::Tensor> g_slots, c10::optional<torch::Tensor> g_tok_off,
+            c10::optional<torch::Tensor> g_blob, c10::optional<torch::Tensor> g_eos) {
   dev_i32(out, "out");
   TORCH_CHECK(logits.is_cuda() && logits.dim() == 2 && logits.stride(1) == 1, "logits [B, V]");
   const bool f32 = logits.scalar_type() == torch::kFloat32;
@@ -459,10 +485,53 @@ void sample(torch::Tensor out, torch::Tensor logits, c10::optional<torch::Tensor
     tstride = pen_table->size(1);
     nslots = (int)pen_table->size(0);
   }
-  check(k8sllm_sample_pen(out.data_ptr<int>(), logits.data_ptr(), f32 ? 1 : 0, B, logits.stride(0), V, t, k, p, r,
-                          pv.data_ptr<float>(), pi.data_ptr<int>(), advance ? 1 : 0, ps, tb, tstride, pp, nslots,
-                          cur()),
+  // guide state (ops.GuideState): mask [rows, W] / trans [rows, 256] / state [slots] / slots [B] int32,
+  // the vocabulary as CSR (tok_off int32 [V + 1], blob uint8) and the eos ids int32
+  const int *gs = nullptr, *gt = nullptr, *go = nullptr, *ge = nullptr;
+  int* gst = nullptr;
+  const void *gm = nullptr, *gb = nullptr;
+  int gW = 0, grows = 0, gnslots = 0, n_eos = 0;
+  if (g_mask) {
+    TORCH_CHECK(g_trans && g_state && g_slots && g_tok_off && g_blob && g_eos,
+                "sample: a guide needs trans, state, slots, tok_off, blob and eos");
+    check_guide_state(*g_mask, *g_trans, *g_tok_off, *g_blob, *g_eos, V);
+    dev_i32(*g_state, "guide state"); dev_i32(*g_slots, "guide slots");
+    TORCH_CHECK(g_state->is_contiguous() && g_state->numel() > 0, "sample: guide state [slots]");
+    TORCH_CHECK(g_slots->is_contiguous() && g_slots->numel() >= B, "sample: guide slots [B]");
+    gm = g_mask->data_ptr();
+    gW = (int)g_mask->size(1);
+    grows = (int)g_mask->size(0);
+    gt = g_trans->data_ptr<int>();
+    gst = g_state->data_ptr<int>();
+    gnslots = (int)g_state->numel();
+    gs = g_slots->data_ptr<int>();
+    go = g_tok_off->data_ptr<int>();
+    gb = g_blob->data_ptr();
+    n_eos = (int)g_eos->numel();
+    ge = n_eos ? g_eos->data_ptr<int>() : nullptr;
+  }
+  check(k8sllm_sample_guided(out.data_ptr<int>(), logits.data_ptr(), f32 ? 1 : 0, B, logits.stride(0), V, t, k, p, r,
+                             pv.data_ptr<float>(), pi.data_ptr<int>(), advance ? 1 : 0, ps, tb, tstride, pp, nslots,
+                             gs, gst, gnslots, gm, gW, gt, grows, go, gb, ge, n_eos, cur()),
         "sample");
+}
+
+// Fill the mask rows of one guide (ops.GuideState.load): rows int32 [n] (device) are its absolute rows
+void guide_mask_build(torch::Tensor mask, torch::Tensor trans, torch::Tensor accept, torch::Tensor popc,
+                      torch::Tensor rows, torch::Tensor tok_off, torch::Tensor blob, torch::Tensor eos) {
+  const int64_t V = tok_off.numel() - 1;
+  check_guide_state(mask, trans, tok_off, blob, eos, V);
+  dev_i32(popc, "popc"); dev_i32(rows, "rows");
+  TORCH_CHECK(accept.is_cuda() && accept.scalar_type() == torch::kUInt8 && accept.is_contiguous() &&
+                  accept.numel() == mask.size(0),
+              "guide accept: uint8 [rows]");
+  TORCH_CHECK(popc.is_contiguous() && popc.numel() == mask.size(0), "guide popc: int32 [rows]");
+  TORCH_CHECK(rows.is_contiguous() && rows.numel() <= mask.size(0), "guide rows: int32 [n]");
+  check(k8sllm_guide_mask_build(mask.data_ptr(), (int)mask.size(1), trans.data_ptr<int>(), accept.data_ptr(),
+                                popc.data_ptr<int>(), rows.data_ptr<int>(), (int)rows.numel(), (int)mask.size(0),
+                                tok_off.data_ptr<int>(), blob.data_ptr(), (int)V,
+                                eos.numel() ? eos.data_ptr<int>() : nullptr, (int)eos.numel(), cur()),
+        "guide_mask_build");
 }
 
 void penalty_reset(torch::Tensor table, torch::Tensor params, int64_t vocab, int64_t slot, torch::Tensor ids,
@@ -1241,7 +1310,11 @@ PYBIND11_MODULE(_k8sllm_ops, m) {
   m.def("embed_norm_partial", &embed_norm_partial);
   m.def("sample", &sample, py::arg("out"), py::arg("logits"), py::arg("temps"), py::arg("top_k"), py::arg("top_p"),
         py::arg("rng"), py::arg("advance") = false, py::arg("pen_table") = py::none(),
-        py::arg("pen_params") = py::none(), py::arg("pen_slots") = py::none(), py::arg("pen_vocab") = 0);
+        py::arg("pen_params") = py::none(), py::arg("pen_slots") = py::none(), py::arg("pen_vocab") = 0,
+        py::arg("g_mask") = py::none(), py::arg("g_trans") = py::none(), py::arg("g_state") = py::none(),
+        py::arg("g_slots") = py::none(), py::arg("g_tok_off") = py::none(), py::arg("g_blob") = py::none(),
+        py::arg("g_eos") = py::none());
+  m.def("guide_mask_build", &guide_mask_build);
   m.def("penalty_reset", &penalty_reset);
   m.def("token_logprobs", &token_logprobs);
   m.def("moe_route", &moe_route);

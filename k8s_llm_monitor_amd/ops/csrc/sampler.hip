@@ -27,6 +27,15 @@
 // pipeline above; the final kernel counts the drawn token in the row's slot, so a captured decode
 // step keeps its own state the way it advances the RNG counter.  Without a table the kernels
 // are the <T, false> instantiations: the plain loads.
+//
+// Guides (constrained decoding, guide.hip / ops.GuideState): a row with gslot[row] >= 0 whose slot
+// holds a state >= 0 is guided - it reads every logit through `ldp<T, PEN, true>`, where a token
+// whose bit in the state's mask row is clear reads as -inf (after penalisation, before everything
+// else: greedy, the partial path and the whole-row top-k / top-p path all see the same row).  The
+// 8 logits of a vector load take one mask byte.  The final kernel walks the drawn token's bytes
+// from the slot's state and stores the new state, so a captured decode step advances the guide
+// as it advances the RNG counter.  Without a guide state the kernels are the <T, PEN, false>
+// instantiations, whose loads are those above.
 #include <type_traits>
 
 #include "common.h"
@@ -63,18 +72,23 @@ __device__ __forceinline__ float penalise(float x, uint32_t e, const PenRow& q) 
 
 // Logit i of a row as the sampler reads it: plain (PEN = false), or penalised by the row's table
 // entries `cnt` (16-byte aligned) and parameters.
-template <typename T, bool PEN>
+// GD: a token whose bit in the mask row `gm` (16-byte aligned) is clear reads as -inf.
+template <typename T, bool PEN, bool GD>
 __device__ __forceinline__ float ldp(const T* __restrict__ x, const uint16_t* __restrict__ cnt, const PenRow& q,
-                                     int i) {
-  const float v = ld<T>(x, i);
-  if constexpr (PEN) return penalise(v, cnt[i], q);
+                                     const uint32_t* __restrict__ gm, int i) {
+  float v = ld<T>(x, i);
+  if constexpr (PEN) v = penalise(v, cnt[i], q);
+  if constexpr (GD) {
+    if (((gm[i >> 5] >> (i & 31)) & 1u) == 0u) v = -INFINITY;
+  }
   return v;
 }
 
-// 8 logits from a 16-byte aligned bf16 address (and their 8 table entries, one 16-byte load)
-template <bool PEN>
+// 8 logits from a 16-byte aligned bf16 address (and their 8 table entries, one 16-byte load; and
+// their 8 mask bits, one byte: i is a multiple of 8)
+template <bool PEN, bool GD>
 __device__ __forceinline__ void ldp8(const bf16_t* __restrict__ x, const uint16_t* __restrict__ cnt,
-                                     const PenRow& q, int i, float* v) {
+                                     const PenRow& q, const uint32_t* __restrict__ gm, int i, float* v) {
   unpack8(*reinterpret_cast<const uint4*>(x + i), v);
   if constexpr (PEN) {
     const uint4 e = *reinterpret_cast<const uint4*>(cnt + i);
@@ -84,6 +98,12 @@ __device__ __forceinline__ void ldp8(const bf16_t* __restrict__ x, const uint16_
       v[2 * j] = penalise(v[2 * j], w[j] & 0xffffu, q);
       v[2 * j + 1] = penalise(v[2 * j + 1], w[j] >> 16, q);
     }
+  }
+  if constexpr (GD) {
+    const uint32_t m = reinterpret_cast<const uint8_t*>(gm)[i >> 3];
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      if (((m >> j) & 1u) == 0u) v[j] = -INFINITY;
   }
 }
 
@@ -163,14 +183,15 @@ __device__ __forceinline__ float order_key_inv(uint32_t u) {
 }
 
 // Whole-row path for rows with top-k / top-p (one workgroup); returns the token on every thread.
-template <typename T, bool PEN>
-__device__ int sample_row_filtered(const T* __restrict__ x, const uint16_t* __restrict__ cnt, const PenRow& q, int V,
-                                   float temp, int k, float p, uint64_t key, float* sv, int* si) {
+template <typename T, bool PEN, bool GD>
+__device__ int sample_row_filtered(const T* __restrict__ x, const uint16_t* __restrict__ cnt, const PenRow& q,
+                                   const uint32_t* __restrict__ gm, int V, float temp, int k, float p, uint64_t key,
+                                   float* sv, int* si) {
   const int tid = threadIdx.x;
   const float itemp = 1.f / temp;
   float mx = -INFINITY, mn = INFINITY;
   for (int i = tid; i < V; i += kST) {
-    const float v = ldp<T, PEN>(x, cnt, q, i) * itemp;
+    const float v = ldp<T, PEN, GD>(x, cnt, q, gm, i) * itemp;
     mx = fmaxf(mx, v);
     mn = fminf(mn, v);
   }
@@ -184,7 +205,8 @@ __device__ int sample_row_filtered(const T* __restrict__ x, const uint16_t* __re
     for (int bit = 31; bit >= 0; --bit) {
       const uint32_t cand = t | (1u << bit);
       float c = 0.f;  // V < 2^24: an exact count
-      for (int i = tid; i < V; i += kST) c += (order_key(ldp<T, PEN>(x, cnt, q, i) * itemp) >= cand) ? 1.f : 0.f;
+      for (int i = tid; i < V; i += kST)
+        c += (order_key(ldp<T, PEN, GD>(x, cnt, q, gm, i) * itemp) >= cand) ? 1.f : 0.f;
       c = block_sum<kST>(c, sv);
       if (c >= (float)k) t = cand;
     }
@@ -194,7 +216,7 @@ __device__ int sample_row_filtered(const T* __restrict__ x, const uint16_t* __re
     // mass over the top-k survivors only (thr = -inf without top-k: the whole row)
     float z = 0.f;
     for (int i = tid; i < V; i += kST) {
-      const float v = ldp<T, PEN>(x, cnt, q, i) * itemp;
+      const float v = ldp<T, PEN, GD>(x, cnt, q, gm, i) * itemp;
       z += (v >= thr) ? __expf(v - mx) : 0.f;
     }
     z = block_sum<kST>(z, sv);
@@ -204,7 +226,7 @@ __device__ int sample_row_filtered(const T* __restrict__ x, const uint16_t* __re
       const float mid = 0.5f * (lo + hi);
       float s = 0.f;
       for (int i = tid; i < V; i += kST) {
-        const float v = ldp<T, PEN>(x, cnt, q, i) * itemp;
+        const float v = ldp<T, PEN, GD>(x, cnt, q, gm, i) * itemp;
         s += (v >= mid) ? __expf(v - mx) : 0.f;
       }
       s = block_sum<kST>(s, sv);
@@ -214,7 +236,7 @@ __device__ int sample_row_filtered(const T* __restrict__ x, const uint16_t* __re
   }
   ArgMax a{-INFINITY, 0x7fffffff};
   for (int i = tid; i < V; i += kST) {
-    const float v = ldp<T, PEN>(x, cnt, q, i) * itemp;
+    const float v = ldp<T, PEN, GD>(x, cnt, q, gm, i) * itemp;
     if (v >= thr) a = better(a, ArgMax{v + gumbel(key, i), i});
   }
   return block_argmax(a, sv, si).i;
@@ -225,16 +247,16 @@ __device__ __forceinline__ bool row_filtered(int V, float temp, int k, float p) 
 }
 
 // part `part` of one row -> pv/pi[part] (pv, pi: the row's P partials)
-template <typename T, bool PEN>
+template <typename T, bool PEN, bool GD>
 __device__ __forceinline__ void sample_partial_row(float* __restrict__ pv, int* __restrict__ pi,
                                                    const T* __restrict__ x, const uint16_t* __restrict__ cnt,
-                                                   const PenRow& q, long stride, int V, int P, int part, int row,
-                                                   float temp, int k, float p, const int64_t* __restrict__ rng,
-                                                   float* sv, int* si) {
+                                                   const PenRow& q, const uint32_t* __restrict__ gm, long stride,
+                                                   int V, int P, int part, int row, float temp, int k, float p,
+                                                   const int64_t* __restrict__ rng, float* sv, int* si) {
   const int tid = threadIdx.x;
   if (row_filtered(V, temp, k, p)) {
     if (part != 0) return;
-    const int tok = sample_row_filtered<T, PEN>(x, cnt, q, V, temp, k, p, row_key(rng, row), sv, si);
+    const int tok = sample_row_filtered<T, PEN, GD>(x, cnt, q, gm, V, temp, k, p, row_key(rng, row), sv, si);
     if (tid == 0) pi[0] = tok;
     return;
   }
@@ -253,14 +275,16 @@ __device__ __forceinline__ void sample_partial_row(float* __restrict__ pv, int* 
   if constexpr (std::is_same<T, bf16_t>::value) {
     for (int i = lo + tid * 8; i < hv; i += kST * 8) {
       float v[8];
-      ldp8<PEN>(x, cnt, q, i, v);
+      ldp8<PEN, GD>(x, cnt, q, gm, i, v);
 #pragma unroll
       for (int j = 0; j < 8; ++j)
         a = better(a, ArgMax{greedy ? v[j] : v[j] * itemp + gumbel(key, i + j), i + j});
     }
   }
-  for (int i = hv + tid; i < hi; i += kST)
-    a = better(a, ArgMax{greedy ? ldp<T, PEN>(x, cnt, q, i) : ldp<T, PEN>(x, cnt, q, i) * itemp + gumbel(key, i), i});
+  for (int i = hv + tid; i < hi; i += kST) {
+    const float v = ldp<T, PEN, GD>(x, cnt, q, gm, i);
+    a = better(a, ArgMax{greedy ? v : v * itemp + gumbel(key, i), i});
+  }
   a = block_argmax(a, sv, si);
   if (tid == 0) {
     pv[part] = a.v;
@@ -270,7 +294,9 @@ __device__ __forceinline__ void sample_partial_row(float* __restrict__ pv, int* 
 
 // grid (B, P): partial argmax of part `blockIdx.y` of row `blockIdx.x` -> pv/pi[row * P + part].
 // PEN: rows with a slot (pslot[row] in [0, nslots)) are penalised - a row-uniform branch.
-template <typename T, bool PEN>
+// GD: rows with a guide slot (gslot[row] in [0, gnslots)) whose state is a row of the guide arena
+// ([0, grows)) read their logits through that row of gmask [grows][gW] - row-uniform too.
+template <typename T, bool PEN, bool GD>
 __global__ __launch_bounds__(kST) void sample_partial_kernel(float* __restrict__ pv, int* __restrict__ pi,
                                                              const T* __restrict__ logits, long stride, int V, int P,
                                                              const float* __restrict__ temps,
@@ -279,12 +305,21 @@ __global__ __launch_bounds__(kST) void sample_partial_kernel(float* __restrict__
                                                              const int64_t* __restrict__ rng,
                                                              const int* __restrict__ pslot,
                                                              const uint16_t* __restrict__ table, long tstride,
-                                                             const float4* __restrict__ pparams, int nslots) {
+                                                             const float4* __restrict__ pparams, int nslots,
+                                                             const int* __restrict__ gslot,
+                                                             const int* __restrict__ gstate, int gnslots,
+                                                             const uint32_t* __restrict__ gmask, int gW, int grows) {
   __shared__ float sv[kST / 64];
   __shared__ int si[kST / 64];
   const int row = blockIdx.x, part = blockIdx.y;
   int slot = -1;
   if constexpr (PEN) slot = pslot[row];  // first, so the load is in flight with the row's parameters
+  const uint32_t* gm = nullptr;
+  if constexpr (GD) {
+    const int gs = gslot[row];
+    const int st = (unsigned)gs < (unsigned)gnslots ? gstate[gs] : -1;
+    if ((unsigned)st < (unsigned)grows) gm = gmask + (long)st * gW;
+  }
   const T* x = logits + (long)row * stride;
   const float temp = temps ? temps[row] : 0.f;
   const int k = top_k ? top_k[row] : 0;
@@ -294,12 +329,27 @@ __global__ __launch_bounds__(kST) void sample_partial_kernel(float* __restrict__
   if constexpr (PEN) {
     if (slot >= 0 && slot < nslots) {
       const float4 q = pparams[slot];
-      sample_partial_row<T, true>(pv, pi, x, table + (long)slot * tstride, PenRow{q.x, q.y, q.z, q.w}, stride, V, P,
-                                  part, row, temp, k, p, rng, sv, si);
+      if constexpr (GD) {
+        if (gm != nullptr) {
+          sample_partial_row<T, true, true>(pv, pi, x, table + (long)slot * tstride, PenRow{q.x, q.y, q.z, q.w}, gm,
+                                            stride, V, P, part, row, temp, k, p, rng, sv, si);
+          return;
+        }
+      }
+      sample_partial_row<T, true, false>(pv, pi, x, table + (long)slot * tstride, PenRow{q.x, q.y, q.z, q.w}, nullptr,
+                                         stride, V, P, part, row, temp, k, p, rng, sv, si);
       return;
     }
   }
-  sample_partial_row<T, false>(pv, pi, x, nullptr, PenRow{}, stride, V, P, part, row, temp, k, p, rng, sv, si);
+  if constexpr (GD) {
+    if (gm != nullptr) {
+      sample_partial_row<T, false, true>(pv, pi, x, nullptr, PenRow{}, gm, stride, V, P, part, row, temp, k, p, rng,
+                                         sv, si);
+      return;
+    }
+  }
+  sample_partial_row<T, false, false>(pv, pi, x, nullptr, PenRow{}, nullptr, stride, V, P, part, row, temp, k, p, rng,
+                                      sv, si);
 }
 
 // one thread per row: the best of the P partials (or part 0's answer for a filtered row)
@@ -310,13 +360,19 @@ __global__ __launch_bounds__(64) void sample_final_kernel(int* __restrict__ out,
                                                           const float* __restrict__ top_p,
                                                           int64_t* __restrict__ rng_advance,
                                                           const int* __restrict__ pslot,
-                                                          uint16_t* __restrict__ table, long tstride, int nslots) {
+                                                          uint16_t* __restrict__ table, long tstride, int nslots,
+                                                          const int* __restrict__ gslot, int* __restrict__ gstate,
+                                                          int gnslots, const int* __restrict__ gtrans, int grows,
+                                                          const int* __restrict__ tok_off,
+                                                          const uint8_t* __restrict__ blob,
+                                                          const int* __restrict__ eos_ids, int n_eos) {
   const int row = blockIdx.x * 64 + threadIdx.x;
   // the partial kernel has drawn this step's numbers: advance the counter for the next step here
   // (one lane, a vector store) instead of a separate `rng[1] += 1` launch after every sample
   if (rng_advance != nullptr && row == 0) rng_advance[1] = rng_advance[1] + 1;
   if (row >= B) return;
   const int slot = table != nullptr ? pslot[row] : -1;  // issued first: in flight while the partials are read
+  const int gs = gstate != nullptr ? gslot[row] : -1;
   const float temp = temps ? temps[row] : 0.f;
   const int k = top_k ? top_k[row] : 0;
   const float p = top_p ? top_p[row] : 1.f;
@@ -335,6 +391,17 @@ __global__ __launch_bounds__(64) void sample_final_kernel(int* __restrict__ out,
     uint16_t* e = table + (long)slot * tstride + tok;
     const uint32_t c = *e;
     if ((c & kPenCount) != kPenCount) *e = (uint16_t)(c + 1u);
+  }
+  // walk the drawn token's bytes from the row's guide state (live rows hold distinct slots); an
+  // eos token, a token outside [0, V), a token without bytes and a walk that would die leave it
+  if ((unsigned)gs < (unsigned)gnslots && (unsigned)tok < (unsigned)V) {
+    int st = gstate[gs];
+    if ((unsigned)st >= (unsigned)grows) return;
+    for (int e = 0; e < n_eos; ++e)
+      if (eos_ids[e] == tok) return;
+    const int b0 = tok_off[tok], b1 = tok_off[tok + 1];
+    for (int j = b0; j < b1 && (unsigned)st < (unsigned)grows; ++j) st = gtrans[(long)st * 256 + blob[j]];
+    if (b1 > b0 && (unsigned)st < (unsigned)grows) gstate[gs] = st;
   }
 }
 
@@ -384,32 +451,58 @@ extern "C" int k8sllm_sample_parts(long B, int V) {
 // pv/pi: workspace of at least B * k8sllm_sample_parts(B, V) entries.  Penalties: `table` (null =
 // none) [nslots][tstride] with tstride a multiple of 8 and a 16-byte aligned base, `pparams`
 // [nslots] x (rep, 1/rep, presence, frequency), `pslot` [B] (-1 = the row has no penalties).
-extern "C" int k8sllm_sample_pen(int* out, const void* logits, int is_fp32, long B, long stride, int V,
-                                 const float* temps, const int* top_k, const float* top_p, const int64_t* rng,
-                                 float* pv, int* pi, int advance, const int* pslot, void* table, long tstride,
-                                 const float* pparams, int nslots, hipStream_t s) {
+// Guides: `gmask` (null = none) [grows][gW] with gW a multiple of 4 words covering V and a 16-byte
+// aligned base, `gtrans` [grows][256] absolute rows, `gstate` [gnslots] (-1 = unguided), `gslot` [B]
+// (-1 = the row has no guide), the vocabulary as CSR (`tok_off` [V + 1], `blob`) and the eos ids.
+extern "C" int k8sllm_sample_guided(int* out, const void* logits, int is_fp32, long B, long stride, int V,
+                                    const float* temps, const int* top_k, const float* top_p, const int64_t* rng,
+                                    float* pv, int* pi, int advance, const int* pslot, void* table, long tstride,
+                                    const float* pparams, int nslots, const int* gslot, int* gstate, int gnslots,
+                                    const void* gmask, int gW, const int* gtrans, int grows, const int* tok_off,
+                                    const void* blob, const int* eos_ids, int n_eos, hipStream_t s) {
   if (B <= 0) return 0;
   if (table != nullptr && (pslot == nullptr || pparams == nullptr || tstride < V || (tstride & 7) != 0 ||
                            (reinterpret_cast<uintptr_t>(table) & 15) != 0 ||
                            (reinterpret_cast<uintptr_t>(pparams) & 15) != 0))
     return (int)hipErrorInvalidValue;
+  if (gmask != nullptr && (gslot == nullptr || gstate == nullptr || gtrans == nullptr || tok_off == nullptr ||
+                           blob == nullptr || gnslots <= 0 || grows <= 0 || (gW & 3) != 0 || (long)gW * 32 < V ||
+                           n_eos < 0 || (n_eos > 0 && eos_ids == nullptr) ||
+                           (reinterpret_cast<uintptr_t>(gmask) & 15) != 0))
+    return (int)hipErrorInvalidValue;
   const int P = k8sllm_sample_parts(B, V);
   dim3 grid((unsigned)B, P);
   uint16_t* tb = (uint16_t*)table;
   const float4* pp = (const float4*)pparams;
-#define K8SLLM_SAMPLE_PARTIAL(T, PEN)                                                                              \
-  hipLaunchKernelGGL((sample_partial_kernel<T, PEN>), grid, dim3(kST), 0, s, pv, pi, (const T*)logits, stride, V, P, \
-                     temps, top_k, top_p, rng, pslot, tb, tstride, pp, nslots)
-  if (is_fp32) {
-    if (tb) K8SLLM_SAMPLE_PARTIAL(float, true); else K8SLLM_SAMPLE_PARTIAL(float, false);
-  } else {
-    if (tb) K8SLLM_SAMPLE_PARTIAL(bf16_t, true); else K8SLLM_SAMPLE_PARTIAL(bf16_t, false);
-  }
+  const uint32_t* gm = (const uint32_t*)gmask;
+#define K8SLLM_SAMPLE_PARTIAL(T, PEN, GD)                                                                       \
+  hipLaunchKernelGGL((sample_partial_kernel<T, PEN, GD>), grid, dim3(kST), 0, s, pv, pi, (const T*)logits, stride, V, \
+                     P, temps, top_k, top_p, rng, pslot, tb, tstride, pp, nslots, gslot, gstate, gnslots, gm, gW, grows)
+#define K8SLLM_SAMPLE_T(T)                                                                        \
+  do {                                                                                            \
+    if (gm) {                                                                                     \
+      if (tb) K8SLLM_SAMPLE_PARTIAL(T, true, true); else K8SLLM_SAMPLE_PARTIAL(T, false, true);   \
+    } else {                                                                                      \
+      if (tb) K8SLLM_SAMPLE_PARTIAL(T, true, false); else K8SLLM_SAMPLE_PARTIAL(T, false, false); \
+    }                                                                                             \
+  } while (0)
+  if (is_fp32) K8SLLM_SAMPLE_T(float); else K8SLLM_SAMPLE_T(bf16_t);
+#undef K8SLLM_SAMPLE_T
 #undef K8SLLM_SAMPLE_PARTIAL
   hipLaunchKernelGGL(sample_final_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, out, pv, pi, (int)B, V, P,
                      temps, top_k, top_p, advance && rng ? const_cast<int64_t*>(rng) : nullptr, pslot, tb, tstride,
-                     nslots);
+                     nslots, gslot, gm ? gstate : nullptr, gnslots, gtrans, grows, tok_off, (const uint8_t*)blob,
+                     eos_ids, n_eos);
   return (int)hipGetLastError();
+}
+
+extern "C" int k8sllm_sample_pen(int* out, const void* logits, int is_fp32, long B, long stride, int V,
+                                 const float* temps, const int* top_k, const float* top_p, const int64_t* rng,
+                                 float* pv, int* pi, int advance, const int* pslot, void* table, long tstride,
+                                 const float* pparams, int nslots, hipStream_t s) {
+  return k8sllm_sample_guided(out, logits, is_fp32, B, stride, V, temps, top_k, top_p, rng, pv, pi, advance, pslot,
+                              table, tstride, pparams, nslots, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, nullptr,
+                              nullptr, nullptr, 0, s);
 }
 
 extern "C" int k8sllm_sample(int* out, const void* logits, int is_fp32, long B, long stride, int V,

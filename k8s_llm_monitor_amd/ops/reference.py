@@ -314,6 +314,45 @@ def token_logprobs(logits_row: torch.Tensor, token: int, n: int):
     return lp, ids, lps
 
 
+def guide_advance(trans, state: int, token_bytes: bytes) -> int:
+    """The DFA state after walking ``token_bytes`` from ``state`` over ``trans`` ``[n, 256]``
+    (-1 = dead); -1 as soon as a transition is dead."""
+    s = int(state)
+    for b in token_bytes:
+        if s < 0:
+            return -1
+        s = int(trans[s][b])
+    return s
+
+
+def guide_mask(trans, accept, vocab_bytes, eos_ids) -> torch.Tensor:
+    """bool ``[n, V]``: the tokens a guided row in DFA state ``s`` may draw.
+
+    Bit ``(s, t)`` is set iff token ``t`` has at least one byte and walking its bytes from ``s``
+    never hits -1; for ``t`` in ``eos_ids`` it is set iff ``accept[s]``.  Tokens without bytes are
+    never allowed.  All states walk a token position together (one gather per byte position)."""
+    import numpy as np
+
+    tr = np.asarray(trans).astype(np.int64)
+    n, V = tr.shape[0], len(vocab_bytes)
+    ext = np.concatenate([np.where(tr < 0, n, tr), np.full((1, 256), n, dtype=np.int64)])  # row n: dead
+    lens = np.array([len(b) for b in vocab_bytes], dtype=np.int64)
+    width = int(lens.max()) if V else 0
+    tb = np.zeros((V, max(width, 1)), dtype=np.int64)
+    for t, b in enumerate(vocab_bytes):
+        tb[t, : len(b)] = list(b)
+    cur = np.repeat(np.arange(n, dtype=np.int64)[:, None], V, axis=1)
+    for j in range(width):
+        live = np.flatnonzero(lens > j)
+        cur[:, live] = ext[cur[:, live], tb[live, j][None, :]]
+    ok = (cur < n) & (lens > 0)[None, :]
+    acc = np.asarray(accept).astype(bool)
+    for t in eos_ids:
+        if 0 <= int(t) < V:
+            ok[:, int(t)] = acc
+    return torch.from_numpy(ok)
+
+
 def moe_route(logits: torch.Tensor, k: int, renorm: bool):
     p = torch.softmax(logits.float(), dim=-1)
     w, ids = torch.topk(p, k, dim=-1)

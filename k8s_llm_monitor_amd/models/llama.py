@@ -199,6 +199,12 @@ class CausalLM:
     # "mxfp4", where DEC_WEIGHTS = "mxfp4": the same over the mxfp4 codes and block scales
     # (gemm_tile.hip F4) - prefill and decode read one tensor, a quarter of the bf16 bytes.
     PREFILL_WEIGHTS = "bf16"
+    # The last layer of a dense TP = 1 prefill runs o, gate_up and down on the rows of
+    # ``meta.logits_idx`` only (its qkv, KV write and attention still see every row): the layers
+    # above need every row of the residual stream, the final norm and the head only those.  Every
+    # GEMM of that tail is one whose rows do not depend on each other (the tile kernel, or the CPU
+    # reference), so the logits are bit-identical to the full-row form's.  False: the full-row form (A/B).
+    LAST_LAYER_ROWS = True
 
     def __init__(self, cfg: ModelConfig, device: torch.device | str = "cpu", dtype=torch.bfloat16, seed: int = 0,
                  pstate: Optional[ParallelState] = None, init_std: float = 0.02, init: str = "random",
@@ -749,6 +755,8 @@ class CausalLM:
             n = len(self.layers)
             for i, L in enumerate(self.layers):
                 kv = kv_caches[i] if kv_caches is not None else None
+                if i + 1 == n and self._last_rows_ok(L, h, meta):
+                    return self._logits(self._last_rows(L, self._attn_core(L, x, meta, kv), residual, meta))
                 y = self._attention(L, x, meta, kv)
                 x = ops.fused_add_rms_norm(y, residual, L["mlp_norm"], c.norm_eps)
                 y = self._mlp(L, x, meta)
@@ -846,6 +854,8 @@ class CausalLM:
         for i, L in enumerate(self.layers):
             kv = kv_caches[i] if kv_caches is not None else None
             o = self._attn_core(L, x, meta, kv, rowscale=(ss, eps) if ss is not None else None)
+            if i + 1 == n and self.LAST_LAYER_ROWS and meta.logits_idx is not None:
+                return self._last_rows_fused(L, o, residual, meta.logits_idx)
             x, ss = ops.gemm_tile_resid(o, L["wo"], residual, L["mlp_norm"], wscale=self._wsc(L, "wo"))
             act = ops.prefill_linear(x, L["w13"], swiglu=self._swg, rowscale=(ss, eps), wscale=self._wsc(L, "w13"))
             if i + 1 < n:
@@ -859,12 +869,58 @@ class CausalLM:
                 x = ops.fused_add_rms_norm(y.contiguous(), residual, self.final_norm, eps)
         return x
 
+    def _last_rows_fused(self, L: dict, o: torch.Tensor, residual: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
+        """The last layer of ``_prefill_fused_norm`` from the attention output ``o`` on, over the
+        logit rows ``idx`` alone (LAST_LAYER_ROWS): the full-row form's tile GEMMs - o + residual,
+        gate_up + SwiGLU with the row scale, down - launched on the gathered rows (the tile kernel
+        and its epilogues treat every row alone: the same bits), then the final norm.  The GEMMs are
+        called as tile GEMMs whatever the row count: fused_norm_ok routed the whole step there.
+        No rows (a chunk that ends inside every prompt): nothing to compute."""
+        eps = self.cfg.norm_eps
+        if idx.numel() == 0:
+            return residual.new_empty(0, residual.shape[1])
+        o, res = o[idx].contiguous(), residual[idx].contiguous()
+        x, ss = ops.gemm_tile_resid(o, L["wo"], res, L["mlp_norm"], wscale=self._wsc(L, "wo"))
+        act = ops.gemm_tile(x, L["w13"], swiglu=self._swg, algo=ops.TILE_ALGO, rowscale=(ss, eps),
+                            wscale=self._wsc(L, "w13"))
+        y = ops.gemm_tile(act, L["w2"], algo=ops.TILE_ALGO, wscale=self._wsc(L, "w2"))
+        return ops.fused_add_rms_norm(y, res, self.final_norm, eps)
+
+    def _last_rows_ok(self, L: dict, h: torch.Tensor, meta: AttnMeta) -> bool:
+        """``forward``'s layer loop may run its last layer's tail on the logit rows alone
+        (``_last_rows``): a dense Llama at TP = 1 without biases whose o / gate_up / down take a GEMM
+        with row-independent rows at any row count - the CPU forms, or on the GPU the tile kernel
+        over fragment-packed (or encoded) weights, which prefill_linear sends there whatever the row
+        count.  Row-major weights on the GPU go to hipBLASLt below TILE_MIN_M rows, whose choice of
+        kernel (and so its rounding) depends on the row count: those keep the full-row form."""
+        c = self.cfg
+        if not self.LAST_LAYER_ROWS or meta.logits_idx is None or not meta.is_prefill:
+            return False
+        if c.arch != "llama" or c.is_moe or self.tp != 1 or "bo" in L:
+            return False
+        return not h.is_cuda or (self._w13_il and all(L[k].dim() == 4 for k in ("wo", "w13", "w2")))
+
+    def _last_rows(self, L: dict, o: torch.Tensor, residual: torch.Tensor, meta: AttnMeta) -> torch.Tensor:
+        """The last layer of ``forward``'s loop from the attention output ``o`` on, over the logit
+        rows alone (``_last_rows_ok``), and the final norm: ``_attention``'s and ``_mlp``'s own calls
+        on the gathered rows."""
+        eps, idx = self.cfg.norm_eps, meta.logits_idx
+        if idx.numel() == 0:
+            return residual.new_empty(0, residual.shape[1])
+        o, res = o[idx].contiguous(), residual[idx].contiguous()
+        y = ops.prefill_linear(o, L["wo"], wscale=self._wsc(L, "wo"))
+        x = ops.fused_add_rms_norm(y, res, L["mlp_norm"], eps)
+        y = self._mlp(L, x, meta)
+        return ops.fused_add_rms_norm(y.contiguous(), res, self.final_norm, eps)
+
     def _logits(self, x: torch.Tensor, rows: Optional[int] = None) -> torch.Tensor:
         """LM head (+ the TP all-gather of the vocab shards).  ``x``: the final-normed rows,
         row-major, or fragment-packed with ``rows`` valid rows (decode).  With a decode copy of the
         head (``lm_head_d``) up to dec_rows_max() rows at a time (128 for dense TP=1 models, else
         64) go through gemm_decode.hip, one stream of the head per launch - the decode step's and a
         prefill step's last-token logits alike; hipBLASLt otherwise."""
+        if x.dim() == 2 and x.shape[0] == 0:  # a step without logit rows (a chunk that ends inside every prompt)
+            return x.new_empty(0, self.cfg.vocab_size)
         hd, hq = self.lm_head_d, self.lm_head_q
         f8_only = hd is None and hq is not None  # the codes are the head's only decode form (_release_bf16)
         nv = (hd if hd is not None else hq).shape[0] * 16 if hd is not None or hq is not None else 0

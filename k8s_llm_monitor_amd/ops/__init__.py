@@ -67,7 +67,8 @@ def fused_add_rms_norm(x: torch.Tensor, residual: torch.Tensor, w: torch.Tensor,
         return out.copy_(y) if out is not None else y
     if out is None:
         out = torch.empty(x.shape, dtype=x.dtype, device=x.device)
-    native().fused_add_rms_norm(out, x, residual, w, eps)
+    if x.numel():  # no rows (a prefill step without logit rows): nothing to launch
+        native().fused_add_rms_norm(out, x, residual, w, eps)
     return out
 
 
@@ -1782,6 +1783,17 @@ TILE_FORMS: tuple = (
 ) + tuple((fmt, epi, 0, rs, 0) for fmt in (1, 2) for epi, rs in (
     (TILE_EPI_BF16, 0), (TILE_EPI_SWIGLU8, 0), (TILE_EPI_SWIGLU8, 1), (TILE_EPI_ROPE, 0), (TILE_EPI_ROPE, 1),
     (TILE_EPI_RESID, 0)))
+# kTilePersist, beside the table: the dense bf16 schedule-1 rows (epi, row scale) that are also
+# compiled as a persistent kernel - a grid of min(tiles, CUs) workgroups walking the tiles, the next
+# tile's ring fill under the epilogue (csrc/gemm_tile.hip PERSIST) - and whether tile_plan routes a
+# launch with more tiles than CUs there by itself (profiles/r23/README.md); native().gemm_tile_persist_forms()
+# reports the header's rows (tests/test_tile_persist_cpu.py compares the two).
+TILE_PERSIST_FORMS: tuple = ((TILE_EPI_ROPE, 1, 1), (TILE_EPI_RESID, 0, 1), (TILE_EPI_SWIGLU8, 1, 1))
+# A/B only (module constants, not environment switches): TILE_PERSIST -1 = as the table routes, 1 = the
+# persistent form wherever it is compiled, 0 = nowhere; TILE_PERSIST_CUS: the persistent grid's size, 0 =
+# the device's CU count (tests cap it at 3 so that every workgroup crosses a seam on small shapes).
+TILE_PERSIST = -1
+TILE_PERSIST_CUS = 0
 _TILE_EPI_NAMES = ("plain", "swiglu=1 (per-128 pairing)", "RoPE", "residual", "swiglu=8")
 # the table by key (every prefill GEMM asks it): row -> has schedule 0; (format, epilogue) pairs; grouped formats
 _TILE_SCH0 = {f[:4]: f[4] for f in TILE_FORMS}
@@ -1904,7 +1916,8 @@ def _gemm_tile(x: torch.Tensor, w: torch.Tensor, wscale: Optional[torch.Tensor],
                            offsets=offsets.contiguous() if grouped else None,
                            swiglu=8 if epi == TILE_EPI_SWIGLU8 else int(swg), algo=algo, rope_pos=pos, rope_cs=cs,
                            rope_heads=heads, rs_part=rs_part, rs_eps=rs_eps, resid=resid, hw=hw,
-                           norm_w=norm_w.contiguous() if norm_w is not None else None, ss_out=ss, wscale=wscale)
+                           norm_w=norm_w.contiguous() if norm_w is not None else None, ss_out=ss, wscale=wscale,
+                           persist=TILE_PERSIST, cus=TILE_PERSIST_CUS)
         return out if resid is None else (hw, ss)
     if quant:  # the dequantised values: exactly the bf16 encoding's
         w = dequantize_codes(w, wscale, x.dtype)

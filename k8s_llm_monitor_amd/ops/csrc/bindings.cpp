@@ -69,8 +69,9 @@ int k8sllm_gather_rows(void* out, const void* x, const int* idx, long n, int d, 
 int k8sllm_gemm_tile(const void* X, const void* W, void* Y, int M, int N, int K, const int* offsets, int E, long w_es,
                      int epi, int algo, const int* rope_pos, const float* rope_cs, int rope_heads,
                      const float* rs_part, int rs_np, float rs_eps, void* resid, void* hw, const void* norm_w,
-                     float* ss_out, int wpk, const void* wscale, int wfmt, hipStream_t s);
+                     float* ss_out, int wpk, const void* wscale, int wfmt, int persist, int cus, hipStream_t s);
 int k8sllm_gemm_tile_forms(int* out, int cap);
+int k8sllm_gemm_tile_persist_forms(int* out, int cap);
 int k8sllm_moe_grouped_gemm(const void* X, const void* W, void* Y, const int* offsets, int E, long rows, int N, int K,
                             long w_es, int epi, hipStream_t s);
 int k8sllm_gemm_skinny(const void* A, long lda, const void* Wp, float* partial, void* Y, long ldy, int M, int N, int K,
@@ -639,14 +640,17 @@ void moe_grouped_gemm(torch::Tensor y, torch::Tensor x, torch::Tensor w, torch::
 // epilogue; rs_part: the deferred RMSNorm row scale; resid / hw / norm_w / ss_out: the residual epilogue.
 // Which combinations are compiled and every limit on M, N, K, E and the schedule: tile_plan
 // (gemm_tile_forms.h).  Here: the tensors' layouts, dtypes, devices and sizes.
+// persist / cus (A/B runs; tile_plan): -1 = the persistent form where the table routes the launch,
+// 1 = wherever it is compiled, 0 = nowhere; cus: the persistent grid's size, 0 = the device's CUs.
 void gemm_tile(torch::Tensor y, torch::Tensor x, torch::Tensor w, c10::optional<torch::Tensor> offsets, int64_t swiglu,
                int64_t algo, c10::optional<torch::Tensor> rope_pos, c10::optional<torch::Tensor> rope_cs,
                int64_t rope_heads, c10::optional<torch::Tensor> rs_part, double rs_eps,
                c10::optional<torch::Tensor> resid, c10::optional<torch::Tensor> hw,
                c10::optional<torch::Tensor> norm_w, c10::optional<torch::Tensor> ss_out,
-               c10::optional<torch::Tensor> wscale) {
+               c10::optional<torch::Tensor> wscale, int64_t persist, int64_t cus) {
   using namespace k8sllm;
   dev_bf16(y, "y"); dev_bf16(x, "x");
+  TORCH_CHECK(persist >= -1 && persist <= 1 && cus >= 0 && cus <= (1 << 20), "gemm_tile: persist -1, 0 or 1; cus >= 0");
   const int fmt = w.scalar_type() == torch::kFloat8_e4m3fn ? TILE_W_F8 : w.scalar_type() == torch::kUInt8 ? TILE_W_F4 : TILE_W_BF16;
   const bool quant = fmt != TILE_W_BF16;
   const std::string whats = std::string("gemm_tile (") + (fmt == TILE_W_F4 ? "mxfp4)" : fmt == TILE_W_F8 ? "fp8)" : "bf16)");
@@ -739,18 +743,32 @@ void gemm_tile(torch::Tensor y, torch::Tensor x, torch::Tensor w, c10::optional<
                          rs ? rs_part->data_ptr<float>() : nullptr, rs_np, (float)rs_eps,
                          rsd ? resid->data_ptr() : nullptr, rsd ? hw->data_ptr() : nullptr,
                          rsd ? norm_w->data_ptr() : nullptr, rsd ? ss_out->data_ptr<float>() : nullptr, wpk ? 1 : 0, sp,
-                         fmt, cur()),
+                         fmt, (int)persist, (int)cus, cur()),
         what);
 }
 
 // tile_plan (gemm_tile_forms.h), what a launch with these arguments does: (err, schedule, row of
 // gemm_tile_forms(), m-tiles, n-tiles, workgroups).  experts 0: a dense launch; rs_np 0: no row
-// scale.  No launch.
+// scale.  ext: two more - (.., the row of gemm_tile_persist_forms() that runs or -1 for the one-tile
+// form, the grid) - for a device of `cus` CUs and the A/B override `persist` (-1: as the table routes).
+// No launch.
 std::vector<int64_t> gemm_tile_plan(int64_t fmt, int64_t M, int64_t N, int64_t K, int64_t epi, int64_t sch, int64_t experts,
-                                    int64_t rs_np) {
-  const k8sllm::TilePlan p =
-      k8sllm::tile_plan((int)fmt, (int)M, (int)N, (int)K, (int)epi, (int)sch, (int)experts, (int)rs_np);
+                                    int64_t rs_np, int64_t persist, int64_t cus, bool ext) {
+  const k8sllm::TilePlan p = k8sllm::tile_plan((int)fmt, (int)M, (int)N, (int)K, (int)epi, (int)sch, (int)experts,
+                                               (int)rs_np, (int)persist, (int)cus);
+  if (ext) return {p.err, p.sch, p.form, p.n_mt, p.n_nt, p.nwg, p.persist, p.grid};
   return {p.err, p.sch, p.form, p.n_mt, p.n_nt, p.nwg};
+}
+
+// The persistent instantiations of gemm_tile (kTilePersist): (epi, row scale, routed there by default) per row.
+std::vector<std::vector<int64_t>> gemm_tile_persist_forms() {
+  std::vector<int> v(3 * k8sllm::kTileNPersist);
+  const int n = k8sllm_gemm_tile_persist_forms(v.data(), k8sllm::kTileNPersist);
+  TORCH_CHECK(n == k8sllm::kTileNPersist, "gemm_tile_persist_forms: ", n, " rows compiled, ", k8sllm::kTileNPersist,
+              " in the header");
+  std::vector<std::vector<int64_t>> rows;
+  for (int i = 0; i < n; ++i) rows.emplace_back(v.begin() + 3 * i, v.begin() + 3 * i + 3);
+  return rows;
 }
 
 // The compiled forms of gemm_tile (kTileForms): (weight format, epi, grouped, row scale, also at
@@ -1294,9 +1312,12 @@ PYBIND11_MODULE(_k8sllm_ops, m) {
         py::arg("algo") = 1, py::arg("rope_pos") = py::none(), py::arg("rope_cs") = py::none(),
         py::arg("rope_heads") = 0, py::arg("rs_part") = py::none(), py::arg("rs_eps") = 1e-5,
         py::arg("resid") = py::none(), py::arg("hw") = py::none(), py::arg("norm_w") = py::none(),
-        py::arg("ss_out") = py::none(), py::arg("wscale") = py::none());
-  m.def("gemm_tile_plan", &gemm_tile_plan);
+        py::arg("ss_out") = py::none(), py::arg("wscale") = py::none(), py::arg("persist") = -1, py::arg("cus") = 0);
+  m.def("gemm_tile_plan", &gemm_tile_plan, py::arg("fmt"), py::arg("M"), py::arg("N"), py::arg("K"), py::arg("epi"),
+        py::arg("sch"), py::arg("experts"), py::arg("rs_np"), py::arg("persist") = -1,
+        py::arg("cus") = (int64_t)k8sllm::kTileCUs, py::arg("ext") = false);
   m.def("gemm_tile_forms", &gemm_tile_forms);
+  m.def("gemm_tile_persist_forms", &gemm_tile_persist_forms);
   m.def("gelu_tanh", &gelu_tanh);
   m.def("embedding", &embedding);
   m.def("resolve_ids", &resolve_ids);

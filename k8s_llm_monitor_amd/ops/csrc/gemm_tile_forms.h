@@ -56,6 +56,29 @@ constexpr TileForm kTileForms[] = {
 };
 constexpr int kTileNForms = sizeof(kTileForms) / sizeof(kTileForms[0]);
 
+// The persistent instantiations, beside the table: the dense bf16 schedule-1 rows (epi, rs) that are
+// ALSO compiled with PERSIST (a grid of min(tiles, CUs) workgroups that walk the tiles, the next
+// tile's ring fill overlapping the epilogue: gemm_tile.hip) - the launches of the fused-norm prefill
+// layer.  on: tile_plan routes the row there by itself (measured faster: profiles/r23/README.md);
+// 0: only when forced.  ops.TILE_PERSIST_FORMS is the Python copy (tests/test_tile_persist_cpu.py).
+struct TilePersistForm {
+  int epi, rs, on;
+};
+constexpr TilePersistForm kTilePersist[] = {
+    {TILE_EPI_ROPE, 1, 1},     // qkv: RoPE + row scale
+    {TILE_EPI_RESID, 0, 1},    // o, down: residual add + the next norm's operands
+    {TILE_EPI_SWIGLU8, 1, 1},  // gate_up: SwiGLU (per-16 pairing) + row scale
+};
+constexpr int kTileNPersist = sizeof(kTilePersist) / sizeof(kTilePersist[0]);
+constexpr int kTileCUs = 256;  // MI355X; the launcher plans with the device's own count
+
+// The row of kTilePersist that is (epi, rs), or -1.
+constexpr int tile_persist_index(int epi, bool rs) {
+  for (int i = 0; i < kTileNPersist; ++i)
+    if (kTilePersist[i].epi == epi && (kTilePersist[i].rs != 0) == rs) return i;
+  return -1;
+}
+
 constexpr int kTileMaxExperts = 256;  // grouped: the kernel walks the offsets of every expert per workgroup
 constexpr int kTileSch1MinK = 192;    // schedule 1's peeled ring tail needs three k-tiles
 constexpr int kTileRsMaxNp = 64;      // row scale: the kernel loads a fixed 16 x 4 partial sums per row
@@ -86,7 +109,9 @@ struct TilePlan {
   int sch;         // the schedule that runs (0 or 1)
   int form;        // the row of kTileForms
   int n_mt, n_nt;  // m-tiles (grouped: ceil(M / 256) + E, the bound over any split of the rows), n-tiles
-  int nwg;         // workgroups: n_mt * n_nt
+  int nwg;         // tiles: n_mt * n_nt
+  int persist;     // the row of kTilePersist that runs, or -1: the one-tile form, one workgroup per tile
+  int grid;        // workgroups launched: nwg, or min(nwg, CUs) for a persistent launch
 };
 
 // THE plan of k8sllm_gemm_tile: the launcher, the binding and the CPU tests (native().gemm_tile_plan
@@ -111,8 +136,15 @@ struct TilePlan {
 //
 // The order of the checks decides the code of a doubly-wrong request: -4 (a quantised W asked for
 // a form its format does not have) before -1 before -3 before -2.
-constexpr TilePlan tile_plan(int fmt, int M, int N, int K, int epi, int sch, int E, int rs_np) {
-  TilePlan p{-4, 0, -1, 0, 0, 0};
+//
+// Persistent or not: a dense bf16 schedule-1 launch whose (epi, rs) is a row of kTilePersist and that
+// has more tiles than the device has CUs (`cus`; up to one tile per CU the one-tile form is the same
+// launch) runs persistent where the row is `on`.  `persist` overrides the rows' `on` for A/B runs: 1
+// every such launch, 0 none, -1 (the default) as the table says.  Everything else - grouped, fp8 /
+// mxfp4, schedule 0, rows not in the table - is the one-tile form whatever is asked.
+constexpr TilePlan tile_plan(int fmt, int M, int N, int K, int epi, int sch, int E, int rs_np, int persist = -1,
+                             int cus = kTileCUs) {
+  TilePlan p{-4, 0, -1, 0, 0, 0, -1, 0};
   if (fmt < 0 || fmt >= kTileNFmts) return p;
   if (M <= 0) return p.err = 0, p;
   const TileFmt& f = kTileFmts[fmt];
@@ -137,8 +169,13 @@ constexpr TilePlan tile_plan(int fmt, int M, int N, int K, int epi, int sch, int
   p.n_mt = M / 256 + (M % 256 != 0) + E;
   p.n_nt = N / 256 + (N % 256 != 0);
   if ((long)p.n_mt * p.n_nt > (1L << 30)) return p.err = -2, p;
-  p.nwg = p.n_mt * p.n_nt;
+  p.nwg = p.grid = p.n_mt * p.n_nt;
   p.err = 0;
+  const int pi = fmt == TILE_W_BF16 && !grouped && sch == 1 ? tile_persist_index(epi, rs) : -1;
+  if (pi >= 0 && cus > 0 && p.nwg > cus && (persist < 0 ? kTilePersist[pi].on != 0 : persist != 0)) {
+    p.persist = pi;
+    p.grid = cus;
+  }
   return p;
 }
 

@@ -3,6 +3,11 @@ t = fixed + per_k * K.  `fixed` is the per-launch + per-tile prologue / epilogue
 first DMA burst, the store tail), `per_k` the main loop.  Random operands, hipGraph replay.
 
     python tools/gemm_k_sweep.py [--m 16384] [--n 4096] [--ks 512,1024,2048,4096,8192]
+
+``--prod``: the same fit for the four launches of the fused-norm prefill layer at the Llama-3-8B
+shapes, each with its production epilogue over fragment-packed weights (PROD below): the fixed cost
+per tile round and the main-loop rate of qkv + RoPE + row scale, o + residual, gate_up + SwiGLU8 +
+row scale and down + residual (profiles/r23/README.md).
 """
 from __future__ import annotations
 
@@ -26,8 +31,58 @@ def fit(ks: list[int], ts: list[float]) -> tuple[float, float]:
     return mt - b * mk, b
 
 
+# --prod: the four launches of the fused-norm prefill layer (Llama-3-8B), each over its own K sweep
+# around the production depth: (name, N, ks).  rs_np = K / 128 <= 64 bounds the row-scaled ones.
+PROD = (("qkv+rope_rs", 6144, (1024, 2048, 4096, 8192)), ("o_resid", 4096, (1024, 2048, 4096, 8192)),
+        ("gate_up+swiglu8_rs", 28672, (1024, 2048, 4096, 8192)), ("down_resid", 4096, (3584, 7168, 14336)))
+
+
+def prod_launch(name: str, M: int, N: int, K: int, dev: str = "cuda"):
+    """One production launch over fragment-packed random weights, as a timeit callable."""
+    from k8s_llm_monitor_amd.ops import reference as ref
+
+    x = torch.randn(M, K, device=dev, dtype=torch.bfloat16)
+    w = torch.randn(N, K, device=dev, dtype=torch.bfloat16) * 0.02
+    ssq = (torch.rand(M, K // 128, device=dev) * 128 + 64).contiguous()
+    if name.startswith("qkv"):
+        cs = ref.rope_cos_sin(8192, 128, 500000.0).to(dev).float().contiguous()
+        pos = (torch.arange(M, device=dev) % 8192).to(torch.int32)
+        y, wp = torch.empty(M, N, device=dev, dtype=torch.bfloat16), ops.pack_skinny(w)
+        return lambda i: ops.gemm_tile(x, wp, out=y, algo=1, rope=(pos, cs, N // 128 - 8), rowscale=(ssq, 1e-5))
+    if name.startswith("gate_up"):
+        y, wp = torch.empty(M, N // 2, device=dev, dtype=torch.bfloat16), ops.pack_skinny(ops.interleave_gate_up8(w))
+        return lambda i: ops.gemm_tile(x, wp, swiglu=8, out=y, algo=1, rowscale=(ssq, 1e-5))
+    resid = torch.randn(M, N, device=dev, dtype=torch.bfloat16)
+    hw, nw, wp = torch.empty_like(resid), torch.ones(N, device=dev, dtype=torch.bfloat16), ops.pack_skinny(w)
+    ss = torch.empty(M, N // 128, device=dev, dtype=torch.float32)
+    return lambda i: ops.gemm_tile_resid(x, wp, resid, nw, hw=hw, ss=ss)
+
+
+def prod(a) -> None:
+    for name, N, ks in PROD:
+        if a.only and name not in a.only.split(","):
+            continue
+        fns = {K: prod_launch(name, a.m, N, K) for K in ks}
+        res: dict = {}
+        for _ in range(a.rounds):
+            for K, fn in fns.items():
+                res.setdefault(K, []).append(timeit(fn, a.iters, per_graph=4))
+        ts = [min(res[K]) for K in ks]
+        f, b = fit(list(ks), ts)
+        for K, t in zip(ks, ts):
+            print(json.dumps({"op": name, "M": a.m, "N": N, "K": K, "us": round(t, 1),
+                              "us_all": [round(v, 1) for v in res[K]],
+                              "PFps": round(2 * a.m * N * K / t / 1e9, 3)}), flush=True)
+        rounds = -(-(((a.m + 255) // 256) * ((N + 255) // 256)) // 256)
+        print(json.dumps({"op": name, "fit_fixed_us": round(f, 1), "fit_us_per_1k_K": round(b * 1024, 2),
+                          "tile_rounds": rounds, "fixed_us_per_tile_round": round(f / rounds, 2),
+                          "loop_PFps": round(2 * a.m * N / (b * 1e9), 3)}), flush=True)
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
+    ap.add_argument("--prod", action="store_true", help="the four production epilogues at their own shapes (PROD)")
+    ap.add_argument("--only", default="", help="--prod: comma list of launches")
     ap.add_argument("--m", type=int, default=16384)
     ap.add_argument("--n", type=int, default=4096)
     ap.add_argument("--ks", default="512,1024,2048,4096,8192")
@@ -38,6 +93,9 @@ def main() -> None:
     ap.add_argument("--packed", action="store_true", help="also time the fragment-packed weight layout")
     a = ap.parse_args()
     torch.manual_seed(0)
+    if a.prod:
+        prod(a)
+        return
     ks = [int(k) for k in a.ks.split(",")]
     impls: dict = {}
     for K in ks:

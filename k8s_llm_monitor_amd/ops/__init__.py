@@ -626,6 +626,9 @@ def deinterleave_gate_up8(w: torch.Tensor) -> torch.Tensor:
 # (splits, n-tiles per wave, waves, weight ring depth) per decode projection shape (N, K) at
 # M <= 64: ~256 equal workgroups (measured: tools/bench_decode_gemm.py,
 # profiles/r04/decode_gemm_sweep.jsonl).  Shapes not listed get an automatic pick.
+# Round 24 (row-wide write-through slab stores, one split per XCD; same picks, same slabs;
+# profiles/r24/launch_final_*.jsonl, M = 64 / M = 1 us against the parent in the same session):
+# qkv 11.5 / 9.8 (12.7 / 9.8), o 9.2 / 7.2 (10.2 / 7.45), down 21.7 / 19.5 (22.9 / 20.3).
 DEC_TABLE: dict = {
     # Llama-3-8B at TP=1 (profiles/r04/decode_gemm_sweep_v1.jsonl, M = 64 / M = 1 us):
     # qkv: 6 waves -> 64 column groups x 4 splits = 256 workgroups (8 waves left 64 CUs idle):
@@ -649,6 +652,7 @@ DEC_TABLE: dict = {
 # and (4, 1, 4, 8) 15.0 us against 14.0, down 38.2 and 33.6 against 29.7; qkv on 8- or 4-wave
 # workgroups 22.5 / 24.0 against 16.7.  The LM head takes two n-tiles per wave: 8 m-tiles x 4
 # n-tiles of accumulators exceed the 256 registers of a wave at two waves per SIMD.
+# Round 24 at M = 128 (profiles/r24): qkv 15.4 (17.2), o 12.9 (14.3), down 26.9 (30.2).
 DEC_TABLE_M128: dict = {
     (6144, 4096, 0): (4, 1, 6, 8),      # qkv      16.7 / 14.7 / 12.6
     (4096, 4096, 0): (8, 1, 8, 8),      # o        14.0 / 11.8 / 10.2
@@ -667,6 +671,54 @@ DEC_TABLE_F8: dict = {}
 # mxfp4 weights: the same, for the shapes that measure better on another pick of DEC_F4_FORMS or
 # (None) on the bf16 copy.
 DEC_TABLE_F4: dict = {}
+
+
+# The SLAB epilogue and the split placement of gemm_dec_kernel (csrc/gemm_decode.hip), A/B only
+# (module constants, not environment switches; -1 = as dec_slab_shipped routes, 0 = off, 1 = on
+# wherever the launch can take it).  None of them changes a slab bit.
+#   DEC_SLAB_ROWS   above 16 rows the accumulators are parked as rows in the dead A ring and stored
+#                   as 16-byte pieces of whole rows (off, and up to 16 rows: one float per lane);
+#   DEC_SLAB_WT     those 16-byte stores write through (sc1); only with DEC_SLAB_ROWS;
+#   DEC_XCD_SPLITS  dense launches of 2, 4 or 8 splits whose workgroup count is a multiple of 8 deal
+#                   one split to each XCD (dec_xcd_map), so an L2 fetches one A slice.
+# They reach the kernel through native().gemm_dec; native().gemm_dec_plan reports what a launch does
+# and dec_slab_plan mirrors it (tests/test_dec_slab_plan_cpu.py).
+DEC_SLAB_ROWS = -1
+DEC_SLAB_WT = -1
+DEC_XCD_SPLITS = -1
+
+
+def dec_slab_shipped(rows: int) -> tuple:
+    """(rows, wt, xcd) as shipped for a SLAB launch of ``rows`` rows: dec_slab_shipped of
+    csrc/gemm_dec_forms.h (from the A/B of profiles/r24/README.md) - all on above one m-tile; at
+    one m-tile only the placement."""
+    wide = int(rows > 16)
+    return (wide, wide, 1)
+
+
+def dec_xcd_ok(gx: int, splits: int) -> bool:
+    return splits in (2, 4, 8) and (gx * splits) % 8 == 0
+
+
+def dec_xcd_map(L: int, splits: int) -> tuple:
+    """(column group, split) of the workgroup with linear id ``L`` = x + gx * y under the
+    one-split-per-XCD placement: dec_xcd_map of csrc/gemm_dec_forms.h."""
+    c, j, per = L % 8, L // 8, 8 // splits
+    return j * per + c // splits, c % splits
+
+
+def dec_slab_plan(M: int, N: int, cfg: tuple, grouped: bool = False, sw: Optional[tuple] = None) -> tuple:
+    """(row-wide stores, write-through, one split per XCD) of a SLAB launch of ``cfg`` = (splits,
+    ntw, waves, depth) at ``M`` rows over N columns: what dec_plan decides.  ``sw``: the three
+    switches, default the module constants."""
+    sr, sw_, sx = (DEC_SLAB_ROWS, DEC_SLAB_WT, DEC_XCD_SPLITS) if sw is None else sw
+    S, ntw, waves, _ = cfg
+    d = dec_slab_shipped(M)
+    gx = -(-(N // 16) // (ntw * waves))
+    rows = int((d[0] if sr < 0 else sr) != 0 and M > 16 and M * N * 4 < 0x7fffffff)
+    wt = int(bool(rows) and (d[1] if sw_ < 0 else sw_) != 0)
+    xcd = int((d[2] if sx < 0 else sx) != 0 and not grouped and dec_xcd_ok(gx, S))
+    return rows, wt, xcd
 
 
 def dec_config(N: int, K: int, epi: int, experts: int = 1, rows: int = 0, f8: bool = False,
@@ -867,7 +919,8 @@ def _dec_gemm(name: str, a: torch.Tensor, w: torch.Tensor, wscale: Optional[torc
                            (" with the wide deferred norm" if wn else "") +
                            (" over fp8 weights" if f8 else f" over mxfp4 weights in {S} K slices" if f4 else ""))
     r = native().gemm_dec(a, w, wscale if enc else None, workspace, out, S, epi, ntw, waves, depth, M, *rn,
-                          row_w if E else None, DEC_F4_DEPTH_FORCE if f4 else 0)
+                          row_w if E else None, DEC_F4_DEPTH_FORCE if f4 else 0, DEC_SLAB_ROWS, DEC_SLAB_WT,
+                          DEC_XCD_SPLITS)
     if r < 0:
         raise RuntimeError(f"{name}: configuration {cfg} not compiled for N={N} K={K} epi={epi}")
     return r

@@ -81,7 +81,7 @@ int k8sllm_gemm_skinny(const void* A, long lda, const void* Wp, float* partial, 
 int k8sllm_gemm_dec(const void* A, const void* W, const void* wscale, int wf, float* partial, void* Y, long ldy, int M,
                     int N, int K, int splits, int epi, int ntw, int waves, int depth, int f4_depth, const float* rn_ss,
                     int rn_nc, int rn_d, float rn_eps, int experts, long a_es, long w_eb, long s_eb, long y_es,
-                    const float* rw, int rw_ld, hipStream_t s);
+                    const float* rw, int rw_ld, int sw_rows, int sw_wt, int sw_xcd, hipStream_t s);
 int k8sllm_gemm_dec_forms(int* out, int cap);
 int k8sllm_gemm_dec_f8_forms(int* out, int cap);
 int k8sllm_gemm_dec_f4_forms(int* out, int cap);
@@ -908,12 +908,16 @@ int64_t gemm_skinny(torch::Tensor a, torch::Tensor wp, c10::optional<torch::Tens
 // of these experts, where given); epi 1 (dense): y [M, N] bf16 (row stride y.stride(0)); epi 2:
 // packed SwiGLU y [ceil(M/16), N/64, 64, 8] ([E, ...] per expert).  rn_ss: deferred RMSNorm of the
 // A rows (dense).  f4_depth: the mxfp4 ring depth (8 / 16 k-steps), 0 = the launcher's choice.
+// sw_rows / sw_wt / sw_xcd: ops.DEC_SLAB_ROWS / DEC_SLAB_WT / DEC_XCD_SPLITS (-1 as shipped, 0 off,
+// 1 on; the shorter overload below passes -1): the slab epilogue's row-wide stores, their
+// write-through form and the one-split-per-XCD placement - the slabs are the same bits either way.
 // Row limit, slicing and forms are dec_plan's (gemm_dec_forms.h).  Returns the slab count (1 for
 // epi 1 / 2); -1 if the configuration is not available (the caller falls back to gemm_skinny).
-int64_t gemm_dec(torch::Tensor a, torch::Tensor w, c10::optional<torch::Tensor> wscale,
-                 c10::optional<torch::Tensor> partial, c10::optional<torch::Tensor> y, int64_t splits, int64_t epi,
-                 int64_t ntw, int64_t waves, int64_t depth, int64_t rows, c10::optional<torch::Tensor> rn_ss,
-                 double rn_eps, c10::optional<torch::Tensor> row_w, int64_t f4_depth) {
+int64_t gemm_dec_sw(torch::Tensor a, torch::Tensor w, c10::optional<torch::Tensor> wscale,
+                    c10::optional<torch::Tensor> partial, c10::optional<torch::Tensor> y, int64_t splits, int64_t epi,
+                    int64_t ntw, int64_t waves, int64_t depth, int64_t rows, c10::optional<torch::Tensor> rn_ss,
+                    double rn_eps, c10::optional<torch::Tensor> row_w, int64_t f4_depth, int64_t sw_rows,
+                    int64_t sw_wt, int64_t sw_xcd) {
   dev_bf16(a, "a");
   const auto wt = w.scalar_type();
   const int wf = wt == torch::kFloat8_e4m3fn ? k8sllm::DEC_W_F8 : wt == torch::kUInt8 ? k8sllm::DEC_W_F4 : k8sllm::DEC_W_BF16;
@@ -950,7 +954,7 @@ int64_t gemm_dec(torch::Tensor a, torch::Tensor w, c10::optional<torch::Tensor> 
   rownorm_args(rn_ss, M, K, rp, rn_nc);
   const bool scaled = epi == 0 && row_w.has_value();  // (other epilogues have always ignored row_w)
   const k8sllm::DecPlan p = k8sllm::dec_plan(wf, M, N, K, (int)splits, (int)epi, (int)ntw, (int)waves, (int)depth,
-                                             (int)f4_depth, E, scaled, rn_nc);
+                                             (int)f4_depth, E, scaled, rn_nc, (int)sw_rows, (int)sw_wt, (int)sw_xcd);
   const int MT = (M + 15) / 16;
   TORCH_CHECK(M > 0 && M <= p.max_m && (!g || E >= 1), what, ": 1..", p.max_m, " rows", g ? ", >= 1 expert" : "");
   const bool per_e = g && a.dim() == 5;
@@ -988,20 +992,37 @@ int64_t gemm_dec(torch::Tensor a, torch::Tensor w, c10::optional<torch::Tensor> 
   const long s_eb = g && sp ? wscale->stride(0) * wscale->element_size() : 0;
   const int rc = k8sllm_gemm_dec(a.data_ptr(), w.data_ptr(), sp, wf, pp, yp, ldy, M, N, K, (int)splits, (int)epi,
                                  (int)ntw, (int)waves, (int)depth, (int)f4_depth, rp, rn_nc, K, (float)rn_eps, E,
-                                 a_es, w_eb, s_eb, y_es, rw, rw_ld, cur());
+                                 a_es, w_eb, s_eb, y_es, rw, rw_ld, (int)sw_rows, (int)sw_wt, (int)sw_xcd, cur());
   if (rc < 0) return -1;
   check(rc, what);
   return p.slabs;
 }
 
+int64_t gemm_dec(torch::Tensor a, torch::Tensor w, c10::optional<torch::Tensor> wscale,
+                 c10::optional<torch::Tensor> partial, c10::optional<torch::Tensor> y, int64_t splits, int64_t epi,
+                 int64_t ntw, int64_t waves, int64_t depth, int64_t rows, c10::optional<torch::Tensor> rn_ss,
+                 double rn_eps, c10::optional<torch::Tensor> row_w, int64_t f4_depth) {
+  return gemm_dec_sw(a, w, wscale, partial, y, splits, epi, ntw, waves, depth, rows, rn_ss, rn_eps, row_w, f4_depth,
+                     -1, -1, -1);
+}
+
 // dec_plan (gemm_dec_forms.h), what a launch with these arguments does: (err, m-tiles, kchunk,
-// mxfp4 ring depth, wide-norm, grid x, y, z, slabs, row limit).  experts 0: a dense launch.  No launch.
+// mxfp4 ring depth, wide-norm, grid x, y, z, slabs, row limit, row-wide slab stores, write-through, one
+// split per XCD).  experts 0: a dense launch.  sw_*: the three switches (the shorter overload: -1, as
+// shipped).  No launch.
+std::vector<int64_t> gemm_dec_plan_sw(int64_t wf, int64_t M, int64_t N, int64_t K, int64_t splits, int64_t epi,
+                                      int64_t ntw, int64_t waves, int64_t depth, int64_t f4_depth, int64_t experts,
+                                      bool has_row_w, int64_t rn_nc, int64_t sw_rows, int64_t sw_wt, int64_t sw_xcd) {
+  const k8sllm::DecPlan p = k8sllm::dec_plan((int)wf, (int)M, (int)N, (int)K, (int)splits, (int)epi, (int)ntw,
+                                             (int)waves, (int)depth, (int)f4_depth, (int)experts, has_row_w, (int)rn_nc,
+                                             (int)sw_rows, (int)sw_wt, (int)sw_xcd);
+  return {p.err, p.mt, p.kchunk, p.d4, p.rnw, p.gx, p.gy, p.gz, p.slabs, p.max_m, p.rows, p.wt, p.xcd};
+}
+
 std::vector<int64_t> gemm_dec_plan(int64_t wf, int64_t M, int64_t N, int64_t K, int64_t splits, int64_t epi, int64_t ntw,
                                    int64_t waves, int64_t depth, int64_t f4_depth, int64_t experts, bool has_row_w,
                                    int64_t rn_nc) {
-  const k8sllm::DecPlan p = k8sllm::dec_plan((int)wf, (int)M, (int)N, (int)K, (int)splits, (int)epi, (int)ntw,
-                                             (int)waves, (int)depth, (int)f4_depth, (int)experts, has_row_w, (int)rn_nc);
-  return {p.err, p.mt, p.kchunk, p.d4, p.rnw, p.gx, p.gy, p.gz, p.slabs, p.max_m};
+  return gemm_dec_plan_sw(wf, M, N, K, splits, epi, ntw, waves, depth, f4_depth, experts, has_row_w, rn_nc, -1, -1, -1);
 }
 
 // The rows of kDecForms with fp8-weight instantiations (kDecF8Forms), as indices into gemm_dec_forms().
@@ -1348,9 +1369,11 @@ PYBIND11_MODULE(_k8sllm_ops, m) {
   m.def("gemm_skinny_forms", &gemm_skinny_forms);
   m.def("gemm_skinny_plan", &gemm_skinny_plan);
   m.def("gemm_dec_plan", &gemm_dec_plan);
+  m.def("gemm_dec_plan", &gemm_dec_plan_sw);
   m.attr("SKINNY_MAX_M") = k8sllm::kSkinnyMaxM;
   m.attr("SKINNY_GROUPED_MAX_M") = k8sllm::kSkinnyGroupedMaxM;
   m.def("gemm_dec", &gemm_dec);
+  m.def("gemm_dec", &gemm_dec_sw);
   m.def("gemm_dec_forms", &gemm_dec_forms);
   m.def("gemm_dec_f8_forms", &gemm_dec_f8_forms);
   m.def("gemm_dec_f4_forms", &gemm_dec_f4_forms);

@@ -103,7 +103,30 @@ struct DecPlan {
   int rnw;         // 1: the wide deferred-norm instantiation
   int gx, gy, gz;  // grid: column groups, splits, experts
   int slabs;       // what the caller is told: fp32 slabs written (SLAB), else 1
+  int rows;        // SLAB: the row-wide 16-byte slab stores (else one float per lane)
+  int wt;          // SLAB: those stores write through (sc1); only with rows
+  int xcd;         // SLAB: one split per XCD (dec_xcd_map), else the identity map
 };
+
+// The kernel's flags argument: the three fields above.
+enum { kDecRows = 1, kDecWt = 2, kDecXcd = 4 };
+
+// One split per XCD.  Workgroups are observed to be dealt round-robin over the 8 XCDs, so the
+// linear ids L = x + gx * y with equal L % 8 share an L2.  For `splits` in {2, 4, 8} and gx * splits
+// a multiple of 8: XCD c = L % 8 takes split c % splits, and its j-th workgroup (j = L / 8) takes
+// column group j * (8 / splits) + c / splits - a bijection onto [0, gx) x [0, splits), so every
+// workgroup of the plain grid is still run exactly once wherever the dispatcher puts it.
+// ops.dec_xcd_map is the Python copy (tests/test_dec_slab_plan_cpu.py).
+struct DecXY {
+  int x, y;
+};
+constexpr bool dec_xcd_ok(int gx, int splits) {
+  return (splits == 2 || splits == 4 || splits == 8) && (gx * splits) % 8 == 0;
+}
+constexpr DecXY dec_xcd_map(int L, int splits) {
+  const int c = L & 7, j = L >> 3, per = 8 / splits;
+  return DecXY{j * per + c / splits, c % splits};
+}
 
 // The row of kDecForms that is (epi, ntw, waves, depth), or -1.
 constexpr int dec_form_index(int epi, int ntw, int waves, int depth) {
@@ -112,6 +135,19 @@ constexpr int dec_form_index(int epi, int ntw, int waves, int depth) {
     if (f.epi == epi && f.ntw == ntw && f.waves == waves && f.depth == depth) return i;
   }
   return -1;
+}
+
+// What ships (switch -1) for a SLAB launch of M rows: by row class, from the A/B of
+// profiles/r24/README.md.  Above one m-tile everything is on (64 rows: qkv 12.7 -> 11.5 us, o
+// 10.2 -> 9.2, down 22.9 -> 21.7).  At one m-tile the row-wide stores do not pay (0.2 us slower at 1
+// row; they are not compiled there) and only the placement stays (o 7.45 -> 7.2 us at 1 row, qkv
+// 10.5 -> 10.35 at 16).  ops.dec_slab_shipped mirrors it.
+struct DecSlabSw {
+  int rows, wt, xcd;
+};
+constexpr DecSlabSw dec_slab_shipped(int M) {
+  const int wide = M > 16;
+  return DecSlabSw{wide, wide, 1};
 }
 
 // THE plan of k8sllm_gemm_dec: the launcher, the binding (its row limit and slab count) and the
@@ -137,9 +173,15 @@ constexpr int dec_form_index(int epi, int ntw, int waves, int depth) {
 // max(depth, kDecAChunk) k-steps (one unrolled main-loop iteration); mxfp4 whole 256-deep A chunks,
 // and the ring depth d4 dividing the slice's k-steps: the kDecF4Forms row's depth at one m-tile,
 // 8 above, and 0 -> the deepest of those that divides.
+//
+// sw_rows, sw_wt, sw_xcd: the A/B switches ops.DEC_SLAB_ROWS, DEC_SLAB_WT and DEC_XCD_SPLITS: 1 on
+// wherever the launch can take it, 0 off, -1 as shipped (dec_slab_shipped).  SLAB launches only:
+// rows at two m-tiles and up (the one-m-tile kernels do not hold that path) where a slab stays under
+// 2 GiB (32-bit buffer offsets), wt only with rows, xcd on dense launches that dec_xcd_ok accepts.
 constexpr DecPlan dec_plan(int wf, int M, int N, int K, int splits, int epi, int ntw, int waves, int depth,
-                           int f4_depth, int experts, bool has_row_w, int rn_nc) {
-  DecPlan p{-1, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+                           int f4_depth, int experts, bool has_row_w, int rn_nc, int sw_rows = -1, int sw_wt = -1,
+                           int sw_xcd = -1) {
+  DecPlan p{-1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   const bool grouped = experts >= 1 || has_row_w, quant = wf != DEC_W_BF16;
   p.max_m = grouped ? kDecNarrowMaxM : kDecMaxM;
   if ((wf != DEC_W_BF16 && wf != DEC_W_F8 && wf != DEC_W_F4) || experts < 0 || M < 1 || M > p.max_m) return p;
@@ -179,6 +221,12 @@ constexpr DecPlan dec_plan(int wf, int M, int N, int K, int splits, int epi, int
   p.gy = splits;
   p.gz = experts > 1 ? experts : 1;
   p.slabs = epi == DEC_SLAB ? p.gz * splits : 1;
+  if (epi == DEC_SLAB) {
+    const DecSlabSw d = dec_slab_shipped(M);
+    p.rows = (sw_rows < 0 ? d.rows : sw_rows) != 0 && p.mt > 1 && (long)M * N * 4 < 0x7fffffffL;
+    p.wt = p.rows && (sw_wt < 0 ? d.wt : sw_wt) != 0;
+    p.xcd = (sw_xcd < 0 ? d.xcd : sw_xcd) != 0 && !grouped && dec_xcd_ok(p.gx, splits);
+  }
   p.err = 0;
   return p;
 }

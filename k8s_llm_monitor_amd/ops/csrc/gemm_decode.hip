@@ -57,6 +57,7 @@ constexpr int kRnMax = 4;   // narrow deferred-norm rows: up to 16 partials (4 p
 constexpr int kRnWide = 16;  // wide rows: up to 256 partials (16 x 16 B per thread)
 
 constexpr int kDecCH = 8;  // k-steps (32 deep) per A chunk
+constexpr int kDecSC1 = 16;  // buffer-op aux bits: sc1 (write-through stores)
 
 template <int MT, int WAVES>
 struct DecGeom {
@@ -110,7 +111,7 @@ template <int MT, int NTW, int WAVES, int EPI, int DEPTH, bool RNW = false, int 
 __global__ __launch_bounds__(64 * WAVES, 1) void gemm_dec_kernel(
     const bf16_t* __restrict__ A, const bf16_t* __restrict__ W, float* __restrict__ partial,
     bf16_t* __restrict__ Y, long ldy, int M, int N, int K, int kchunk, const float* __restrict__ rn_ss, int rn_nc,
-    float rn_inv_d, float rn_eps, DecGroup grp, const float* __restrict__ wscale) {
+    float rn_inv_d, float rn_eps, DecGroup grp, const float* __restrict__ wscale, int flags) {
   constexpr bool F8 = WF == DEC_W_F8, F4 = WF == DEC_W_F4;
   static_assert(!F8 || (!RNW && DEPTH % 2 == 0), "fp8 weights: narrow deferred norm, whole k-step pairs in the ring");
   static_assert(!F4 || (!RNW && DEPTH % 4 == 0), "mxfp4 weights: narrow deferred norm, whole k-step quads in the ring");
@@ -125,10 +126,23 @@ __global__ __launch_bounds__(64 * WAVES, 1) void gemm_dec_kernel(
   __shared__ float s_inv[MT * 16];
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   const int ksteps = K >> 5;
-  const int kb = blockIdx.y * (kchunk >> 5);  // first k-step of this workgroup's K slice
+  // (column group, split) of this workgroup.  kDecXcd (dense SLAB launches of 2, 4 or 8 splits whose
+  // workgroup count is a multiple of 8: dec_plan): workgroups with equal linear id mod 8 - the ones
+  // the dispatcher is observed to deal to one XCD - take the same split, so an XCD's L2 fetches
+  // one split's A slice instead of all of them.  A bijection onto the same (x, y) set
+  // (dec_xcd_map): placement is only ever a speed guess.
+  int bx = blockIdx.x, by = blockIdx.y;
+  if constexpr (EPI == DEC_SLAB) {
+    if (flags & kDecXcd) {
+      const DecXY m = dec_xcd_map(blockIdx.x + gridDim.x * blockIdx.y, gridDim.y);
+      bx = m.x;
+      by = m.y;
+    }
+  }
+  const int kb = by * (kchunk >> 5);  // first k-step of this workgroup's K slice
   const int nsteps = kchunk >> 5;             // host: kchunk | K, (kchunk / 32) % ITER == 0
   const int niter = nsteps / ITER;
-  const int tile0 = (blockIdx.x * WAVES + wave) * NTW;  // this wave's first n-tile
+  const int tile0 = (bx * WAVES + wave) * NTW;  // this wave's first n-tile
 
   // ---- weight stream: DEPTH k-steps x NTW fragments in flight per wave, filled after chunk 0's
   // staging loads (below)
@@ -377,6 +391,58 @@ __global__ __launch_bounds__(64 * WAVES, 1) void gemm_dec_kernel(
   iteration(it, std::true_type{});
 
   // ---- epilogue.  C layout of a 16x16 tile: col = lane & 15, rows (lane >> 4) * 4 + r.
+  if constexpr (EPI == DEC_SLAB && MT > 1) {
+    if (flags & kDecRows) {
+      // Row-wide slab stores (two m-tiles and up: at one the 4-byte stores below are as fast or
+      // faster, profiles/r24/README.md, and the one-m-tile kernels stay free of this path).  The
+      // A ring is dead after the last k-step: every wave parks the values the 4-byte path stores
+      // (same factors, same order: bit-identical slabs) in a padded row image
+      // [MT * 16][16 NTW WAVES + 4] there, and each thread then stores 16-byte pieces of whole
+      // rows - at 8 waves a wave instruction writes two 512-byte row segments, every 128-byte
+      // line whole.  Banks: a ds_write_b32's 32-lane half holds two 4-row lane groups,
+      // 4 LD = 16 (mod 32) dwords apart, so its 32 lanes hit 32 banks; a ds_read_b128's 16-lane
+      // group reads 16 distinct 16-byte slots of one row at 8 waves (at 6 and 4 waves a group
+      // that straddles two rows pays one 2-way conflict: the pad shifts the second row by a slot).
+      constexpr int COLS = 16 * NTW * WAVES, LD = COLS + 4, PPR = COLS / 4;  // PPR: 16-byte pieces per row
+      static_assert(MT * 16 * LD * 4 <= 2 * G::SLOT, "the row image fits the dead A ring");
+      static_assert((MT * 16 * PPR) % (64 * WAVES) == 0, "whole passes of the workgroup over the image");
+      float* img = reinterpret_cast<float*>(sA);
+      __syncthreads();  // other waves may still be reading A fragments
+#pragma unroll
+      for (int m = 0; m < MT; ++m)
+#pragma unroll
+        for (int t = 0; t < NTW; ++t)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int rl = m * 16 + (lane >> 4) * 4 + r;
+            float v = acc[m][t][r] * (rn_ss != nullptr ? s_inv[rl] : 1.f);
+            if constexpr (F8) v *= wsc[t];
+            if (grp.rw != nullptr && rl < M) v = v * grp.rw[(long)rl * grp.rw_ld + ex];
+            img[rl * LD + (wave * NTW + t) * 16 + (lane & 15)] = v;
+          }
+      __syncthreads();
+      // this workgroup's slab: rows x N fp32 (dec_plan: under 2 GiB), columns col0 .. col0 + COLS - 1
+      // as far as N reaches (the ragged last workgroup).  Buffer stores: rows at or past M are
+      // also past the descriptor's range.
+      const __amdgpu_buffer_rsrc_t rs = dec_rsrc(partial + (long)(ex * gridDim.y + by) * M * N, (long)M * N * 4);
+      const int col0 = bx * COLS;
+#pragma unroll
+      for (int q0 = 0; q0 < MT * 16 * PPR; q0 += 64 * WAVES) {
+        const int q = q0 + threadIdx.x;
+        const int row = q / PPR, c = (q % PPR) * 4;
+        if (row < M && col0 + c < N) {
+          const u32x4 v = *reinterpret_cast<const u32x4*>(img + row * LD + c);
+          const uint32_t off = (uint32_t)((row * N + col0 + c) * 4);
+          // write-through (kDecWt): the line leaves L2 as it is written, not at the kernel's end
+          if (flags & kDecWt)
+            __builtin_amdgcn_raw_buffer_store_b128(v, rs, off, 0, kDecSC1);
+          else
+            __builtin_amdgcn_raw_buffer_store_b128(v, rs, off, 0, 0);
+        }
+      }
+      return;
+    }
+  }
 #pragma unroll
   for (int m = 0; m < MT; ++m) {
     float rs[4];
@@ -415,7 +481,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void gemm_dec_kernel(
             if constexpr (EPI == DEC_BF16)
               Y[(long)row * ldy + col] = f2bf(v);
             else
-              partial[((long)(ex * gridDim.y + blockIdx.y) * M + row) * N + col] =
+              partial[((long)(ex * gridDim.y + by) * M + row) * N + col] =
                   grp.rw != nullptr ? v * grp.rw[(long)row * grp.rw_ld + ex] : v;
           }
         }
@@ -536,6 +602,7 @@ struct DecLaunch {  // what every instantiation is launched with
   DecGroup dg;
   const float* wscale;  // fp8 weights: one scale per packed weight row; mxfp4: the packed block scales (else null)
   int d4 = 0;           // mxfp4: the ring depth in k-steps (8 or 16)
+  int flags = 0;        // kDecRows | kDecWt | kDecXcd (SLAB launches: dec_plan)
 };
 
 // Launches <mt m-tiles, form F> for 1 <= mt <= MT: the instantiations 1..MT of the form and no
@@ -551,7 +618,7 @@ bool dec_launch(int mt, const DecLaunch& l) {
     constexpr int depth = WF == DEC_W_F4 ? D4 : f.depth;
     hipLaunchKernelGGL((gemm_dec_kernel<MT, f.ntw, f.waves, f.epi, depth, RNW, WF>), l.grid, l.blk, 0, l.s, l.A,
                        l.W, l.partial, l.Y, l.ldy, l.M, l.N, l.K, l.kchunk, l.rn_ss, l.rn_nc, l.inv_d, l.rn_eps, l.dg,
-                       l.wscale);
+                       l.wscale, l.flags);
     return true;
   }
 }
@@ -598,22 +665,27 @@ static_assert(kDecAChunk == kDecCH && kDecRnNarrow == 4 * kRnMax && kDecRnWide =
 // A / SWIGLU8 outputs (a_es 0: A shared); SLAB slabs [E * splits][M][N], scaled by rw [M][rw_ld]
 // where given.  ntw x waves n-tiles per workgroup - the last workgroup may hold fewer; depth:
 // weight k-steps in flight per wave (mxfp4: f4_depth, see dec_plan).
+// sw_rows / sw_wt / sw_xcd: dec_plan's switches for the SLAB epilogue and the split placement
+// (-1 as shipped).
 // Returns 0, or dec_plan's negative code when the shape / configuration is not supported (the
 // caller then uses gemm_skinny).
 extern "C" int k8sllm_gemm_dec(const void* A, const void* W, const void* wscale, int wf, float* partial, void* Y,
                                long ldy, int M, int N, int K, int splits, int epi, int ntw, int waves, int depth,
                                int f4_depth, const float* rn_ss, int rn_nc, int rn_d, float rn_eps, int experts,
                                long a_es, long w_eb, long s_eb, long y_es, const float* rw, int rw_ld,
-                               hipStream_t s) {
+                               int sw_rows, int sw_wt, int sw_xcd, hipStream_t s) {
   if (M <= 0) return 0;
   if (wf != DEC_W_BF16 && wscale == nullptr) return -1;
   const DecPlan p = dec_plan(wf, M, N, K, splits, epi, ntw, waves, depth, f4_depth, experts, rw != nullptr,
-                             rn_ss != nullptr ? rn_nc : 0);
+                             rn_ss != nullptr ? rn_nc : 0, sw_rows, sw_wt, sw_xcd);
   if (p.err < 0) return p.err;
+  // (16-byte stores need a 16-byte aligned workspace; any other keeps the 4-byte stores, same bits)
+  const bool rows = p.rows && reinterpret_cast<uintptr_t>(partial) % 16 == 0;
+  const int flags = (rows ? kDecRows : 0) | (rows && p.wt ? kDecWt : 0) | (p.xcd ? kDecXcd : 0);
   const DecLaunch l{dim3(p.gx, p.gy, p.gz), dim3(64 * waves), s, (const bf16_t*)A, (const bf16_t*)W, partial,
                     (bf16_t*)Y, ldy, M, N, K, p.kchunk, rn_ss, rn_nc, rn_d > 0 ? 1.f / (float)rn_d : 0.f, rn_eps,
                     DecGroup{a_es, y_es, w_eb, s_eb, rw, rw_ld}, wf == DEC_W_BF16 ? nullptr : (const float*)wscale,
-                    p.d4};
+                    p.d4, flags};
   bool ok = false;
   switch (wf) {
     case DEC_W_BF16: ok = dec_dispatch<DEC_W_BF16>(epi, ntw, waves, depth, p.rnw, p.mt, l); break;

@@ -17,6 +17,8 @@ both in one session (each checked against the bf16 launch over its own dequantis
 the timed bf16 cases stream the last encoding's).  ``--f4-depths 8,16`` times the mxfp4 cases
 once per forced F4 ring depth (ops.DEC_F4_DEPTH_FORCE; 0 = the launcher's choice) where the
 launcher takes it.  ``--ops 70b_gate_up``, ``--ops q3_gate_up,q3_down,q3_lm_head`` (Qwen3-8B) etc.: SHAPES.
+``--slab-sw 000,100,110,001,111``: every bf16 slab configuration once per setting of
+(ops.DEC_SLAB_ROWS, DEC_SLAB_WT, DEC_XCD_SPLITS) - ``_sw`` cases, interleaved in one session.
 ``--experts E``: the grouped (grid.z = expert) launches of a Mixtral-8x7B MoE layer over E local
 experts instead - gate_up and down (``--ops``), bf16 stacks on ops.dec_config's pick against the
 ``--wdtype`` code stacks on ops.dec_grouped_q_config's (and the bf16 stacks on that pick where it
@@ -142,6 +144,9 @@ def main() -> None:
     ap.add_argument("--f4-depths", default="0", help="F4 ring depths to time the mxfp4 cases at (0 = automatic)")
     ap.add_argument("--no-base", action="store_true", help="leave out the row-major skinny / hipBLASLt case")
     ap.add_argument("--experts", type=int, default=0, help="E > 0: the grouped launches of a Mixtral MoE layer")
+    ap.add_argument("--slab-sw", default=None,
+                    help="time every bf16 slab configuration once per setting of (ops.DEC_SLAB_ROWS, DEC_SLAB_WT, "
+                         "DEC_XCD_SPLITS), e.g. 000,100,110,001,111 (digits 0 / 1; s = as shipped)")
     a = ap.parse_args()
     encs = [e for e in a.wdtype.split(",") if e != "bf16"]
     if any(e not in ("fp8", "mxfp4") for e in encs):
@@ -226,8 +231,21 @@ def main() -> None:
                     continue
                 err = (dec_out(cfg) - ref).abs().max().item() / max(scale, 1e-6)
                 tag = "dec" + "_".join(map(str, cfg))
-                cases[tag] = (lambda i, cfg=cfg: ops.dec_gemm(xp, wdec[i % ncopy], epi, M, workspace=wsp,
-                                                              out=act if epi == 2 else yb, cfg=cfg))
+
+                def run_sw(i, cfg=cfg, sw=None):
+                    if sw is not None:
+                        ops.DEC_SLAB_ROWS, ops.DEC_SLAB_WT, ops.DEC_XCD_SPLITS = sw
+                    try:
+                        return ops.dec_gemm(xp, wdec[i % ncopy], epi, M, workspace=wsp, out=act if epi == 2 else yb, cfg=cfg)
+                    finally:
+                        ops.DEC_SLAB_ROWS = ops.DEC_SLAB_WT = ops.DEC_XCD_SPLITS = -1
+
+                if a.slab_sw and epi == 0:
+                    for word in a.slab_sw.split(","):
+                        sw = tuple(-1 if ch == "s" else int(ch) for ch in word)
+                        cases[tag + "_sw" + word] = (lambda i, run_sw=run_sw, sw=sw: run_sw(i, sw=sw))
+                else:
+                    cases[tag] = run_sw
                 print(json.dumps({"op": name, "M": M, "cfg": cfg, "rel_err": round(err, 5)}), flush=True)
                 for enc, (wq, ws, wchk) in quant.items():
                     pre, kw = ("f8_", dict(f8=True)) if enc == "fp8" else ("f4_", dict(f4=True, K=K))

@@ -14,6 +14,9 @@ down on 4 split-K slabs instead of 8 (half the bytes add_norm_partial reads) - 6
 rows, 3.78 vs 3.75 at 16: slower, DEC_TABLE unchanged; profiles/r06/decode_step_split4_ab.jsonl.)
 ``rows128`` - CausalLM.DEC_ROWS_MAX 128 vs 64: a 128-row decode step on gemm_decode.hip's 8 m-tile
 kernels vs the generic layer loop (``--rows 64,128``; at 64 rows both sides run the same code).
+``slabrows`` / ``slabwt`` / ``xcd`` - gemm_decode.hip's row-wide 16-byte slab stores, their
+write-through form and the one-split-per-XCD placement (ops.DEC_SLAB_ROWS / DEC_SLAB_WT /
+DEC_XCD_SPLITS), on vs off (profiles/r24/README.md).
 ``--decode-weights fp8`` builds the engine with the fp8 encoding beside the bf16 weights; ``f8``
 then A/Bs a step streaming fp8 weights (on; the row-complete o projection off, the fp8-mode
 default) against the same engine routed to its bf16 copies with the bf16 defaults (off), and
@@ -48,7 +51,13 @@ SWITCHES = {"rc": lambda m, on: m.set_decode_fusion(rc=on),
             # before it (off: CausalLM.DEC_ROWS_MAX = 64, the generic layer loop on the tile GEMM);
             # run with --rows 64,128
             "rows128": lambda m, on: setattr(type(m), "DEC_ROWS_MAX", 64 if on is False else 128),
-            "f8": lambda m, on: _f8(m, on)}
+            "f8": lambda m, on: _f8(m, on),
+            # gemm_decode.hip's slab epilogue and split placement (ops.DEC_SLAB_ROWS / DEC_SLAB_WT /
+            # DEC_XCD_SPLITS): on vs off, the other two as shipped; slabwt runs the row-wide stores on
+            # both sides (write-through exists only on them); reset: all three as shipped
+            "slabrows": lambda m, on: _slab(on, "DEC_SLAB_ROWS"),
+            "slabwt": lambda m, on: _slab(on, "DEC_SLAB_WT", DEC_SLAB_ROWS=1),
+            "xcd": lambda m, on: _slab(on, "DEC_XCD_SPLITS")}
 _DEC_DEFAULT: dict = {}
 _F8_FORMS: list = []
 
@@ -62,6 +71,13 @@ def _f8(m, on) -> None:
         _F8_FORMS.append((ops.DEC_F8_FORMS, ops.DEC_F4_FORMS))
     ops.DEC_F8_FORMS, ops.DEC_F4_FORMS = ((), ()) if on is False else _F8_FORMS[0]
     m.set_decode_fusion(rc=m.RC_O_MAX_ROWS if on is False else None)
+
+
+def _slab(on, name: str, **fixed) -> None:
+    ops = _ops()
+    for k, v in fixed.items():
+        setattr(ops, k, -1 if on is None else v)
+    setattr(ops, name, -1 if on is None else int(on))
 
 
 def _dec_table(on, alt: dict) -> None:

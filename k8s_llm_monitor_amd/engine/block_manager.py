@@ -150,11 +150,11 @@ class BlockManager:
         nat = _native() if use_native else None
         if nat is not None and hasattr(nat, "BlockPool"):
             self.pool = nat.BlockPool(num_blocks)
-            self._hashes = lambda toks: nat.block_hashes(toks, block_size, 0)
+            self._hashes = lambda toks, seed=0: nat.block_hashes(toks, block_size, seed)
             self.native = True
         else:
             self.pool = PyBlockPool(num_blocks)
-            self._hashes = lambda toks: py_block_hashes(toks, block_size, 0)
+            self._hashes = lambda toks, seed=0: py_block_hashes(toks, block_size, seed)
             self.native = False
         self.prefix_caching = prefix_caching
         self.watermark_blocks = max(1, int(watermark * num_blocks)) if num_blocks > 64 else 0
@@ -170,14 +170,17 @@ class BlockManager:
     # ------------------------------------------------------------------ prefix cache
     def _prefix_hashes(self, seq: Sequence) -> list:
         """Hashes of the full blocks that may be reused: at least one token must remain to run
-        through the model (its logits give the first new token)."""
+        through the model (its logits give the first new token).  The chain is seeded with the
+        sequence's ``hash_seed``: 0 for the base model (today's hashes), a stable non-zero value per
+        LoRA adapter - KV computed under an adapter is not the base model's, nor another adapter's."""
         if not self.prefix_caching:
             return []
         n = seq.num_tokens
         max_full = (n - 1) // self.block_size
         key = (n, max_full)
         if getattr(seq, "_hash_key", None) != key:
-            seq._hashes = self._hashes(seq.all_ids[: max_full * self.block_size]) if max_full > 0 else []
+            seq._hashes = (self._hashes(seq.all_ids[: max_full * self.block_size], getattr(seq, "hash_seed", 0))
+                           if max_full > 0 else [])
             seq._hash_key = key
         return seq._hashes
 

@@ -62,6 +62,8 @@ class _EngineInfo:
         self.model_cfg = mc
         self.cfg = cfg
         self.tokenizer = tokenizer_from_dir(weights, mc) if weights else tokenizer_for(mc)
+        # the replicas' adapter names (every replica loads the same EngineConfig.lora_adapters)
+        self.adapters = {str(k): i for i, k in enumerate(getattr(cfg, "lora_adapters", None) or {})}
 
 
 def _replica_main(conn, idx: int, cfg: dict, device: str) -> None:
@@ -202,6 +204,10 @@ class ReplicaRouter:
             except ValueError as e:
                 fut.set_exception(e)
                 return fut
+        if params is not None and params.adapter is not None and params.adapter not in self.engine.adapters:
+            fut.set_exception(ValueError(f"unknown adapter {params.adapter!r} "
+                                         f"(configured: {sorted(self.engine.adapters) or 'none'})"))
+            return fut
         p = asdict(params or SamplingParams())
         p["stop_token_ids"] = tuple(p["stop_token_ids"])
         key = next(self._keys)

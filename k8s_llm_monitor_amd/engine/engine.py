@@ -14,6 +14,7 @@ replicated (same logits, same RNG counter) so no token broadcast is needed.
 """
 from __future__ import annotations
 
+import hashlib
 import os
 import queue
 import threading
@@ -27,7 +28,7 @@ from typing import Optional, Union
 import torch
 
 from .. import ops
-from ..models.checkpoint import config_from_hf, load_checkpoint
+from ..models.checkpoint import config_from_hf, load_checkpoint, load_lora
 from ..models.config import ModelConfig, get_config
 from ..models.llama import CausalLM
 from ..parallel.state import ParallelState, get_state, serving_timeouts
@@ -92,6 +93,12 @@ class EngineConfig:
     # constrained decoding (engine/guide.py): the most DFA states one guide may have; the guide
     # state (allocated by the first guided request) holds max_num_seqs * guide_max_states rows
     guide_max_states: int = 512
+    # per-request LoRA adapters: name -> PEFT adapter directory (models/checkpoint.load_lora).  All
+    # are loaded at start-up and stay resident beside the one base model (CausalLM.enable_lora); a
+    # request names one through SamplingParams.adapter.  lora_max_rank: the arena's rank capacity
+    # (at most 64), an adapter of a higher rank is refused
+    lora_adapters: dict = field(default_factory=dict)
+    lora_max_rank: int = 64
 
 
 class _View:
@@ -129,10 +136,22 @@ class LLMEngine:
                               prefill_weights=cfg.prefill_weights)
         if cfg.weights:
             load_checkpoint(self.model, cfg.weights)
+        # per-request LoRA: adapter name -> slot of the model's arena (its index), and what stats() reports
+        self.adapters: dict[str, int] = {}
+        self._adapter_info: list[dict] = []
+        if cfg.lora_adapters:
+            self.model.enable_lora(len(cfg.lora_adapters), cfg.lora_max_rank)
+            for slot, (name, path) in enumerate(cfg.lora_adapters.items()):
+                ad = load_lora(path, name=str(name))
+                self.model.load_adapter(slot, ad)
+                self.adapters[str(name)] = slot
+                self._adapter_info.append({"name": str(name), "rank": ad.r, "targets": list(ad.target_modules)})
         self.runner = ModelRunner(self.model, RunnerConfig(
             max_num_seqs=cfg.max_num_seqs, max_model_len=cfg.max_model_len, kv_cache_gb=cfg.kv_cache_gb,
             num_blocks=cfg.num_blocks, use_graphs=cfg.use_graphs, seed=cfg.seed,
             kv_cache_dtype=cfg.kv_cache_dtype))
+        if self.adapters:
+            self.runner.lora_setup()
         self.blocks = BlockManager(self.runner.num_blocks, prefix_caching=cfg.prefix_caching)
         self.sched = Scheduler(SchedulerConfig(max_num_seqs=cfg.max_num_seqs,
                                                max_prefill_tokens=cfg.max_prefill_tokens,
@@ -215,13 +234,23 @@ class LLMEngine:
                 self._vocab_bytes = vocab_bytes(self.tokenizer, self.model_cfg.vocab_size)
             self.runner.guide_enable(self._vocab_bytes, self.model_cfg.eos_ids, self.cfg.guide_max_states)
             self.runner.gd.load(guide)  # a guide this vocabulary cannot follow is refused here
+        lora_slot, hash_seed = -1, 0
+        if params is not None and params.adapter is not None:
+            if params.adapter not in self.adapters:
+                raise ValueError(f"unknown adapter {params.adapter!r} (configured: {sorted(self.adapters) or 'none'})")
+            lora_slot = self.adapters[params.adapter]
+            # KV blocks computed under an adapter are its own: a stable non-zero seed of the hash chain
+            hash_seed = int.from_bytes(hashlib.blake2b(f"lora:{params.adapter}".encode(), digest_size=8).digest(),
+                                       "little") | 1
+            self.runner.lora_enable()
         ids = self.tokenizer.encode(prompt) if isinstance(prompt, str) else list(prompt)
         limit = self.runner.max_len - 1
         if len(ids) > limit - 1:  # keep room for at least one generated token; trim the middle
             keep = limit - 1
             ids = ids[: keep // 2] + ids[len(ids) - (keep - keep // 2):]
         seq = Sequence(prompt_ids=ids, params=params or SamplingParams(),
-                       request_id=request_id or uuid.uuid4().hex[:16], user=user, deadline=deadline, guide=guide)
+                       request_id=request_id or uuid.uuid4().hex[:16], user=user, deadline=deadline, guide=guide,
+                       lora_slot=lora_slot, hash_seed=hash_seed)
         if want_lp:
             seq.output_logprobs = []
         self.sched.add(seq)
@@ -539,6 +568,8 @@ class LLMEngine:
                   "decode_weights": self.cfg.decode_weights, "prefill_weights": self.cfg.prefill_weights,
                   **self.runner.kv_stats(), **self.runner.penalty_stats(), **self.runner.guide_stats(),
                   "logprobs_enabled": self.runner.lp_on,
+                  "lora_enabled": self.runner.lora_on, "lora_adapters": [dict(a) for a in self._adapter_info],
+                  "lora_bytes": self.model.lora.nbytes if self.model.lora is not None else 0,
                   "resident_weight_bytes": self.model.resident_weight_bytes(),
                   "decode_encodings": self.model.decode_encodings(),
                   "prefill_encodings": self.model.prefill_encodings()})
@@ -877,6 +908,10 @@ class EngineService:
             except ValueError as e:
                 fut.set_exception(e)
                 return fut
+        if params is not None and params.adapter is not None and params.adapter not in self.engine.adapters:
+            fut.set_exception(ValueError(f"unknown adapter {params.adapter!r} "
+                                         f"(configured: {sorted(self.engine.adapters) or 'none'})"))
+            return fut
         if isinstance(prompt, str):
             # tokenize on the caller's thread: the native BPE releases the GIL, so a burst's HTTP
             # handler threads encode in parallel instead of the engine thread encoding the whole

@@ -110,6 +110,14 @@ class ModelRunner:
         self._want_sent = np.full(B, -1, dtype=np.int32)  # what d_want holds (as of the last upload)
         self.h_lp: list = [None, None]
         self._pf_lp: list = [None, None]  # pinned records of in-flight prefill steps
+        # per-request LoRA (lora_setup, once adapters are configured): the decode rows' adapter slots -
+        # a graph input of its own like d_pslot - and a second set of decode graphs for steps with
+        # adapter rows, captured from the first adapter request on (lora_enable); a step without an
+        # adapter row replays the plain graphs
+        self.d_lslot: Optional[torch.Tensor] = None
+        self._lslot_sent = None
+        self.lora_on = False
+        self.graphs_lora: dict[int, list] = {}
         self.decode_ws = ops.decode_workspace(B, model.hq, D, self.max_blocks_per_seq * BLOCK_SIZE, dev, model.hkv) \
             if self.is_gpu else None
         # pinned host staging, double-buffered: with pipelined decode the host fills step N+1's
@@ -177,7 +185,7 @@ class ModelRunner:
         self._pen_free = list(range(self.B - 1, -1, -1))
         if self.graphs:
             buckets = sorted(self.graphs)
-            self.graphs = {}
+            self.graphs, self.graphs_lora = {}, {}
             self.capture_graphs(buckets)
 
     def penalty_release(self, seq) -> None:
@@ -232,7 +240,7 @@ class ModelRunner:
         self._gd_free = list(range(self.B - 1, -1, -1))
         if self.graphs:
             buckets = sorted(self.graphs)
-            self.graphs = {}
+            self.graphs, self.graphs_lora = {}, {}
             self.capture_graphs(buckets)
 
     def guide_release(self, seq) -> None:
@@ -280,6 +288,41 @@ class ModelRunner:
                 "guides_resident": g.guides_resident if g is not None else 0,
                 "guide_slots_in_use": len(self._gd_slot)}
 
+    # --------------------------------------------------------------------- per-request LoRA
+    def lora_setup(self) -> None:
+        """The model holds adapters (CausalLM.enable_lora): allocate the decode rows' slot buffer."""
+        if self.d_lslot is None:
+            self.d_lslot = torch.full((self.B,), -1, dtype=torch.int32, device=self.device)
+            self._lslot_sent = np.full(self.B, -1, dtype=np.int32)
+
+    def lora_enable(self) -> None:
+        """The first adapter request: from now on decode graphs exist in a second set, for steps
+        with adapter rows (captured here for the buckets captured so far)."""
+        if self.lora_on:
+            return
+        if self.d_lslot is None:
+            raise RuntimeError("lora_enable before lora_setup")
+        self.lora_on = True
+        if self.graphs:
+            self.capture_graphs(sorted(self.graphs), only_lora=True)
+
+    def _upload_lslot(self, seqs: list) -> bool:
+        """Decode rows -> adapter slots, copied to ``d_lslot`` in front of the step only when it
+        differs from what the device holds.  False: no row of the step uses an adapter (nothing is
+        uploaded - the step runs the plain path, which does not read the buffer)."""
+        if not self.lora_on:
+            return False
+        sl = [getattr(s, "lora_slot", -1) for s in seqs]
+        if max(sl, default=-1) < 0:
+            return False
+        m = np.full(self.B, -1, dtype=np.int32)
+        m[: len(seqs)] = sl
+        if not np.array_equal(m, self._lslot_sent):
+            self._lslot_sent = m
+            h = torch.from_numpy(m)
+            self.d_lslot.copy_(h.pin_memory() if self.is_gpu else h, non_blocking=True)
+        return True
+
     # --------------------------------------------------------------------- token log-probabilities
     def logprob_enable(self) -> None:
         """Allocate the logprob buffers on first use.  Decode graphs captured without the extra
@@ -295,7 +338,7 @@ class ModelRunner:
         self.lp_on = True
         if self.graphs:
             buckets = sorted(self.graphs)
-            self.graphs = {}
+            self.graphs, self.graphs_lora = {}, {}
             self.capture_graphs(buckets)
 
     @staticmethod
@@ -383,7 +426,8 @@ class ModelRunner:
                      cst=len(seqs) if paged else 0, bt=len(seqs) * W, dbt=nd * Wd, dlen=nd,
                      mcu=len(seqs) + 2 if kA else 0, mqs=nq if kA else 0, mst=nq if kA else 0,
                      mlidx=len(seqs) if kA else 0, pslot=R if self.pen is not None else 0,
-                     want=R if self.lp_on else 0, gslot=R if self.gd is not None else 0)
+                     want=R if self.lp_on else 0, gslot=R if self.gd is not None else 0,
+                     lslot=T if self.lora_on and any(getattr(s, "lora_slot", -1) >= 0 for s in rows) else 0)
         off, o = {}, 0
         for k, n in sizes.items():
             off[k] = o
@@ -426,6 +470,12 @@ class ModelRunner:
             for i, (s, c, n) in enumerate(zip(seqs, starts, lens)):
                 slot = self._guide_slot(s, take=True)
                 v["gslot"][nd + i] = slot if c + n >= s.num_tokens else -1
+        if sizes["lslot"]:  # one adapter slot per token row of the step
+            v["lslot"][:nd] = [getattr(q, "lora_slot", -1) for q in decode]
+            o = nd
+            for s, n in zip(seqs, lens):
+                v["lslot"][o:o + n] = getattr(s, "lora_slot", -1)
+                o += n
         lp_want = None
         if self.lp_on:
             # a chunk short of its prompt's end samples a token nobody keeps: no logprobs for it
@@ -458,6 +508,8 @@ class ModelRunner:
         dv = {k: d[off[k]:off[k] + n] for k, n in sizes.items()}
         meta = AttnMeta(is_prefill=True, positions=dv["pos"], slot_mapping=dv["slots"], cu_seqlens=dv["cu"],
                         qb_seq=dv["qs"], qb_start=dv["st"], logits_idx=dv["lidx"].long())
+        if sizes["lslot"]:
+            meta.lora_slot = dv["lslot"]
         if paged:
             meta.ctx_start = dv["cst"]
             meta.block_tables = dv["bt"].view(len(seqs), W)
@@ -509,22 +561,26 @@ class ModelRunner:
         return DecodeHandle(R, ev, out, lp=h_lp, lp_want=lp_want)
 
     # --------------------------------------------------------------------- decode
-    def _decode_body(self, b: int) -> None:
+    def _decode_body(self, b: int, lora: bool = False) -> None:
         # pipelined decode: a row whose input is the token sampled by the previous step (still in
         # flight when this step was enqueued) takes it from d_out on the device (d_src = its row
         # there); other rows take the host-provided id - resolved by the model's first kernel
         meta = AttnMeta(is_prefill=False, positions=self.d_pos[:b], slot_mapping=self.d_slots[:b],
                         block_tables=self.d_bt[:b], seq_lens=self.d_lens[:b], decode_ws=self.decode_ws,
-                        dec_src=self.d_src[:b], dec_prev=self.d_out)
+                        dec_src=self.d_src[:b], dec_prev=self.d_out, lora_slot=self.d_lslot[:b] if lora else None)
         logits = self.model.forward(self.d_ids[:b], meta, self.kv)
         self._sample(logits, self.d_temp[:b], self.d_topk[:b], self.d_topp[:b], out=self.d_out[:b],
                      pslot=self.d_pslot[:b], gslot=self.d_gslot[:b])
         if self.lp_on:  # after the sampler on the stream: it reads the tokens just drawn
             ops.token_logprobs(logits, self.d_out[:b], self.d_want[:b], out=self.d_lp[:b])
 
-    def capture_graphs(self, buckets: Optional[list[int]] = None) -> None:
+    def capture_graphs(self, buckets: Optional[list[int]] = None, only_lora: bool = False) -> None:
+        """Capture the decode graphs of ``buckets`` (all by default): the plain set and, once an
+        adapter request was seen (lora_on), the set for steps with adapter rows; ``only_lora``: the
+        latter alone (lora_enable)."""
         if not (self.is_gpu and self.cfg.use_graphs):
             return
+        kinds = ([] if only_lora else [False]) + ([True] if self.lora_on else [])
         torch.cuda.synchronize()
         # replays must not disturb real sequences: capture with empty rows (len 0, no cache write)
         self.d_lens.zero_()
@@ -536,26 +592,31 @@ class ModelRunner:
         if self.lp_on:  # ... and compute no logprobs
             self.d_want.fill_(-1)
             self._want_sent[:] = -1
+        if self.d_lslot is not None:  # ... and apply no adapter
+            self.d_lslot.fill_(-1)
+            self._lslot_sent[:] = -1
         rng_state, out_state = self.rng.clone(), self.d_out.clone()
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
-            for _ in range(2):
-                self._decode_body(self.B)
+            for lora in kinds:
+                for _ in range(2):
+                    self._decode_body(self.B, lora)
         torch.cuda.current_stream().wait_stream(s)
         torch.cuda.synchronize()
         self.graph_pool = torch.cuda.graph_pool_handle()
         for b in sorted(buckets or self.buckets, reverse=True):
             n_el = _Staging.prefix(self.B, self.max_blocks_per_seq, b)
-            gs = []
-            for st in (self.stage if self.graph_h2d else [None]):
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, pool=self.graph_pool):
-                    if st is not None:
-                        self.d_all[:n_el].copy_(st.h_all[:n_el], non_blocking=True)
-                    self._decode_body(b)
-                gs.append(g)
-            self.graphs[b] = gs
+            for lora in kinds:
+                gs = []
+                for st in (self.stage if self.graph_h2d else [None]):
+                    g = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(g, pool=self.graph_pool):
+                        if st is not None:
+                            self.d_all[:n_el].copy_(st.h_all[:n_el], non_blocking=True)
+                        self._decode_body(b, lora)
+                    gs.append(g)
+                (self.graphs_lora if lora else self.graphs)[b] = gs
         torch.cuda.synchronize()
         self.rng.copy_(rng_state)
         self.d_out.copy_(out_state)
@@ -607,9 +668,10 @@ class ModelRunner:
         if self.gd is not None:
             self._upload_gslot(seqs)
         lp_want = self._upload_want(seqs) if self.lp_on else None
+        lora = self._upload_lslot(seqs)
         if publish is not None:
             publish(st.message(n, b, n_el))
-        return self._launch_staged(st, n, b, n_el, lp_want)
+        return self._launch_staged(st, n, b, n_el, lp_want, lora)
 
     def decode_launch_raw(self, n: int, b: int, n_el: int, words: np.ndarray) -> "DecodeHandle":
         """TP worker: launch the decode step the leader staged (its raw staging words)."""
@@ -619,10 +681,11 @@ class ModelRunner:
         return self._launch_staged(st, n, b, n_el)
 
     def _launch_staged(self, st: "_Staging", n: int, b: int, n_el: int,
-                       lp_want: Optional[list] = None) -> "DecodeHandle":
+                       lp_want: Optional[list] = None, lora: bool = False) -> "DecodeHandle":
         """``lp_want`` (logprobs enabled and some row of the step asks): the rows' wants - their
-        records are read back beside the tokens."""
-        gs = self.graphs.get(b)
+        records are read back beside the tokens.  ``lora``: some row of the step uses an adapter -
+        the graph set captured with ``d_lslot`` as an input."""
+        gs = (self.graphs_lora if lora else self.graphs).get(b)
         if gs is not None and self.graph_h2d:
             gs[st.idx].replay()  # its first node copies this staging buffer (n_el = the bucket's prefix)
         else:
@@ -630,7 +693,7 @@ class ModelRunner:
             if gs is not None:
                 gs[0].replay()
             else:
-                self._decode_body(b)
+                self._decode_body(b, lora)
         self.n_steps["decode"] += 1
         if self.on_launched is not None:
             self.on_launched()

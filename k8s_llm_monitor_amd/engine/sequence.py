@@ -34,6 +34,8 @@ class SamplingParams:
     # {"regex": str}, {"json_schema": dict}; the answer then matches it in full when it finishes
     # with "stop" (cut by max_tokens or the deadline it may be an incomplete match)
     guide: Optional[dict] = None
+    # per-request LoRA: the name of a configured adapter (EngineConfig.lora_adapters), None = the base model
+    adapter: Optional[str] = None
 
     def has_penalties(self) -> bool:
         return self.repetition_penalty != 1.0 or self.presence_penalty != 0.0 or self.frequency_penalty != 0.0
@@ -80,6 +82,10 @@ class Sequence:
     user: object = None  # opaque payload for the caller (future, callback, ...)
     deadline: Optional[float] = None  # time.perf_counter() by which the answer is due (engine.add_request)
     guide: object = None  # the compiled engine.guide.Guide of params.guide (engine.add_request)
+    # per-request LoRA (engine.add_request): the adapter's slot in the model's arena (-1: the base
+    # model) and the seed of its prefix-cache hash chain (0: the base model's hashes)
+    lora_slot: int = -1
+    hash_seed: int = 0
 
     @property
     def num_tokens(self) -> int:

@@ -83,6 +83,7 @@ class LocalEngineBackend:
         eng = service.engine
         mml = getattr(getattr(eng, "cfg", None), "max_model_len", None) or (1 << 30)
         self.max_len = min(int(mml), int(eng.model_cfg.max_position))  # the engine's per-sequence cap
+        self.adapters = set(getattr(eng, "adapters", None) or ())  # the configured LoRA adapters' names
 
     def max_prompt_tokens(self, max_tokens: Optional[int] = None) -> int:
         """Prompt tokens that still leave room for ``max_tokens`` answer tokens (preamble included);
@@ -97,8 +98,11 @@ class LocalEngineBackend:
                  request_id: Optional[str] = None, ignore_eos: bool = False,
                  top_p: Optional[float] = None, presence_penalty: Optional[float] = None,
                  frequency_penalty: Optional[float] = None, repetition_penalty: Optional[float] = None,
-                 logprobs: bool = False, top_logprobs: int = 0, guide: Optional[dict] = None) -> GenResult:
-        """``logprobs`` / ``top_logprobs`` (0..20): the result carries ``logprobs``, one entry per
+                 logprobs: bool = False, top_logprobs: int = 0, guide: Optional[dict] = None,
+                 adapter: Optional[str] = None) -> GenResult:
+        """``adapter``: the name of a configured LoRA adapter (``llm.lora_adapters``) the answer is
+        generated under; an unknown name is a ``ValueError``.
+        ``logprobs`` / ``top_logprobs`` (0..20): the result carries ``logprobs``, one entry per
         answer token - its log-probability under the model's distribution (before penalties,
         temperature and top-k / top-p) and that many most likely alternatives.  ``guide``
         (engine/guide.py: ``{"choice": [...]}``, ``{"regex": "..."}`` or ``{"json_schema": {...}}``):
@@ -113,7 +117,7 @@ class LocalEngineBackend:
                            repetition_penalty=d.repetition_penalty if repetition_penalty is None else repetition_penalty,
                            presence_penalty=d.presence_penalty if presence_penalty is None else presence_penalty,
                            frequency_penalty=d.frequency_penalty if frequency_penalty is None else frequency_penalty,
-                           logprobs=logprobs, top_logprobs=top_logprobs, guide=guide)
+                           logprobs=logprobs, top_logprobs=top_logprobs, guide=guide, adapter=adapter)
         budget = self.answer_budget_s
         fut = self.svc.submit(P.SYSTEM_PREAMBLE + prompt, p, request_id,
                               deadline=time.perf_counter() + budget if budget else None)
@@ -369,6 +373,7 @@ class AnalysisService:
         self.backend = backend
         self.routes = dict(routes or {})
         self.guide_max_states = 512  # llm.guide_max_states (set by the application)
+        self.analysis_adapters: dict = {}  # llm.analysis_adapters: analysis type -> LoRA adapter name (application)
         self.manager = manager
         self.client = client
         self.analyzer = analyzer
@@ -459,8 +464,9 @@ class AnalysisService:
 
     # ------------------------------------------------------------------ entry points
     def _respond(self, rid: str, kind: str, prompt: str, extra: dict, max_tokens: Optional[int] = None,
-                 ignore_eos: bool = False, logprobs: bool = False, guide: Optional[dict] = None) -> AnalysisResponse:
-        """``guide``: passed on to the backend (``generate(guide=)``).
+                 ignore_eos: bool = False, logprobs: bool = False, guide: Optional[dict] = None,
+                 adapter: Optional[str] = None) -> AnalysisResponse:
+        """``guide`` / ``adapter``: passed on to the backend (``generate(guide=, adapter=)``).
         ``logprobs``: the record's result gains ``mean_logprob`` and ``min_logprob`` over the
         answer's tokens (None for an empty answer or a backend without a model) - how sure the
         model was of what it wrote."""
@@ -471,6 +477,8 @@ class AnalysisService:
             lp_kw = {"logprobs": True} if logprobs else {}
             if guide is not None:
                 lp_kw["guide"] = guide
+            if adapter is not None:
+                lp_kw["adapter"] = adapter
             g = backend.generate(prompt, max_tokens=max_tokens or self.max_tokens, request_id=rid,
                                  ignore_eos=ignore_eos, **lp_kw)
             if logprobs:
@@ -519,15 +527,28 @@ class AnalysisService:
         yield resp
 
     def query(self, question: str, max_tokens: Optional[int] = None, ignore_eos: bool = False,
-              context_text: Optional[str] = None, logprobs: bool = False) -> AnalysisResponse:
+              context_text: Optional[str] = None, logprobs: bool = False,
+              adapter: Optional[str] = None) -> AnalysisResponse:
         """POST /api/v1/query (README.md:91-96; not implemented by the reference).  ``context_text``
         lets a caller supply the cluster state itself (e.g. another collector's snapshot).
-        ``logprobs``: the result carries ``mean_logprob`` / ``min_logprob`` of the answer."""
+        ``logprobs``: the result carries ``mean_logprob`` / ``min_logprob`` of the answer.
+        ``adapter``: a configured LoRA adapter's name (an unknown one is a ``ValueError``)."""
+        self.check_adapter(adapter, "query")
         rid = uuid.uuid4().hex
         ctx = context_text if context_text else self.cluster_context()
         ctx = self._fit(ctx, P.build_query_prompt("", question), max_tokens, "query")
         prompt = P.build_query_prompt(ctx, question)
-        return self._respond(rid, "query", prompt, {"question": question}, max_tokens, ignore_eos, logprobs)
+        return self._respond(rid, "query", prompt, {"question": question}, max_tokens, ignore_eos, logprobs,
+                             adapter=adapter)
+
+    def check_adapter(self, adapter, kind: str) -> None:
+        """``adapter`` (None: the base model) must be a LoRA adapter the backend serving ``kind``
+        has loaded: the caller's error (HTTP 400) before any work is queued."""
+        if adapter is None:
+            return
+        known = getattr(self.backend_for(kind), "adapters", None) or ()
+        if not isinstance(adapter, str) or adapter not in known:
+            raise ValueError(f"unknown adapter {adapter!r} (configured: {sorted(known) or 'none'})")
 
     def analyze(self, req: AnalysisRequest) -> AnalysisResponse:
         kind = req.type or "anomaly_detection"
@@ -541,6 +562,9 @@ class AnalysisService:
         if kind not in ("anomaly_detection", "root_cause"):
             raise ValueError(f"unknown analysis type: {kind}")
         mt = int(params.get("max_tokens") or 0) or None
+        # the request's adapter, else the one configured for this analysis type (llm.analysis_adapters)
+        adapter = params.get("adapter") if params.get("adapter") is not None else self.analysis_adapters.get(kind)
+        self.check_adapter(adapter, kind)
         guide = None
         if params.get("response_schema") is not None:  # the answer is compact JSON of this schema
             from ..engine.guide import compile_guide
@@ -552,7 +576,7 @@ class AnalysisService:
         ctx = self._fit(self.cluster_context(), P.build_analysis_prompt(kind, "", params), mt, kind)
         prompt = P.build_analysis_prompt(kind, ctx, params)
         return self._respond(uuid.uuid4().hex, kind, prompt, {"parameters": params}, mt,
-                             logprobs=params.get("logprobs") is True, guide=guide)
+                             logprobs=params.get("logprobs") is True, guide=guide, adapter=adapter)
 
     def explain_pod_communication(self, analysis, max_tokens: Optional[int] = None,
                                   ignore_eos: bool = False) -> AnalysisResponse:

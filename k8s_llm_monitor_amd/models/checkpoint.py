@@ -28,6 +28,9 @@ Name maps (HF -> this framework):
 from __future__ import annotations
 
 import json
+import math
+import re
+from dataclasses import dataclass, field
 from pathlib import Path
 from typing import Iterator, Optional, Union
 
@@ -354,3 +357,115 @@ def save_checkpoint(model, path: PathLike, max_shard_bytes: int = 4 << 30) -> Pa
     if n > 1:
         (out / "model.safetensors.index.json").write_text(json.dumps({"metadata": {}, "weight_map": index}, indent=2))
     return out
+
+
+# ----------------------------------------------------------------------------- LoRA adapters (PEFT layout)
+
+
+LORA_PREFIX = "base_model.model.model.layers."
+_LORA_KEY = re.compile(r"^base_model\.model\.model\.layers\.(\d+)\.(?:self_attn|mlp)\."
+                       r"([a-z]+_proj)\.lora_([AB])\.weight$")
+_LORA_PARENT = {"q_proj": "self_attn", "k_proj": "self_attn", "v_proj": "self_attn", "o_proj": "self_attn",
+                "down_proj": "mlp", "gate_proj": "mlp", "up_proj": "mlp"}
+
+
+@dataclass
+class LoraAdapter:
+    """One low-rank adapter as PEFT stores it: ``tensors[(layer, module)] = (lora_A [r, in], lora_B
+    [out, r])`` for ``module`` in ``target_modules``; the served delta is ``scaling * B (A x)``."""
+
+    r: int
+    lora_alpha: float
+    target_modules: tuple
+    tensors: dict = field(default_factory=dict)
+    use_rslora: bool = False
+    name: str = ""
+
+    @property
+    def scaling(self) -> float:
+        return self.lora_alpha / (math.sqrt(self.r) if self.use_rslora else self.r)
+
+    @property
+    def nbytes(self) -> int:
+        return sum(a.numel() * a.element_size() + b.numel() * b.element_size() for a, b in self.tensors.values())
+
+
+def load_lora(path: PathLike, name: Optional[str] = None) -> LoraAdapter:
+    """Read a PEFT LoRA directory (``adapter_config.json`` + ``adapter_model.safetensors``, memory-
+    mapped) without the ``peft`` package.  Raises ValueError, naming the reason, for what the
+    serving path does not apply (DoRA, trained biases, ``modules_to_save``) and for tensors it does
+    not consume."""
+    p = Path(path)
+    name = name or p.name
+    cfg = json.loads((p / "adapter_config.json").read_text())
+    if cfg.get("peft_type", "LORA") != "LORA":
+        raise ValueError(f"LoRA {name}: peft_type {cfg.get('peft_type')!r} is not supported (LORA only)")
+    if cfg.get("use_dora"):
+        raise ValueError(f"LoRA {name}: use_dora is not supported (DoRA rescales the merged weight's columns)")
+    if cfg.get("bias", "none") != "none":
+        raise ValueError(f"LoRA {name}: bias {cfg.get('bias')!r} is not supported (the projections take no bias; "
+                         "only bias = 'none')")
+    if cfg.get("modules_to_save"):
+        raise ValueError(f"LoRA {name}: modules_to_save {cfg['modules_to_save']!r} is not supported (one base model "
+                         "stays resident; an adapter cannot replace whole modules)")
+    r, alpha = int(cfg["r"]), float(cfg.get("lora_alpha", cfg["r"]))
+    if r < 1:
+        raise ValueError(f"LoRA {name}: rank r = {r}")
+    tm = cfg.get("target_modules") or ()
+    targets = tuple(sorted({tm} if isinstance(tm, str) else set(tm)))
+    src = SafetensorsDir(p / "adapter_model.safetensors")
+    halves: dict = {}
+    unused = []
+    for k in src.keys():
+        m = _LORA_KEY.match(k)
+        if not m or m.group(2) not in targets or _LORA_PARENT.get(m.group(2)) != k.split(".")[5]:
+            unused.append(k)
+            continue
+        halves.setdefault((int(m.group(1)), m.group(2)), {})[m.group(3)] = src.get(k)
+    if unused:
+        unused.sort()
+        raise ValueError(f"LoRA {name}: adapter tensors not consumed: {unused[:8]}{' ...' if len(unused) > 8 else ''}")
+    tensors = {}
+    for key, h in sorted(halves.items()):
+        if set(h) != {"A", "B"}:
+            raise ValueError(f"LoRA {name}: layer {key[0]} {key[1]} has lora_{'A' if 'A' in h else 'B'} only")
+        tensors[key] = (h["A"], h["B"])
+    return LoraAdapter(r=r, lora_alpha=alpha, target_modules=targets, tensors=tensors,
+                       use_rslora=bool(cfg.get("use_rslora", False)), name=name)
+
+
+def save_lora(adapter: LoraAdapter, path: PathLike) -> Path:
+    """Write ``adapter`` in the PEFT layout :func:`load_lora` reads."""
+    from safetensors.torch import save_file
+
+    out = Path(path)
+    out.mkdir(parents=True, exist_ok=True)
+    cfg = {"peft_type": "LORA", "task_type": "CAUSAL_LM", "r": adapter.r, "lora_alpha": adapter.lora_alpha,
+           "target_modules": list(adapter.target_modules), "use_rslora": adapter.use_rslora, "bias": "none",
+           "use_dora": False, "modules_to_save": None, "lora_dropout": 0.0}
+    (out / "adapter_config.json").write_text(json.dumps(cfg, indent=2))
+    sd = {}
+    for (layer, mod), (A, B) in adapter.tensors.items():
+        base = f"{LORA_PREFIX}{layer}.{_LORA_PARENT[mod]}.{mod}."
+        sd[base + "lora_A.weight"] = A.detach().to("cpu").contiguous().clone()
+        sd[base + "lora_B.weight"] = B.detach().to("cpu").contiguous().clone()
+    save_file(sd, str(out / "adapter_model.safetensors"), metadata={"format": "pt"})
+    return out
+
+
+def merge_lora(model, adapter: LoraAdapter) -> None:
+    """Fold ``adapter`` into a TP=1 model's weights in place, ``W + scaling * B A`` computed in fp32
+    and rounded to the model's dtype: the model an adapter applied at run time must equal (tests, export)."""
+    c, D = model.cfg, model.D
+    nq, nk = c.n_heads * D, c.n_kv_heads * D
+    rows = {"q_proj": ("wqkv", 0, nq), "k_proj": ("wqkv", nq, nq + nk), "v_proj": ("wqkv", nq + nk, nq + 2 * nk),
+            "o_proj": ("wo", 0, c.d_model), "down_proj": ("w2", 0, c.d_model)}
+    canon = [{k: model.canonical(L, k).float().clone() for k in ("wqkv", "wo", "w13", "w2")} for L in model.layers]
+    for (layer, mod), (A, B) in adapter.tensors.items():
+        key, lo, hi = rows[mod]
+        canon[layer][key][lo:hi] += adapter.scaling * (B.float().to(model.device) @ A.float().to(model.device))
+    model.begin_load()
+    for L, cw in zip(model.layers, canon):
+        for k, w in cw.items():
+            L[k] = w.to(model.dtype).contiguous()
+    model._init_skinny()

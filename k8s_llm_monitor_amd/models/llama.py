@@ -52,6 +52,13 @@ the codes (``_release_bf16``).  ``PREFILL_WEIGHTS = "mxfp4"`` does the same over
 ``L[key]`` is the packed e2m1 codes ([out/16, in/128, 64, 16] uint8) and ``*_qs`` their packed e8m0
 block scales; ``ops.is_codes`` is true of either.
 
+Per-request LoRA adapters (``enable_lora`` / ``load_adapter``, ``AttnMeta.lora_slot``): one base model
+stays resident and a step's rows may each name an adapter of the arena (ops.LoraState).  On the skinny
+decode loop an adapter's delta is one more split-K slab after the qkv, o and down GEMMs (ops.lora_slab;
+their consumers sum ``ns + 1`` slabs); the generic layer loop adds it in place (ops.lora_add) to the
+plain qkv (before the rotation), o and dense down outputs.  A step without ``lora_slot`` takes exactly
+the paths it takes without adapters.
+
 ``to_resident`` / ``to_canonical`` convert one projection between CANONICAL and another layout;
 ``_init_skinny`` / ``_init_dec`` move a model forward, ``begin_load`` takes it out of service
 (LOADING) until the loader's closing ``_init_skinny``.
@@ -107,6 +114,9 @@ class AttnMeta:
     # TP > 1 prefill as two micro-batches of whole sequences: (meta of rows [0, TA), meta of rows
     # [TA, T), TA); their row-parallel all-reduces overlap each other's compute (_prefill_overlap)
     micro: Optional[tuple] = None
+    # per-request LoRA: the adapter slot of every row of the step ([T] int32, -1 = the base model);
+    # None when no row uses an adapter - the step then takes exactly the paths it takes without LoRA
+    lora_slot: Optional[torch.Tensor] = None
 
 
 def _seed_for(name: str, seed: int) -> int:
@@ -266,6 +276,8 @@ class CausalLM:
         # the decode path's state, (re)built by _init_skinny
         self._skinny_ws = self.lm_head_d = self.lm_head_q = self.lm_head_qs = None
         self._rc_o, self._dec_wide, self._attn_rope = 0, False, False
+        self.lora: Optional[ops.LoraState] = None  # the resident adapters' arena (enable_lora)
+        self._lora_cap = 0
         self._build()
         self._init_skinny()
         self.cos_sin = None
@@ -407,6 +419,74 @@ class CausalLM:
                     del w2
             self.layers.append(L)
 
+    # ------------------------------------------------------------------ per-request LoRA adapters
+    # PEFT target module -> (adapted projection, its block inside the fused qkv)
+    LORA_MODULES = {"q_proj": ("wqkv", 0), "k_proj": ("wqkv", 1), "v_proj": ("wqkv", 2), "o_proj": ("wo", 0),
+                    "down_proj": ("w2", 0)}
+
+    def enable_lora(self, slots: int, max_rank: int = 64) -> "ops.LoraState":
+        """Allocate the adapters' arena (ops.LoraState, ``slots`` adapters of rank up to
+        ``max_rank``) and one more slab per projection in the decode workspace.  The fused qkv is
+        one adapted projection of rank capacity 3 x the rounded ``max_rank``: q, k and v at their own
+        rank rows, B block-diagonal over their output ranges.  Steps name their rows' adapters
+        through ``AttnMeta.lora_slot``; without it nothing changes."""
+        c = self.cfg
+        if self.tp > 1:
+            raise ValueError("LoRA adapters need tp_size == 1 (the TP workers replay the leader's staging words, "
+                             "which carry no adapter slots)")
+        if c.arch == "gpt2":
+            raise ValueError("LoRA adapters are not supported for arch 'gpt2' (Llama-family models only)")
+        if max_rank < 1:
+            raise ValueError(f"lora_max_rank must be >= 1, not {max_rank}")
+        cap = -(-int(max_rank) // ops.LORA_RANK_ALIGN) * ops.LORA_RANK_ALIGN
+        d, no = c.d_model, self.hq * self.D
+        dims = {"wqkv": ((self.hq + 2 * self.hkv) * self.D, d, 3 * cap), "wo": (d, no, cap)}
+        if not c.is_moe:
+            dims["w2"] = (d, self.f_local, cap)
+        self.lora = ops.LoraState(slots, c.n_layers, dims, self.device, self.dtype)
+        self._lora_cap, self._lora_max_rank = cap, int(max_rank)
+        if self._skinny_ws is not None:
+            self._skinny_ws = torch.empty(self._skinny_ws_numel(), dtype=torch.float32, device=self.device)
+        return self.lora
+
+    def load_adapter(self, slot: int, adapter) -> None:
+        """Make arena slot ``slot`` the adapter (models/checkpoint.py ``LoraAdapter``): every
+        ``(layer, module)`` pair into its projection, zeros where the adapter has no target.  Raises
+        ValueError, naming the reason, for what the serving path cannot apply."""
+        if self.lora is None:
+            raise ValueError("load_adapter: no LoRA arena (enable_lora first)")
+        c, name = self.cfg, getattr(adapter, "name", "") or "adapter"
+        for t in adapter.target_modules:
+            if t in ("gate_proj", "up_proj"):
+                raise ValueError(f"LoRA {name}: target module {t!r} is not supported (the decode gate_up GEMM fuses "
+                                 "SwiGLU into its epilogue; the delta would have to enter before it)")
+            if t not in self.LORA_MODULES:
+                raise ValueError(f"LoRA {name}: unknown target module {t!r}")
+            if t == "down_proj" and c.is_moe:
+                raise ValueError(f"LoRA {name}: target module 'down_proj' is not supported on a MoE model")
+        if adapter.r > self._lora_max_rank:
+            raise ValueError(f"LoRA {name}: rank {adapter.r} exceeds lora_max_rank {self._lora_max_rank}")
+        d, D = c.d_model, self.D
+        shapes = {"q_proj": (self.hq * D, d), "k_proj": (self.hkv * D, d), "v_proj": (self.hkv * D, d),
+                  "o_proj": (d, self.hq * D), "down_proj": (d, self.f_local)}
+        n0 = {0: 0, 1: self.hq * D, 2: (self.hq + self.hkv) * D}
+        for (layer, mod), (A, B) in adapter.tensors.items():
+            if mod not in adapter.target_modules:
+                raise ValueError(f"LoRA {name}: tensors for {mod!r}, which is not among its target modules")
+            if not 0 <= layer < c.n_layers:
+                raise ValueError(f"LoRA {name}: layer {layer} outside the base model's {c.n_layers} layers")
+            out, inn = shapes[mod]
+            if tuple(A.shape) != (adapter.r, inn) or tuple(B.shape) != (out, adapter.r):
+                raise ValueError(f"LoRA {name}: layer {layer} {mod} lora_A {list(A.shape)} / lora_B {list(B.shape)} do "
+                                 f"not match the base model's [{out}, {inn}] at rank {adapter.r}")
+        for p in self.lora.dims:  # a reload of the slot leaves nothing of the adapter before
+            self.lora.A[p][:, slot].zero_()
+            self.lora.B[p][:, slot].zero_()
+        for (layer, mod), (A, B) in adapter.tensors.items():
+            proj, blk = self.LORA_MODULES[mod]
+            self.lora.load(slot, layer, proj, A, B, r0=blk * self._lora_cap, n0=n0[blk] if proj == "wqkv" else 0)
+        self.lora.set_scaling(slot, adapter.scaling)
+
     def resident_weight_bytes(self) -> int:
         """Bytes of every distinct weight tensor this rank holds (parameters, decode-layout copies,
         the LM head's packed copy and the fp8 / mxfp4 encodings with their scales; a tensor referenced
@@ -446,21 +526,31 @@ class CausalLM:
         x = ops.embedding(ids, self.embed, vocab_start=self.v_lo)
         return tp_all_reduce(x, self.ps)
 
-    def _attention(self, L: dict, x: torch.Tensor, meta: AttnMeta, kv) -> torch.Tensor:
-        o = self._attn_core(L, x, meta, kv)
+    def _lora_slot(self, meta: AttnMeta) -> Optional[torch.Tensor]:
+        """The step's adapter slots, where it has adapter rows and this model holds adapters."""
+        return meta.lora_slot if self.lora is not None else None
+
+    def _attention(self, L: dict, x: torch.Tensor, meta: AttnMeta, kv, li: int = -1) -> torch.Tensor:
+        o = self._attn_core(L, x, meta, kv, li=li)
         y = ops.prefill_linear(o, L["wo"], wscale=self._wsc(L, "wo")) if "bo" not in L else F.linear(o, L["wo"])
+        slot = self._lora_slot(meta)
+        if slot is not None:
+            ops.lora_add(self.lora, li, "wo", o, y, slot)
         if "bo" in L and self.rank == 0:
             y += L["bo"]
         return tp_all_reduce(y, self.ps)
 
     def _attn_core(self, L: dict, x: Optional[torch.Tensor], meta: AttnMeta, kv, slabs: Optional[tuple] = None,
                    rows: Optional[int] = None, rownorm: Optional[tuple] = None,
-                   rowscale: Optional[tuple] = None) -> torch.Tensor:
+                   rowscale: Optional[tuple] = None, li: int = -1) -> torch.Tensor:
         """QKV projection, RoPE + KV-cache write, attention; returns the per-head output [T, Hq*D].
         ``slabs = (workspace, splits)``: decode QKV by the split-K skinny GEMM over ``x`` (row-major
         or fragment-packed with ``rows`` valid rows), reduced inside rope_and_cache; the attention
-        output is then written fragment-packed for the o_proj skinny GEMM."""
+        output is then written fragment-packed for the o_proj skinny GEMM.  A step with adapter rows
+        (``meta.lora_slot``; ``li`` = the layer's index) adds the adapters' qkv delta before the
+        rotation: one more slab, or ops.lora_add on the plain projection's output."""
         c = self.cfg
+        lslot = self._lora_slot(meta)
         k_cache, v_cache, kv_scale = (tuple(kv) + (None,))[:3] if kv is not None else (None, None, None)
         partial, ns = None, 0
         roped = False  # q / k already rotated by the qkv GEMM's epilogue
@@ -469,6 +559,8 @@ class CausalLM:
         if slabs is not None:
             ws, splits = slabs
             ns = self._proj_slabs(L, "wqkv", x, T, splits, rownorm)
+            if lslot is not None:
+                ns = ops.lora_slab(self.lora, li, "wqkv", x, T, ws, ns, lslot, rownorm=rownorm)
             if self._attn_rope and not meta.is_prefill and k_cache is not None and c.arch == "llama":
                 # the attention kernel reduces the slabs, applies RoPE and writes the new k / v
                 out = ops.packed_empty(T, self.hq * self.D, self.dtype, self.device)
@@ -479,13 +571,16 @@ class CausalLM:
             qkv = torch.empty(T, ops.w_out(L["wqkv"]), dtype=self.dtype, device=self.device)
         elif "bqkv" in L:
             qkv = F.linear(x, L["wqkv"], L["bqkv"])
-        elif c.arch == "llama" and self.D == 128 and self.cos_sin is not None and not c.qk_norm:
+        elif c.arch == "llama" and self.D == 128 and self.cos_sin is not None and not c.qk_norm and lslot is None:
             # prefill-sized qkv on the tile kernel: RoPE of q / k fused into its epilogue (not for a
-            # QK-norm model: its heads are normalised between the projection and the rotation)
+            # QK-norm model: its heads are normalised between the projection and the rotation, nor on
+            # a step with adapter rows: the rotation comes after the adapters' delta)
             qkv, roped = ops.prefill_linear(x, L["wqkv"], rope=(meta.positions, cs, self.hq + self.hkv),
                                             rowscale=rowscale, wscale=self._wsc(L, "wqkv"))
         else:
             qkv = ops.prefill_linear(x, L["wqkv"], wscale=self._wsc(L, "wqkv"))
+            if lslot is not None:
+                ops.lora_add(self.lora, li, "wqkv", x, qkv, lslot)
         ops.rope_and_cache(qkv, meta.positions, cs, k_cache, v_cache,
                            meta.slot_mapping if k_cache is not None else None, self.hq, self.hkv, self.D,
                            apply_rope=c.arch == "llama" and not roped, partial=partial, nslabs=ns, kv_scale=kv_scale,
@@ -513,7 +608,7 @@ class CausalLM:
                                  self.D, self.scale, workspace=meta.decode_ws, out=out, kv_scale=kv_scale)
         return o
 
-    def _mlp(self, L: dict, x: torch.Tensor, meta: AttnMeta) -> torch.Tensor:
+    def _mlp(self, L: dict, x: torch.Tensor, meta: AttnMeta, li: int = -1) -> torch.Tensor:
         c = self.cfg
         if c.arch == "gpt2":
             h = ops.gelu_tanh(F.linear(x, L["w1"], L["b1"]))
@@ -531,7 +626,11 @@ class CausalLM:
             h = ops.prefill_linear(x, L["w13"], swiglu=self._swg, wscale=self._wsc(L, "w13"))
         else:
             h = ops.silu_mul(F.linear(x, L["w13"]), interleaved=False)
-        return tp_all_reduce(ops.prefill_linear(h, L["w2"], wscale=self._wsc(L, "w2")), self.ps)
+        y = ops.prefill_linear(h, L["w2"], wscale=self._wsc(L, "w2"))
+        slot = self._lora_slot(meta)
+        if slot is not None and "w2" in self.lora.dims:
+            ops.lora_add(self.lora, li, "w2", h, y, slot)
+        return tp_all_reduce(y, self.ps)
 
     def _moe(self, L: dict, x: torch.Tensor, meta: AttnMeta) -> torch.Tensor:
         """Top-k MoE over this rank's experts [e_lo, e_hi).  Tokens are sorted by expert (moe_align)
@@ -747,19 +846,21 @@ class CausalLM:
             residual = h
             if self._use_skinny(meta, h):
                 return self._decode_layers_skinny(None, residual, meta, kv_caches)
-            if self._fused_norm_ok(h):
+            # a step with adapter rows: the plain layer loop below, ops.lora_add after qkv, o and down
+            lora = self._lora_slot(meta) is not None
+            if not lora and self._fused_norm_ok(h):
                 return self._logits(self._prefill_fused_norm(residual, meta, kv_caches))
-            if meta.micro is not None and self.overlap_ok():
+            if not lora and meta.micro is not None and self.overlap_ok():
                 return self._logits(self._prefill_overlap(residual, meta, kv_caches))
             x = ops.rms_norm(h, self.layers[0]["attn_norm"], c.norm_eps)
             n = len(self.layers)
             for i, L in enumerate(self.layers):
                 kv = kv_caches[i] if kv_caches is not None else None
-                if i + 1 == n and self._last_rows_ok(L, h, meta):
+                if i + 1 == n and not lora and self._last_rows_ok(L, h, meta):
                     return self._logits(self._last_rows(L, self._attn_core(L, x, meta, kv), residual, meta))
-                y = self._attention(L, x, meta, kv)
+                y = self._attention(L, x, meta, kv, li=i)
                 x = ops.fused_add_rms_norm(y, residual, L["mlp_norm"], c.norm_eps)
-                y = self._mlp(L, x, meta)
+                y = self._mlp(L, x, meta, li=i)
                 if i + 1 < n:
                     x = ops.fused_add_rms_norm(y, residual, self.layers[i + 1]["attn_norm"], c.norm_eps)
                 else:
@@ -1059,7 +1160,8 @@ class CausalLM:
         dec_rows_max() - DEC_MAX_M for a model on the wide path - not what DEC_ROWS_MAX says at
         the moment, so flipping that switch at run time stays inside the buffer.  MoE: the expert
         down projections write one slab group per local expert, and the EP all-to-all decode runs
-        up to SKINNY_GROUPED_MAX_M received rows per grouped launch."""
+        up to SKINNY_GROUPED_MAX_M received rows per grouped launch.  With resident LoRA adapters
+        (enable_lora) every dense projection has room for one more slab: an adapter's delta."""
         c, split = self.cfg, self._split_qkv
         d, nq, no = c.d_model, (self.hq + 2 * self.hkv) * self.D, self.hq * self.D
         dec_rows = ops.DEC_MAX_M if self._dec_wide else ops.SKINNY_MAX_M
@@ -1075,11 +1177,12 @@ class CausalLM:
                     s = max(s, cfg[0] if cfg else 1)
             return s
 
+        extra = 1 if self.lora is not None else 0  # an adapter's delta is one more slab (ops.lora_slab)
         if c.is_moe:
             mlp = (self.e_hi - self.e_lo) * ops.skinny_nslabs(c.ffn_dim, 1) * d
         else:
-            mlp = most(d, self.f_local) * d
-        n = max(most(nq, d) * nq, most(d, no) * d, mlp)
+            mlp = (most(d, self.f_local) + extra) * d
+        n = max((most(nq, d) + extra) * nq, (most(d, no) + extra) * d, mlp)
         return n * (ops.SKINNY_GROUPED_MAX_M if c.is_moe else dec_rows)
 
     # decode buckets up to this many rows take the row-complete o projection by default: per decode
@@ -1122,18 +1225,21 @@ class CausalLM:
         c, ws, n = self.cfg, self._skinny_ws, len(self.layers)
         eps = c.norm_eps
         M = residual.shape[0]
+        lslot = self._lora_slot(meta)  # adapter rows: every adapted projection gets one more slab
         # first = layer 0's (A operand, rownorm), already produced with the embedding (embed_norm_partial)
         xw, rn = first if first is not None else self._norm_tail(residual, None, 0, self.layers[0]["attn_norm"])
         for i, L in enumerate(self.layers):
             kv = kv_caches[i] if kv_caches is not None else None
-            op = self._attn_core(L, xw, meta, kv, slabs=(ws, self._split_qkv), rows=M, rownorm=rn)
+            op = self._attn_core(L, xw, meta, kv, slabs=(ws, self._split_qkv), rows=M, rownorm=rn, li=i)
             rc = None
-            if M <= self._rc_o and "w13_d" in L:
+            if M <= self._rc_o and "w13_d" in L and lslot is None:  # (no slab for an adapter's delta to join)
                 # o projection row-complete: residual += o and the gate_up GEMM's normed input in
                 # the same launch (no split-K slabs, no add_norm launch)
                 rc = ops.dec_gemm_rc(op, L["wo_d"], M, residual, L["mlp_norm"], eps)
             if rc is None:
                 ns = self._proj_slabs(L, "wo", op, M, self._split_o)
+                if lslot is not None:
+                    ns = ops.lora_slab(self.lora, i, "wo", op, M, ws, ns, lslot)
                 if c.is_moe and self.tp > 1 and self.moe_decode == "a2a":
                     # EP all-to-all MoE: residual += o (all-reduced), then the complete, replicated
                     # MLP output comes back from _moe_a2a_decode
@@ -1161,6 +1267,8 @@ class CausalLM:
             else:
                 act = ops.skinny_swiglu(xw, L["w13_p"], rows=M, packed_out=True, rownorm=rn)
             ns = self._proj_slabs(L, "w2", act, M, self._split_d)
+            if lslot is not None:
+                ns = ops.lora_slab(self.lora, i, "w2", act, M, ws, ns, lslot)
             if i + 1 < n:
                 xw, rn = self._norm_tail(residual, ws, ns, self.layers[i + 1]["attn_norm"], rows=M)
         # final norm feeds the LM head: fragment-packed for the decode GEMM (gemm_decode.hip), or

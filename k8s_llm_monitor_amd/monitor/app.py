@@ -72,7 +72,8 @@ def engine_config(cfg: Config):
                         max_prefill_tokens=cfg.llm.max_prefill_tokens, chunked_prefill=cfg.llm.chunked_prefill,
                         prefix_caching=cfg.llm.prefix_caching, weights=cfg.llm.weights or None,
                         decode_weights=cfg.llm.decode_weights, prefill_weights=cfg.llm.prefill_weights,
-                        kv_cache_dtype=cfg.llm.kv_cache_dtype, guide_max_states=cfg.llm.guide_max_states)
+                        kv_cache_dtype=cfg.llm.kv_cache_dtype, guide_max_states=cfg.llm.guide_max_states,
+                        lora_adapters=dict(cfg.llm.lora_adapters or {}), lora_max_rank=cfg.llm.lora_max_rank)
 
 
 def make_llm_backend(cfg: Config, pstate=None, device: Optional[str] = None):
@@ -163,6 +164,7 @@ def build_monitor(cfg: Config, backend=None, start_manager: bool = True, llm: bo
                                  token_budget=cfg.analysis.prompt_token_budget, max_tokens=cfg.llm.max_tokens,
                                  routes=make_routes(cfg))
     m.analysis.guide_max_states = cfg.llm.guide_max_states
+    m.analysis.analysis_adapters = dict(cfg.llm.analysis_adapters or {})
     m.app = MonitorApp(m.client, m.manager, m.analysis, m.engine_service, llm_timeout_s=float(cfg.llm.timeout))
     m.app.guide_max_states = cfg.llm.guide_max_states
     if hasattr(backend_llm, "answer_budget_s"):  # the engine stops generations before the write timeout

@@ -90,6 +90,13 @@ class LLMConfig:
     # root_cause -> a Llama-3-70B TP=8 server's ".../v1"); unrouted types use this server's backend.
     # YAML mapping, or "type=url,type=url" from the environment (LLM_ROUTES)
     routes: dict = field(default_factory=dict)
+    # per-request LoRA adapters (docs/engine.md): name -> PEFT adapter directory, all loaded at
+    # start-up beside the one resident base model; a request picks one by name.  lora_max_rank: the
+    # rank capacity of the arena (at most 64).  analysis_adapters: analysis type -> adapter name, the
+    # default for /api/v1/analyze requests of that type without parameters.adapter
+    lora_adapters: dict = field(default_factory=dict)
+    lora_max_rank: int = 64
+    analysis_adapters: dict = field(default_factory=dict)
 
 
 @dataclass

@@ -387,6 +387,14 @@ class MonitorApp:
         if want_lp and d.get("stream") is True:
             raise http_error(400, "logprobs are not supported with stream: true")
         lp_kw = {"logprobs": True} if want_lp else {}
+        if d.get("adapter") is not None:  # a configured LoRA adapter's name; an unknown one is a 400
+            if d.get("stream") is True:
+                raise http_error(400, "adapter is not supported with stream: true")
+            try:
+                self.analysis.check_adapter(d["adapter"], "query")
+            except ValueError as e:
+                raise http_error(400, str(e))
+            lp_kw["adapter"] = d["adapter"]
         if d.get("stream") is True:  # Server-Sent Events: {"delta"} events, then event "done" = the record
             gen = self.analysis.query_stream(question, max_tokens=mt, ignore_eos=bool(d.get("ignore_eos", False)),
                                              context_text=ctx_text)
@@ -491,6 +499,10 @@ class MonitorApp:
         if guide is not None:
             pen["guide"] = guide
         backend = self.analysis.backend
+        # the usual convention: a ``model`` equal to a configured LoRA adapter's name selects that
+        # adapter; any other value is what it was before - not looked at
+        if isinstance(d.get("model"), str) and d["model"] in (getattr(backend, "adapters", None) or ()):
+            pen["adapter"] = d["model"]
         try:
             prompt = self.analysis.fit_chat(parts, mt)
             g = self._bounded(lambda: backend.generate(prompt, max_tokens=mt, temperature=temp, top_p=top_p, **pen))
@@ -510,7 +522,8 @@ class MonitorApp:
         if want_lp:
             choice["logprobs"] = {"content": g.get("logprobs") or []}
         return json_reply({"id": "chatcmpl-" + uuid.uuid4().hex, "object": "chat.completion",
-                           "created": int(time.time()), "model": g.get("model") or d.get("model", ""),
+                           "created": int(time.time()),
+                           "model": pen.get("adapter") or g.get("model") or d.get("model", ""),
                            "choices": [choice], "usage": usage})
 
     def _guide_spec(self, d: dict) -> Optional[dict]:

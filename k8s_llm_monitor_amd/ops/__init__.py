@@ -1066,6 +1066,131 @@ def packed_empty(M: int, K: int, dtype, device) -> torch.Tensor:
     return torch.empty(-(-M // 16), K // 32, 64, 8, dtype=dtype, device=device)
 
 
+# ---------------------------------------------------------------- per-request LoRA adapters
+
+LORA_PROJ = ("wqkv", "wo", "w2")  # the adapted projections (the fused qkv is one of them)
+LORA_RANK_ALIGN = 32  # rank capacities are whole r-steps of lora_expand_kernel
+LORA_MAX_CAP = 224  # kernel limit of a projection's rank capacity (the expand kernel's LDS image of t)
+
+
+class LoraState:
+    """The device arena of the resident low-rank adapters (csrc/lora.hip), one slot per adapter.
+
+    Per adapted projection ``p`` of ``LORA_PROJ`` with shape ``dims[p] = (N, K, R)``: ``A[p]``
+    ``[layers, slots, R, K]`` and ``B[p]`` ``[layers, slots, N, R]`` in ``dtype`` (bf16 on the GPU),
+    zero where an adapter has a smaller rank or lacks the target; ``scaling`` fp32 ``[slots]``
+    (``lora_alpha / r``, or ``/ sqrt(r)`` with rslora).  ``R`` is the projection's rank capacity, a
+    multiple of ``LORA_RANK_ALIGN``.  A step's row names its slot through ``ops.lora_slab`` /
+    ``ops.lora_add`` (``slot`` int32, -1 = no adapter)."""
+
+    def __init__(self, slots: int, layers: int, dims: dict, device, dtype=torch.bfloat16):
+        self.slots, self.layers = int(slots), int(layers)
+        if self.slots <= 0 or self.layers <= 0:
+            raise ValueError("a LoRA state needs slots and layers")
+        self.dims, self.dtype = {}, dtype
+        self.A, self.B = {}, {}
+        dev = torch.device(device)
+        for p, (N, K, R) in dims.items():
+            if p not in LORA_PROJ:
+                raise ValueError(f"LoRA: {p!r} is not an adapted projection {LORA_PROJ}")
+            R = -(-int(R) // LORA_RANK_ALIGN) * LORA_RANK_ALIGN
+            if R > LORA_MAX_CAP:
+                raise ValueError(f"LoRA: rank capacity {R} of {p} exceeds the kernels' {LORA_MAX_CAP}")
+            if dev.type == "cuda" and (N % 16 or K % 32):
+                raise ValueError(f"LoRA: {p} [{N}, {K}] needs N % 16 == 0 and K % 32 == 0")
+            self.dims[p] = (int(N), int(K), R)
+            self.A[p] = torch.zeros(self.layers, self.slots, R, K, dtype=dtype, device=dev)
+            self.B[p] = torch.zeros(self.layers, self.slots, N, R, dtype=dtype, device=dev)
+        self.scaling = torch.zeros(self.slots, dtype=torch.float32, device=dev)
+        self.device = self.scaling.device
+
+    @property
+    def nbytes(self) -> int:
+        return sum(t.numel() * t.element_size() for t in (*self.A.values(), *self.B.values(), self.scaling))
+
+    def set_scaling(self, slot: int, scaling: float) -> None:
+        self.scaling[slot] = float(scaling)
+
+    def load(self, slot: int, layer: int, proj: str, A: torch.Tensor, B: torch.Tensor,
+             r0: int = 0, n0: int = 0) -> None:
+        """Adapter ``slot``'s pair of ``(layer, proj)``: ``A`` [r, K] into rank rows ``[r0, r0 + r)``
+        and ``B`` [n, r] into output rows ``[n0, n0 + n)`` of the same rank columns - the fused qkv
+        takes q, k and v at rank offsets 0, cap, 2 cap and their output ranges (B block-diagonal)."""
+        if not 0 <= slot < self.slots:
+            raise ValueError(f"slot {slot} outside [0, {self.slots})")
+        N, K, R = self.dims[proj]
+        r = A.shape[0]
+        if A.shape[1] != K or B.shape[1] != r or r0 + r > R or n0 + B.shape[0] > N:
+            raise ValueError(f"LoRA {proj}: A {list(A.shape)} / B {list(B.shape)} do not fit [{N}, {K}] at rank "
+                             f"capacity {R} (rank offset {r0}, row offset {n0})")
+        self.A[proj][layer, slot, r0:r0 + r] = A.to(self.device, self.dtype)
+        self.B[proj][layer, slot, n0:n0 + B.shape[0], r0:r0 + r] = B.to(self.device, self.dtype)
+
+
+def lora_shrink_plan(K: int) -> int:
+    """K slices S of a lora_shrink launch (``t_part`` [S, M, R]); mirror of k8sllm_lora_shrink_plan,
+    which the binding reports (compared by tests/test_lora_gpu.py)."""
+    nk = K // 32
+    s0 = min(16, max(1, K // 512))
+    per = -(-nk // s0)
+    return -(-nk // per)
+
+
+def _lora_t(state: "LoraState", layer: int, proj: str, x: torch.Tensor, rows: int, slot: torch.Tensor,
+            rownorm: Optional[tuple]) -> tuple:
+    """lora_shrink launch: (t_part [S, M, R] fp32, S)."""
+    N, K, R = state.dims[proj]
+    S = lora_shrink_plan(K)
+    t_part = torch.empty(S * rows * R, dtype=torch.float32, device=x.device)
+    ss, eps = (None, 0.0) if rownorm is None else (rownorm[0], float(rownorm[1]))
+    used = native().lora_shrink(x, state.A[proj][layer], slot, t_part, rows, ss, eps)
+    if used != S:
+        raise RuntimeError(f"lora_shrink: the kernel used {used} K slices, the plan says {S}")
+    return t_part, S
+
+
+def lora_slab(state: "LoraState", layer: int, proj: str, a: torch.Tensor, rows: int, workspace: torch.Tensor,
+              ns: int, slot: torch.Tensor, rownorm: Optional[tuple] = None) -> int:
+    """One more split-K slab for a decode projection: slab ``ns`` of ``workspace`` ([.., rows, N] fp32)
+    ``= scaling[s] * B[s] (A[s] a[row])`` for rows with ``s = slot[row] >= 0``, exact zeros for the
+    others; returns ``ns + 1``.  ``a``: the projection's A operand, fragment-packed with ``rows``
+    valid rows or row-major; ``rownorm = (ss_part, eps)``: its deferred RMSNorm, as the GEMM got it.
+    CPU: ``ref.lora_delta`` in fp32."""
+    N, K, R = state.dims[proj]
+    M = _rows(a, rows)
+    if workspace.numel() < (ns + 1) * M * N:
+        raise ValueError(f"lora_slab: the workspace has no room for slab {ns} of [{M}, {N}]")
+    if not _gpu(a):
+        x = _cpu_a(a, rows)
+        d = ref.lora_delta(x, state.A[proj][layer], state.B[proj][layer], state.scaling, slot)
+        sc = _rn_scale(rownorm, M, K)
+        workspace[ns * M * N:(ns + 1) * M * N].view(M, N).copy_(d * sc if sc is not None else d)
+        return ns + 1
+    t_part, S = _lora_t(state, layer, proj, a, M, slot, rownorm)
+    native().lora_expand(t_part, S, state.B[proj][layer], state.scaling, slot, workspace, M, ns)
+    return ns + 1
+
+
+def lora_add(state: "LoraState", layer: int, proj: str, x: torch.Tensor, y: torch.Tensor, slot: torch.Tensor
+             ) -> torch.Tensor:
+    """``y[row] <- dtype(float(y[row]) + scaling[s] * B[s] (A[s] x[row]))`` in place for rows with
+    ``s = slot[row] >= 0``; the other rows are not touched.  ``x`` [M, K], ``y`` [M, N] row-major.
+    CPU: ``ref.lora_delta`` in fp32."""
+    M = x.shape[0]
+    if y.shape[0] != M or y.shape[1] != state.dims[proj][0] or x.shape[1] != state.dims[proj][1]:
+        raise ValueError(f"lora_add: x {list(x.shape)} / y {list(y.shape)} do not match {proj} {state.dims[proj][:2]}")
+    if M == 0:
+        return y
+    if not _gpu(x):
+        d = ref.lora_delta(x, state.A[proj][layer], state.B[proj][layer], state.scaling, slot)
+        on = (slot[:M] >= 0).nonzero().flatten()
+        y[on] = (y[on].float() + d[on]).to(y.dtype)
+        return y
+    t_part, S = _lora_t(state, layer, proj, x, M, slot, None)
+    native().lora_expand(t_part, S, state.B[proj][layer], state.scaling, slot, y, M, -1)
+    return y
+
+
 def proj_add_rms_norm(a: torch.Tensor, wp: torch.Tensor, residual: torch.Tensor, norm_w: torch.Tensor, eps: float,
                       workspace: Optional[torch.Tensor] = None, splits: Optional[int] = None,
                       out: Optional[torch.Tensor] = None, rows: Optional[int] = None,

@@ -93,6 +93,11 @@ int k8sllm_embed_norm_partial(void* out, long out_stride, void* residual, const 
                               const int* prev, const void* emb, int vocab, const void* w, int M, int d,
                               float* ss_part, hipStream_t s);
 int k8sllm_reduce_slabs(void* out, const float* partial, int S, long n, hipStream_t s);
+int k8sllm_lora_shrink_plan(int K);
+int k8sllm_lora_shrink(const void* x, int packed, long xstride, const void* A, const int* slot, const float* ss_part,
+                       int ss_cols, float eps, float* t_part, long M, int R, int K, int nslots, hipStream_t s);
+int k8sllm_lora_expand(const float* t_part, int S, const void* B, const float* scaling, const int* slot, float* slab,
+                       void* y, long ystride, long M, int N, int R, int nslots, hipStream_t s);
 int k8sllm_reduce_add_rmsnorm(void* out, void* residual, const float* partial, int S, int M, const void* w, int d,
                               float eps, long out_stride, void* out2, hipStream_t s);
 void* k8sllm_car_create(int rank, int world, long max_elems, void* handles, int* err);
@@ -1221,6 +1226,80 @@ void reduce_slabs(torch::Tensor out, torch::Tensor partial, int64_t S) {
   check(k8sllm_reduce_slabs(out.data_ptr(), partial.data_ptr<float>(), (int)S, out.numel(), cur()), "reduce_slabs");
 }
 
+// Per-request LoRA (lora.hip, ops.lora_slab / ops.lora_add).  K slices of a shrink launch over depth K.
+int64_t lora_shrink_plan(int64_t K) { return k8sllm_lora_shrink_plan((int)K); }
+
+// t_part [S, M, R] fp32 = A[slot[row]] . x[row] per K slice; x fragment-packed [ceil(M/16), K/32, 64, 8] or
+// row-major [M, K]; A [slots, R, K] bf16; slot int32 [>= M] (-1: no adapter); ss_part [>= M, cols] fp32: the
+// deferred RMSNorm's partial sums of squares.  Returns S.
+int64_t lora_shrink(torch::Tensor x, torch::Tensor A, torch::Tensor slot, torch::Tensor t_part, int64_t rows,
+                    c10::optional<torch::Tensor> ss_part, double eps) {
+  dev_bf16(x, "x"); dev_bf16(A, "A"); dev_i32(slot, "slot");
+  TORCH_CHECK(A.dim() == 3 && A.is_contiguous(), "lora_shrink: A [slots, R, K]");
+  const int nslots = (int)A.size(0), R = (int)A.size(1), K = (int)A.size(2);
+  const long M = rows;
+  const int S = k8sllm_lora_shrink_plan(K);
+  TORCH_CHECK(S > 0 && R % 16 == 0 && M > 0 && nslots > 0, "lora_shrink: K % 32, R % 16, rows > 0");
+  const bool packed = x.dim() == 4;
+  long xstride = 0;
+  if (packed) {
+    TORCH_CHECK(x.is_contiguous() && x.size(0) == (M + 15) / 16 && x.size(1) * 32 == K && x.size(2) == 64 &&
+                    x.size(3) == 8, "lora_shrink: packed x must be [ceil(M/16), K/32, 64, 8]");
+  } else {
+    TORCH_CHECK(x.dim() == 2 && x.size(0) >= M && x.size(1) == K && x.stride(1) == 1 && x.stride(0) % 8 == 0 &&
+                    (uintptr_t)x.data_ptr() % 16 == 0, "lora_shrink: x [M, K] bf16 rows, 16-byte aligned");
+    xstride = x.stride(0);
+  }
+  TORCH_CHECK(slot.is_contiguous() && slot.numel() >= M, "lora_shrink: slot int32 [M]");
+  TORCH_CHECK(t_part.is_cuda() && t_part.scalar_type() == torch::kFloat32 && t_part.is_contiguous() &&
+                  t_part.numel() >= (int64_t)S * M * R, "lora_shrink: t_part fp32 [S, M, R]");
+  const float* ss = nullptr;
+  int cols = 0;
+  if (ss_part.has_value()) {
+    TORCH_CHECK(ss_part->is_cuda() && ss_part->scalar_type() == torch::kFloat32 && ss_part->is_contiguous() &&
+                    ss_part->dim() == 2 && ss_part->size(0) >= M, "lora_shrink: ss_part fp32 [M, cols]");
+    ss = ss_part->data_ptr<float>();
+    cols = (int)ss_part->size(1);
+  }
+  check(k8sllm_lora_shrink(x.data_ptr(), packed ? 1 : 0, xstride, A.data_ptr(), slot.data_ptr<int>(), ss, cols,
+                           (float)eps, t_part.data_ptr<float>(), M, R, K, nslots, cur()),
+        "lora_shrink");
+  return S;
+}
+
+// delta = scaling[slot] * B[slot] . sum_s t_part[s]: into the fp32 slab ``slab_index`` of ``out`` ([.., M, N]
+// slabs; rows without an adapter written as zeros), or added in place to bf16 ``out`` [M, N] (slab_index < 0).
+void lora_expand(torch::Tensor t_part, int64_t S, torch::Tensor B, torch::Tensor scaling, torch::Tensor slot,
+                 torch::Tensor out, int64_t rows, int64_t slab_index) {
+  dev_bf16(B, "B"); dev_i32(slot, "slot");
+  TORCH_CHECK(B.dim() == 3 && B.is_contiguous(), "lora_expand: B [slots, N, R]");
+  const int nslots = (int)B.size(0), N = (int)B.size(1), R = (int)B.size(2);
+  const long M = rows;
+  TORCH_CHECK(S > 0 && M > 0 && N % 16 == 0 && R % 32 == 0 && R <= 224, "lora_expand: N % 16, R % 32, R <= 224");
+  TORCH_CHECK(t_part.is_cuda() && t_part.scalar_type() == torch::kFloat32 && t_part.is_contiguous() &&
+                  t_part.numel() >= S * M * R, "lora_expand: t_part fp32 [S, M, R]");
+  TORCH_CHECK(scaling.is_cuda() && scaling.scalar_type() == torch::kFloat32 && scaling.is_contiguous() &&
+                  scaling.numel() == nslots, "lora_expand: scaling fp32 [slots]");
+  TORCH_CHECK(slot.is_contiguous() && slot.numel() >= M, "lora_expand: slot int32 [M]");
+  float* slab = nullptr;
+  void* y = nullptr;
+  long ystride = 0;
+  if (slab_index >= 0) {
+    TORCH_CHECK(out.is_cuda() && out.scalar_type() == torch::kFloat32 && out.is_contiguous() &&
+                    out.numel() >= (slab_index + 1) * M * N, "lora_expand: workspace too small for the slab");
+    slab = out.data_ptr<float>() + slab_index * M * N;
+  } else {
+    dev_bf16(out, "y");
+    TORCH_CHECK(out.dim() == 2 && out.size(0) >= M && out.size(1) == N && out.stride(1) == 1,
+                "lora_expand: y [M, N] bf16 rows");
+    y = out.data_ptr();
+    ystride = out.stride(0);
+  }
+  check(k8sllm_lora_expand(t_part.data_ptr<float>(), (int)S, B.data_ptr(), scaling.data_ptr<float>(),
+                           slot.data_ptr<int>(), slab, y, ystride, M, N, R, nslots, cur()),
+        "lora_expand");
+}
+
 void reduce_add_rms_norm(torch::Tensor out, torch::Tensor residual, c10::optional<torch::Tensor> partial, int64_t S,
                          torch::Tensor w, double eps, c10::optional<torch::Tensor> out_packed) {
   dev_bf16(out, "out"); dev_bf16(residual, "residual"); dev_bf16(w, "w");
@@ -1380,6 +1459,9 @@ PYBIND11_MODULE(_k8sllm_ops, m) {
   m.def("gemm_dec_rc", &gemm_dec_rc);
   m.def("reduce_add_rms_norm", &reduce_add_rms_norm);
   m.def("reduce_slabs", &reduce_slabs);
+  m.def("lora_shrink_plan", &lora_shrink_plan);
+  m.def("lora_shrink", &lora_shrink);
+  m.def("lora_expand", &lora_expand);
   m.def("add_norm_partial", &add_norm_partial);
   m.def("car_create", &car_create);
   m.def("car_open", &car_open);

@@ -376,3 +376,23 @@ def moe_combine(y: torch.Tensor, inv_idx: torch.Tensor, w: torch.Tensor, T: int)
     K = w.shape[1]
     g = y.double()[inv_idx.long()].view(T, K, -1)  # K products and their sum, rounded once
     return (g * w.double().unsqueeze(-1)).sum(1).to(y.dtype)
+
+
+def lora_delta(x: torch.Tensor, A: torch.Tensor, B: torch.Tensor, scaling: torch.Tensor, slot: torch.Tensor,
+               dtype=torch.float32) -> torch.Tensor:
+    """Per-row low-rank adapter delta ``scaling[s] * B[s] @ (A[s] @ x[row])``, ``s = slot[row]``; rows
+    with ``slot < 0`` have no adapter and give exact zeros.  ``x`` [M, K], ``A`` [slots, R, K], ``B``
+    [slots, N, R], ``scaling`` [slots], ``slot`` [M] integers; computed in ``dtype`` (fp32; the tests
+    ask for fp64) one row at a time, so a row's result never depends on the other rows' slots."""
+    M, N = x.shape[0], B.shape[1]
+    out = torch.zeros(M, N, dtype=dtype, device=x.device)
+    sl = slot[:M].tolist()
+    conv: dict = {}
+    for i, s in enumerate(sl):
+        if s < 0:
+            continue
+        if s not in conv:
+            conv[s] = (A[s].to(dtype), B[s].to(dtype), scaling[s].to(dtype))
+        a, b, sc = conv[s]
+        out[i] = sc * (b @ (a @ x[i].to(dtype)))
+    return out

@@ -140,9 +140,11 @@ class LLMEngine:
         self.adapters: dict[str, int] = {}
         self._adapter_info: list[dict] = []
         if cfg.lora_adapters:
-            self.model.enable_lora(len(cfg.lora_adapters), cfg.lora_max_rank)
-            for slot, (name, path) in enumerate(cfg.lora_adapters.items()):
-                ad = load_lora(path, name=str(name))
+            # every adapter is read first: the gate_up arena is allocated only where one targets it
+            ads = [load_lora(path, name=str(name)) for name, path in cfg.lora_adapters.items()]
+            mlp = any(t in ("gate_proj", "up_proj") for ad in ads for t in ad.target_modules)
+            self.model.enable_lora(len(ads), cfg.lora_max_rank, mlp=mlp)
+            for slot, ((name, path), ad) in enumerate(zip(cfg.lora_adapters.items(), ads)):
                 self.model.load_adapter(slot, ad)
                 self.adapters[str(name)] = slot
                 self._adapter_info.append({"name": str(name), "rank": ad.r, "targets": list(ad.target_modules)})

@@ -459,7 +459,8 @@ def merge_lora(model, adapter: LoraAdapter) -> None:
     c, D = model.cfg, model.D
     nq, nk = c.n_heads * D, c.n_kv_heads * D
     rows = {"q_proj": ("wqkv", 0, nq), "k_proj": ("wqkv", nq, nq + nk), "v_proj": ("wqkv", nq + nk, nq + 2 * nk),
-            "o_proj": ("wo", 0, c.d_model), "down_proj": ("w2", 0, c.d_model)}
+            "o_proj": ("wo", 0, c.d_model), "down_proj": ("w2", 0, c.d_model),
+            "gate_proj": ("w13", 0, c.ffn_dim), "up_proj": ("w13", c.ffn_dim, 2 * c.ffn_dim)}
     canon = [{k: model.canonical(L, k).float().clone() for k in ("wqkv", "wo", "w13", "w2")} for L in model.layers]
     for (layer, mod), (A, B) in adapter.tensors.items():
         key, lo, hi = rows[mod]

@@ -56,7 +56,10 @@ Per-request LoRA adapters (``enable_lora`` / ``load_adapter``, ``AttnMeta.lora_s
 stays resident and a step's rows may each name an adapter of the arena (ops.LoraState).  On the skinny
 decode loop an adapter's delta is one more split-K slab after the qkv, o and down GEMMs (ops.lora_slab;
 their consumers sum ``ns + 1`` slabs); the generic layer loop adds it in place (ops.lora_add) to the
-plain qkv (before the rotation), o and dense down outputs.  A step without ``lora_slot`` takes exactly
+plain qkv (before the rotation), o and dense down outputs.  The gate_up delta (``enable_lora(mlp=True)``,
+arena "w13" in the resident w13's row order) enters before SwiGLU: the decode gate_up GEMM adds it to
+its accumulator (ops.dec_gemm ``delta``, over the PACKED w13), the generic layer loop runs gate_up
+plain, adds it and pairs gate and up in ops.silu_mul.  A step without ``lora_slot`` takes exactly
 the paths it takes without adapters.
 
 ``to_resident`` / ``to_canonical`` convert one projection between CANONICAL and another layout;
@@ -278,6 +281,7 @@ class CausalLM:
         self._rc_o, self._dec_wide, self._attn_rope = 0, False, False
         self.lora: Optional[ops.LoraState] = None  # the resident adapters' arena (enable_lora)
         self._lora_cap = 0
+        self._lora_w13_layout = CANONICAL  # the row order of the gate_up arena's B (enable_lora(mlp=True))
         self._build()
         self._init_skinny()
         self.cos_sin = None
@@ -422,15 +426,20 @@ class CausalLM:
     # ------------------------------------------------------------------ per-request LoRA adapters
     # PEFT target module -> (adapted projection, its block inside the fused qkv)
     LORA_MODULES = {"q_proj": ("wqkv", 0), "k_proj": ("wqkv", 1), "v_proj": ("wqkv", 2), "o_proj": ("wo", 0),
-                    "down_proj": ("w2", 0)}
+                    "down_proj": ("w2", 0), "gate_proj": ("w13", 0), "up_proj": ("w13", 1)}
 
-    def enable_lora(self, slots: int, max_rank: int = 64) -> "ops.LoraState":
+    def enable_lora(self, slots: int, max_rank: int = 64, mlp: bool = False) -> "ops.LoraState":
         """Allocate the adapters' arena (ops.LoraState, ``slots`` adapters of rank up to
         ``max_rank``) and one more slab per projection in the decode workspace.  The fused qkv is
         one adapted projection of rank capacity 3 x the rounded ``max_rank``: q, k and v at their own
-        rank rows, B block-diagonal over their output ranges.  Steps name their rows' adapters
-        through ``AttnMeta.lora_slot``; without it nothing changes."""
+        rank rows, B block-diagonal over their output ranges.  ``mlp``: also the fused gate_up
+        ("w13", rank capacity 2 x: gate and up at their own rank rows, B block-diagonal, its rows in
+        the row order of the resident w13) - opt-in because it about doubles the arena (B is
+        [2 F, 2 cap] per layer and slot); without it adapters on gate_proj / up_proj are refused.
+        Steps name their rows' adapters through ``AttnMeta.lora_slot``; without it nothing changes."""
         c = self.cfg
+        if mlp and c.is_moe:
+            raise ValueError("LoRA adapters on gate_proj / up_proj (mlp=True) are not supported on a MoE model")
         if self.tp > 1:
             raise ValueError("LoRA adapters need tp_size == 1 (the TP workers replay the leader's staging words, "
                              "which carry no adapter slots)")
@@ -443,8 +452,11 @@ class CausalLM:
         dims = {"wqkv": ((self.hq + 2 * self.hkv) * self.D, d, 3 * cap), "wo": (d, no, cap)}
         if not c.is_moe:
             dims["w2"] = (d, self.f_local, cap)
+        if mlp:
+            dims["w13"] = (2 * self.f_local, d, 2 * cap)
         self.lora = ops.LoraState(slots, c.n_layers, dims, self.device, self.dtype)
         self._lora_cap, self._lora_max_rank = cap, int(max_rank)
+        self._lora_w13_layout = CANONICAL if self._layout == LOADING else self._layout  # the row order of B["w13"]
         if self._skinny_ws is not None:
             self._skinny_ws = torch.empty(self._skinny_ws_numel(), dtype=torch.float32, device=self.device)
         return self.lora
@@ -457,9 +469,10 @@ class CausalLM:
             raise ValueError("load_adapter: no LoRA arena (enable_lora first)")
         c, name = self.cfg, getattr(adapter, "name", "") or "adapter"
         for t in adapter.target_modules:
-            if t in ("gate_proj", "up_proj"):
-                raise ValueError(f"LoRA {name}: target module {t!r} is not supported (the decode gate_up GEMM fuses "
-                                 "SwiGLU into its epilogue; the delta would have to enter before it)")
+            if t in ("gate_proj", "up_proj") and "w13" not in self.lora.dims:
+                raise ValueError(f"LoRA {name}: target module {t!r} is not supported by this arena (the decode gate_up "
+                                 "GEMM fuses SwiGLU into its epilogue, so the delta enters before it through an arena "
+                                 "of its own: enable_lora(.., mlp=True))")
             if t not in self.LORA_MODULES:
                 raise ValueError(f"LoRA {name}: unknown target module {t!r}")
             if t == "down_proj" and c.is_moe:
@@ -468,7 +481,8 @@ class CausalLM:
             raise ValueError(f"LoRA {name}: rank {adapter.r} exceeds lora_max_rank {self._lora_max_rank}")
         d, D = c.d_model, self.D
         shapes = {"q_proj": (self.hq * D, d), "k_proj": (self.hkv * D, d), "v_proj": (self.hkv * D, d),
-                  "o_proj": (d, self.hq * D), "down_proj": (d, self.f_local)}
+                  "o_proj": (d, self.hq * D), "down_proj": (d, self.f_local),
+                  "gate_proj": (self.f_local, d), "up_proj": (self.f_local, d)}
         n0 = {0: 0, 1: self.hq * D, 2: (self.hq + self.hkv) * D}
         for (layer, mod), (A, B) in adapter.tensors.items():
             if mod not in adapter.target_modules:
@@ -482,10 +496,45 @@ class CausalLM:
         for p in self.lora.dims:  # a reload of the slot leaves nothing of the adapter before
             self.lora.A[p][:, slot].zero_()
             self.lora.B[p][:, slot].zero_()
+        rows13 = None
         for (layer, mod), (A, B) in adapter.tensors.items():
             proj, blk = self.LORA_MODULES[mod]
+            if proj == "w13":
+                # gate / up rows [0, F) / [F, 2F) of the canonical w13, scattered to where the
+                # resident layout keeps them
+                if rows13 is None:
+                    rows13 = self._w13_row_order(self._lora_w13_layout).argsort()
+                dst = rows13[blk * self.f_local:(blk + 1) * self.f_local]
+                r0 = blk * self._lora_cap
+                self.lora.A[proj][layer, slot, r0:r0 + adapter.r] = A.to(self.device, self.dtype)
+                self.lora.B[proj][layer, slot, dst.to(self.device), r0:r0 + adapter.r] = B.to(self.device, self.dtype)
+                continue
             self.lora.load(slot, layer, proj, A, B, r0=blk * self._lora_cap, n0=n0[blk] if proj == "wqkv" else 0)
         self.lora.set_scaling(slot, adapter.scaling)
+
+    def _w13_row_order(self, layout: str) -> torch.Tensor:
+        """``order[n]`` = the canonical ([gate; up]) row of w13 that ``layout`` keeps at row ``n``."""
+        idx = torch.arange(2 * self.f_local).view(-1, 1)
+        if layout == PACKED:
+            idx = ops.interleave_gate_up8(idx)
+        elif layout == INTERLEAVED:
+            idx = ops.interleave_gate_up(idx)
+        return idx.flatten()
+
+    def _lora_relayout(self) -> None:
+        """After the resident layout changed (_init_skinny / _init_dec): the rows of the w13 arena's
+        B follow the resident w13's new row order, so a loaded adapter never meets a stale pairing."""
+        if self.lora is None or "w13" not in self.lora.dims or self._layout == LOADING:
+            return
+        old, new = self._lora_w13_layout, self._layout
+        if old == new:
+            return
+        # resident_new[n] = canonical[order_new[n]] = resident_old[inverse(order_old)[order_new[n]]]
+        src = self._w13_row_order(old).argsort()[self._w13_row_order(new)].to(self.device)
+        B = self.lora.B["w13"]
+        for layer in range(B.shape[0]):  # one layer's copy at a time
+            B[layer] = B[layer].index_select(1, src)
+        self._lora_w13_layout = new
 
     def resident_weight_bytes(self) -> int:
         """Bytes of every distinct weight tensor this rank holds (parameters, decode-layout copies,
@@ -622,12 +671,19 @@ class CausalLM:
             if not meta.is_prefill and self.tp > 1 and self.moe_decode == "a2a":
                 return self._moe_a2a_decode(L, x)
             return tp_all_reduce(self._moe(L, x, meta), self.ps)
-        if self._w13_il:
+        slot = self._lora_slot(meta)
+        if slot is not None and "w13" in self.lora.dims:
+            # adapter rows on gate / up: the delta enters before the activation, so the gate_up GEMM
+            # runs plain, the delta is added in the resident row order and silu_mul pairs it up
+            gu = (ops.prefill_linear(x, L["w13"], swiglu=False, wscale=self._wsc(L, "w13")) if self._w13_il
+                  else F.linear(x, L["w13"]))
+            ops.lora_add(self.lora, li, "w13", x, gu, slot)
+            h = ops.silu_mul(gu, pairing={PACKED: 8, INTERLEAVED: 1}.get(self._layout, 0))
+        elif self._w13_il:
             h = ops.prefill_linear(x, L["w13"], swiglu=self._swg, wscale=self._wsc(L, "w13"))
         else:
             h = ops.silu_mul(F.linear(x, L["w13"]), interleaved=False)
         y = ops.prefill_linear(h, L["w2"], wscale=self._wsc(L, "w2"))
-        slot = self._lora_slot(meta)
         if slot is not None and "w2" in self.lora.dims:
             ops.lora_add(self.lora, li, "w2", h, y, slot)
         return tp_all_reduce(y, self.ps)
@@ -1081,8 +1137,22 @@ class CausalLM:
         """Llama-family decode steps of up to dec_rows_max() rows (128 for dense TP=1 models on the
         shared-A decode GEMM, 64 otherwise) run every projection through the decode GEMMs over
         fragment-packed weights (see _init_skinny)."""
-        return (self._skinny_ws is not None and not meta.is_prefill and h.shape[0] <= self.dec_rows_max()
+        if self._skinny_ws is None or not self._lora_w13_skinny_ok(meta):
+            return False
+        return (not meta.is_prefill and h.shape[0] <= self.dec_rows_max()
                 and meta.logits_idx is None and self.SKINNY_DECODE)
+
+    def _lora_w13_skinny_ok(self, meta: AttnMeta) -> bool:
+        """A step with adapter rows over a gate_up arena stays on the skinny decode loop where the
+        gate_up launch can take the delta before its SwiGLU epilogue: gemm_decode over the PACKED
+        w13 (the arena's B rows are in its order), at most 16 deferred-norm sums per row.  Otherwise
+        - gemm_skinny's w13_p, the INTERLEAVED two-copy layout - the step takes the generic layer
+        loop, as row counts above the limit do."""
+        if self._lora_slot(meta) is None or "w13" not in self.lora.dims:
+            return True
+        L = self.layers[0]
+        return (self._layout == PACKED and self._lora_w13_layout == PACKED and ("w13_d" in L or "w13_q" in L)
+                and self.cfg.d_model // 512 <= 16)
 
     def _init_skinny(self) -> None:
         """(Re)build everything derived from the weights: the resident layout of the projections
@@ -1125,6 +1195,7 @@ class CausalLM:
                         L[key] = relayout(L[key], key, old, new).contiguous()
         self._layout = new
         if not dec:
+            self._lora_relayout()
             return
         # (In-launch split-K epilogues - RoPE + KV write in the qkv GEMM, residual add + norm
         # producer in the o / down GEMMs, reduced by each tile's last-arriving workgroup - measured
@@ -1148,6 +1219,7 @@ class CausalLM:
         self._split_qkv = self._split_o = self._split_d = split
         self._init_dec()
         self._dec_wide = self._dec_wide_ok()
+        self._lora_relayout()
         self._skinny_ws = torch.empty(self._skinny_ws_numel(), dtype=torch.float32, device=self.device)
         self.set_decode_fusion()
 
@@ -1161,7 +1233,8 @@ class CausalLM:
         the moment, so flipping that switch at run time stays inside the buffer.  MoE: the expert
         down projections write one slab group per local expert, and the EP all-to-all decode runs
         up to SKINNY_GROUPED_MAX_M received rows per grouped launch.  With resident LoRA adapters
-        (enable_lora) every dense projection has room for one more slab: an adapter's delta."""
+        (enable_lora) every dense projection has room for one more slab: an adapter's delta; the
+        gate_up delta (enable_lora(mlp=True)) is one [rows, 2F] image at the start of the workspace."""
         c, split = self.cfg, self._split_qkv
         d, nq, no = c.d_model, (self.hq + 2 * self.hkv) * self.D, self.hq * self.D
         dec_rows = ops.DEC_MAX_M if self._dec_wide else ops.SKINNY_MAX_M
@@ -1183,6 +1256,8 @@ class CausalLM:
         else:
             mlp = (most(d, self.f_local) + extra) * d
         n = max((most(nq, d) + extra) * nq, (most(d, no) + extra) * d, mlp)
+        if self.lora is not None and "w13" in self.lora.dims:
+            n = max(n, 2 * self.f_local)
         return n * (ops.SKINNY_GROUPED_MAX_M if c.is_moe else dec_rows)
 
     # decode buckets up to this many rows take the row-complete o projection by default: per decode
@@ -1263,7 +1338,14 @@ class CausalLM:
             xw, rn = rc  # the dense MLP's input, from either form of the o projection
             if "w13_d" in L or "w13_q" in L:
                 act = ops.packed_empty(M, self.f_local, self.dtype, self.device)
-                self._dec(xw, L.get("w13_d"), L.get("w13_q"), L.get("w13_qs"), 2, M, out=act, rownorm=rn)
+                dkw = {}
+                if lslot is not None and "w13" in self.lora.dims:
+                    # the adapters' gate_up delta, one fp32 [M, 2F] image in the packed w13's row order
+                    # at the start of the workspace - free here: _norm_tail has consumed the o slabs
+                    # and the down GEMM writes after the gate_up launch has read it (stream order)
+                    ops.lora_slab(self.lora, i, "w13", xw, M, ws, 0, lslot, rownorm=rn)
+                    dkw = dict(delta=ws, delta_slot=lslot, delta_slots=self.lora.slots)
+                self._dec(xw, L.get("w13_d"), L.get("w13_q"), L.get("w13_qs"), 2, M, out=act, rownorm=rn, **dkw)
             else:
                 act = ops.skinny_swiglu(xw, L["w13_p"], rows=M, packed_out=True, rownorm=rn)
             ns = self._proj_slabs(L, "w2", act, M, self._split_d)

@@ -858,7 +858,7 @@ def dequantize_codes(w: torch.Tensor, scale: torch.Tensor, dtype=torch.bfloat16)
 
 def _dec_gemm(name: str, a: torch.Tensor, w: torch.Tensor, wscale: Optional[torch.Tensor], epi: int, rows: int,
               workspace: Optional[torch.Tensor], out: Optional[torch.Tensor], rownorm: Optional[tuple],
-              row_w: Optional[torch.Tensor], cfg: Optional[tuple], E: int) -> int:
+              row_w: Optional[torch.Tensor], cfg: Optional[tuple], E: int, delta: Optional[tuple] = None) -> int:
     """The one body of dec_gemm (``E`` = 0), dec_gemm_grouped and dec_gemm_grouped_q (``E`` experts,
     ``w`` and ``wscale`` [E, ...] stacks): checks, configuration, the CPU reference - one per-expert
     loop with the kernel's split-K slicing over the dequantised values - and the one native launch."""
@@ -883,6 +883,14 @@ def _dec_gemm(name: str, a: torch.Tensor, w: torch.Tensor, wscale: Optional[torc
     if cfg is None:
         raise ValueError(f"{name}: no configuration for N={N} K={K} epi={epi} " + (f"experts={E}" if E else f"rows={M}"))
     S, ntw, waves, depth = cfg
+    if delta is not None:
+        dl, dslot, dn = delta
+        if epi != DEC_SWIGLU8 or E:
+            raise ValueError(f"{name}: a pre-activation delta goes with the SwiGLU epilogue of a dense launch only")
+        if rownorm is not None and rownorm[0].shape[1] > 16:
+            raise ValueError(f"{name}: a delta goes with at most 16 deferred-norm sums per row")
+        if dl.dtype != torch.float32 or dl.numel() < M * N or dslot is None or dslot.numel() < M or dn < 1:
+            raise ValueError(f"{name}: delta must be fp32 [{M}, {N}] with delta_slot [{M}] and delta_slots >= 1")
     if not _gpu(a):
         sc = _rn_scale(rownorm, M, K)
         for e in range(max(E, 1)):
@@ -900,6 +908,9 @@ def _dec_gemm(name: str, a: torch.Tensor, w: torch.Tensor, wscale: Optional[torc
             y = x @ wf.t()
             if sc is not None:
                 y = y * sc
+            if delta is not None:  # packed order, after the row scale, before any rounding
+                on = ((dslot[:M] >= 0) & (dslot[:M] < dn)).nonzero().flatten()
+                y[on] = y[on] + dl.reshape(-1)[:M * N].view(M, N)[on].float()
             o = out[e] if E else out
             if epi == 1:
                 o[:M].copy_(y.to(o.dtype))
@@ -920,7 +931,7 @@ def _dec_gemm(name: str, a: torch.Tensor, w: torch.Tensor, wscale: Optional[torc
                            (" over fp8 weights" if f8 else f" over mxfp4 weights in {S} K slices" if f4 else ""))
     r = native().gemm_dec(a, w, wscale if enc else None, workspace, out, S, epi, ntw, waves, depth, M, *rn,
                           row_w if E else None, DEC_F4_DEPTH_FORCE if f4 else 0, DEC_SLAB_ROWS, DEC_SLAB_WT,
-                          DEC_XCD_SPLITS)
+                          DEC_XCD_SPLITS, *((dl, dslot, dn) if delta is not None else ()))
     if r < 0:
         raise RuntimeError(f"{name}: configuration {cfg} not compiled for N={N} K={K} epi={epi}")
     return r
@@ -928,7 +939,9 @@ def _dec_gemm(name: str, a: torch.Tensor, w: torch.Tensor, wscale: Optional[torc
 
 def dec_gemm(a: torch.Tensor, wp: torch.Tensor, epi: int, rows: int, workspace: Optional[torch.Tensor] = None,
              out: Optional[torch.Tensor] = None, rownorm: Optional[tuple] = None,
-             cfg: Optional[tuple] = None, wscale: Optional[torch.Tensor] = None) -> int:
+             cfg: Optional[tuple] = None, wscale: Optional[torch.Tensor] = None,
+             delta: Optional[torch.Tensor] = None, delta_slot: Optional[torch.Tensor] = None,
+             delta_slots: int = 0) -> int:
     """gemm_dec over a fragment-packed activation ``a`` and packed weight ``wp`` (pack_skinny: under
     ONE_LAYOUT the model's only copy, which prefill's tile GEMM reads too; else a copy for decode).
     epi 0: fp32 split-K slabs into ``workspace`` [S, M, N], returns S; epi 1: ``out`` [M, N] bf16;
@@ -940,8 +953,14 @@ def dec_gemm(a: torch.Tensor, wp: torch.Tensor, epi: int, rows: int, workspace: 
     bytes, bit-identical to the bf16 launch of the same configuration over the dequantised
     weights; a form without an fp8 instantiation raises.  Or the mxfp4 encoding (pack_skinny_f4's
     codes, ``wscale`` its packed block scales), under the same contract.
+    ``delta`` (epi 2 only): fp32 [M, N] over the packed row index (column n belongs to packed weight
+    row n - what ``lora_slab(.., "w13", ..)`` writes), added to the accumulator of the rows whose
+    ``delta_slot[row]`` (int32) lies in ``[0, delta_slots)`` after the deferred-norm and fp8 row
+    scales and before gate and up are rounded to bf16; the other rows compute exactly what a launch
+    without delta computes.  Not with more than 16 deferred-norm sums per row.
     CPU: the fp32 reference with the same split-K slicing (over the dequantised values)."""
-    return _dec_gemm("gemm_dec", a, wp, wscale, epi, rows, workspace, out, rownorm, None, cfg, 0)
+    dl = None if delta is None else (delta, delta_slot, int(delta_slots))
+    return _dec_gemm("gemm_dec", a, wp, wscale, epi, rows, workspace, out, rownorm, None, cfg, 0, delta=dl)
 
 
 def dec_gemm_grouped(a: torch.Tensor, wp: torch.Tensor, epi: int, rows: int, workspace: Optional[torch.Tensor] = None,
@@ -1068,7 +1087,9 @@ def packed_empty(M: int, K: int, dtype, device) -> torch.Tensor:
 
 # ---------------------------------------------------------------- per-request LoRA adapters
 
-LORA_PROJ = ("wqkv", "wo", "w2")  # the adapted projections (the fused qkv is one of them)
+# the adapted projections: the fused qkv is one of them, and so is the fused gate_up ("w13": its B
+# rows in the row order of the model's resident w13, so the delta's column n is packed weight row n)
+LORA_PROJ = ("wqkv", "wo", "w2", "w13")
 LORA_RANK_ALIGN = 32  # rank capacities are whole r-steps of lora_expand_kernel
 LORA_MAX_CAP = 224  # kernel limit of a projection's rank capacity (the expand kernel's LDS image of t)
 
@@ -1231,15 +1252,25 @@ def layer_norm(x, w, b, eps):
     return out
 
 
-def silu_mul(x: torch.Tensor, out: Optional[torch.Tensor] = None, interleaved: bool = False) -> torch.Tensor:
+def silu_mul(x: torch.Tensor, out: Optional[torch.Tensor] = None, interleaved: bool = False,
+             pairing: Optional[int] = None) -> torch.Tensor:
     """silu(gate) * up over [.., 2F] gate_up activations: [F gate | F up], or ``interleaved``
-    [64 gate | 64 up] per 128 columns (the output of the single resident, interleaved w13)."""
+    [64 gate | 64 up] per 128 columns (the output of the single resident, interleaved w13).
+    ``pairing`` (where given, it decides): 0 and 1 name those two, 8 is [8 gate | 8 up] per 16
+    columns - the output of a plain GEMM over a PACKED w13 (interleave_gate_up8)."""
+    if pairing is None:
+        pairing = 1 if interleaved else 0
+    if pairing not in (0, 1, 8):
+        raise ValueError(f"silu_mul: pairing {pairing!r} is not 0, 1 or 8")
+    F2 = x.shape[-1]
+    if pairing == 8 and F2 % 16:
+        raise ValueError(f"silu_mul: {F2} gate_up columns are no whole [8 gate | 8 up] groups")
     if not _gpu(x):
-        y = ref.silu_mul(x, interleaved)
+        y = ref.silu_mul(x, pairing=pairing)
         return out.copy_(y) if out is not None else y
     if out is None:
-        out = torch.empty(*x.shape[:-1], x.shape[-1] // 2, dtype=x.dtype, device=x.device)
-    native().silu_mul(out, x.contiguous(), interleaved)
+        out = torch.empty(*x.shape[:-1], F2 // 2, dtype=x.dtype, device=x.device)
+    native().silu_mul_pairing(out, x.contiguous(), pairing)
     return out
 
 

@@ -17,7 +17,7 @@ int k8sllm_rmsnorm(void* out, const void* x, void* residual, const void* w, long
                    long x_stride, long out_stride, hipStream_t s);
 int k8sllm_layernorm(void* out, const void* x, const void* w, const void* b, long rows, int d, float eps,
                      hipStream_t s);
-int k8sllm_silu_mul(void* out, const void* x, long rows, int F, int interleaved, hipStream_t s);
+int k8sllm_silu_mul(void* out, const void* x, long rows, int F, int pairing, hipStream_t s);
 int k8sllm_gelu_tanh(void* out, const void* x, long n, hipStream_t s);
 int k8sllm_embedding(void* out, const int* ids, const void* weight, long T, int d, int vocab_start, int rows,
                      hipStream_t s);
@@ -81,7 +81,8 @@ int k8sllm_gemm_skinny(const void* A, long lda, const void* Wp, float* partial, 
 int k8sllm_gemm_dec(const void* A, const void* W, const void* wscale, int wf, float* partial, void* Y, long ldy, int M,
                     int N, int K, int splits, int epi, int ntw, int waves, int depth, int f4_depth, const float* rn_ss,
                     int rn_nc, int rn_d, float rn_eps, int experts, long a_es, long w_eb, long s_eb, long y_es,
-                    const float* rw, int rw_ld, int sw_rows, int sw_wt, int sw_xcd, hipStream_t s);
+                    const float* rw, int rw_ld, int sw_rows, int sw_wt, int sw_xcd, const float* delta, const int* dslot,
+                    int nslots, hipStream_t s);
 int k8sllm_gemm_dec_forms(int* out, int cap);
 int k8sllm_gemm_dec_f8_forms(int* out, int cap);
 int k8sllm_gemm_dec_f4_forms(int* out, int cap);
@@ -188,14 +189,19 @@ void layer_norm(torch::Tensor out, torch::Tensor x, torch::Tensor w, torch::Tens
 }
 
 // interleaved: x columns are [64 gate | 64 up] per 128 (ops.interleave_gate_up) instead of [F | F]
-void silu_mul(torch::Tensor out, torch::Tensor x, bool interleaved) {
+// pairing of gate and up inside x [.., 2F]: 0 [F gate | F up], 1 [64 gate | 64 up] per 128 columns,
+// 8 [8 gate | 8 up] per 16 (the row order of a PACKED w13, ops.interleave_gate_up8)
+void silu_mul_pairing(torch::Tensor out, torch::Tensor x, int64_t pairing) {
   dev_bf16(out, "out"); dev_bf16(x, "x");
   TORCH_CHECK(x.is_contiguous() && out.is_contiguous(), "silu_mul: contiguous");
   const int F = (int)out.size(-1);
   TORCH_CHECK(x.size(-1) == 2 * F, "silu_mul: x last dim must be 2*F");
-  TORCH_CHECK(!interleaved || F % 64 == 0, "silu_mul: interleaved gate/up needs F % 64 == 0");
-  check(k8sllm_silu_mul(out.data_ptr(), x.data_ptr(), out.numel() / F, F, interleaved ? 1 : 0, cur()), "silu_mul");
+  TORCH_CHECK(pairing == 0 || pairing == 1 || pairing == 8, "silu_mul: pairing 0, 1 (per 128 columns) or 8 (per 16)");
+  TORCH_CHECK(pairing != 1 || F % 64 == 0, "silu_mul: interleaved gate/up needs F % 64 == 0");
+  check(k8sllm_silu_mul(out.data_ptr(), x.data_ptr(), out.numel() / F, F, (int)pairing, cur()), "silu_mul");
 }
+
+void silu_mul(torch::Tensor out, torch::Tensor x, bool interleaved) { silu_mul_pairing(out, x, interleaved ? 1 : 0); }
 
 void gelu_tanh(torch::Tensor out, torch::Tensor x) {
   dev_bf16(out, "out"); dev_bf16(x, "x");
@@ -918,11 +924,16 @@ int64_t gemm_skinny(torch::Tensor a, torch::Tensor wp, c10::optional<torch::Tens
 // write-through form and the one-split-per-XCD placement - the slabs are the same bits either way.
 // Row limit, slicing and forms are dec_plan's (gemm_dec_forms.h).  Returns the slab count (1 for
 // epi 1 / 2); -1 if the configuration is not available (the caller falls back to gemm_skinny).
-int64_t gemm_dec_sw(torch::Tensor a, torch::Tensor w, c10::optional<torch::Tensor> wscale,
-                    c10::optional<torch::Tensor> partial, c10::optional<torch::Tensor> y, int64_t splits, int64_t epi,
-                    int64_t ntw, int64_t waves, int64_t depth, int64_t rows, c10::optional<torch::Tensor> rn_ss,
-                    double rn_eps, c10::optional<torch::Tensor> row_w, int64_t f4_depth, int64_t sw_rows,
-                    int64_t sw_wt, int64_t sw_xcd) {
+// delta / delta_slot / delta_slots (the longest overload; epi 2, dense, at most 16 deferred-norm
+// sums per row): fp32 [M, N] over the packed row index, 16-byte aligned, added to the accumulator
+// of the rows whose delta_slot[row] (int32 [M]) lies in [0, delta_slots) before gate and up are
+// rounded; the other rows compute what a launch without delta computes.
+int64_t gemm_dec_delta(torch::Tensor a, torch::Tensor w, c10::optional<torch::Tensor> wscale,
+                       c10::optional<torch::Tensor> partial, c10::optional<torch::Tensor> y, int64_t splits, int64_t epi,
+                       int64_t ntw, int64_t waves, int64_t depth, int64_t rows, c10::optional<torch::Tensor> rn_ss,
+                       double rn_eps, c10::optional<torch::Tensor> row_w, int64_t f4_depth, int64_t sw_rows,
+                       int64_t sw_wt, int64_t sw_xcd, c10::optional<torch::Tensor> delta,
+                       c10::optional<torch::Tensor> delta_slot, int64_t delta_slots) {
   dev_bf16(a, "a");
   const auto wt = w.scalar_type();
   const int wf = wt == torch::kFloat8_e4m3fn ? k8sllm::DEC_W_F8 : wt == torch::kUInt8 ? k8sllm::DEC_W_F4 : k8sllm::DEC_W_BF16;
@@ -967,6 +978,23 @@ int64_t gemm_dec_sw(torch::Tensor a, torch::Tensor w, c10::optional<torch::Tenso
   TORCH_CHECK(a.is_contiguous() && a.dim() == 4 + ag && (!per_e || a.size(0) == E) && a.size(ag) >= MT &&
                   a.size(ag + 1) * 32 == K && a.size(ag + 2) == 64 && a.size(ag + 3) == 8,
               what, ": a must be fragment-packed [ceil(M/16), K/32, 64, 8]", g ? " or [E, ...]" : "");
+  const float* dp = nullptr;
+  const int* dsp = nullptr;
+  if (delta.has_value()) {
+    TORCH_CHECK(epi == 2, what, ": a pre-activation delta goes with the SwiGLU epilogue (epi 2) only");
+    TORCH_CHECK(!g && !row_w.has_value(), what, ": a grouped launch takes no delta");
+    TORCH_CHECK(rn_nc <= k8sllm::kDecRnNarrow, what, ": a delta goes with at most ", k8sllm::kDecRnNarrow,
+                " deferred-norm sums per row, not ", rn_nc);
+    TORCH_CHECK(delta->is_cuda() && delta->scalar_type() == torch::kFloat32 && delta->is_contiguous() &&
+                    delta->numel() >= (int64_t)M * N && reinterpret_cast<uintptr_t>(delta->data_ptr()) % 16 == 0 &&
+                    (int64_t)M * N * 4 < 0x7fffffffLL,
+                what, ": delta must be fp32, contiguous, 16-byte aligned, [M, N] under 2 GiB");
+    TORCH_CHECK(delta_slot.has_value() && delta_slot->is_cuda() && delta_slot->scalar_type() == torch::kInt32 &&
+                    delta_slot->is_contiguous() && delta_slot->numel() >= M && delta_slots >= 1,
+                what, ": delta_slot must be int32 [M] with delta_slots >= 1");
+    dp = delta->data_ptr<float>();
+    dsp = delta_slot->data_ptr<int>();
+  }
   if (p.err < 0) return -1;
   float* pp = nullptr;
   void* yp = nullptr;
@@ -997,10 +1025,20 @@ int64_t gemm_dec_sw(torch::Tensor a, torch::Tensor w, c10::optional<torch::Tenso
   const long s_eb = g && sp ? wscale->stride(0) * wscale->element_size() : 0;
   const int rc = k8sllm_gemm_dec(a.data_ptr(), w.data_ptr(), sp, wf, pp, yp, ldy, M, N, K, (int)splits, (int)epi,
                                  (int)ntw, (int)waves, (int)depth, (int)f4_depth, rp, rn_nc, K, (float)rn_eps, E,
-                                 a_es, w_eb, s_eb, y_es, rw, rw_ld, (int)sw_rows, (int)sw_wt, (int)sw_xcd, cur());
+                                 a_es, w_eb, s_eb, y_es, rw, rw_ld, (int)sw_rows, (int)sw_wt, (int)sw_xcd, dp, dsp,
+                                 (int)delta_slots, cur());
   if (rc < 0) return -1;
   check(rc, what);
   return p.slabs;
+}
+
+int64_t gemm_dec_sw(torch::Tensor a, torch::Tensor w, c10::optional<torch::Tensor> wscale,
+                    c10::optional<torch::Tensor> partial, c10::optional<torch::Tensor> y, int64_t splits, int64_t epi,
+                    int64_t ntw, int64_t waves, int64_t depth, int64_t rows, c10::optional<torch::Tensor> rn_ss,
+                    double rn_eps, c10::optional<torch::Tensor> row_w, int64_t f4_depth, int64_t sw_rows,
+                    int64_t sw_wt, int64_t sw_xcd) {
+  return gemm_dec_delta(a, w, wscale, partial, y, splits, epi, ntw, waves, depth, rows, rn_ss, rn_eps, row_w, f4_depth,
+                        sw_rows, sw_wt, sw_xcd, c10::nullopt, c10::nullopt, 0);
 }
 
 int64_t gemm_dec(torch::Tensor a, torch::Tensor w, c10::optional<torch::Tensor> wscale,
@@ -1407,6 +1445,7 @@ PYBIND11_MODULE(_k8sllm_ops, m) {
   m.def("fused_add_rms_norm", &fused_add_rms_norm);
   m.def("layer_norm", &layer_norm);
   m.def("silu_mul", &silu_mul);
+  m.def("silu_mul_pairing", &silu_mul_pairing);
   m.def("moe_grouped_gemm", &moe_grouped_gemm);
   m.def("gemm_tile", &gemm_tile, py::arg("y"), py::arg("x"), py::arg("w"), py::arg("offsets"), py::arg("swiglu"),
         py::arg("algo") = 1, py::arg("rope_pos") = py::none(), py::arg("rope_cs") = py::none(),
@@ -1453,6 +1492,7 @@ PYBIND11_MODULE(_k8sllm_ops, m) {
   m.attr("SKINNY_GROUPED_MAX_M") = k8sllm::kSkinnyGroupedMaxM;
   m.def("gemm_dec", &gemm_dec);
   m.def("gemm_dec", &gemm_dec_sw);
+  m.def("gemm_dec", &gemm_dec_delta);
   m.def("gemm_dec_forms", &gemm_dec_forms);
   m.def("gemm_dec_f8_forms", &gemm_dec_f8_forms);
   m.def("gemm_dec_f4_forms", &gemm_dec_f4_forms);

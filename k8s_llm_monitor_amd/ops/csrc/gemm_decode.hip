@@ -45,7 +45,34 @@ struct DecGroup {
   long w_eb, s_eb;  // bytes between experts' weights / their scales (s_eb: quantised stacks)
   const float* rw;        // [M][rw_ld] routing weights (SLAB epilogue) or null
   int rw_ld;
+  // Pre-activation delta of a dense SWIGLU8 launch (the adapters' gate_up delta, ops.lora_slab), or
+  // null: delta [M][N] fp32 over the packed row index, added to the rows whose dslot[row] names an
+  // adapter of the arena (0 <= slot < nslots) before gate and up are rounded to bf16.
+  const float* delta;
+  const int* dslot;
+  int nslots;
 };
+
+// v + d as two roundings: v (a product the compiler holds in a register) is pinned first, so the
+// add is never contracted into an fma with the factors of v.  The fp8 launch multiplies the
+// accumulator by the row's power-of-two scale and the bf16 launch over the dequantised weights does
+// not: fused, the two would round differently.
+__device__ __forceinline__ float dec_add_delta(float v, float d) {
+  asm volatile("" : "+v"(v));
+  return v + d;
+}
+
+// One lane's part of the SWIGLU8 store: v is this lane's pre-activation (gate in lanes with
+// l & 8 == 0, the matching up in lane l ^ 8); gate and up are rounded to bf16 first, as the unfused
+// GEMM -> silu_mul does, and the gate lane stores feature f of `row` fragment-packed.
+__device__ __forceinline__ void dec_swiglu_store(bf16_t* __restrict__ Y, int F, int f, int row, int lane, float v) {
+  const float o = __shfl_xor(v, 8, kWave);
+  if ((lane & 8) == 0) {
+    const float g = bf2f(f2bf(v)), u = bf2f(f2bf(o));
+    Y[(((long)(row >> 4) * (F >> 5) + (f >> 5)) * 64 + ((f >> 3) & 3) * 16 + (row & 15)) * 8 + (f & 7)] =
+        f2bf(g * u / (1.f + __expf(-g)));
+  }
+}
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t dec_rsrc(const void* base, long bytes) {
   const uint64_t a = reinterpret_cast<uint64_t>(base);
@@ -443,6 +470,54 @@ __global__ __launch_bounds__(64 * WAVES, 1) void gemm_dec_kernel(
       return;
     }
   }
+  if constexpr (EPI == DEC_SWIGLU8) {
+    if (grp.delta != nullptr) {
+      // The SWIGLU8 epilogue with a pre-activation delta (host: a dense launch, narrow deferred
+      // norm, M * N * 4 under 2 GiB).  A row's slot follows lora.hip's row_slot: rows past M and
+      // slots outside the arena have no adapter.  The delta loads are buffer loads, all issued
+      // before the first is used; a lane whose row has no adapter (or whose n-tile lies past N)
+      // gets an offset past the descriptor's range, which reads nothing.  Those rows then take
+      // exactly the statements of the plain epilogue below: bit-identical to a launch without delta.
+      int sl[MT][4];
+#pragma unroll
+      for (int m = 0; m < MT; ++m)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) sl[m][r] = grp.dslot[min(m * 16 + (lane >> 4) * 4 + r, M - 1)];
+      const __amdgpu_buffer_rsrc_t drs = dec_rsrc(grp.delta, (long)M * N * 4);
+      float dv[MT][NTW][4];
+#pragma unroll
+      for (int m = 0; m < MT; ++m)
+#pragma unroll
+        for (int t = 0; t < NTW; ++t)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int row = m * 16 + (lane >> 4) * 4 + r;
+            const bool on = row < M && sl[m][r] >= 0 && sl[m][r] < grp.nslots && tile0 + t < (N >> 4);
+            const uint32_t off = on ? (uint32_t)((row * N + (tile0 + t) * 16 + (lane & 15)) * 4) : 0x80000000u;
+            dv[m][t][r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(drs, off, 0, 0));
+          }
+#pragma unroll
+      for (int m = 0; m < MT; ++m) {
+        float rs[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) rs[r] = rn_ss != nullptr ? s_inv[m * 16 + (lane >> 4) * 4 + r] : 1.f;
+#pragma unroll
+        for (int t = 0; t < NTW; ++t) {
+          const int tile = tile0 + t;
+          if (tile >= (N >> 4)) continue;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int row = m * 16 + (lane >> 4) * 4 + r;
+            float v = acc[m][t][r] * rs[r];
+            if constexpr (F8) v *= wsc[t];
+            if (row < M && sl[m][r] >= 0 && sl[m][r] < grp.nslots) v = dec_add_delta(v, dv[m][t][r]);
+            dec_swiglu_store(Y, N >> 1, tile * 8 + (lane & 7), row, lane, v);
+          }
+        }
+      }
+      return;
+    }
+  }
 #pragma unroll
   for (int m = 0; m < MT; ++m) {
     float rs[4];
@@ -455,20 +530,11 @@ __global__ __launch_bounds__(64 * WAVES, 1) void gemm_dec_kernel(
       if constexpr (EPI == DEC_SWIGLU8) {
         // n-tile rows [8 gate | 8 up] of features 8 tile .. 8 tile + 7: lane l (l & 8 == 0) holds
         // the gate of feature 8 tile + (l & 7), lane l ^ 8 the matching up
-        const int F = N >> 1;
-        const int f = tile * 8 + (lane & 7);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           float v = acc[m][t][r] * rs[r];
           if constexpr (F8) v *= wsc[t];  // the [8 gate | 8 up] interleave permuted the scales with the rows
-          const float o = __shfl_xor(v, 8, kWave);
-          const int row = m * 16 + (lane >> 4) * 4 + r;
-          if ((lane & 8) == 0) {
-            // gate and up rounded to bf16 first, as the unfused GEMM -> silu_mul does
-            const float g = bf2f(f2bf(v)), u = bf2f(f2bf(o));
-            Y[(((long)(row >> 4) * (F >> 5) + (f >> 5)) * 64 + ((f >> 3) & 3) * 16 + (row & 15)) * 8 + (f & 7)] =
-                f2bf(g * u / (1.f + __expf(-g)));
-          }
+          dec_swiglu_store(Y, N >> 1, tile * 8 + (lane & 7), m * 16 + (lane >> 4) * 4 + r, lane, v);
         }
       } else {
         const int col = tile * 16 + (lane & 15);
@@ -667,15 +733,24 @@ static_assert(kDecAChunk == kDecCH && kDecRnNarrow == 4 * kRnMax && kDecRnWide =
 // weight k-steps in flight per wave (mxfp4: f4_depth, see dec_plan).
 // sw_rows / sw_wt / sw_xcd: dec_plan's switches for the SLAB epilogue and the split placement
 // (-1 as shipped).
+// delta / dslot / nslots: the pre-activation delta of a SWIGLU8 launch (DecGroup), or null.
 // Returns 0, or dec_plan's negative code when the shape / configuration is not supported (the
-// caller then uses gemm_skinny).
+// caller then uses gemm_skinny); -6: a delta this launch cannot take.
 extern "C" int k8sllm_gemm_dec(const void* A, const void* W, const void* wscale, int wf, float* partial, void* Y,
                                long ldy, int M, int N, int K, int splits, int epi, int ntw, int waves, int depth,
                                int f4_depth, const float* rn_ss, int rn_nc, int rn_d, float rn_eps, int experts,
                                long a_es, long w_eb, long s_eb, long y_es, const float* rw, int rw_ld,
-                               int sw_rows, int sw_wt, int sw_xcd, hipStream_t s) {
+                               int sw_rows, int sw_wt, int sw_xcd, const float* delta, const int* dslot,
+                               int nslots, hipStream_t s) {
   if (M <= 0) return 0;
   if (wf != DEC_W_BF16 && wscale == nullptr) return -1;
+  // the pre-activation delta: the SWIGLU8 epilogue of a dense launch with the narrow deferred norm
+  // (the wide one stands behind the row-complete o projection, which adapter steps do not take),
+  // 16-byte aligned and under 2 GiB (32-bit buffer offsets)
+  if (delta != nullptr &&
+      (epi != DEC_SWIGLU8 || experts >= 1 || rw != nullptr || (rn_ss != nullptr && rn_nc > kDecRnNarrow) ||
+       dslot == nullptr || nslots < 1 || reinterpret_cast<uintptr_t>(delta) % 16 || (long)M * N * 4 >= 0x7fffffffL))
+    return -6;
   const DecPlan p = dec_plan(wf, M, N, K, splits, epi, ntw, waves, depth, f4_depth, experts, rw != nullptr,
                              rn_ss != nullptr ? rn_nc : 0, sw_rows, sw_wt, sw_xcd);
   if (p.err < 0) return p.err;
@@ -684,7 +759,9 @@ extern "C" int k8sllm_gemm_dec(const void* A, const void* W, const void* wscale,
   const int flags = (rows ? kDecRows : 0) | (rows && p.wt ? kDecWt : 0) | (p.xcd ? kDecXcd : 0);
   const DecLaunch l{dim3(p.gx, p.gy, p.gz), dim3(64 * waves), s, (const bf16_t*)A, (const bf16_t*)W, partial,
                     (bf16_t*)Y, ldy, M, N, K, p.kchunk, rn_ss, rn_nc, rn_d > 0 ? 1.f / (float)rn_d : 0.f, rn_eps,
-                    DecGroup{a_es, y_es, w_eb, s_eb, rw, rw_ld}, wf == DEC_W_BF16 ? nullptr : (const float*)wscale,
+                    DecGroup{a_es, y_es, w_eb, s_eb, rw, rw_ld, delta, delta != nullptr ? dslot : nullptr,
+                             delta != nullptr ? nslots : 0},
+                    wf == DEC_W_BF16 ? nullptr : (const float*)wscale,
                     p.d4, flags};
   bool ok = false;
   switch (wf) {

@@ -112,9 +112,11 @@ __global__ __launch_bounds__(256) void layernorm_kernel(bf16_t* __restrict__ out
 }
 
 // SwiGLU: x = [gate | up] per row (width 2F), out = silu(gate) * up (width F).
-// IL: gate/up interleaved per 128 columns as [64 gate | 64 up] (the single resident w13 layout,
-// ops.interleave_gate_up, shared with the decode skinny SwiGLU epilogue); else [F gate | F up].
-template <bool IL>
+// IL 1: gate/up interleaved per 128 columns as [64 gate | 64 up] (the single resident w13 layout,
+// ops.interleave_gate_up, shared with the decode skinny SwiGLU epilogue); IL 8: per 16 columns as
+// [8 gate | 8 up] (the row order of a packed w13, ops.interleave_gate_up8: a thread's 8 features
+// c .. c + 7 have their gates at column 2c and their ups at 2c + 8); IL 0: [F gate | F up].
+template <int IL>
 __global__ __launch_bounds__(256) void silu_mul_kernel(bf16_t* __restrict__ out, const bf16_t* __restrict__ x,
                                                        long rows, int F) {
   // grid (ceil(F/8 / 256), min(rows, 65535)): 2-D indexing, no 64-bit division per element
@@ -125,8 +127,8 @@ __global__ __launch_bounds__(256) void silu_mul_kernel(bf16_t* __restrict__ out,
     float g[8], u[8], o[8];
     // the gate_up activations are read exactly once: non-temporal loads
     typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
-    const int gc = IL ? ((c >> 6) << 7) + (c & 63) : c;
-    const int uc = IL ? gc + 64 : F + c;
+    const int gc = IL == 8 ? 2 * c : IL ? ((c >> 6) << 7) + (c & 63) : c;
+    const int uc = IL == 8 ? gc + 8 : IL ? gc + 64 : F + c;
     const u32x4_t ga = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(xr + gc));
     const u32x4_t ua = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(xr + uc));
     unpack8(make_uint4(ga.x, ga.y, ga.z, ga.w), g);
@@ -241,14 +243,16 @@ int k8sllm_layernorm(void* out, const void* x, const void* w, const void* b, lon
   return (int)hipGetLastError();
 }
 
-int k8sllm_silu_mul(void* out, const void* x, long rows, int F, int interleaved, hipStream_t s) {
-  if (F % 8 != 0 || (interleaved && F % 64 != 0)) return -1;
+int k8sllm_silu_mul(void* out, const void* x, long rows, int F, int pairing, hipStream_t s) {
+  if (F % 8 != 0 || (pairing != 0 && pairing != 1 && pairing != 8) || (pairing == 1 && F % 64 != 0)) return -1;
   if (rows <= 0) return 0;
   const dim3 grid((F / 8 + 255) / 256, (unsigned)(rows < 65535 ? rows : 65535));
-  if (interleaved)
-    hipLaunchKernelGGL(silu_mul_kernel<true>, grid, dim3(256), 0, s, (bf16_t*)out, (const bf16_t*)x, rows, F);
+  if (pairing == 8)
+    hipLaunchKernelGGL(silu_mul_kernel<8>, grid, dim3(256), 0, s, (bf16_t*)out, (const bf16_t*)x, rows, F);
+  else if (pairing == 1)
+    hipLaunchKernelGGL(silu_mul_kernel<1>, grid, dim3(256), 0, s, (bf16_t*)out, (const bf16_t*)x, rows, F);
   else
-    hipLaunchKernelGGL(silu_mul_kernel<false>, grid, dim3(256), 0, s, (bf16_t*)out, (const bf16_t*)x, rows, F);
+    hipLaunchKernelGGL(silu_mul_kernel<0>, grid, dim3(256), 0, s, (bf16_t*)out, (const bf16_t*)x, rows, F);
   return (int)hipGetLastError();
 }
 

@@ -35,12 +35,19 @@ def layer_norm(x, w, b, eps):
     return F.layer_norm(x.float(), (x.shape[-1],), w.float(), b.float(), eps).to(x.dtype)
 
 
-def silu_mul(x: torch.Tensor, interleaved: bool = False) -> torch.Tensor:
-    """silu(gate) * up; ``interleaved``: columns are [64 gate | 64 up] per 128."""
+def silu_mul(x: torch.Tensor, interleaved: bool = False, pairing: int | None = None) -> torch.Tensor:
+    """silu(gate) * up; ``interleaved``: columns are [64 gate | 64 up] per 128.  ``pairing`` says the
+    same as a number and knows one more form: 0 [F gate | F up], 1 per 128 columns, 8 [8 gate | 8 up]
+    per 16 columns (the row order of ops.interleave_gate_up8)."""
     f = x.shape[-1] // 2
     xf = x.double()  # fp32 loses silu(gate) below -88 (exp overflows) while silu(gate) * up is still normal
-    if interleaved:
-        t = xf.reshape(*xf.shape[:-1], f // 64, 2, 64)
+    if pairing is None:
+        pairing = 1 if interleaved else 0
+    if pairing not in (0, 1, 8):
+        raise ValueError(f"silu_mul: pairing {pairing!r} is not 0, 1 or 8")
+    if pairing:
+        w = 64 if pairing == 1 else 8
+        t = xf.reshape(*xf.shape[:-1], f // w, 2, w)
         return (F.silu(t[..., 0, :]) * t[..., 1, :]).reshape(*xf.shape[:-1], f).to(x.dtype)
     return (F.silu(xf[..., :f]) * xf[..., f:]).to(x.dtype)
 

@@ -26,6 +26,8 @@ from concurrent.futures import Future
 from dataclasses import asdict
 from typing import Optional, Sequence as Seq, Union
 
+import numpy as np
+
 from .guide import compile_guide
 from .sequence import SamplingParams
 
@@ -40,6 +42,10 @@ class RemoteSeq:
         self.prompt_ids = d.get("prompt_ids", [])
         self.output_logprobs = d.get("output_logprobs")  # None unless the request asked (SamplingParams.logprobs)
         self.replica = d.get("replica")
+        # an embedding request's vector: it travels as its raw little-endian float32 bytes
+        self.embed_dim = d.get("embed_dim", 0)
+        emb = d.get("embedding")
+        self.embedding = np.frombuffer(emb, dtype="<f4").copy() if emb is not None else None
 
     def timings(self) -> dict:
         return dict(self._timings)
@@ -96,9 +102,14 @@ def _replica_main(conn, idx: int, cfg: dict, device: str) -> None:
             return
         try:
             text, seq = fut.result()
-            send(("done", key, {"text": text, "timings": seq.timings(), "finish_reason": seq.finish_reason,
-                                "output_ids": list(seq.output_ids), "prompt_ids": list(seq.prompt_ids),
-                                "output_logprobs": seq.output_logprobs, "replica": idx}))
+            body = {"text": text, "timings": seq.timings(), "finish_reason": seq.finish_reason,
+                    "output_ids": list(seq.output_ids), "prompt_ids": list(seq.prompt_ids),
+                    "output_logprobs": seq.output_logprobs, "replica": idx}
+            if seq.embed_dim:
+                body["embed_dim"] = seq.embed_dim
+                if seq.embedding is not None:
+                    body["embedding"] = np.ascontiguousarray(seq.embedding, dtype="<f4").tobytes()
+            send(("done", key, body))
         except (EngineOverloaded, EngineUnavailable) as e:
             send(("busy", key, str(e)))
         except BaseException as e:  # noqa: BLE001
@@ -110,10 +121,10 @@ def _replica_main(conn, idx: int, cfg: dict, device: str) -> None:
         except EOFError:
             break
         if kind == "req":
-            prompt, params, rid, stream, budget = (tuple(body) + (False, None))[:5]
+            prompt, params, rid, stream, budget, embed = (tuple(body) + (False, None, None))[:6]
             cb = (lambda ids, k=key: send(("tok", k, ids))) if stream else None
             deadline = time.perf_counter() + budget if budget is not None else None
-            fut = svc.submit(prompt, SamplingParams(**params), rid, on_tokens=cb, deadline=deadline)
+            fut = svc.submit(prompt, SamplingParams(**params), rid, on_tokens=cb, deadline=deadline, embed=embed)
             live[key] = fut
             fut.add_done_callback(lambda f, k=key: (live.pop(k, None), on_done(k, f)))
         elif kind == "cancel":
@@ -189,9 +200,11 @@ class ReplicaRouter:
         return self._error is None and all(r.proc.is_alive() for r in self.replicas)
 
     def submit(self, prompt: Union[str, list], params: Optional[SamplingParams] = None,
-               request_id: Optional[str] = None, on_tokens=None, deadline: Optional[float] = None) -> Future:
+               request_id: Optional[str] = None, on_tokens=None, deadline: Optional[float] = None,
+               embed: Optional[int] = None) -> Future:
         """As EngineService.submit; ``on_tokens`` is called on the router's reader thread with the
-        token ids the replica streams back (``tok`` messages) before the answer arrives."""
+        token ids the replica streams back (``tok`` messages) before the answer arrives.  ``embed``
+        is forwarded; the vector comes back in the ``done`` message (``RemoteSeq.embedding``)."""
         fut: Future = Future()
         if self._error is not None:
             fut.set_exception(RuntimeError(f"replica failed: {self._error}"))
@@ -219,7 +232,7 @@ class ReplicaRouter:
             if on_tokens is not None:
                 self._streams[key] = on_tokens
         budget = deadline - time.perf_counter() if deadline is not None else None  # replica clocks differ
-        r.send(("req", key, (prompt, p, request_id, on_tokens is not None, budget)))
+        r.send(("req", key, (prompt, p, request_id, on_tokens is not None, budget, embed)))
         return fut
 
     def cancel(self, fut: Future) -> bool:

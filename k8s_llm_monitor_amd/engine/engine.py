@@ -168,7 +168,7 @@ class LLMEngine:
         self.init_s = time.perf_counter() - t0
         self.counters = {"requests": 0, "finished": 0, "prompt_tokens": 0, "generated_tokens": 0,
                          "prefill_steps": 0, "decode_steps": 0, "mixed_steps": 0, "preemptions": 0,
-                         "deadline_stops": 0, "step_failures": 0}
+                         "deadline_stops": 0, "step_failures": 0, "embed_requests": 0, "embed_tokens": 0}
         self.is_leader = self.ps.tp_rank == 0
         self._inflight = None  # (seqs, DecodeHandle) of the enqueued, not yet read back decode step
         # (plan, DecodeHandle, step id) of the enqueued, not yet read back prefill-only step
@@ -205,10 +205,20 @@ class LLMEngine:
         serving_timeouts(self.ps)
 
     def add_request(self, prompt: Union[str, list[int]], params: Optional[SamplingParams] = None,
-                    request_id: Optional[str] = None, user=None, deadline: Optional[float] = None) -> Sequence:
+                    request_id: Optional[str] = None, user=None, deadline: Optional[float] = None,
+                    embed: Optional[int] = None) -> Sequence:
         """``deadline`` (time.perf_counter clock): the sequence stops with finish_reason "deadline"
         at the first step resolved after it - an answer truncated to what fits the caller's time
-        budget instead of work the caller has stopped waiting for."""
+        budget instead of work the caller has stopped waiting for.
+
+        ``embed``: an embedding request instead of a generation request - the prompt is prefilled
+        like any other and the sequence finishes (finish_reason "embed", no output token) with
+        ``Sequence.embedding``: the last token's final-normed hidden row cut to ``embed``
+        dimensions (0 or True: all ``d_model``) and L2-normalised."""
+        if embed is not None and embed is not False:
+            return self._add_embed(prompt, params, request_id, user, deadline, embed)
+        if not getattr(self.model, "has_head", True):
+            raise ValueError("embedding-only checkpoint (no lm_head): generation requests are refused")
         if params is not None and params.has_penalties():
             if not params.repetition_penalty > 0:
                 raise ValueError(f"repetition_penalty must be > 0, not {params.repetition_penalty!r}")
@@ -261,6 +271,59 @@ class LLMEngine:
         self.counters["requests"] += 1
         self.counters["prompt_tokens"] += len(ids)
         return seq
+
+    def _add_embed(self, prompt, params, request_id, user, deadline, embed) -> Sequence:
+        """``add_request`` for an embedding request.  Nothing of the sampler applies, so anything a
+        caller set there is refused rather than ignored; the input is never trimmed in the middle
+        (a vector of a different text would look like an answer)."""
+        d = self.model_cfg.d_model
+        if self.ps.tp_size > 1:  # the workers replay the leader's steps and would run the head and the sampler
+            raise ValueError("embedding requests are not supported with tensor parallelism (tp_size > 1)")
+        if embed is True:
+            embed = 0
+        if isinstance(embed, bool) or not isinstance(embed, int) or not 0 <= embed <= d:
+            raise ValueError(f"embed must be an integer in [0, {d}] (0: all {d} dimensions), not {embed!r}")
+        p = params
+        if p is not None and (p.adapter is not None or p.guide is not None or p.logprobs or p.top_logprobs
+                              or p.has_penalties()):
+            raise ValueError("an embedding request takes no adapter, guide, logprobs or sampling penalties")
+        ids = self.tokenizer.encode(prompt) if isinstance(prompt, str) else list(prompt)
+        if not ids:
+            raise ValueError("empty prompt")
+        if len(ids) > self.runner.max_len - 1:
+            raise ValueError(f"embedding input of {len(ids)} tokens exceeds the limit of {self.runner.max_len - 1}")
+        seq = Sequence(prompt_ids=ids, params=params or SamplingParams(),
+                       request_id=request_id or uuid.uuid4().hex[:16], user=user, deadline=deadline,
+                       embed_dim=embed or d)
+        self.sched.add(seq)
+        self.runner.embed_enable()
+        if self.trace is not None:
+            self.trace.append((time.perf_counter(), "add", 1, len(ids)))
+        self.counters["requests"] += 1
+        self.counters["prompt_tokens"] += len(ids)
+        self.counters["embed_requests"] += 1
+        self.counters["embed_tokens"] += len(ids)
+        return seq
+
+    def _finish_embed(self, seq: Sequence, emb, row: int, now: float) -> None:
+        """The step that computed the last row of an embedding sequence's prompt was read back:
+        the sequence takes its vector and finishes without a token (it never decodes)."""
+        seq.prefilled = False
+        seq.t_first_token = seq.t_finish = now
+        if seq.deadline is not None and now >= seq.deadline:
+            self.counters["deadline_stops"] += 1
+            self._finish(seq, "deadline")
+            return
+        seq.embedding = emb[row, : seq.embed_dim].numpy().copy()
+        self._finish(seq, "embed")
+
+    def embed(self, prompts: list, dim: Optional[int] = None) -> list:
+        """The embeddings (fp32 numpy vectors, unit L2 norm) of ``prompts`` (strings or token-id
+        lists), ``dim``: their first ``dim`` dimensions renormalised; beside :meth:`generate`."""
+        seqs = [self.add_request(p, embed=dim or 0) for p in prompts]
+        while any(s.status not in (SeqStatus.FINISHED, SeqStatus.ABORTED) for s in seqs):
+            self.step()
+        return [s.embedding for s in seqs]
 
     def _on_free(self, seq) -> None:
         """A sequence gave up its blocks (finished, aborted, preempted): its penalty and guide
@@ -387,6 +450,7 @@ class LLMEngine:
         self._pf_inflight = None
         toks = self.runner.decode_collect(h)
         lps = self.runner.collect_logprobs(h)
+        embs = self.runner.collect_embeddings(h)
         self._check_collectives()
         self.counters["prefill_steps"] += 1
         if self.trace is not None:
@@ -397,6 +461,10 @@ class LLMEngine:
             if seq.pending_first != sid:
                 continue  # a chunk short of the prompt's end, or freed (preempted / aborted) since
             seq.pending_first = 0
+            if seq.embed_dim:
+                self._finish_embed(seq, embs, row, now)
+                done.append(seq)
+                continue
             seq.prefilled = True
             seq.output_ids.append(int(tok))
             if seq.output_logprobs is not None:
@@ -498,11 +566,16 @@ class LLMEngine:
             self.counters["decode_steps"] += 1
             rows, nd = plan.seqs, len(plan.seqs)
         lps = self.runner.collect_logprobs(h)
+        embs = self.runner.collect_embeddings(h) if plan.is_prefill else None
         now = time.perf_counter()
         done = []
         for i, (seq, tok) in enumerate(zip(rows, toks)):
             if i >= nd and not self.sched.chunk_done(seq):
                 continue  # a chunk short of the prompt's end: no token yet
+            if i >= nd and seq.embed_dim:  # its token, if the step drew one, is dropped
+                self._finish_embed(seq, embs, i, now)
+                done.append(seq)
+                continue
             seq.output_ids.append(int(tok))
             if seq.output_logprobs is not None:
                 seq.output_logprobs.append(lps[i] if lps is not None else None)
@@ -569,7 +642,7 @@ class LLMEngine:
                   "graph_buckets": sorted(self.runner.graphs), "max_num_seqs": self.cfg.max_num_seqs,
                   "decode_weights": self.cfg.decode_weights, "prefill_weights": self.cfg.prefill_weights,
                   **self.runner.kv_stats(), **self.runner.penalty_stats(), **self.runner.guide_stats(),
-                  "logprobs_enabled": self.runner.lp_on,
+                  "logprobs_enabled": self.runner.lp_on, "embed_enabled": self.runner.embed_on,
                   "lora_enabled": self.runner.lora_on, "lora_adapters": [dict(a) for a in self._adapter_info],
                   "lora_bytes": self.model.lora.nbytes if self.model.lora is not None else 0,
                   "resident_weight_bytes": self.model.resident_weight_bytes(),
@@ -892,14 +965,19 @@ class EngineService:
         return self._q.qsize() + len(self.engine.sched.waiting)
 
     def submit(self, prompt: Union[str, list[int]], params: Optional[SamplingParams] = None,
-               request_id: Optional[str] = None, on_tokens=None, deadline: Optional[float] = None) -> Future:
+               request_id: Optional[str] = None, on_tokens=None, deadline: Optional[float] = None,
+               embed: Optional[int] = None) -> Future:
         """``on_tokens(ids)`` (optional, streaming): called on the engine thread with each batch of
         newly generated token ids, before the future resolves; keep it cheap (e.g. a queue put).
-        ``deadline``: time.perf_counter() value by which the answer is due (see class docstring)."""
+        ``deadline``: time.perf_counter() value by which the answer is due (see class docstring).
+        ``embed`` (``LLMEngine.add_request``): an embedding request - the future resolves to
+        ``(None, seq)`` with the vector in ``seq.embedding``, as generation resolves to ``(text, seq)``."""
         fut: Future = Future()
         if not self.healthy:
             fut.set_exception(EngineUnavailable(f"engine unhealthy: {self._error!r}"))
             return fut
+        if embed is False:
+            embed = None
         if params is not None and params.guide is not None:
             # compile on the caller's thread (a bad spec is this request's ValueError); the engine
             # thread then finds the guide in the compiler's cache
@@ -938,7 +1016,7 @@ class EngineService:
         tr = self.engine.trace
         if tr is not None:
             tr.append((time.perf_counter(), "submit", 1, 0))
-        self._q.put((prompt, params, request_id, fut, on_tokens, deadline))
+        self._q.put((prompt, params, request_id, fut, on_tokens, deadline, embed))
         return fut
 
     def cancel(self, fut: Future) -> bool:
@@ -971,6 +1049,8 @@ class EngineService:
         """Tokens ``seq`` is expected to still generate: its max_tokens minus what it already has
         (a preempted sequence keeps its answer so far), or - when it may stop on EOS - at most the
         observed 90th-percentile answer length (AnswerLengths) minus that."""
+        if seq.embed_dim:  # an embedding request generates nothing
+            return 0
         gen = sum(1 for t in seq.output_ids if t >= 0)
         rem = max(0, seq.params.max_tokens - gen)
         if seq.params.ignore_eos:
@@ -1117,11 +1197,11 @@ class EngineService:
         coalesce = (block or gather) and cfg.admit_window_ms > 0
         t_end = time.perf_counter() + cfg.admit_window_ms * 1e-3
         while item is not None:
-            prompt, params, rid, fut, on_tokens, deadline = item
+            prompt, params, rid, fut, on_tokens, deadline, embed = item
             try:
                 if fut.cancelled():  # cancelled while queued
                     raise _Skip()
-                seq = self.engine.add_request(prompt, params, rid, user=fut, deadline=deadline)
+                seq = self.engine.add_request(prompt, params, rid, user=fut, deadline=deadline, embed=embed)
                 if on_tokens is not None:
                     self._streams[seq.seq_id] = [seq, 0, on_tokens]
             except _Skip:
@@ -1221,12 +1301,13 @@ class EngineService:
         if self._streams:
             self._push_streams()
         for seq in finished:
-            if not seq.params.ignore_eos and seq.finish_reason in ("stop", "length"):
+            # (an embedding sequence has no answer: a stream of zero lengths would drag the quantile)
+            if not seq.embed_dim and not seq.params.ignore_eos and seq.finish_reason in ("stop", "length"):
                 self.answer_lens.record(sum(1 for t in seq.output_ids if t >= 0))
             fut = seq.user
             if isinstance(fut, Future) and not fut.done():
                 self.latencies_ms.append(seq.timings()["latency_ms"])
-                fut.set_result((eng.decode_text(seq), seq))
+                fut.set_result((None if seq.embed_dim else eng.decode_text(seq), seq))
         if finished and eng.trace is not None:
             eng.trace.append((time.perf_counter(), "resolved", len(finished), 0))
 

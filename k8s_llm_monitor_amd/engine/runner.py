@@ -118,6 +118,13 @@ class ModelRunner:
         self._lslot_sent = None
         self.lora_on = False
         self.graphs_lora: dict[int, list] = {}
+        # embedding requests (ops.pool_l2 after the final norm of a prefill step), off until the
+        # first one (embed_enable): prefill steps then stage the rows' embedding widths, the pooled
+        # rows go into one device buffer (grown on demand; steps are ordered on the stream) and are
+        # read back into one of two pinned fp32 buffers, beside the tokens
+        self.embed_on = False
+        self._d_emb: Optional[torch.Tensor] = None
+        self._pf_emb: list = [None, None]
         self.decode_ws = ops.decode_workspace(B, model.hq, D, self.max_blocks_per_seq * BLOCK_SIZE, dev, model.hkv) \
             if self.is_gpu else None
         # pinned host staging, double-buffered: with pipelined decode the host fills step N+1's
@@ -371,6 +378,20 @@ class ModelRunner:
         return [(f[0], [(i, v) for i, v in zip(t[:w], f[1:1 + w]) if i >= 0]) if w >= 0 else None
                 for w, f, t in zip(handle.lp_want, lps, ids)]
 
+    # --------------------------------------------------------------------- embedding requests
+    def embed_enable(self) -> None:
+        """The first embedding request: prefill steps stage ``edim`` from now on.  Decode steps and
+        their graphs never carry an embedding row, so nothing is captured again."""
+        self.embed_on = True
+
+    @staticmethod
+    def collect_embeddings(handle: "DecodeHandle") -> Optional[torch.Tensor]:
+        """After :meth:`decode_collect`: the step's pooled rows, fp32 [>= rows, d_model] on the host
+        (row r of the step is valid where that row was an embedding row), or None when it had none."""
+        if handle.emb is not None and handle.event is not None:
+            handle.event.synchronize()
+        return handle.emb
+
     # --------------------------------------------------------------------- prefill
     def prefill(self, seqs: list[Sequence], decode: Optional[list] = None) -> list[int]:
         """One prefill (or mixed) step, synchronous: see :meth:`prefill_launch`."""
@@ -427,7 +448,8 @@ class ModelRunner:
                      mcu=len(seqs) + 2 if kA else 0, mqs=nq if kA else 0, mst=nq if kA else 0,
                      mlidx=len(seqs) if kA else 0, pslot=R if self.pen is not None else 0,
                      want=R if self.lp_on else 0, gslot=R if self.gd is not None else 0,
-                     lslot=T if self.lora_on and any(getattr(s, "lora_slot", -1) >= 0 for s in rows) else 0)
+                     lslot=T if self.lora_on and any(getattr(s, "lora_slot", -1) >= 0 for s in rows) else 0,
+                     edim=R if self.embed_on else 0)
         off, o = {}, 0
         for k, n in sizes.items():
             off[k] = o
@@ -484,6 +506,15 @@ class ModelRunner:
                               for s, c, n in zip(seqs, starts, lens)]
             if int(v["want"].max()) >= 0:
                 lp_want = v["want"].tolist()
+        has_emb, want_logits = False, True
+        if self.embed_on:
+            # the row of a chunk that reaches the end of an embedding sequence's prompt is pooled; the
+            # head and the sampler run unless no row of the step needs a token
+            v["edim"][:nd] = 0
+            v["edim"][nd:] = [getattr(s, "embed_dim", 0) if c + n >= s.num_tokens else 0
+                              for s, c, n in zip(seqs, starts, lens)]
+            has_emb = bool(v["edim"].any())
+            want_logits = bool(nd) or not all(getattr(s, "embed_dim", 0) for s in seqs)
         if paged:
             v["cst"][:] = starts
             bt2 = v["bt"].reshape(len(seqs), W)
@@ -510,6 +541,15 @@ class ModelRunner:
                         qb_seq=dv["qs"], qb_start=dv["st"], logits_idx=dv["lidx"].long())
         if sizes["lslot"]:
             meta.lora_slot = dv["lslot"]
+        if has_emb:
+            meta.pool_dim = dv["edim"]
+            if self.is_gpu:  # (the CPU path hands the step's own tensor to the handle)
+                # rows that are no embedding rows keep whatever the buffer held: nobody reads them
+                if self._d_emb is None or self._d_emb.shape[0] < R:
+                    self._d_emb = torch.zeros(max(R, 2 * self.B), self.model.cfg.d_model, dtype=torch.float32,
+                                              device=dev)
+                meta.pooled = self._d_emb[:R]
+        meta.want_logits = want_logits
         if paged:
             meta.ctx_start = dv["cst"]
             meta.block_tables = dv["bt"].view(len(seqs), W)
@@ -537,20 +577,32 @@ class ModelRunner:
         self.n_steps["prefill_context_tokens"] = self.n_steps.get("prefill_context_tokens", 0) + sum(starts)
         self.n_steps["prefill_tokens"] = self.n_steps.get("prefill_tokens", 0) + T
         logits = self.model.forward(dv["ids"], meta, self.kv)
-        tok = self._sample(logits, dv["temp"].view(torch.float32), dv["topk"], dv["topp"].view(torch.float32),
-                           pslot=dv["pslot"], gslot=dv["gslot"])
-        lp = ops.token_logprobs(logits[:R], tok, dv["want"]) if lp_want is not None else None
+        tok = lp = None
+        if want_logits:  # else an embedding-only step: no head (forward), no sampler, no tokens
+            tok = self._sample(logits, dv["temp"].view(torch.float32), dv["topk"], dv["topp"].view(torch.float32),
+                               pslot=dv["pslot"], gslot=dv["gslot"])
+            lp = ops.token_logprobs(logits[:R], tok, dv["want"]) if lp_want is not None else None
+        emb = meta.pooled if has_emb else None
         self.n_steps["prefill"] += 1
         if self.on_launched is not None:  # TP: the custom-AR error flag, read back with the tokens
             self.on_launched()
         if not self.is_gpu:
-            return DecodeHandle(R, None, tok[:R].tolist(), lp=lp, lp_want=lp_want)
+            return DecodeHandle(R, None, tok[:R].tolist() if tok is not None else None, lp=lp, lp_want=lp_want,
+                                emb=emb)
         j = self._pf_oi
         self._pf_oi ^= 1  # two in flight at most: step N+1 is launched before step N is read back
-        if self._pf_out[j] is None or self._pf_out[j].numel() < R:
-            self._pf_out[j] = torch.empty(max(R, 2 * self.B), dtype=torch.int32, pin_memory=True)
-        out = self._pf_out[j]
-        out[:R].copy_(tok[:R], non_blocking=True)
+        out = None
+        if tok is not None:
+            if self._pf_out[j] is None or self._pf_out[j].numel() < R:
+                self._pf_out[j] = torch.empty(max(R, 2 * self.B), dtype=torch.int32, pin_memory=True)
+            out = self._pf_out[j]
+            out[:R].copy_(tok[:R], non_blocking=True)
+        h_emb = None
+        if emb is not None:
+            if self._pf_emb[j] is None or self._pf_emb[j].shape[0] < R:
+                self._pf_emb[j] = torch.empty(max(R, 2 * self.B), emb.shape[1], dtype=torch.float32, pin_memory=True)
+            h_emb = self._pf_emb[j]
+            h_emb[:R].copy_(emb, non_blocking=True)
         h_lp = None
         if lp is not None:
             if self._pf_lp[j] is None or self._pf_lp[j].shape[0] < R:
@@ -558,7 +610,7 @@ class ModelRunner:
             h_lp = self._pf_lp[j]
             h_lp[:R].copy_(lp, non_blocking=True)
         ev, _ = self._chain_event()
-        return DecodeHandle(R, ev, out, lp=h_lp, lp_want=lp_want)
+        return DecodeHandle(R, ev, out, lp=h_lp, lp_want=lp_want, emb=h_emb)
 
     # --------------------------------------------------------------------- decode
     def _decode_body(self, b: int, lora: bool = False) -> None:
@@ -724,10 +776,11 @@ class ModelRunner:
 
     @staticmethod
     def decode_collect(handle: "DecodeHandle") -> list[int]:
-        if handle.event is None:
-            return handle.out
-        handle.event.synchronize()
-        return handle.out[: handle.n].tolist()
+        if handle.event is not None:
+            handle.event.synchronize()
+        if handle.out is None:  # an embedding-only prefill step drew no tokens
+            return [-1] * handle.n
+        return handle.out if handle.event is None else handle.out[: handle.n].tolist()
 
     def kv_stats(self) -> dict:
         """The paged cache as allocated: its encoding, blocks and true bytes (codes + scales for fp8)."""
@@ -798,6 +851,7 @@ class DecodeHandle:
     prev_event: object = None  # the back-to-back predecessor's end event (ModelRunner._chain_event)
     lp: object = None  # the step's packed logprob records (pinned on the GPU), None when no row asked
     lp_want: Optional[list] = None  # with lp: per row what it asked (-1: nothing, its record is stale)
+    emb: object = None  # a prefill step's pooled rows, fp32 [>= n, d_model] (pinned on the GPU), None without embedding rows
 
     def gpu_ms(self) -> Optional[float]:
         """This step's GPU time (after the event completed), or None when not measurable."""

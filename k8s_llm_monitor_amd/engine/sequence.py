@@ -7,6 +7,8 @@ import time
 from dataclasses import dataclass, field
 from typing import Optional
 
+import numpy as np
+
 
 @dataclass
 class SamplingParams:
@@ -86,6 +88,11 @@ class Sequence:
     # model) and the seed of its prefix-cache hash chain (0: the base model's hashes)
     lora_slot: int = -1
     hash_seed: int = 0
+    # embedding requests (engine.add_request embed=): the width asked for (0: a generation request)
+    # and the result - the first embed_dim entries of the last token's final-normed hidden row,
+    # L2-normalised, fp32; None until the sequence finishes with finish_reason "embed"
+    embed_dim: int = 0
+    embedding: Optional[np.ndarray] = None
 
     @property
     def num_tokens(self) -> int:

@@ -64,12 +64,14 @@ class LocalEngineBackend:
 
     def __init__(self, service, max_tokens: int = 2000, temperature: float = 0.1, top_p: float = 1.0,
                  top_k: int = 0, timeout_s: float = 30.0, answer_budget_s: Optional[float] = None,
-                 repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0):
+                 repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0,
+                 embed_append_eos: bool = False):
         """``timeout_s`` is ``llm.timeout``.  ``answer_budget_s`` (default: timeout_s): the time a
         synchronous answer may take - the server sets it below its write timeout
         (``answer_budget``) so the engine ends the generation at the deadline with
         finish_reason "deadline" and the caller gets the answer generated so far, instead of a 504
-        while the GPU keeps generating for a client that has gone."""
+        while the GPU keeps generating for a client that has gone.  ``embed_append_eos`` is
+        ``llm.embed_append_eos`` (:meth:`embed`)."""
         from ..engine import SamplingParams
 
         self.svc = service
@@ -84,6 +86,57 @@ class LocalEngineBackend:
         mml = getattr(getattr(eng, "cfg", None), "max_model_len", None) or (1 << 30)
         self.max_len = min(int(mml), int(eng.model_cfg.max_position))  # the engine's per-sequence cap
         self.adapters = set(getattr(eng, "adapters", None) or ())  # the configured LoRA adapters' names
+        self.embed_append_eos = bool(embed_append_eos)
+        self.d_model = int(eng.model_cfg.d_model)
+        self.vocab_size = int(eng.model_cfg.vocab_size)
+
+    def embed(self, inputs: list, dimensions: Optional[int] = None) -> tuple:
+        """``(vectors, prompt tokens)`` of ``inputs``, each a string or a list of token ids: one
+        fp32 numpy vector of unit L2 norm per input, in input order - the last token's final-normed
+        hidden state, cut to its first ``dimensions`` (default: all ``d_model``) and normalised.
+        A string is encoded with the tokenizer's BOS rule and, with ``llm.embed_append_eos``,
+        followed by the model's EOS token; token ids are taken as given.  All inputs are submitted
+        before the first is awaited, so they share prefill steps; the first failure cancels the
+        rest.  ``ValueError`` for what the engine refuses (an empty or over-long input, ...)."""
+        if dimensions is not None and (isinstance(dimensions, bool) or not isinstance(dimensions, int)
+                                       or not 1 <= dimensions <= self.d_model):
+            raise ValueError(f"dimensions must be an integer in [1, {self.d_model}], not {dimensions!r}")
+        eos = int(self.svc.engine.model_cfg.eos_ids[0])
+        prompts = []
+        for x in inputs:
+            if isinstance(x, str):
+                ids = list(self.tokenizer.encode(x)) if x else []
+                if ids and self.embed_append_eos:
+                    ids.append(eos)
+            else:
+                ids = list(x)
+                if any(isinstance(t, bool) or not isinstance(t, int) or not 0 <= t < self.vocab_size for t in ids):
+                    raise ValueError(f"token ids must be integers in [0, {self.vocab_size})")
+            if not ids:
+                raise ValueError("an embedding input must not be empty")
+            if len(ids) > self.max_len - 1:
+                raise ValueError(f"embedding input of {len(ids)} tokens exceeds the limit of {self.max_len - 1}")
+            prompts.append(ids)
+        budget = self.answer_budget_s
+        t_end = time.perf_counter() + budget if budget else None
+        futs = [self.svc.submit(ids, None, None, deadline=t_end, embed=dimensions or 0) for ids in prompts]
+        out, n_tok = [], 0
+        try:
+            for fut in futs:
+                left = max(0.0, t_end - time.perf_counter()) + 0.75 if t_end is not None else None
+                try:
+                    _, seq = fut.result(timeout=left)
+                except FutTimeout:
+                    raise AnswerBudgetExceeded("embeddings not ready within the answer budget") from None
+                if seq.embedding is None:  # ended by its deadline before the prompt's last step
+                    raise AnswerBudgetExceeded("embeddings not ready within the answer budget")
+                out.append(seq.embedding)
+                n_tok += len(seq.prompt_ids)
+        finally:
+            for fut in futs:
+                if not fut.done():
+                    self.svc.cancel(fut)
+        return out, n_tok
 
     def max_prompt_tokens(self, max_tokens: Optional[int] = None) -> int:
         """Prompt tokens that still leave room for ``max_tokens`` answer tokens (preamble included);

@@ -22,6 +22,8 @@ Name maps (HF -> this framework):
     block_sparse_moe.gate -> router, block_sparse_moe.experts.e.{w1,w3} -> w13[e], .w2 -> w2[e]
     (or the fused-expert form mlp.gate / mlp.experts.gate_up_proj / mlp.experts.down_proj)
   qwen3: llama's names, plus layers.i.self_attn.{q,k}_norm -> q_norm, k_norm
+  (llama family, base-model save form - embedding models: the same names without "model." and no
+    lm_head; CausalLM.has_head is then False and only embedding requests are served)
   gpt2: transformer.wte / wpe / ln_f, h.i.ln_1 / ln_2, attn.c_attn / c_proj, mlp.c_fc / c_proj
     (Conv1D weights are stored [in, out]: transposed on load and on save)
 """
@@ -207,14 +209,20 @@ def load_checkpoint(model, path: PathLike, strict: bool = True) -> list[str]:
             L["w2"] = put(get(p + "mlp.c_proj.weight").t()[:, f_lo:f_hi])
             L["b2"] = put(get(p + "mlp.c_proj.bias"))
     else:
-        model.embed = vocab_rows("model.embed_tokens.weight")
+        # the save form of the base model class (Qwen3Model.save_pretrained; how embedding models
+        # are published) has no "model." prefix - and no head
+        pre = "model." if "model.embed_tokens.weight" in src or "embed_tokens.weight" not in src else ""
+        model.embed = vocab_rows(pre + "embed_tokens.weight")
         if c.tie_embeddings or "lm_head.weight" not in src:
             model.lm_head = model.embed
         else:
             model.lm_head = vocab_rows("lm_head.weight")
-        model.final_norm = put(get("model.norm.weight"))
+        # neither a head nor tied embeddings: the embedding matrix stands in (layouts and decode
+        # copies as ever), but it is no head - the engine serves embedding requests only
+        model.has_head = c.tie_embeddings or "lm_head.weight" in src
+        model.final_norm = put(get(pre + "norm.weight"))
         for i, L in enumerate(model.layers):
-            p = f"model.layers.{i}."
+            p = f"{pre}layers.{i}."
             a = p + "self_attn."
             L["wqkv"] = put(torch.cat([src.slice_rows(a + "q_proj.weight", q_lo, q_hi),
                                        src.slice_rows(a + "k_proj.weight", kv_lo, kv_hi),

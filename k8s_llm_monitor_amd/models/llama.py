@@ -120,6 +120,13 @@ class AttnMeta:
     # per-request LoRA: the adapter slot of every row of the step ([T] int32, -1 = the base model);
     # None when no row uses an adapter - the step then takes exactly the paths it takes without LoRA
     lora_slot: Optional[torch.Tensor] = None
+    # embedding requests (prefill steps only): pool_dim [R] int32 aligned with logits_idx, > 0 = the
+    # row is an embedding row of that many dimensions; forward leaves ops.pool_l2's fp32 [R, d_model]
+    # in ``pooled``.  None = no embedding row.  want_logits False: no row of the step needs a token,
+    # the LM head is not run and forward returns an empty [0, vocab] tensor
+    pool_dim: Optional[torch.Tensor] = None
+    want_logits: bool = True
+    pooled: Optional[torch.Tensor] = None
 
 
 def _seed_for(name: str, seed: int) -> int:
@@ -218,6 +225,10 @@ class CausalLM:
     # GEMM of that tail is one whose rows do not depend on each other (the tile kernel, or the CPU
     # reference), so the logits are bit-identical to the full-row form's.  False: the full-row form (A/B).
     LAST_LAYER_ROWS = True
+    # False after load_checkpoint read a checkpoint with neither an lm_head nor tied embeddings (the
+    # base-model save form embedding models ship as): lm_head is then the embedding matrix standing
+    # in, and the engine refuses generation requests
+    has_head = True
 
     def __init__(self, cfg: ModelConfig, device: torch.device | str = "cpu", dtype=torch.bfloat16, seed: int = 0,
                  pstate: Optional[ParallelState] = None, init_std: float = 0.02, init: str = "random",
@@ -905,15 +916,15 @@ class CausalLM:
             # a step with adapter rows: the plain layer loop below, ops.lora_add after qkv, o and down
             lora = self._lora_slot(meta) is not None
             if not lora and self._fused_norm_ok(h):
-                return self._logits(self._prefill_fused_norm(residual, meta, kv_caches))
+                return self._head(self._prefill_fused_norm(residual, meta, kv_caches), meta)
             if not lora and meta.micro is not None and self.overlap_ok():
-                return self._logits(self._prefill_overlap(residual, meta, kv_caches))
+                return self._head(self._prefill_overlap(residual, meta, kv_caches), meta)
             x = ops.rms_norm(h, self.layers[0]["attn_norm"], c.norm_eps)
             n = len(self.layers)
             for i, L in enumerate(self.layers):
                 kv = kv_caches[i] if kv_caches is not None else None
                 if i + 1 == n and not lora and self._last_rows_ok(L, h, meta):
-                    return self._logits(self._last_rows(L, self._attn_core(L, x, meta, kv), residual, meta))
+                    return self._head(self._last_rows(L, self._attn_core(L, x, meta, kv), residual, meta), meta)
                 y = self._attention(L, x, meta, kv, li=i)
                 x = ops.fused_add_rms_norm(y, residual, L["mlp_norm"], c.norm_eps)
                 y = self._mlp(L, x, meta, li=i)
@@ -924,7 +935,7 @@ class CausalLM:
                         y = y[meta.logits_idx]
                         residual = residual[meta.logits_idx].contiguous()
                     x = ops.fused_add_rms_norm(y.contiguous(), residual, self.final_norm, c.norm_eps)
-        return self._logits(x)
+        return self._head(x, meta)
 
     def overlap_ok(self) -> bool:
         """TP > 1 dense Llama prefill may run as two overlapped micro-batches (_prefill_overlap;
@@ -1069,6 +1080,16 @@ class CausalLM:
         x = ops.fused_add_rms_norm(y, res, L["mlp_norm"], eps)
         y = self._mlp(L, x, meta)
         return ops.fused_add_rms_norm(y.contiguous(), res, self.final_norm, eps)
+
+    def _head(self, x: torch.Tensor, meta: AttnMeta) -> torch.Tensor:
+        """Every exit of ``forward`` outside the decode fast path: ``x`` the final-normed rows
+        (``meta.logits_idx``'s).  Embedding rows (``meta.pool_dim``) are pooled into ``meta.pooled``
+        first; a step whose rows need no token (``want_logits`` False) skips the LM head."""
+        if meta.pool_dim is not None:
+            meta.pooled = ops.pool_l2(x, meta.pool_dim, out=meta.pooled)  # the caller's buffer, or a fresh one
+        if not meta.want_logits:
+            return x.new_empty(0, self.cfg.vocab_size)
+        return self._logits(x)
 
     def _logits(self, x: torch.Tensor, rows: Optional[int] = None) -> torch.Tensor:
         """LM head (+ the TP all-gather of the vocab shards).  ``x``: the final-normed rows,

@@ -12,12 +12,13 @@ import torch.nn.functional as F
 
 
 @torch.no_grad()
-def fp32_logits(model, ids: torch.Tensor, rows: Optional[list] = None, device: Optional[str] = None) -> torch.Tensor:
-    """Logits [len(rows), vocab] of prompt ``ids`` (1-D) at positions ``rows`` (default: the last
-    token), causal attention over the whole prompt.  TP=1 Llama arch (RoPE, RMSNorm, SwiGLU)."""
+def fp32_hidden(model, ids: torch.Tensor, rows: Optional[list] = None, device: Optional[str] = None) -> torch.Tensor:
+    """Final-normed hidden rows [len(rows), d_model] of prompt ``ids`` (1-D) at positions ``rows``
+    (default: the last token), causal attention over the whole prompt: what the LM head and the
+    embedding pooling (``ops.pool_l2``) read.  TP=1 Llama arch (RoPE, RMSNorm, SwiGLU)."""
     c = model.cfg
     if c.arch != "llama" or c.is_moe or model.tp != 1:
-        raise ValueError("fp32_logits: dense Llama-architecture models at TP=1")
+        raise ValueError("fp32_hidden: dense Llama-architecture models at TP=1")
     dev = torch.device(device) if device is not None else ids.device
 
     def w(t: torch.Tensor) -> torch.Tensor:
@@ -52,5 +53,12 @@ def fp32_logits(model, ids: torch.Tensor, rows: Optional[list] = None, device: O
         f = gu.shape[1] // 2
         x = x + (F.silu(gu[:, :f]) * gu[:, f:]) @ w(model.canonical(L, "w2")).t()
     rows = [T - 1] if rows is None else rows
-    h = F.rms_norm(x[rows], (c.d_model,), w(model.final_norm), c.norm_eps)
-    return (h @ w(model.canonical_head()).t())[:, : c.vocab_size]
+    return F.rms_norm(x[rows], (c.d_model,), w(model.final_norm), c.norm_eps)
+
+
+@torch.no_grad()
+def fp32_logits(model, ids: torch.Tensor, rows: Optional[list] = None, device: Optional[str] = None) -> torch.Tensor:
+    """Logits [len(rows), vocab] of prompt ``ids`` (1-D) at positions ``rows`` (default: the last
+    token): ``fp32_hidden`` times the LM head."""
+    h = fp32_hidden(model, ids, rows, device)
+    return (h @ model.canonical_head().to(h.device).float().t())[:, : model.cfg.vocab_size]

@@ -98,7 +98,8 @@ def make_llm_backend(cfg: Config, pstate=None, device: Optional[str] = None):
         return (LocalEngineBackend(svc, cfg.llm.max_tokens, cfg.llm.temperature, cfg.llm.top_p, cfg.llm.top_k,
                                    timeout_s=float(cfg.llm.timeout), repetition_penalty=cfg.llm.repetition_penalty,
                                    presence_penalty=cfg.llm.presence_penalty,
-                                   frequency_penalty=cfg.llm.frequency_penalty), eng, svc)
+                                   frequency_penalty=cfg.llm.frequency_penalty,
+                                   embed_append_eos=cfg.llm.embed_append_eos), eng, svc)
     if prov == "openai":
         return OpenAIBackend(cfg.llm.api_key, cfg.llm.base_url, cfg.llm.model, cfg.llm.max_tokens,
                              cfg.llm.temperature, float(cfg.llm.timeout), presence_penalty=cfg.llm.presence_penalty,
@@ -167,6 +168,7 @@ def build_monitor(cfg: Config, backend=None, start_manager: bool = True, llm: bo
     m.analysis.analysis_adapters = dict(cfg.llm.analysis_adapters or {})
     m.app = MonitorApp(m.client, m.manager, m.analysis, m.engine_service, llm_timeout_s=float(cfg.llm.timeout))
     m.app.guide_max_states = cfg.llm.guide_max_states
+    m.app.embed_max_inputs = cfg.llm.embed_max_inputs
     if hasattr(backend_llm, "answer_budget_s"):  # the engine stops generations before the write timeout
         backend_llm.answer_budget_s = m.app.answer_budget_s()
     m.analysis.analyzer = m.app.analyzer if analyzer is None else analyzer

@@ -11,7 +11,8 @@ the in-process MI355X engine (``openai`` keeps the reference's remote semantics:
 plus ``tp_size``, ``dp_replicas``, ``max_batch``, ``kv_cache_gb``, ``max_model_len``, ``dtype``,
 ``seed``, ``use_graphs``, ``decode_weights``, ``prefill_weights``, ``kv_cache_dtype``, and the
 sampling penalties ``repetition_penalty``, ``presence_penalty``, ``frequency_penalty`` and
-``guide_max_states`` (constrained decoding).
+``guide_max_states`` (constrained decoding), and ``embed_append_eos`` / ``embed_max_inputs``
+(``POST /v1/embeddings``).
 """
 from __future__ import annotations
 
@@ -97,6 +98,12 @@ class LLMConfig:
     lora_adapters: dict = field(default_factory=dict)
     lora_max_rank: int = 64
     analysis_adapters: dict = field(default_factory=dict)
+    # POST /v1/embeddings (docs/api.md): embed_append_eos - a string input is followed by the
+    # model's EOS token before it is embedded (Qwen3-Embedding pools that token; token-id inputs
+    # are taken as given); embed_max_inputs - the most inputs of one request (one prefill step's
+    # sequences at the default max_batch)
+    embed_append_eos: bool = False
+    embed_max_inputs: int = 64
 
 
 @dataclass

@@ -9,6 +9,7 @@ plus the analysis routes the reference only advertised or planned:
   POST /api/v1/analyze                     AnalysisRequest {"type", "parameters", "context"}
   GET  /api/v1/analysis[/<request_id>]     stored AnalysisResponse records
   GET  /api/v1/metrics/engine              engine queue / batch / KV-cache / latency stats
+  POST /v1/embeddings                      OpenAI-compatible embeddings of the local model
   POST /api/v1/analyze/pod-communication   + "llm" key (explanation) when a model is configured
                                            (send "explain": false for the reference body only)
 
@@ -19,6 +20,7 @@ answers 504 instead of being cut off silently.
 """
 from __future__ import annotations
 
+import base64
 import json
 import socket
 import logging
@@ -113,6 +115,7 @@ class MonitorApp:
         self.write_timeout_s = write_timeout_s
         self.llm_timeout_s = llm_timeout_s
         self.guide_max_states = 512  # llm.guide_max_states (set by the application)
+        self.embed_max_inputs = 64  # llm.embed_max_inputs (set by the application)
         self.analyzer = None
         if client is not None:
             from .analysis.network import NetworkAnalyzer
@@ -150,6 +153,7 @@ class MonitorApp:
                 "/api/v1/analysis": self.analysis_list,
                 "/api/v1/metrics/engine": self.metrics_engine,
                 "/v1/chat/completions": self.chat_completions,
+                "/v1/embeddings": self.embeddings,
                 "/metrics": self.prometheus,
             }
             fn = exact.get(path)
@@ -525,6 +529,59 @@ class MonitorApp:
                            "created": int(time.time()),
                            "model": pen.get("adapter") or g.get("model") or d.get("model", ""),
                            "choices": [choice], "usage": usage})
+
+    def embeddings(self, method, body, q) -> Reply:
+        """OpenAI-compatible embeddings: ``{"input": str | [str] | [int] | [[int]], "model"?,
+        "dimensions"?, "encoding_format"?: "float" | "base64"}`` -> ``{"object": "list", "model",
+        "data": [{"object": "embedding", "index", "embedding"}], "usage"}`` in input order.  A
+        vector is the last token's final-normed hidden state of the local model, cut to
+        ``dimensions`` and L2-normalised (``LocalEngineBackend.embed``); ``base64`` carries its
+        little-endian float32 bytes.  Whatever is wrong with the request is a 400 with a message;
+        503 / 504 as on the chat route."""
+        _only(method, "POST")
+        if self.analysis is None:
+            raise http_error(503, "Analysis engine not available")
+        d = _decode_object(body)
+        if d is None:
+            raise http_error(400, "Invalid JSON body")
+        backend = self.analysis.backend
+        if not hasattr(backend, "embed"):
+            raise http_error(400, f"the {getattr(backend, 'provider', 'configured')} backend serves no embeddings "
+                                  "(llm.provider: local-rocm does)")
+        inp = d.get("input")
+        if isinstance(inp, str) or (isinstance(inp, list) and inp and all(
+                isinstance(t, int) and not isinstance(t, bool) for t in inp)):
+            inp = [inp]  # one input: a string or one list of token ids
+        if not isinstance(inp, list) or not inp:
+            raise http_error(400, "input must be a non-empty string, list of strings, or list(s) of token ids")
+        if len(inp) > self.embed_max_inputs:
+            raise http_error(400, f"at most {self.embed_max_inputs} inputs per request, got {len(inp)}")
+        for i, x in enumerate(inp):
+            if not isinstance(x, (str, list)) or not x:
+                raise http_error(400, f"input {i} must be a non-empty string or list of token ids")
+        fmt = d.get("encoding_format", "float")
+        if fmt not in ("float", "base64"):
+            raise http_error(400, "encoding_format must be \"float\" or \"base64\"")
+        dims = d.get("dimensions")
+        try:
+            vecs, n_tok = self._bounded(lambda: backend.embed(inp, dimensions=dims))
+        except _BUSY as e:
+            return self._busy_reply(e)
+        except ValueError as e:  # the backend or the engine refused the request
+            raise http_error(400, str(e))
+        except FutTimeout:
+            raise http_error(504, "embeddings not ready within the server write timeout")
+        except Exception as e:  # noqa: BLE001
+            raise http_error(500, f"{type(e).__name__}: {e}")
+        data = []
+        for i, v in enumerate(vecs):
+            if fmt == "base64":
+                emb = base64.b64encode(v.astype("<f4", copy=False).tobytes()).decode("ascii")
+            else:
+                emb = [float(t) for t in v]
+            data.append({"object": "embedding", "index": i, "embedding": emb})
+        return json_reply({"object": "list", "model": getattr(backend, "model", "") or d.get("model", ""),
+                           "data": data, "usage": {"prompt_tokens": n_tok, "total_tokens": n_tok}})
 
     def _guide_spec(self, d: dict) -> Optional[dict]:
         """The guide a chat-completions body asks for (None: none), compiled once here so that a

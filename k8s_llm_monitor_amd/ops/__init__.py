@@ -1879,6 +1879,37 @@ def token_logprobs(logits: torch.Tensor, tokens: torch.Tensor, want: torch.Tenso
     return out
 
 
+def pool_l2(x: torch.Tensor, dim, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Last-token pooling of embedding requests (``ref.pool_l2``): row ``r`` of ``x`` (bf16 or
+    fp32 [R, d], the final-normed hidden rows; a view with a wider row stride is fine) cut to its
+    first ``dim[r]`` columns and L2-normalised into ``out`` fp32 [R, d], zeros beyond them.  Rows
+    with ``dim[r] <= 0`` are left as they are in ``out`` (zeros in a fresh one).  ``dim`` is int32
+    [R] on ``x``'s device, or host values (a list or a CPU tensor), which are checked against ``d``
+    here; values already on the GPU are not read back, the kernel clamps them to ``d``."""
+    if x.dim() != 2 or x.dtype not in (torch.bfloat16, torch.float32) or (x.shape[1] and x.stride(1) != 1):
+        raise ValueError(f"pool_l2: x is bf16 or fp32 [R, d] with unit column stride, got {x.dtype} {list(x.shape)}")
+    R, d = x.shape
+    if not isinstance(dim, torch.Tensor) or not dim.is_cuda:
+        dim = torch.as_tensor(dim).reshape(-1)
+        if dim.is_floating_point() or dim.numel() < R:
+            raise ValueError("pool_l2: dim holds R integers")
+        if R and int(dim[:R].max()) > d:
+            raise ValueError(f"pool_l2: dim {int(dim[:R].max())} exceeds the row width {d}")
+        dim = dim.to(device=x.device, dtype=torch.int32)
+    elif dim.dtype != torch.int32 or dim.numel() < R or dim.device != x.device:
+        raise ValueError("pool_l2: dim is int32 [R] on x's device")
+    if out is None:
+        out = torch.zeros(R, d, dtype=torch.float32, device=x.device)
+    elif (out.dtype != torch.float32 or out.dim() != 2 or tuple(out.shape) != (R, d) or not out.is_contiguous()
+          or out.device != x.device):
+        raise ValueError(f"pool_l2: out is contiguous fp32 [{R}, {d}] on x's device")
+    if not _gpu(x):
+        return ref.pool_l2(x, dim, out)
+    if R and d:
+        native().pool_l2(out, x, dim.contiguous())
+    return out
+
+
 def unpack_logprobs(rec_row) -> tuple:
     """``(lp, [(id, lp), ...])`` of one packed record (a host int32 row of ``token_logprobs``):
     the alternatives up to the first empty entry."""

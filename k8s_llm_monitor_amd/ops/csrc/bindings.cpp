@@ -57,6 +57,8 @@ int k8sllm_sample_parts(long B, int V);
 long k8sllm_token_logprobs_ws(long B, int V);
 int k8sllm_token_logprobs(int* out, const void* logits, int is_fp32, long B, long stride, int V, const int* tok,
                           const int* want, void* ws, hipStream_t s);
+int k8sllm_pool_l2(float* out, const void* x, int is_fp32, const int* dim, long rows, int d, long x_stride,
+                   hipStream_t s);
 int k8sllm_moe_route(const void* logits, long T, int E, int K, int renorm, int* topk_ids, float* topk_w,
                      hipStream_t s);
 int k8sllm_moe_router(const void* x, const void* wr, long T, int d, int E, int K, int renorm, int* ids, float* w,
@@ -557,6 +559,25 @@ void penalty_reset(torch::Tensor table, torch::Tensor params, int64_t vocab, int
                              ids.data_ptr<int>(), (int)n_prompt, (int)n_out, params.data_ptr<float>(), (float)rep,
                              (float)inv_rep, (float)presence, (float)frequency, cur()),
         "penalty_reset");
+}
+
+// Last-token pooling (ops.pool_l2): x bf16 / fp32 [R, d] (rows may be strided), dim int32 [>= R], out fp32 [R, d]
+void pool_l2(torch::Tensor out, torch::Tensor x, torch::Tensor dim) {
+  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.stride(1) == 1 && x.stride(0) >= x.size(1),
+              "pool_l2: x must be a 2-D GPU tensor with unit column stride");
+  const bool f32 = x.scalar_type() == torch::kFloat32;
+  TORCH_CHECK(f32 || x.scalar_type() == torch::kBFloat16, "pool_l2: x must be bfloat16 or float32");
+  const long R = x.size(0);
+  const int d = (int)x.size(1);
+  dev_i32(dim, "dim");
+  TORCH_CHECK(dim.numel() >= R, "pool_l2: dim [R]");
+  TORCH_CHECK(out.is_cuda() && out.scalar_type() == torch::kFloat32 && out.is_contiguous() && out.dim() == 2 &&
+                  out.size(0) == R && out.size(1) == d,
+              "pool_l2: out must be contiguous float32 [R, d]");
+  if (R == 0) return;
+  check(k8sllm_pool_l2(out.data_ptr<float>(), x.data_ptr(), f32 ? 1 : 0, dim.data_ptr<int>(), R, d, x.stride(0),
+                       cur()),
+        "pool_l2");
 }
 
 // Token log-probabilities (ops.token_logprobs): out int32 [>= B, 41] packed records, tok / want int32 [>= B]
@@ -1477,6 +1498,7 @@ PYBIND11_MODULE(_k8sllm_ops, m) {
   m.def("guide_mask_build", &guide_mask_build);
   m.def("penalty_reset", &penalty_reset);
   m.def("token_logprobs", &token_logprobs);
+  m.def("pool_l2", &pool_l2);
   m.def("moe_route", &moe_route);
   m.def("moe_router", &moe_router);
   m.def("moe_align", &moe_align);

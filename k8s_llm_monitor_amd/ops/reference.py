@@ -11,6 +11,7 @@ KV-cache layouts (see ``csrc/rope_cache.hip``):
 from __future__ import annotations
 
 import math
+from typing import Optional
 
 import torch
 import torch.nn.functional as F
@@ -383,6 +384,24 @@ def moe_combine(y: torch.Tensor, inv_idx: torch.Tensor, w: torch.Tensor, T: int)
     K = w.shape[1]
     g = y.double()[inv_idx.long()].view(T, K, -1)  # K products and their sum, rounded once
     return (g * w.double().unsqueeze(-1)).sum(1).to(y.dtype)
+
+
+def pool_l2(x: torch.Tensor, dim, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Last-token pooling of embedding requests: row ``r`` of ``x`` [R, d] cut to its first
+    ``dim[r]`` columns and L2-normalised (fp64 inside), zeros beyond them; an all-zero row gives
+    zeros.  Rows with ``dim[r] <= 0`` are not embedding rows: their ``out`` rows stay as they are
+    (zeros in a fresh ``out``).  Returns ``out``, fp32 [R, d]."""
+    R, d = x.shape
+    if out is None:
+        out = torch.zeros(R, d, dtype=torch.float32, device=x.device)
+    for r, n in enumerate(torch.as_tensor(dim).reshape(-1)[:R].tolist()):
+        if n <= 0:
+            continue
+        v = x[r, :n].double()
+        nrm = v.norm()
+        out[r, :n] = (v / nrm if float(nrm) > 0 else torch.zeros_like(v)).float()
+        out[r, n:] = 0
+    return out
 
 
 def lora_delta(x: torch.Tensor, A: torch.Tensor, B: torch.Tensor, scaling: torch.Tensor, slot: torch.Tensor,
